@@ -11,10 +11,16 @@ A~U(0.5,2), dn~U(-0.1,0.1), default_rng(rank); PowerToCorrelation(k, ell=0), def
 One "step" = one pass of the fused kernel over the resident batch (inputs already in HBM).  Rows are independent, so
 ranks shard with no data-path collective (weak scaling: per-GPU work fixed); `value` = rows of all ranks / max time.
 
-Extra objects on the JSON line: "roofline" (algorithmic bytes 2*8*N per row / kernel time measured with HIP events on
-the launch stream, against 8 TB/s), "value_api" (the same steps through cp.PowerToCorrelation.__call__), at N=1 "cpu_baseline" (the numpy
-oracle -- same math as the reference's numpy path -- on a bounded sample, all host cores through a process pool) and "secondary": BASELINE
-configs 3, 4 and 5 at one GPU's share (a few ms to a few tens of ms of GPU time each) with their own roofline figures.
+A plain run sets up, warms up, times the K steps and prints the line; besides the headline it carries "roofline" (algorithmic bytes
+2*8*N per row / kernel time measured with HIP events around the timed steps, against 8 TB/s).  --dump-outputs DIR also writes what the
+timed steps computed (rank 0): DIR/s.npy, the output grid, and DIR/xi.npy, a fixed sample of DUMP_ROWS rows of the result (all rows of a
+smaller batch, in row order; dump_rows() gives their indices).
+
+--full adds everything else, each measured after the timed steps: the same K launches bracketed one by one, "value_api" (the same steps
+through cp.PowerToCorrelation.__call__), the oracle spot check of one row, the figures of the committed profiles (HBM traffic, "roofline_valu"),
+at N=1 "cpu_baseline" (the numpy oracle -- same math as the reference's numpy path -- on a bounded sample, all host cores through a process
+pool, timed before the GPU is touched) and "secondary": BASELINE configs 3, 4 and 5 at one GPU's share (a few ms to a few tens of ms of GPU
+time each) with their own roofline figures; at N > 1 the timed all_gather and the strong splits of configs 4 and 5 ("split_configs").
 
 --config 4 / 5: the 8-GPU configs of BASELINE.json as STRONG splits (1 M P(k) vectors through wallish2018 + brieden2022; 10 M background
 samples; each rank takes its contiguous block of cosmologies / samples, no data-path collective); --gather adds the final RCCL all_gather.
@@ -38,6 +44,14 @@ FP64_PEAK_TFLOPS = 78.6       # MI355X_MICROARCH.md: dense fp64, vector = matrix
 CONFIG4_CHUNK = 65536         # vectors per pass of config 4; tests/test_full_size_gpu.py runs the one-GPU share at this size (imported from here)
 CONFIG4_PROFILE_CHUNKS = 6      # timed chunks of tools/profile_secondary.py 4w / 4b (behind one untimed chunk, which builds the filter's plans)
 BYTES_PER_ROW = 2 * 8 * N_K   # read N f64 + write N f64 (tables are batch-shared, excluded)
+DUMP_ROWS = 2048              # rows of the result --dump-outputs writes: 32 MB of float64 at N = 2048
+
+
+def dump_rows(nb):
+    """Indices of the result rows that --dump-outputs writes for a batch of nb rows: a fixed, seeded sample, ascending."""
+    if nb <= DUMP_ROWS:
+        return np.arange(nb)
+    return np.sort(np.random.default_rng(2048).choice(nb, DUMP_ROWS, replace=False))
 
 
 def _cpu_chunk(args):
@@ -516,15 +530,19 @@ def main():
     ap.add_argument('--steps', type=int, default=200, help='timed steps (default 200: 0.2 s of back-to-back launches -- long enough for a device monitor sampling the run to see the GPU busy)')
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--rows', type=int, default=ROWS_PER_GPU, help='rows per GPU (default: the config-2 batch)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--gather', action='store_true', help='also time the final RCCL all_gather of the result shards (reported separately); the default for N > 1')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--gather', action='store_true', help='also time the final RCCL all_gather of the result shards (reported separately); the default for N > 1 with --full')
     ap.add_argument('--no-gather', action='store_true', help='N > 1: skip the timing of the final all_gather')
     ap.add_argument('--config', type=int, default=2, choices=[2, 4, 5], help='BASELINE.json config: 2 (headline, weak scaling), 4 or 5 (strong splits)')
     ap.add_argument('--ramp-ms', type=float, default=300., help='untimed load before the warmup steps (and before each secondary config), to reach the sustained device state')
     ap.add_argument('--launcher', action='store_true', help='start the rank(s) through torch.distributed.run even for --gpus 1 (RCCL initialised); N > 1 always does')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the configs 3 / 4 / 5 numbers of the N = 1 line (and the split configs 4 / 5 of an N > 1 line)')
-    ap.add_argument('--split-configs', action='store_true', help='under a launcher: the strong splits of configs 4 and 5 on the line ("split_configs"); the default for N > 1')
+    ap.add_argument('--no-secondary', action='store_true', help='--full: skip the configs 3 / 4 / 5 numbers of the N = 1 line (and the split configs 4 / 5 of an N > 1 line)')
+    ap.add_argument('--split-configs', action='store_true', help='under a launcher: the strong splits of configs 4 and 5 on the line ("split_configs"); the default for N > 1 with --full')
+    ap.add_argument('--full', action='store_true', help='also measure and check everything beyond the headline figure (see the module docstring); off: the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the timed steps computed as DIR/<name>.npy (float64; rank 0; a fixed sample of the rows)')
     args = ap.parse_args()
+    if args.dump_outputs and args.config != 2:
+        ap.error('--dump-outputs writes the outputs of the headline (--config 2) only')
     _launch_ranks_if_needed(args)
     if args.config != 2:
         return main_split(args, args.config)
@@ -540,7 +558,7 @@ def main():
 
     T0 = time.perf_counter()
     cpu = None
-    if rank == 0 and args.gpus == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and args.gpus == 1 and not args.no_cpu_baseline:
         log('cpu baseline on %d cores ...' % _host_cores())
         cpu = cpu_baseline()   # before the GPU is touched (fork-safe)
         log('cpu baseline: %.0f transforms/s' % cpu['value'])
@@ -608,46 +626,55 @@ def main():
     elapsed = time.perf_counter() - tic
     kernel_ms = e0.elapsed_time(e1) / args.steps
     rank_ms = [(t_done - tic) / args.steps * 1e3]      # this rank's own K steps, before it waited for the others
-    # untimed, afterwards: the same K launches bracketed one by one (the spread between launches; the minimum is the quiet-device duration)
-    starts = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
-    ends = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
-    for i in range(args.steps):
-        starts[i].record(stream)
-        step()
-        ends[i].record(stream)
-    torch.cuda.synchronize(dev)
-    per_step = [s.elapsed_time(e) for s, e in zip(starts, ends)]
-    kernel_ms_each, kernel_ms_min = float(np.mean(per_step)), float(np.min(per_step))
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: the output grid and (a fixed sample of the rows of) the result of the last timed step
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 's.npy'), np.asarray(f.y[0], dtype=np.float64))
+        sample = torch.as_tensor(dump_rows(nb), device=dev)
+        np.save(os.path.join(args.dump_outputs, 'xi.npy'), out.index_select(0, sample).cpu().numpy().astype(np.float64))
+        log('outputs written to %s' % args.dump_outputs)
+    if args.full:
+        # untimed, afterwards: the same K launches bracketed one by one (the spread between launches; the minimum is the quiet-device duration)
+        starts = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
+        ends = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
+        for i in range(args.steps):
+            starts[i].record(stream)
+            step()
+            ends[i].record(stream)
+        torch.cuda.synchronize(dev)
+        per_step = [s.elapsed_time(e) for s, e in zip(starts, ends)]
+        kernel_ms_each, kernel_ms_min = float(np.mean(per_step)), float(np.min(per_step))
 
-    # the same K steps through the product API (cp.PowerToCorrelation.__call__ on the resident tensor into a resident result: plan
-    # lookup, argument checks and the ctypes call included, no allocation, no host synchronisation inside)
-    out_api = torch.empty_like(out)      # the caller's result buffer (FFTlog.__call__(out=)): a sampler keeps one, as this loop does
-    for _ in range(max(1, args.warmup)):
-        f(rows, out=out_api)
-    torch.cuda.synchronize(dev)
-    if distributed:
-        dist.barrier()
-    tic_api = time.perf_counter()
-    for i in range(args.steps):
-        s_api, xi_api = f(rows, out=out_api)
-    torch.cuda.synchronize(dev)
-    if distributed:
-        dist.barrier()
-    elapsed_api = time.perf_counter() - tic_api
-    assert xi_api.shape == rows.shape and bool(torch.equal(xi_api, out)), 'API path and C-ABI path disagree'
+        # the same K steps through the product API (cp.PowerToCorrelation.__call__ on the resident tensor into a resident result: plan
+        # lookup, argument checks and the ctypes call included, no allocation, no host synchronisation inside)
+        out_api = torch.empty_like(out)      # the caller's result buffer (FFTlog.__call__(out=)): a sampler keeps one, as this loop does
+        for _ in range(max(1, args.warmup)):
+            f(rows, out=out_api)
+        torch.cuda.synchronize(dev)
+        if distributed:
+            dist.barrier()
+        tic_api = time.perf_counter()
+        for i in range(args.steps):
+            s_api, xi_api = f(rows, out=out_api)
+        torch.cuda.synchronize(dev)
+        if distributed:
+            dist.barrier()
+        elapsed_api = time.perf_counter() - tic_api
+        assert xi_api.shape == rows.shape and bool(torch.equal(xi_api, out)), 'API path and C-ABI path disagree'
 
     gather_ms = None
     if distributed:
-        tapi = torch.tensor([elapsed_api], device=dev, dtype=torch.float64)
-        dist.all_reduce(tapi, op=dist.ReduceOp.MAX)
-        elapsed_api = float(tapi[0])
+        if args.full:
+            tapi = torch.tensor([elapsed_api], device=dev, dtype=torch.float64)
+            dist.all_reduce(tapi, op=dist.ReduceOp.MAX)
+            elapsed_api = float(tapi[0])
         tmax = torch.tensor([elapsed, kernel_ms], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed, kernel_ms = float(tmax[0]), float(tmax[1])
         every = torch.zeros(world, device=dev, dtype=torch.float64)
         dist.all_gather_into_tensor(every, torch.tensor(rank_ms, device=dev, dtype=torch.float64))
         rank_ms = [float(v) for v in every]      # a straggler shows at a glance on the first multi-GPU run
-        if (args.gather or world > 1) and not args.no_gather:
+        if (args.gather or (args.full and world > 1)) and not args.no_gather:
             from cosmoprimo_amd.distributed import gather_rows
             full = torch.empty((world * nb, N_K), dtype=out.dtype, device=dev)
             gather_rows(out, n_total=world * nb, out=full)      # equal shards: one all_gather_into_tensor into the preallocated result
@@ -659,15 +686,7 @@ def main():
             dist.barrier()
             gather_ms = (time.perf_counter() - t0) * 1e3
 
-    # sanity: the timed output is the real transform (spot-check one row against the oracle on rank 0)
     if rank == 0:
-        from oracle import fftlog as ofl
-        t = ofl.power_to_correlation(k, ell=0)
-        ref = ofl.apply(t, rows[7].cpu().numpy())[0]
-        w = t.y[0] ** 1.5
-        err = float(np.abs((out[7].cpu().numpy() - ref) * w).max() / np.abs(ref * w).max())
-        assert err < 1e-13, 'bench output failed parity spot-check: %g' % err
-
         total_rows = nb * world * args.steps
         value = total_rows / elapsed
         achieved = BYTES_PER_ROW * nb / (kernel_ms * 1e-3) / 1e9   # GB/s per GPU, dominant (only) kernel
@@ -675,6 +694,26 @@ def main():
         block = __import__('ctypes').c_int()
         lds = __import__('ctypes').c_int()
         lib.cp_fftlog_plan_info(plan.handle, nb, grid, block, lds)
+        line = {
+            'metric': 'batched FFTLog P(k)->xi(r) transforms/sec (N=2048)', 'value': value, 'unit': 'transforms/s',
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3,
+            'ms_per_step_rank_min': min(rank_ms), 'ms_per_step_rank_max': max(rank_ms), 'ms_per_step_by_rank': rank_ms,
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
+            'config': {'workload': 'config 2: %d rows x N_k=%d per GPU, PowerToCorrelation(ell=0), Np=4096, extrap=0' % (nb, N_K),
+                       'rows_per_gpu': nb, 'n_k': N_K, 'padded_size': 4096, 'parallelism': 'rows sharded over %d GPU(s), no collective' % world,
+                       'grid': grid.value, 'block': block.value, 'lds_bytes': lds.value, 'rccl_ranks': world if distributed else 0},
+            'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
+                         'kernel': 'fftlog_kernel<4096,16,IN_HALF_ZERO,OUT_HALF>', 'kernel_ms': kernel_ms, 'algorithmic_bytes_per_launch': BYTES_PER_ROW * nb},
+        }
+    if rank == 0 and args.full:
+        # sanity: the timed output is the real transform (spot-check one row against the oracle)
+        from oracle import fftlog as ofl
+        t = ofl.power_to_correlation(k, ell=0)
+        ref = ofl.apply(t, rows[7].cpu().numpy())[0]
+        w = t.y[0] ** 1.5
+        err = float(np.abs((out[7].cpu().numpy() - ref) * w).max() / np.abs(ref * w).max())
+        assert err < 1e-13, 'bench output failed parity spot-check: %g' % err
+
         traffic, traffic_src = None, None
         import glob
         prof = sorted(glob.glob(os.path.join(ROOT, 'profiles', '*_pmc_summary.json')))
@@ -693,22 +732,11 @@ def main():
             with open(steady[-1]) as fh:
                 summ = json.load(fh)
             rocprof = dict(summ['steady_state'], source=os.path.relpath(steady[-1], ROOT), kernel_ms_hip_events_same_run=(summ.get('same_run_bench_line') or {}).get('kernel_ms_hip_events'))
-        line = {
-            'metric': 'batched FFTLog P(k)->xi(r) transforms/sec (N=2048)', 'value': value, 'unit': 'transforms/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': elapsed / args.steps * 1e3,
-            'ms_per_step_rank_min': min(rank_ms), 'ms_per_step_rank_max': max(rank_ms), 'ms_per_step_by_rank': rank_ms,
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
-            'config': {'workload': 'config 2: %d rows x N_k=%d per GPU, PowerToCorrelation(ell=0), Np=4096, extrap=0' % (nb, N_K),
-                       'rows_per_gpu': nb, 'n_k': N_K, 'padded_size': 4096, 'parallelism': 'rows sharded over %d GPU(s), no collective' % world,
-                       'grid': grid.value, 'block': block.value, 'lds_bytes': lds.value},
-            'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
-                         'traffic': traffic, 'traffic_source': traffic_src, 'kernel': 'fftlog_kernel<4096,16,IN_HALF_ZERO,OUT_HALF>', 'kernel_ms': kernel_ms,
-                         'kernel_ms_bracketed_one_by_one': kernel_ms_each, 'kernel_ms_min': kernel_ms_min, 'rocprof_steady_state': rocprof, 'algorithmic_bytes_per_launch': BYTES_PER_ROW * nb},
-            'roofline_valu': valu,
-            'parity_spot_check_tilted_err': err,
-            'value_api': nb * world * args.steps / elapsed_api,   # same batch through cp.PowerToCorrelation.__call__ (resident tensors)
-        }
-        line['config']['rccl_ranks'] = world if distributed else 0
+        line['roofline'].update(traffic=traffic, traffic_source=traffic_src, kernel_ms_bracketed_one_by_one=kernel_ms_each, kernel_ms_min=kernel_ms_min,
+                                rocprof_steady_state=rocprof)
+        line['roofline_valu'] = valu
+        line['parity_spot_check_tilted_err'] = err
+        line['value_api'] = nb * world * args.steps / elapsed_api   # same batch through cp.PowerToCorrelation.__call__ (resident tensors)
         if cpu is not None:
             line['cpu_baseline'] = cpu
         if world == 1 and not args.no_secondary:
@@ -717,11 +745,12 @@ def main():
             del rows, out, out_api, xi_api
             torch.cuda.empty_cache()
             line['secondary'] = secondary(cp, torch, dev)
+    if rank == 0:
         if gather_ms is not None:
             line['gather_ms'] = gather_ms
             line['value_with_gather'] = nb * world / (elapsed / args.steps + gather_ms * 1e-3)      # a step followed by the gather of its results
-    if distributed and (args.split_configs or (world > 1 and not args.no_secondary)):
-        # BASELINE configs 4 and 5 are DEFINED on the 8 GPUs of a node: a multi-GPU run reports their strong splits on the same line (every rank takes part:
+    if distributed and (args.split_configs or (args.full and world > 1 and not args.no_secondary)):
+        # BASELINE configs 4 and 5 are DEFINED on the 8 GPUs of a node: a multi-GPU --full run reports their strong splits on the same line (every rank takes part:
         # the barriers and the max over ranks are collectives), a few steps each
         try:
             del rows, out, out_api, xi_api

@@ -13,5 +13,6 @@ for c in 3 3b 4 5; do
   rm -rf $R/gpurun_out/prof_c$c $R/gpurun_out/prof_c$c.log
 done
 cd $R
-python3 bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.log
-tail -c 1500 gpurun_out/${tag}_bench.json
+dest=$(dirname "$(ls -t "$R"/*/"${tag}_config5.json" | head -1)")      # the folder the loop above wrote its results into
+python3 bench.py --full > "$dest/${tag}_bench.json" 2> "$dest/${tag}_bench.log"
+tail -c 1500 "$dest/${tag}_bench.json"

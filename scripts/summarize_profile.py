@@ -44,7 +44,7 @@ f8, w8 = cal['copy8'].get('FETCH_SIZE', 0.5), cal['copy8'].get('WRITE_SIZE', 1.)
 read = counters['FETCH_SIZE']['mean'] * 1024 / f8
 write = counters['WRITE_SIZE']['mean'] * 1024 / w8
 out = {
-    'command': 'rocprofv3 --pmc <counters> --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary '
+    'command': 'rocprofv3 --pmc <counters> --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --full '
                '(separate passes: FETCH_SIZE | WRITE_SIZE | SQ_* | SQ_* | GRBM_GUI_ACTIVE; every fftlog_kernel dispatch of the run, device ramp included)',
     'kernel': 'cpfft::fftlog_kernel<4096, 16, 3, 1>',
     'rows_per_launch': rows,

@@ -86,7 +86,7 @@ def kernel_resources():
 
 resources = kernel_resources()
 out = {
-    'command': 'rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary',
+    'command': 'rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary --full',
     'kernel': 'cpfft::fftlog_kernel<4096, 16, 3, 1>', 'rows_per_launch': ROWS, 'algorithmic_bytes_per_launch': ROWS * BYTES_PER_ROW,
     'kernel_resources': resources, 'lds_bytes_dynamic': None if bench_line is None else bench_line['config'].get('lds_bytes'),
     'grid_threads': disp[0][3], 'profiler_trace_columns': {'VGPR_Count': disp[0][2], 'LDS_Block_Size': disp[0][4],

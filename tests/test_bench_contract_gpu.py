@@ -1,5 +1,6 @@
 """GPU: bench.py's contract with the driver -- one JSON line with the agreed keys, at N = 1 directly and under torchrun with one rank (RCCL
-initialised, barriers, the optional gather) -- on a small batch so that the test takes seconds."""
+initialised, barriers, the optional gather), plain and with --full, and the outputs --dump-outputs writes -- on a small batch so that the
+test takes seconds."""
 import json
 import os
 import subprocess
@@ -33,7 +34,7 @@ def check(line, steps, warmup):
 
 
 def test_single_process_line():
-    line = run([sys.executable, 'bench.py', '--rows', '4000', '--steps', '3', '--warmup', '1', '--ramp-ms', '20', '--no-cpu-baseline', '--no-secondary'])
+    line = run([sys.executable, 'bench.py', '--rows', '4000', '--steps', '3', '--warmup', '1', '--ramp-ms', '20', '--no-cpu-baseline', '--no-secondary', '--full'])
     check(line, 3, 1)
     assert line['scaling'] == 'weak' and line['config']['rccl_ranks'] == 0 and line['value_api'] > 0
 
@@ -41,7 +42,7 @@ def test_single_process_line():
 def test_one_rank_under_torchrun():
     base = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1']
     line = run(base + ['--master-port', '29541', 'bench.py', '--gpus', '1', '--rows', '4000', '--steps', '3', '--warmup', '1', '--ramp-ms', '20',
-                       '--no-cpu-baseline', '--no-secondary', '--gather'])
+                       '--no-cpu-baseline', '--no-secondary', '--gather', '--full'])
     check(line, 3, 1)
     assert line['config']['rccl_ranks'] == 1 and line['gather_ms'] > 0 and line['value_with_gather'] > 0
     split = run(base + ['--master-port', '29542', 'bench.py', '--gpus', '1', '--config', '5', '--rows', '200000', '--steps', '2', '--warmup', '1', '--gather'])
@@ -54,9 +55,9 @@ def test_one_rank_under_torchrun():
     for engine in ('wallish2018', 'brieden2022'):
         assert filt['parity_spot_check'][engine]['max_rel_err'] < 1e-9
     assert line['ms_per_step_rank_min'] <= line['ms_per_step_rank_max'] and len(line['ms_per_step_by_rank']) == 1
-    # what a multi-GPU run prints by default (here forced on one rank): the gather timed, the strong splits of configs 4 and 5 on the same line
+    # what a multi-GPU --full run prints by default (here forced on one rank): the gather timed, the strong splits of configs 4 and 5 on the same line
     multi = run(base + ['--master-port', '29544', 'bench.py', '--gpus', '1', '--rows', '3000', '--steps', '2', '--warmup', '1', '--ramp-ms', '20',
-                        '--no-cpu-baseline', '--no-secondary', '--split-configs', '--gather'])
+                        '--no-cpu-baseline', '--no-secondary', '--split-configs', '--gather', '--full'])
     check(multi, 2, 1)
     assert multi['gather_ms'] > 0 and set(multi['split_configs']) == {'config4', 'config5'}
     for name, unit in (('config4', 'filtered vectors/s'), ('config5', 'samples/s')):
@@ -68,7 +69,7 @@ def test_self_launch():
     """`python bench.py --gpus N` without a launcher starts its own ranks: with --launcher also for N = 1 (RCCL then initialised); asking for more
     GPUs than the node has, or a launcher whose world size is not --gpus, exits non-zero instead of printing a line."""
     import torch
-    small = ['--rows', '4000', '--steps', '3', '--warmup', '1', '--ramp-ms', '20', '--no-cpu-baseline', '--no-secondary']
+    small = ['--rows', '4000', '--steps', '3', '--warmup', '1', '--ramp-ms', '20', '--no-cpu-baseline', '--no-secondary', '--full']
     line = run([sys.executable, 'bench.py', '--gpus', '1', '--launcher'] + small)
     check(line, 3, 1)
     assert line['config']['rccl_ranks'] == 1
@@ -80,3 +81,29 @@ def test_self_launch():
     res = subprocess.run([sys.executable, 'bench.py', '--gpus', '2'] + small, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                          universal_newlines=True, timeout=600)
     assert res.returncode != 0 and not any(ln.startswith('{') for ln in res.stdout.splitlines()) and 'WORLD_SIZE' in res.stderr
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the headline keys and nothing that needs a measurement of its own; --dump-outputs writes the output grid
+    and the sampled rows of the last timed step, which are the transforms of the bench's input rows (numpy oracle)."""
+    import numpy as np
+    import bench
+    from oracle import fftlog as ofl
+    from oracle.workloads import pk_eh_default, config2_rows
+    nb, dump = 4000, tmp_path / 'out'
+    line = run([sys.executable, 'bench.py', '--rows', str(nb), '--steps', '3', '--warmup', '1', '--ramp-ms', '20', '--dump-outputs', str(dump)])
+    assert KEYS <= set(line), KEYS - set(line)
+    assert line['steps'] == 3 and line['warmup'] == 1 and line['n_gpus'] == 1 and line['higher_is_better'] is True and line['dtype'] == 'f64'
+    assert line['value'] > 0 and line['ms_per_step'] > 0 and abs(line['value'] - nb / (line['ms_per_step'] * 1e-3)) < 1e-6 * line['value']
+    assert abs(line['roofline']['frac'] - line['roofline']['achieved'] / line['roofline']['peak']) < 1e-12
+    assert not {'cpu_baseline', 'secondary', 'value_api', 'parity_spot_check_tilted_err', 'split_configs', 'gather_ms'} & set(line)
+    s, xi = np.load(dump / 's.npy'), np.load(dump / 'xi.npy')
+    idx = bench.dump_rows(nb)
+    assert s.dtype == xi.dtype == np.float64 and s.shape == (bench.N_K,) and xi.shape == (bench.DUMP_ROWS, bench.N_K) == (idx.size, bench.N_K)
+    k, pk = pk_eh_default(bench.N_K)
+    t = ofl.power_to_correlation(k, ell=0)
+    assert np.allclose(s, t.y[0], rtol=1e-14, atol=0.)
+    rows = config2_rows(k, pk, 0, nb, seed=0, nbatch=nb)[idx]
+    ref = ofl.apply(t, rows[:, None, :])[:, 0]
+    w = t.y[0] ** 1.5
+    assert np.abs((xi - ref) * w).max() / np.abs(ref * w).max() < 1e-12

@@ -4,8 +4,8 @@
 before=$1; out=$2; rounds=${3:-2}
 mkdir -p "$(dirname "$out")"
 for r in $(seq 1 $rounds); do
-  COSMOPRIMO_AMD_LIBRARY=$before python bench.py --no-cpu-baseline > "${out}_before_$r.json" 2> "${out}_before_$r.err"
-  python bench.py --no-cpu-baseline > "${out}_after_$r.json" 2> "${out}_after_$r.err"
+  COSMOPRIMO_AMD_LIBRARY=$before python bench.py --no-cpu-baseline --full > "${out}_before_$r.json" 2> "${out}_before_$r.err"
+  python bench.py --no-cpu-baseline --full > "${out}_after_$r.json" 2> "${out}_after_$r.err"
 done
 python - "$out" "$rounds" <<'PY'
 import json, sys

@@ -3,7 +3,7 @@
 # (gpurun -- bash tools/math_tables_ab.sh)
 line() { python - <<PY
 import json, subprocess, sys
-out = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline"], capture_output=True, text=True).stdout.strip().split("\n")[-1]
+out = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline", "--full"], capture_output=True, text=True).stdout.strip().split("\n")[-1]
 d = json.loads(out)
 s = d["secondary"]
 print("   headline %.4f ms (frac %.4f) | config 3: %.4f ms | 3B: %.3f ms | config 4: wallish2018 %.3e  brieden2022 %.3e vectors/s | config 5: %.4f ms" % (
