@@ -228,7 +228,10 @@ __global__ __launch_bounds__(256) void bg_kernel(const Args A) {
     if (!TIME) {
         // what the wave knows of its samples (cp_cosmo_common.h: inv_efunc_grid_wave): scalar branches instead of per-lane ones
         const bool wave_fld = __any(!gc.lambda), wave_lambda = __any(gc.lambda);
-        const bool wave_safe = CP_BG_LEAN_ORDINATE && !NCDM && __all(gc.Om >= 0. && gc.Or >= 0. && gc.Ode >= 0. && gc.Ok >= 0.);
+        // SAFE also needs E^2 positive, normal and finite at every ordinate (rsqrt_pos has no select for 0 / Inf): matter and radiation not both zero,
+        // no density parameter beyond 1e100 and a dark-energy exponent below 600 over the grid (|log(1 + z)| <= log(1e4) < 9.22, |1 / (1 + z) - 1| < 1)
+        const bool wave_safe = CP_BG_LEAN_ORDINATE && !NCDM && __all(gc.Om >= 0. && gc.Or >= 0. && gc.Ode >= 0. && gc.Ok >= 0. && gc.Om + gc.Or >= 2.2250738585072014e-308 &&
+                                                                     fmax(fmax(gc.Om, gc.Or), fmax(gc.Ode, gc.Ok)) < 1e100 && fabs(gc.ea) * 9.22 + fabs(gc.eb) < 600.);
         auto sweeps = [&](auto safe_tag) {
         constexpr bool SAFE = decltype(safe_tag)::value;
         auto knot = [&](int j) {      // the ordinate at knot j / at the midpoint of interval j: every argument from the grid's tables
@@ -313,6 +316,14 @@ __global__ __launch_bounds__(256) void bg_kernel(const Args A) {
         }
         inc_prev = inc;
     }
+    }
+    // The reference forms the dark-energy factor as (1 + z)^(3 (w0 + wa)) exp(3 wa (1 / (1 + z) - 1)), two factors, where the ordinates above take one
+    // exponential: where one factor underflows to 0 and the other overflows to Inf its E is NaN, and with it every distance, time and age of the
+    // cosmology (its splines take the whole table).  Both factors are monotonic in z, so if that happens anywhere on the grid it happens at the top
+    // knot; only exponents beyond the range of a double get there (|3 (w0 + wa)| log(1 + z) or |3 wa| above 700).
+    if (fabs(gc.ea) * T.lk[NK - 1] > 700. || fabs(gc.eb) > 700.) {
+        const double zp1 = 1. + T.zc[NK - 1];
+        if (__builtin_isnan(pow(zp1, gc.ea) * exp(gc.eb * (1. / zp1 - 1.)))) dq = total = nan;
     }
     {   // knot k + 1 closes the backward elimination: intervals k (from the forward sweep) and k + 1
         const double inc_up = (k == NK - 2) ? 0. : inc_prev;  // inc_{k+1}: the last interval visited going down (none above the last interval)

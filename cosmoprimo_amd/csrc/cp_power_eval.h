@@ -27,7 +27,12 @@ struct EhScalars {
 // x^y for positive, finite, normal x as exp(y log x) with the short forms of cp_math.h: relative error (|y log x| + 1) 2e-16 -- 1e-15 at most over the
 // powers of the fits (|y log x| < 3.1) -- at 65 instructions for the library's ~200.  For the pre-kernel that forms the evaluation's constants: its one lane
 // per cosmology walks ~25 of them in a row, and it runs in front of every evaluation (a fifteenth of brieden2022's kernel time, a twentieth of config 3).
-__device__ __forceinline__ double pow_short(double x, double y) { return exp_mid(y * log_pos(x)); }
+// Zero, negative, subnormal, Inf or NaN x (Omega_b = 0: omega_b^0.75) take the library's pow, out of line: exp_mid clamps its argument, so 0^y would
+// come out as 5e-324 or 2e308 instead of 0 or Inf.
+static __device__ __attribute__((noinline)) double pow_any(double x, double y) { return ::pow(x, y); }
+__device__ __forceinline__ double pow_short(double x, double y) {
+    return x >= 2.2250738585072014e-308 && x <= 1.7976931348623157e308 ? exp_mid(y * log_pos(x)) : pow_any(x, y);
+}
 
 // eisenstein_hu.py:34-92 (+ eisenstein_hu_nowiggle.py:21), operation for operation.  SHORT: the powers through pow_short (the constants of the evaluating
 // kernels: cosmo_consts); the scalars handed to the caller (cp_eh_scalars: rs_drag, z_drag, ...) take the library's pow.
@@ -181,10 +186,12 @@ __device__ __forceinline__ double transfer_nowiggle(const EhScalars& s, double h
     const double ks = k * s.rs_drag;
     const double x = 0.43 * ks;
     // the four quotients as reciprocals (the hardware estimate and two corrections, 1 ulp: a third of the instructions of an IEEE division -- half of what a
-    // sample cost was its divisions); every denominator is >= 1 or a positive constant of the cosmology
+    // sample cost was its divisions); every denominator is >= 1 or a constant of the cosmology
     const double gamma_eff = s.omega_m * (s.alpha_gamma + (1 - s.alpha_gamma) * recip(1 + (x * x) * (x * x)));
     const double q = k * (s.theta_cmb * s.theta_cmb) * recip(gamma_eff);
-    const double L0 = mt ? log_tab(2 * kE + 1.8 * q, mt) : log_pos(2 * kE + 1.8 * q);
+    // (gamma_eff, hence q, is negative at large k where alpha_gamma < 0 -- baryons only, Omega_cdm = 0: the logarithm is NaN there, as the reference's;
+    // log_tab handles positive normal finite arguments only)
+    const double L0 = mt ? log_tab_any(2 * kE + 1.8 * q, mt) : log_pos(2 * kE + 1.8 * q);
     const double C0 = 14.2 + 731.0 * recip(1 + 62.5 * q);
     return L0 * recip(L0 + C0 * (q * q));
 }

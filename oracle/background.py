@@ -269,6 +269,8 @@ def comoving_radial_distance_ncdm(z, p):
     inc = h / 6. * (f(t_last) + 2 * f(t_last + h / 2) + 2 * f(t_last + h / 2) + f(t))
     tab = np.concatenate([[0.], np.cumsum(inc)])
     z = np.asarray(z, dtype='f8')
+    if not np.isfinite(tab).all():      # the reference splines the whole table: one ordinate that is not finite makes every distance NaN
+        return np.full(z.shape, np.nan)
     out = CubicSpline(zc, tab, bc_type='natural', extrapolate=False)(z)
     return np.where((z >= zc[0]) & (z <= zc[-1]), out, np.nan)
 

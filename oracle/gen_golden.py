@@ -2,7 +2,7 @@
 
     python -m oracle.gen_golden [target ...]      # default target: fftlog
 
-Targets -> tests/golden/<name>.npz: fftlog (tables, loggamma, transforms), background, power, sigma, sigma_quad, sigma_api (the module-level sigma integrals with the reference's arguments), api_signatures (json: signatures of the public surface), bao, xi, bao2, bspline, densities, ncdm, variants, power_ncdm, bao_batch, fuzz (random cosmologies from wide priors), fftlog_fuzz (random FFTLog configurations), fftlog_large (the same at padded lengths 16 384 ... 131 072), interp_fuzz (tabulated interpolators with random options), filter_fuzz (BAO filters with random options), params_fuzz (parameter conventions), xi_fuzz (tabulated xi interpolators with random options),
+Targets -> tests/golden/<name>.npz: fftlog (tables, loggamma, transforms), background, power, sigma, sigma_quad, sigma_api (the module-level sigma integrals with the reference's arguments), api_signatures (json: signatures of the public surface), bao, xi, bao2, bspline, densities, ncdm, variants, power_ncdm, bao_batch, fuzz (random cosmologies from wide priors), corners (hand-placed cosmologies at the edges of the parameter space), fftlog_fuzz (random FFTLog configurations), fftlog_large (the same at padded lengths 16 384 ... 131 072), interp_fuzz (tabulated interpolators with random options), filter_fuzz (BAO filters with random options), params_fuzz (parameter conventions), xi_fuzz (tabulated xi interpolators with random options),
 calculator, cosmology_api, api_flows (tests/api_scenarios.py replayed with the reference), abacus (also writes the package data cosmoprimo_amd/data/abacus_cosmologies.json), desi_table (161 rows of the
 reference's data/desi.dat).  Every vector is the output of the reference itself, imported from /root/reference; no reference source is stored.
 See SURVEY.md 8(c) for the list (G1..G8).  TEST INFRASTRUCTURE: the product never imports this module.
@@ -999,6 +999,121 @@ def gen_fuzz(cp):
     save('fuzz', k=k, z=z, zb=zb, **{name: np.stack(v) for name, v in rows.items()})
 
 
+# Hand-placed cosmologies at the edges of the parameter space, where the kernels' fast paths change behaviour: zero baryons or cold dark matter, flat
+# to rounding, strongly closed and open, a cosmological constant and a fluid a few ulp away from it, dark-energy factors that overflow at the top
+# knots (wa = -300: one of the reference's two factors; w0 = -wa = 300: E^2 itself), w0 + wa on either side of 1/3 (the reference refuses more), very light / heavy / degenerate neutrinos, no massless neutrinos, a cold CMB, extreme h; sigma8 and A_s normalisations.
+CORNER_ZB = [0., 0.01, 0.5, 1.5, 3., 10., 100., 1000., 9999.]
+CORNER_ZG = [0., 1e-3, 0.5, 1., 3., 10., 100., 400.]
+
+
+def corner_params():
+    """The named corner cases: a list of (name, parameter dict of plain floats / lists) that the generator and tests/test_corners_gpu.py both use."""
+    base = dict(h=0.7, Omega_cdm=0.25, Omega_b=0.05, n_s=0.96)
+    cases = [
+        ('omega_b_zero', dict(Omega_b=0.)),
+        ('omega_b_tiny', dict(Omega_b=1e-6, sigma8=0.8)),
+        ('omega_b_large', dict(Omega_b=0.2, A_s=2.1e-9)),
+        ('omega_cdm_zero', dict(Omega_cdm=0.)),
+        ('omega_k_zero', dict(Omega_k=0.)),
+        ('omega_k_plus_tiny', dict(Omega_k=1e-12)),
+        ('omega_k_minus_tiny', dict(Omega_k=-1e-12, w0_fld=-0.9, wa_fld=0.1)),
+        ('omega_k_closed', dict(Omega_k=-0.6)),
+        ('omega_k_open', dict(Omega_k=0.9, sigma8=0.8)),
+        ('lambda_exact', dict(w0_fld=-1., wa_fld=0.)),
+        ('fluid_near_lambda', dict(w0_fld=-1. + 1e-15, wa_fld=0.)),
+        ('phantom', dict(w0_fld=-3.)),
+        ('wa_overflow', dict(w0_fld=-1., wa_fld=-300.)),
+        ('w_overflow', dict(w0_fld=300., wa_fld=-300.)),
+        ('w_sum_above_third', dict(w0_fld=-0.5, wa_fld=0.5 + 1. / 3. + 1e-9)),
+        ('w_sum_below_third', dict(w0_fld=-0.5, wa_fld=0.5 + 1. / 3. - 1e-9)),
+        ('m_ncdm_light', dict(m_ncdm=[1e-5])),
+        ('m_ncdm_heavy', dict(m_ncdm=[3.], sigma8=0.8)),
+        ('m_ncdm_degenerate', dict(m_ncdm=[0.1, 0.1, 0.1])),
+        ('n_ur_zero', dict(N_ur=0.)),
+        ('t_cmb_cold', dict(T_cmb=1.)),
+        ('h_low', dict(h=0.2)),
+        ('h_high', dict(h=1.5, A_s=2.1e-9)),
+        ('omega_b_zero_sigma8', dict(Omega_b=0., sigma8=0.8)),
+        ('omega_k_closed_fluid', dict(Omega_k=-0.6, w0_fld=-0.8, wa_fld=0.2)),
+        ('fluid_near_lambda_sigma8', dict(w0_fld=-1. + 1e-15, wa_fld=0., sigma8=0.8)),
+        ('m_ncdm_heavy_open', dict(m_ncdm=[3.], Omega_k=0.3)),
+    ]
+    return [(name, {n: (v if isinstance(v, list) else float(v)) for n, v in dict(base, **par).items()}) for name, par in cases]
+
+
+def corner_outputs(mod, par, fid, k, z, zb):
+    """What is recorded of one corner cosmology: a dict of arrays, <engine>_<quantity> and <quantity> for the background and the compiled parameters
+    (an exception becomes its class name as a string array; NaN and Inf as the reference returns them)."""
+    out = {}
+
+    def record(name, fn):
+        try:
+            out[name] = np.asarray(fn(), dtype='f8')
+        except Exception as exc:
+            out[name] = np.array(type(exc).__name__)
+
+    with warnings.catch_warnings(), np.errstate(all='ignore'):
+        warnings.simplefilter('ignore')
+        for eng in FUZZ_ENGINES:
+            try:
+                cosmo = mod.Cosmology(engine=eng, **par)
+                fo, ba = cosmo.get_fourier(), cosmo.get_background()
+            except Exception as exc:
+                out[eng + '_error'] = np.array(type(exc).__name__)
+                continue
+            record(eng + '_pkz', lambda: fo.pk_interpolator()(k, z))
+            record(eng + '_sigma8_z', lambda: fo.sigma8_z(z))
+            record(eng + '_growth_factor', lambda: ba.growth_factor(z))
+            record(eng + '_growth_rate', lambda: ba.growth_rate(z))
+            if eng != 'bbks':
+                record(eng + '_rs_drag', lambda: cosmo.get_thermodynamics().rs_drag)
+                record(eng + '_z_drag', lambda: cosmo.get_thermodynamics().z_drag)
+            if eng != 'eisenstein_hu_nowiggle_variants':
+                record(eng + '_rsigma8', lambda: cosmo._engine._rsigma8)
+                record(eng + '_A_s', lambda: cosmo._engine._A_s)
+        try:
+            cosmo = mod.Cosmology(engine='eisenstein_hu', **par)
+            ba = cosmo.get_background()
+        except Exception as exc:
+            out['error'] = np.array(type(exc).__name__)
+            return out
+        for name in ['efunc', 'comoving_radial_distance', 'angular_diameter_distance', 'luminosity_distance', 'time', 'Omega_m', 'Omega_de', 'rho_ncdm_tot']:
+            record(name, lambda: getattr(ba, name)(zb))
+        record('age', lambda: ba.age)
+        # the linear growth from its ODE (DefaultBackground; the analytic engines' own Background keeps the CPT92 form)
+        from cosmoprimo.cosmology import DefaultBackground
+        bd = DefaultBackground(cosmo._engine)
+        zg = np.array(CORNER_ZG)
+        record('growth_factor_ode', lambda: bd.growth_factor(zg))
+        record('growth_factor_ode_cb', lambda: bd.growth_factor(zg, mass='cb'))
+        record('growth_rate_ode', lambda: bd.growth_rate(zg))
+        for name in ['h', 'Omega_cdm', 'Omega_b', 'Omega_k', 'T_cmb', 'N_ur', 'w0_fld', 'wa_fld', 'n_s', 'alpha_s', 'beta_s', 'k_pivot', 'Omega_m', 'Omega_de']:
+            record('par_' + name, lambda: cosmo[name])
+        for name in ['m_ncdm', 'T_ncdm_over_cmb']:
+            record('par_' + name, lambda: np.asarray(cosmo[name], dtype='f8').ravel())
+        pk0 = out.get('eisenstein_hu_pkz')
+        if pk0 is not None and pk0.dtype.kind == 'f' and np.isfinite(pk0).all():
+            interp = cosmo.get_fourier().pk_interpolator().to_1d(z=0.)
+            for name in ['wallish2018', 'brieden2022']:
+                record(name, lambda: np.asarray(mod.PowerSpectrumBAOFilter(interp, engine=name, cosmo=cosmo, cosmo_fid=fid).pknow)[::8])
+    return out
+
+
+def gen_corners(cp):
+    """corner_params() x the four analytic engines and the background, as gen_fuzz records them: <case>_<engine>_<quantity>, <case>_<quantity>."""
+    k = np.geomspace(1e-4, 10., 12)
+    z = np.array([0., 0.8, 2.5])
+    zb = np.array(CORNER_ZB)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        fid = cp.Cosmology(engine='eisenstein_hu')
+    out = {}
+    for name, par in corner_params():
+        for key, value in corner_outputs(cp, par, fid, k, z, zb).items():
+            out[name + '_' + key] = value
+    save('corners', k=k, z=z, zb=zb, zg=np.array(CORNER_ZG), **out)
+
+
 # FFTLog configurations drawn at random: class, size (powers of two and not), range, tilt, folds, low-ringing, xy, padding mode, batch shape -- the
 # combinations the hand-picked G3 cases do not visit.  A configuration is a plain dict (tests rebuild the same object from it).
 FFTLOG_FUZZ_N = 60
@@ -1509,6 +1624,8 @@ def main():
         gen_bao_batch(cp)
     if 'fuzz' in which:
         gen_fuzz(cp)
+    if 'corners' in which:
+        gen_corners(cp)
     if 'fftlog_fuzz' in which:
         gen_fftlog_fuzz(cp)
     if 'fftlog_large' in which:
