@@ -1139,19 +1139,52 @@ class BaseCorrelationFunctionBAOFilter(dv.Copyable, metaclass=RegisteredCorrelat
         self.s = np.geomspace(self.xi_interpolator.extrap_smin, self.xi_interpolator.extrap_smax, ns)
 
     def set_xi(self, xi_interpolator, cosmo=None):
-        """Set the input correlation function (reference bao_filter.py:760-770): device rows (ncol, ns)."""
+        """Set the input correlation function (reference bao_filter.py:760-770): device rows (ncol, ns), one per input correlation function.  A 2D
+        interpolator gives (ns, nz) -> rows (nz, ns); a batch of cosmologies (batch, ns, nz) -> rows (batch nz, ns), cosmology-major; a 1D one
+        (ns,) + columns -> rows (ncol, ns)."""
         self._cosmo = cosmo
         self.xi_interpolator = xi_interpolator
         if isinstance(xi_interpolator, CorrelationFunctionInterpolator2D):
-            out = xi_interpolator._eval_device(self.s, xi_interpolator.z, grid=True, ignore_growth=True)   # (ns, nz)
+            out = xi_interpolator._eval_device(self.s, xi_interpolator.z, grid=True, ignore_growth=True)   # (batch..., ns, nz)
+            rows = out.transpose(-1, -2).reshape(-1, self.s.size)
         else:
             out = xi_interpolator._eval_device(self.s)                                                    # (ns,) + columns
+            rows = out.reshape(self.s.size, -1).T
         self.shape = tuple(out.shape)
-        self._xi_rows = out.reshape(self.s.size, -1).T.contiguous()
+        self._xi_rows = rows.contiguous()
+
+    def _batched_2d(self):
+        """The input is a 2D interpolator of a batch of cosmologies: (batch..., ns, nz)."""
+        return isinstance(self.xi_interpolator, CorrelationFunctionInterpolator2D) and len(self.shape) > 2
 
     def _finalize(self):
-        self.xi = self._xi_rows.cpu().numpy().T.reshape(self.shape)
-        self.xinow = self._xinow_rows.cpu().numpy().T.reshape(self.shape)
+        """The host copies are made when ``xi`` / ``xinow`` are first read (as ``pk`` / ``pknow`` of the power spectrum filters)."""
+        self._host = {}
+
+    def _to_host(self, name):
+        """Device rows -> array of the shape the input evaluates to: (ns,) + columns, (ns, nz), or (batch..., ns, nz)."""
+        if name not in self._host:
+            a = dv.to_host(getattr(self, '_{}_rows'.format(name)))
+            if self._batched_2d():
+                self._host[name] = np.swapaxes(a.reshape(self.shape[:-2] + (self.shape[-1], self.s.size)), -1, -2)
+            else:
+                self._host[name] = a.T.reshape(self.shape)
+        return self._host[name]
+
+    @property
+    def xi(self):
+        """Input correlation function at :attr:`s`."""
+        return self._to_host('xi')
+
+    @property
+    def xinow(self):
+        """Correlation function without BAO peak at :attr:`s`."""
+        return self._to_host('xinow')
+
+    @property
+    def xinow_rows(self):
+        """:attr:`xinow` as it sits in HBM: tensor (ncolumns, ns), one row per input correlation function."""
+        return self._xinow_rows
 
     def __call__(self, xi_interpolator, cosmo=None):
         self.set_xi(xi_interpolator, cosmo=cosmo)
@@ -1160,7 +1193,11 @@ class BaseCorrelationFunctionBAOFilter(dv.Copyable, metaclass=RegisteredCorrelat
         return self
 
     def smooth_xi_interpolator(self, **kwargs):
-        """Smooth (no-peak) correlation function interpolator (reference bao_filter.py:778-792)."""
+        """Smooth (no-peak) correlation function interpolator (reference bao_filter.py:778-792).  For a batch of cosmologies: the interpolator of the
+        batch, built on the device rows."""
+        if self._batched_2d():
+            xinow = self._xinow_rows.reshape(-1, self.shape[-1], self.s.size).transpose(-1, -2)       # (batch, ns, nz), on the device
+            return self.xi_interpolator.clone(s=self.s, xi=xinow, **kwargs)
         return self.xi_interpolator.clone(s=self.s, xi=self.xinow, **kwargs)
 
     def smooth_pk_interpolator(self, **kwargs):
@@ -1184,13 +1221,27 @@ class BaseCorrelationFunctionBAOFilter(dv.Copyable, metaclass=RegisteredCorrelat
     rs_drag_ratio = BasePowerSpectrumBAOFilter.rs_drag_ratio
     _scalar_rs_drag_ratio = BasePowerSpectrumBAOFilter._scalar_rs_drag_ratio
 
+    def _batch_size(self):
+        """Number of cosmologies whose correlation functions the input holds row by row (the batch size of ``cosmo``), None for one cosmology."""
+        nb = getattr(self._cosmo, 'batch_size', None) if self._cosmo is not None else None
+        if nb is None:
+            return None
+        nrows = self._xi_rows.shape[0]
+        if nrows % nb:
+            raise ValueError('the input holds {:d} correlation functions, the cosmology {:d} parameter sets'.format(nrows, nb))
+        return nb
+
+    def _columns_per_cosmology(self):
+        return self._xi_rows.shape[0] // self._batch_size()
+
 
 class Kirkby2013CorrelationFunctionBAOFilter(BaseCorrelationFunctionBAOFilter):
 
     """
     Cut the BAO peak and bridge it with a polynomial in 1/s fitted on either side (reference bao_filter.py:835-909).
     For fixed boxes the whole filter is ONE linear map of xi(s): it is built on the host (a weighted 5-parameter least-squares
-    projector on ~200 samples, blended with the identity) and applied to all columns on the device as a dense operator.
+    projector on ~200 samples, blended with the identity) and applied to all columns on the device as a dense operator.  A batch of cosmologies
+    (one rs_drag ratio each, rescaled boxes) runs the whole filter per row in one kernel instead (``cp_kirkby2013_rows``).
     """
     name = 'kirkby2013'
 
@@ -1229,11 +1280,33 @@ class Kirkby2013CorrelationFunctionBAOFilter(BaseCorrelationFunctionBAOFilter):
         return A
 
     def _compute(self):
-        rescale = self._scalar_rs_drag_ratio() if self.rescale_sbox else 1.
+        self._batch_size()      # (the cosmologies of a batch must divide the rows)
+        rescale = self.rs_drag_ratio() if self.rescale_sbox else 1.
+        if np.ndim(rescale):      # one ratio per cosmology: the kernel
+            self._xinow_rows = self._compute_rows(rescale)
+            return
         key = float(rescale)
         if getattr(self, '_op_key', None) != key:
             self._op, self._op_key = LinearOperator.dense(self._operator(key), device=self.device), key
         self._xinow_rows = self._op(self._xi_rows)
+
+    def _compute_rows(self, rescale):
+        """One rs_drag ratio per cosmology (a batch of cosmologies and rescaled boxes): the whole filter of every row in one kernel
+        (``cp_kirkby2013_rows``), the rows cosmology-major, the ratios read where they are (on the device for a batch)."""
+        torch = dv.torch()
+        rescale = dv.to_device(rescale, self.device).reshape(-1)
+        rows = self._xi_rows
+        nrows, ns = rows.shape
+        if nrows % rescale.numel():
+            raise ValueError('the input holds {:d} correlation functions, the cosmology {:d} parameter sets'.format(nrows, rescale.numel()))
+        index = np.flatnonzero(self.smask)
+        fit = (int(index[0]), int(index[-1]) + 1) if index.size else (0, 0)
+        knots, weights = (np.ascontiguousarray(a, dtype='f8') for a in self.window)
+        out = torch.empty_like(rows)
+        _lib.check(_lib.load().cp_kirkby2013_rows(rows.data_ptr(), out.data_ptr(), nrows, ns, dv.upload(self.s, self.device).data_ptr(), fit[0], fit[1],
+                                                  rescale.data_ptr(), nrows // rescale.numel(), _lib.as_double_p(knots), _lib.as_double_p(weights),
+                                                  self.device.index, dv.stream_of(self.device)))
+        return out
 
 
 def CorrelationFunctionBAOFilter(xi_interpolator, engine='kirkby2013', **kwargs):

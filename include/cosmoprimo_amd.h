@@ -626,6 +626,16 @@ int cp_spline_points(const double* d_xk, const double* d_y, const double* d_s, l
  * cp_dst_execute), else 0.  d_scale : optional (nrows) device, 2^e >= max |row| with e <= 1023 (1 for all-zero and non-finite rows), or NULL. */
 int cp_rows_screen(const double* d_x, long long nrows, long long n, int require_positive, unsigned char* d_ok, double* d_scale, int device, void* stream);
 
+/* ---- the kirkby2013 correlation-function BAO filter over rows of many cosmologies (csrc/cp_xi_filter.hip; reference bao_filter.py:835-909) ----
+ * d_xi, d_xinow : (nrows, ns) device (d_xinow may be d_xi); d_s : (ns) device separations; fit samples [fit_begin, fit_end), at least 5, fixed on the
+ * un-rescaled separations; d_rescale : device rs_drag ratios, one per cosmology: row r takes d_rescale[r / rows_per_cosmology] (so at least
+ * ceil(nrows / rows_per_cosmology) of them); knots8, weights8 : host, the 8 knots (positive, ascending) and weights of the fit's window.  Per row,
+ * rho its ratio: precision = interp(s / rho, knots, weights) on the fit samples, center = interp(s / rho, knots[2:6], 1 - weights[2:6]) (np.interp,
+ * 0 outside), the weighted least-squares fit of s^1 .. s^-3 on the fit samples, xinow = (1 - center) xi + center fit.  A NaN among the fit samples
+ * makes the row NaN, as in the reference.  Arguments are checked before any device call (CP_EINVAL). */
+int cp_kirkby2013_rows(const double* d_xi, double* d_xinow, long long nrows, int ns, const double* d_s, int fit_begin, int fit_end, const double* d_rescale,
+                       long long rows_per_cosmology, const double* knots8, const double* weights8, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
