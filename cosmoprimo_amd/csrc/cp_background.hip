@@ -27,6 +27,7 @@
 #include "../../include/cosmoprimo_amd.h"
 #include "cp_cosmo_common.h"
 #include "cp_error.h"
+#include "cp_internal.h"
 
 namespace {
 
@@ -686,11 +687,9 @@ __global__ __launch_bounds__(64) void ncdm_spline_kernel(const NcdmArgs A) {
 const double* cpcosmo::ncdm_knots_device(int device) { return device_ncdm_knots(device); }
 
 extern "C" int cp_background_init(int device) {
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_background_init: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_background_init: cannot select device %d", device);
     const bool ok = device_tables<NK_DIST>(device) && device_tables<NK_TIME>(device) && device_ncdm_knots(device);
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
     if (!ok) return cp::fail(CP_ENOMEM, "cp_background_init: cannot allocate the knot tables on device %d", device);
     return CP_OK;
 }
@@ -713,31 +712,20 @@ extern "C" int cp_growth_ode_tables(long long ncosmo, const cp_param* params, in
     if (mass != 0 && mass != 1) return cp::fail(CP_EINVAL, "cp_growth_ode_tables: mass must be 0 ('m') or 1 ('cb')");
     const int nsp = ncdm ? ncdm->nspecies : 0;
     if (nsp < 0 || (nsp > 0 && !ncdm->tab)) return cp::fail(CP_EINVAL, "cp_growth_ode_tables: bad massive-neutrino tables");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_growth_ode_tables: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_growth_ode_tables: cannot select device %d", device);
     GrowthArgs A;
     A.ncosmo = ncosmo;
-    for (int k = 0; k < CP_BG_NPARAMS; ++k) {
-        A.p[k].ptr = params[k].ptr;
-        A.p[k].value = params[k].value;
-    }
+    cpcosmo::copy_params(A.p, params, CP_BG_NPARAMS);
     A.second_is_omega_m = second_is_omega_m;
     A.mass = mass;
     A.nsp = nsp;
     A.ncdm_tab = nsp ? ncdm->tab : nullptr;
     A.ncdm_knots = nsp ? device_ncdm_knots(device) : nullptr;
     A.tab = d_tab;
-    int rc = CP_OK;
-    if (nsp && !A.ncdm_knots) {
-        rc = cp::fail(CP_ENOMEM, "cp_growth_ode_tables: cannot allocate the massive-neutrino knots on device %d", device);
-    } else {
-        hipLaunchKernelGGL(growth_ode_kernel, dim3((unsigned)((ncosmo + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), A);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = cp::fail(CP_EDEVICE, "cp_growth_ode_tables: launch failed: %s", hipGetErrorString(e));
-    }
-    if (prev >= 0) (void)hipSetDevice(prev);
-    return rc;
+    if (nsp && !A.ncdm_knots) return cp::fail(CP_ENOMEM, "cp_growth_ode_tables: cannot allocate the massive-neutrino knots on device %d", device);
+    hipLaunchKernelGGL(growth_ode_kernel, dim3((unsigned)((ncosmo + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), A);
+    return cp::launch_status("cp_growth_ode_tables");
 }
 
 extern "C" int cp_ncdm_knots(double* zc_out, int n) {
@@ -753,9 +741,8 @@ extern "C" int cp_ncdm_tables(long long ncosmo, int nspecies, cp_param h, cp_par
     if (nspecies > NCDM_MAX_SPECIES) return cp::fail(CP_EUNSUPPORTED, "cp_ncdm_tables: at most %d massive species", NCDM_MAX_SPECIES);
     if (nq < 1 || nq > NCDM_MAX_NQ) return cp::fail(CP_EINVAL, "cp_ncdm_tables: quadrature size must be in [1, %d]", NCDM_MAX_NQ);
     if (!m_ncdm || !T_ncdm_over_cmb || !nodes || !weights || !d_tab) return cp::fail(CP_EINVAL, "cp_ncdm_tables: null pointer");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_ncdm_tables: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_ncdm_tables: cannot select device %d", device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     NcdmArgs A;
     A.ncosmo = ncosmo;
@@ -763,27 +750,18 @@ extern "C" int cp_ncdm_tables(long long ncosmo, int nspecies, cp_param h, cp_par
     A.nq = nq;
     A.h.ptr = h.ptr; A.h.value = h.value;
     A.T_cmb.ptr = T_cmb.ptr; A.T_cmb.value = T_cmb.value;
-    for (int s = 0; s < nspecies; ++s) {
-        A.m[s].ptr = m_ncdm[s].ptr; A.m[s].value = m_ncdm[s].value;
-        A.T_over[s].ptr = T_ncdm_over_cmb[s].ptr; A.T_over[s].value = T_ncdm_over_cmb[s].value;
-    }
+    cpcosmo::copy_params(A.m, m_ncdm, nspecies);
+    cpcosmo::copy_params(A.T_over, T_ncdm_over_cmb, nspecies);
     A.knots = device_ncdm_knots(device);
     A.tab = d_tab;
-    int rc = CP_OK;
-    if (!A.knots) {
-        rc = cp::fail(CP_ENOMEM, "cp_ncdm_tables: cannot allocate the knots on device %d", device);
-    } else {
-        NcdmRule R;
-        for (int q = 0; q < nq; ++q) R.v[q] = nodes[q], R.v[nq + q] = weights[q];
-        for (int q = 2 * nq; q < 2 * NCDM_MAX_NQ; ++q) R.v[q] = 0.;
-        const long long n1 = ncosmo * nspecies * CP_NCDM_NKNOTS, n2 = ncosmo * nspecies * 2;
-        hipLaunchKernelGGL(ncdm_momenta_kernel, dim3((unsigned)((n1 + 127) / 128)), dim3(128), 0, st, A, R);
-        hipLaunchKernelGGL(ncdm_spline_kernel, dim3((unsigned)((n2 + 63) / 64)), dim3(64), 0, st, A);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = cp::fail(CP_EDEVICE, "cp_ncdm_tables: launch failed: %s", hipGetErrorString(e));
-    }
-    if (prev >= 0) (void)hipSetDevice(prev);
-    return rc;
+    if (!A.knots) return cp::fail(CP_ENOMEM, "cp_ncdm_tables: cannot allocate the knots on device %d", device);
+    NcdmRule R;
+    for (int q = 0; q < nq; ++q) R.v[q] = nodes[q], R.v[nq + q] = weights[q];
+    for (int q = 2 * nq; q < 2 * NCDM_MAX_NQ; ++q) R.v[q] = 0.;
+    const long long n1 = ncosmo * nspecies * CP_NCDM_NKNOTS, n2 = ncosmo * nspecies * 2;
+    hipLaunchKernelGGL(ncdm_momenta_kernel, dim3((unsigned)((n1 + 127) / 128)), dim3(128), 0, st, A, R);
+    hipLaunchKernelGGL(ncdm_spline_kernel, dim3((unsigned)((n2 + 63) / 64)), dim3(64), 0, st, A);
+    return cp::launch_status("cp_ncdm_tables");
 }
 
 extern "C" int cp_background_knots(double* zc_out, int n) {
@@ -823,16 +801,12 @@ extern "C" int cp_distance_from_radial(const double* d_chi, const double* d_z, l
         return cp::fail(CP_EINVAL, "cp_distance_from_radial: kind %d is not a derived distance", kind);
     if (n == 0) return CP_OK;
     if (!d_chi || !d_z || !d_out) return cp::fail(CP_EINVAL, "cp_distance_from_radial: null pointer");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_distance_from_radial: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_distance_from_radial: cannot select device %d", device);
     const long long blocks = (n + 255) / 256;
     hipLaunchKernelGGL(distance_from_radial_kernel, dim3((unsigned)(blocks < 256 * 16 ? blocks : 256 * 16)), dim3(256), 0, static_cast<hipStream_t>(stream), d_chi, d_z,
                        n, K, kind, d_out);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_distance_from_radial: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_distance_from_radial");
 }
 
 extern "C" int cp_background_distance(long long ncosmo, long long nz, const cp_param* params, int second_is_omega_m, const double* d_z,
@@ -853,22 +827,15 @@ extern "C" int cp_background_eval(long long ncosmo, long long nz, const cp_param
         if (kind < 0 || base > CP_BG_KIND_LAST || ((kind & CP_BG_AS_FRACTION) && (base < CP_BG_RHO_G || (base >= CP_BG_T_CMB_Z && base <= CP_BG_AGE) || base >= CP_BG_RS)))
             return cp::fail(CP_EINVAL, "cp_background_distance: unknown kind %d", kind);
     }
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_background_distance: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_background_distance: cannot select device %d", device);
     const bool is_time = kind == CP_BG_TIME || kind == CP_BG_AGE;
     const void* tab = is_time ? static_cast<const void*>(device_tables<NK_TIME>(device)) : static_cast<const void*>(device_tables<NK_DIST>(device));
-    if (!tab) {
-        if (prev >= 0) (void)hipSetDevice(prev);
-        return cp::fail(CP_ENOMEM, "cp_background_distance: cannot allocate the knot tables on device %d", device);
-    }
+    if (!tab) return cp::fail(CP_ENOMEM, "cp_background_distance: cannot allocate the knot tables on device %d", device);
     Args A;
     A.ncosmo = ncosmo;
     A.nz = nz;
-    for (int k = 0; k < CP_BG_NPARAMS; ++k) {
-        A.p[k].ptr = params[k].ptr;
-        A.p[k].value = params[k].value;
-    }
+    cpcosmo::copy_params(A.p, params, CP_BG_NPARAMS);
     A.second_is_omega_m = second_is_omega_m;
     A.z = d_z;
     A.z_shared = z_shared;
@@ -879,10 +846,7 @@ extern "C" int cp_background_eval(long long ncosmo, long long nz, const cp_param
     A.species = nsp ? ncdm->species : -1;
     A.ncdm_tab = nsp ? ncdm->tab : nullptr;
     A.ncdm_knots = nsp ? device_ncdm_knots(device) : nullptr;
-    if (nsp && !A.ncdm_knots) {
-        if (prev >= 0) (void)hipSetDevice(prev);
-        return cp::fail(CP_ENOMEM, "cp_background_eval: cannot allocate the massive-neutrino knots on device %d", device);
-    }
+    if (nsp && !A.ncdm_knots) return cp::fail(CP_ENOMEM, "cp_background_eval: cannot allocate the massive-neutrino knots on device %d", device);
     const long long nsamp = ncosmo * nz;
     const int block = 256;
     const long long grid = (nsamp + block - 1) / block;
@@ -891,10 +855,7 @@ extern "C" int cp_background_eval(long long ncosmo, long long nz, const cp_param
     else if (is_time) hipLaunchKernelGGL((bg_kernel<NK_TIME, true, false>), dim3((unsigned)grid), dim3(block), 0, static_cast<hipStream_t>(stream), A);
     else if (A.nsp) hipLaunchKernelGGL((bg_kernel<NK_DIST, false, true>), dim3((unsigned)grid), dim3(block), 0, static_cast<hipStream_t>(stream), A);
     else hipLaunchKernelGGL((bg_kernel<NK_DIST, false, false>), dim3((unsigned)grid), dim3(block), 0, static_cast<hipStream_t>(stream), A);
-    hipError_t e = hipGetLastError();
-    if (prev >= 0) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_background_distance: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_background_distance");
 }
 
 // ---- derived parameters of a batch of cosmologies (BaseCosmoParams.__getitem__ -> _get_derived, cosmology.py:331-415), one launch -------------------
@@ -951,19 +912,12 @@ extern "C" int cp_derived_parameters(long long ncosmo, const cp_param* params, d
     if (ncosmo < 0) return cp::fail(CP_EINVAL, "cp_derived_parameters: negative size");
     if (ncosmo == 0) return CP_OK;
     if (!params || !d_out) return cp::fail(CP_EINVAL, "cp_derived_parameters: null pointer");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_derived_parameters: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_derived_parameters: cannot select device %d", device);
     DerivedArgs A;
     A.ncosmo = ncosmo;
-    for (int k = 0; k < CP_BG_NPARAMS; ++k) {
-        A.p[k].ptr = params[k].ptr;
-        A.p[k].value = params[k].value;
-    }
+    cpcosmo::copy_params(A.p, params, CP_BG_NPARAMS);
     A.out = d_out;
     hipLaunchKernelGGL(derived_parameters_kernel, dim3((unsigned)((ncosmo + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), A);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_derived_parameters: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_derived_parameters");
 }

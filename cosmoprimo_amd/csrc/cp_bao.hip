@@ -24,18 +24,6 @@
 
 namespace {
 
-struct DeviceScope {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceScope(int device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != device) ok = hipSetDevice(device) == hipSuccess;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 __global__ __launch_bounds__(256) void wallish_finish_kernel(const double* __restrict__ pk, const double* __restrict__ a, const double* __restrict__ b,
                                                              const double* __restrict__ tophat, double* __restrict__ out, long long total, int n) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -185,12 +173,6 @@ unsigned grid_tiles(long long nb, int n) {
     return (unsigned)(items < 256 * 16 ? (items < 1 ? 1 : items) : 256 * 16);
 }
 
-int finish(const char* what, int status_device_ok) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "%s: launch failed: %s", what, hipGetErrorString(e));
-    return CP_OK;
-}
-
 
 // ---- wallish2018: second derivatives at the knots and the box, one kernel ---------------------------------------------------------------------
 // The wave-level solve, the two arg-max searches and the removal of the box are device functions of cp_wallish_dd.h (shared with the forward
@@ -282,11 +264,11 @@ extern "C" int cp_wallish_finish(const double* d_pk, const double* d_a, const do
     if (nrows < 0 || n < 1) return cp::fail(CP_EINVAL, "cp_wallish_finish: bad sizes");
     if (nrows == 0) return CP_OK;
     if (!d_pk || !d_a || !d_tophat || !d_out) return cp::fail(CP_EINVAL, "cp_wallish_finish: null pointer");
-    DeviceScope scope(device);
-    if (!scope.ok) return cp::fail(CP_EDEVICE, "cp_wallish_finish: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_wallish_finish: cannot select device %d", device);
     hipLaunchKernelGGL(wallish_finish_kernel, dim3(grid_for(nrows * n)), dim3(256), 0, static_cast<hipStream_t>(stream), d_pk, d_a, d_b, d_tophat, d_out,
                        nrows * n, n);
-    return finish("cp_wallish_finish", 0);
+    return cp::launch_status("cp_wallish_finish");
 }
 
 extern "C" int cp_brieden_ratio(const double* d_rows, const double* d_now, const double* d_g0, const double* d_correction, const double* d_ratio_fid,
@@ -294,11 +276,11 @@ extern "C" int cp_brieden_ratio(const double* d_rows, const double* d_now, const
     if (nb < 0 || n < 1) return cp::fail(CP_EINVAL, "cp_brieden_ratio: bad sizes");
     if (nb == 0) return CP_OK;
     if (!d_rows || !d_now || !d_g0 || !d_correction || !d_ratio_fid || !d_pknow || !d_ratio) return cp::fail(CP_EINVAL, "cp_brieden_ratio: null pointer");
-    DeviceScope scope(device);
-    if (!scope.ok) return cp::fail(CP_EDEVICE, "cp_brieden_ratio: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_brieden_ratio: cannot select device %d", device);
     hipLaunchKernelGGL(brieden_ratio_kernel, dim3(grid_for(nb * n)), dim3(256), 0, static_cast<hipStream_t>(stream), d_rows, d_now, d_g0, d_correction,
                        d_ratio_fid, d_pknow, d_ratio, nb, n);
-    return finish("cp_brieden_ratio", 0);
+    return cp::launch_status("cp_brieden_ratio");
 }
 
 extern "C" int cp_brieden_knots(const double* d_envelope, const double* d_pknow, const double* d_ratio_now_fid, const double* d_k_fid,
@@ -307,11 +289,11 @@ extern "C" int cp_brieden_knots(const double* d_envelope, const double* d_pknow,
     if (nb < 0 || n < 2) return cp::fail(CP_EINVAL, "cp_brieden_knots: bad sizes");
     if (nb == 0) return CP_OK;
     if (!d_envelope || !d_pknow || !d_ratio_now_fid || !d_k_fid || !d_rescale || !d_xk || !d_yk) return cp::fail(CP_EINVAL, "cp_brieden_knots: null pointer");
-    DeviceScope scope(device);
-    if (!scope.ok) return cp::fail(CP_EDEVICE, "cp_brieden_knots: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_brieden_knots: cannot select device %d", device);
     hipLaunchKernelGGL(brieden_knots_kernel, dim3(grid_tiles(nb, n)), dim3(256), 0, static_cast<hipStream_t>(stream), d_envelope, d_pknow,
                        d_ratio_now_fid, d_k_fid, d_rescale, extrap_kmin, extrap_kmax, d_xk, d_yk, nb, n);
-    return finish("cp_brieden_knots", 0);
+    return cp::launch_status("cp_brieden_knots");
 }
 
 // ---- brieden2022: the re-sampling of the smooth spectrum (bao_filter.py:500-509) as ONE kernel, a wave per cosmology --------------------------
@@ -669,7 +651,7 @@ int launch_resample(ResampleArgs& A, const char* who, int device, void* stream) 
         default: go(std::integral_constant<int, 8>{}); break;
     }
     if (st != CP_OK) return cp::fail(st, "%s: cannot configure the kernel's LDS", who);
-    return finish(who, 0);
+    return cp::launch_status(who);
 }
 
 bool resample_sizes_ok(int n) { return (n + 63) / 64 >= RS_SMIN && (n + 63) / 64 <= RS_SMAX; }
@@ -684,8 +666,8 @@ extern "C" int cp_brieden_resample(const double* d_envelope, const double* d_pkn
         return cp::fail(CP_EUNSUPPORTED, "cp_brieden_resample: %d samples per cosmology (129 ... 512): cp_brieden_knots, cp_spline_columns, cp_brieden_finish", n);
     if (nb == 0) return CP_OK;
     if (!d_envelope || !d_pknow || !d_ratio_now_fid || !d_k_fid || !d_log_k_fid || !d_rescale || !d_pk || !d_out) return cp::fail(CP_EINVAL, "cp_brieden_resample: null pointer");
-    DeviceScope scope(device);
-    if (!scope.ok) return cp::fail(CP_EDEVICE, "cp_brieden_resample: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_brieden_resample: cannot select device %d", device);
     ResampleArgs A = {};
     A.envelope = d_envelope; A.pknow = d_pknow; A.ratio_now_fid = d_ratio_now_fid; A.k_fid = d_k_fid; A.log_k_fid = d_log_k_fid; A.rescale = d_rescale;
     A.kmin = extrap_kmin; A.kmax = extrap_kmax; A.pk = d_pk; A.out = d_out; A.nb = nb; A.n = n; A.nk = nk; A.first = first;
@@ -702,8 +684,8 @@ extern "C" int cp_brieden_smooth(const double* d_pk_peaks, const double* d_now, 
     if (!d_pk_peaks || !d_now || !d_g0 || !d_correction || !d_ratio_fid || !d_peaks || !d_operator || !d_ratio_now_fid || !d_k_fid || !d_log_k_fid || !d_rescale ||
         !d_pk || !d_out)
         return cp::fail(CP_EINVAL, "cp_brieden_smooth: null pointer");
-    DeviceScope scope(device);
-    if (!scope.ok) return cp::fail(CP_EDEVICE, "cp_brieden_smooth: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_brieden_smooth: cannot select device %d", device);
     ResampleArgs A = {};
     A.envelope = d_pk_peaks; A.pknow = d_now; A.ratio_now_fid = d_ratio_now_fid; A.k_fid = d_k_fid; A.log_k_fid = d_log_k_fid; A.rescale = d_rescale;
     A.kmin = extrap_kmin; A.kmax = extrap_kmax; A.pk = d_pk; A.out = d_out; A.nb = nb; A.n = n; A.nk = nk; A.first = first;
@@ -716,11 +698,11 @@ extern "C" int cp_brieden_finish(const double* d_pk, const double* d_resampled, 
     if (nb < 0 || nk < 1 || n < 0 || first < 0 || first + n > nk) return cp::fail(CP_EINVAL, "cp_brieden_finish: bad sizes");
     if (nb == 0) return CP_OK;
     if (!d_pk || !d_resampled || !d_out) return cp::fail(CP_EINVAL, "cp_brieden_finish: null pointer");
-    DeviceScope scope(device);
-    if (!scope.ok) return cp::fail(CP_EDEVICE, "cp_brieden_finish: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_brieden_finish: cannot select device %d", device);
     hipLaunchKernelGGL(brieden_finish_kernel, dim3(grid_tiles(nb, n > 0 ? n : 1)), dim3(256), 0, static_cast<hipStream_t>(stream), d_pk, d_resampled, d_out, nb, nk,
                        first, n);
-    return finish("cp_brieden_finish", 0);
+    return cp::launch_status("cp_brieden_finish");
 }
 
 extern "C" int cp_wallish_dd_box(const double* d_y, long long nrows, int n, int margin_first, int margin_second, int offset_first, int offset_second,
@@ -730,8 +712,8 @@ extern "C" int cp_wallish_dd_box(const double* d_y, long long nrows, int n, int 
     if (nrows == 0) return CP_OK;
     if (!d_y || !d_box) return cp::fail(CP_EINVAL, "cp_wallish_dd_box: null device pointer");
     if ((nrows + 3) / 4 > 2147483647LL) return cp::fail(CP_EUNSUPPORTED, "cp_wallish_dd_box: too many sequences for one launch");
-    DeviceScope scope(device);
-    if (!scope.ok) return cp::fail(CP_EDEVICE, "cp_wallish_dd_box: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_wallish_dd_box: cannot select device %d", device);
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu <= 0) ncu = 256;
     const size_t lds = ((size_t)4 * (n + 64) + 2 * DD_NTAB) * sizeof(double);
@@ -747,9 +729,7 @@ extern "C" int cp_wallish_dd_box(const double* d_y, long long nrows, int n, int 
     if (n == 1024) CP_DD_LAUNCH(16);
     else CP_DD_LAUNCH(32);
 #undef CP_DD_LAUNCH
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_wallish_dd_box: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_wallish_dd_box");
 }
 
 // ---- wallish2018: the clamped spline through the spliced knots, evaluated on the filter's wavenumbers, and the wiggle damping -- one kernel ----
@@ -957,7 +937,7 @@ struct cp_splice_plan {
 extern "C" int cp_splice_plan_destroy(cp_splice_plan* p) {
     if (!p) return CP_OK;
     {
-        DeviceScope scope(p->device);
+        cp::DeviceScope scope(p->device);
         if (p->d_tab) (void)hipFree(p->d_tab);
         if (p->d_qj) (void)hipFree(p->d_qj);
         if (p->d_qcol) (void)hipFree(p->d_qcol);
@@ -1112,8 +1092,8 @@ extern "C" int cp_splice_plan_create(cp_splice_plan** out, int nknots, const dou
     p->T.n = n; p->T.nq = nq; p->T.S = S; p->T.halo = halo;
     p->T.ntab_left = ntab_left; p->T.uniform_end = uniform_end;
     p->T.h0 = h0; p->T.rh0 = 1. / h0; p->T.inv0 = inv0;
-    DeviceScope scope(device);
-    bool ok = scope.ok && hipMalloc(&p->d_tab, tab.size() * sizeof(double)) == hipSuccess && hipMalloc(&p->d_qj, qj.size() * sizeof(int)) == hipSuccess &&
+    cp::DeviceScope scope(device);
+    bool ok = scope.ok() && hipMalloc(&p->d_tab, tab.size() * sizeof(double)) == hipSuccess && hipMalloc(&p->d_qj, qj.size() * sizeof(int)) == hipSuccess &&
               hipMalloc(&p->d_qcol, qcol.size() * sizeof(int)) == hipSuccess && hipMalloc(&p->d_qw, qw.size() * sizeof(double)) == hipSuccess;
     ok = ok && hipMemcpy(p->d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(p->d_qj, qj.data(), qj.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
@@ -1179,8 +1159,8 @@ extern "C" int cp_splice_apply(const cp_splice_plan* p, const double* d_src0, in
     }
     if (d_tophat && p->T.nq != n0) return cp::fail(CP_EINVAL, "cp_splice_apply: the damping step needs one query per column of the first array");
     if ((nrows + 3) / 4 > 2147483647LL) return cp::fail(CP_EUNSUPPORTED, "cp_splice_apply: too many rows for one launch");
-    DeviceScope scope(p->device);
-    if (!scope.ok) return cp::fail(CP_EDEVICE, "cp_splice_apply: cannot select device %d", p->device);
+    cp::DeviceScope scope(p->device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_splice_apply: cannot select device %d", p->device);
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess || ncu <= 0) ncu = 256;
     const long long blocks = (nrows + 3) / 4;
@@ -1188,9 +1168,8 @@ extern "C" int cp_splice_apply(const cp_splice_plan* p, const double* d_src0, in
         cpsu::Args U;
         U.T = p->U;
         U.src0 = d_src0; U.src1 = d_src1 ? d_src1 : d_src0; U.n0 = n0; U.n1 = d_src1 ? n1 : n0; U.nrows = nrows; U.tophat = d_tophat; U.out = d_out;
-        const hipError_t e = cpsu::launch(U, (unsigned)(blocks < ncu ? blocks : ncu), p->uniform_lds_bytes, static_cast<hipStream_t>(stream));
-        if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_splice_apply: launch failed: %s", hipGetErrorString(e));
-        return CP_OK;
+        return cp::launch_status("cp_splice_apply",
+                                 cpsu::launch(U, (unsigned)(blocks < ncu ? blocks : ncu), p->uniform_lds_bytes, static_cast<hipStream_t>(stream)));
     }
     SpliceArgs A;
     A.T = p->T;
@@ -1199,7 +1178,5 @@ extern "C" int cp_splice_apply(const cp_splice_plan* p, const double* d_src0, in
     const long long per_cu = p->lds_bytes ? (160 * 1024) / (long long)p->lds_bytes : 1;
     const long long resident = (long long)ncu * (per_cu < 1 ? 1 : per_cu);
     hipLaunchKernelGGL(splice_kernel, dim3((unsigned)(blocks < resident ? blocks : resident)), dim3(256), p->lds_bytes, static_cast<hipStream_t>(stream), A);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_splice_apply: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_splice_apply");
 }

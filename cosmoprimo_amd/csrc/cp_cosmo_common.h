@@ -29,6 +29,11 @@ struct Param {
     double value;       // broadcast value
 };
 
+// the parameters of an entry point (cp_param of the C ABI) as the kernels take them
+inline void copy_params(Param* dst, const cp_param* src, int n) {
+    for (int i = 0; i < n; ++i) dst[i] = Param{src[i].ptr, src[i].value};
+}
+
 struct Cosmo {
     double h, Omega_cdm, Omega_b, Omega_k, T_cmb, N_ur, w0, wa;  // inputs
     double Omega_g, Omega_ur, Omega_de;                            // derived, cosmology.py:355-383

@@ -577,14 +577,11 @@ struct cp_dst_plan {
 
 extern "C" int cp_dst_plan_destroy(cp_dst_plan* p) {
     if (!p) return CP_OK;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != p->device) (void)hipSetDevice(p->device);
+    cp::DeviceScope scope(p->device);
     if (p->d_tw) (void)hipFree(p->d_tw);
     if (p->d_rot) (void)hipFree(p->d_rot);
     if (p->d_kx) (void)hipFree(p->d_kx);
     if (p->d_ln_kx) (void)hipFree(p->d_ln_kx);
-    if (prev >= 0 && prev != p->device) (void)hipSetDevice(prev);
     delete p;
     return CP_OK;
 }
@@ -601,9 +598,8 @@ extern "C" int cp_dst_plan_create(cp_dst_plan** out, int n, const double* kx, in
     cp_dst_plan* p = new (std::nothrow) cp_dst_plan();
     if (!p) return cp::fail(CP_ENOMEM, "cp_dst_plan_create: host allocation failed");
     p->n = n; p->device = device; p->d_tw = nullptr; p->d_rot = nullptr; p->d_kx = nullptr; p->d_ln_kx = nullptr;
-    int prev = -1, status = CP_OK;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) status = cp::fail(CP_EDEVICE, "cp_dst_plan_create: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    int status = scope.ok() ? CP_OK : cp::fail(CP_EDEVICE, "cp_dst_plan_create: cannot select device %d", device);
     if (status == CP_OK && (hipMalloc(&p->d_tw, tw.size() * sizeof(cplx)) != hipSuccess || hipMalloc(&p->d_rot, n * sizeof(cplx)) != hipSuccess ||
                             (kx && (hipMalloc(&p->d_kx, n * sizeof(double)) != hipSuccess || hipMalloc(&p->d_ln_kx, 8 * (size_t)n * sizeof(double)) != hipSuccess))))
         status = cp::fail(CP_ENOMEM, "cp_dst_plan_create: device allocation failed");
@@ -615,7 +611,6 @@ extern "C" int cp_dst_plan_create(cp_dst_plan** out, int n, const double* kx, in
         hipLaunchKernelGGL(dst_log_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, p->d_kx, p->d_ln_kx, n);
         if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) status = cp::fail(CP_EDEVICE, "cp_dst_plan_create: cannot tabulate log k");
     }
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
     if (status != CP_OK) {
         cp_dst_plan_destroy(p);
         return status;
@@ -632,9 +627,8 @@ extern "C" int cp_dst_execute(const cp_dst_plan* p, const double* d_in, double* 
     if (nrows == 0) return CP_OK;
     if (!d_in || !d_out) return cp::fail(CP_EINVAL, "cp_dst_execute: null device pointer");
     if (fused && !p->d_kx) return cp::fail(CP_EINVAL, "cp_dst_execute: the fused log / exp maps need the abscissa given at plan creation");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != p->device && hipSetDevice(p->device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_dst_execute: cannot select device %d", p->device);
+    cp::DeviceScope scope(p->device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_dst_execute: cannot select device %d", p->device);
     Args A;
     A.in = d_in; A.out = d_out; A.nrows = nrows; A.tw = p->d_tw; A.rot = p->d_rot; A.kx = p->d_kx; A.ikx = p->d_ln_kx ? p->d_ln_kx + 3 * (size_t)p->n : nullptr; A.fused = fused; A.split = (flags & CP_DST_SPLIT) != 0;
     const long long npairs = (nrows + 1) / 2;
@@ -643,10 +637,7 @@ extern "C" int cp_dst_execute(const cp_dst_plan* p, const double* d_in, double* 
     if (p->n == 256) launch<256>(inverse != 0, A, grid, s);
     else if (p->n == 1024) launch<1024>(inverse != 0, A, grid, s);
     else launch<4096>(inverse != 0, A, grid, s);
-    hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != p->device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_dst_execute: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_dst_execute");
 }
 
 namespace {
@@ -698,15 +689,14 @@ static int dst_forward_analytic(const cp_dst_plan* p, int engine, long long ncos
     if (st != CP_OK) return st;
     const int nsp = ncdm ? ncdm->nspecies : 0;
     if (nsp < 0 || (nsp > 0 && !ncdm->tab)) return cp::fail(CP_EINVAL, "cp_dst_forward_analytic: bad massive-neutrino tables");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != p->device && hipSetDevice(p->device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_dst_forward_analytic: cannot select device %d", p->device);
+    cp::DeviceScope scope(p->device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_dst_forward_analytic: cannot select device %d", p->device);
     GenArgs G{};
     G.dst.in = nullptr; G.dst.out = d_out; G.dst.nrows = ncosmo; G.dst.tw = p->d_tw; G.dst.rot = p->d_rot; G.dst.kx = nullptr; G.dst.ikx = nullptr; G.dst.fused = 0;
     G.dst.split = (flags & CP_DST_SPLIT) != 0;
     G.ncosmo = ncosmo;
-    for (int i = 0; i < CP_BG_NPARAMS; ++i) G.bg[i] = cpcosmo::Param{bg_params[i].ptr, bg_params[i].value};
-    for (int i = 0; i < CP_PK_NPARAMS; ++i) G.pw[i] = cpcosmo::Param{pk_params[i].ptr, pk_params[i].value};
+    cpcosmo::copy_params(G.bg, bg_params, CP_BG_NPARAMS);
+    cpcosmo::copy_params(G.pw, pk_params, CP_PK_NPARAMS);
     G.second_is_omega_m = second_is_omega_m;
     G.ncdm_tab = nsp ? ncdm->tab : nullptr;
     G.nsp = nsp;
@@ -724,10 +714,7 @@ static int dst_forward_analytic(const cp_dst_plan* p, int engine, long long ncos
     if (engine == CP_ENGINE_EH) launch_generate<CP_ENGINE_EH>(G, grid, s);
     else if (engine == CP_ENGINE_EH_NOWIGGLE) launch_generate<CP_ENGINE_EH_NOWIGGLE>(G, grid, s);
     else launch_generate<CP_ENGINE_BBKS>(G, grid, s);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != p->device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_dst_forward_analytic: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_dst_forward_analytic");
 }
 
 
@@ -751,9 +738,8 @@ extern "C" int cp_wallish_tail(const cp_dst_plan* p, const cp_splice_plan* splic
                         U.src_u, U.nq);
     if (nrows == 0) return CP_OK;
     if (!d_coef || !d_pk || !d_box || !d_out) return cp::fail(CP_EINVAL, "cp_wallish_tail: null device pointer");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != p->device && hipSetDevice(p->device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_wallish_tail: cannot select device %d", p->device);
+    cp::DeviceScope scope(p->device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_wallish_tail: cannot select device %d", p->device);
     TailArgs G{};
     G.nrows = nrows; G.coef = d_coef; G.tw = p->d_tw; G.rot = p->d_rot; G.ikx = p->d_ln_kx + 3 * (size_t)p->n;
     G.U = U;
@@ -767,10 +753,7 @@ extern "C" int cp_wallish_tail(const cp_dst_plan* p, const cp_splice_plan* splic
     constexpr int lds = (4096 + Plan<4096, 16>::TW_TOTAL - 4096) * (int)sizeof(cplx) + 2 * cpdd::DD_NTAB * (int)sizeof(double);
     (void)cp::allow_full_lds<&wallish_tail_kernel<49>>();
     hipLaunchKernelGGL(wallish_tail_kernel<49>, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), G);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != p->device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_wallish_tail: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_wallish_tail");
 }
 
 
@@ -808,9 +791,8 @@ extern "C" int cp_wallish_full(const cp_dst_plan* p, const cp_splice_plan* splic
     if (st != CP_OK) return st;
     const int nsp = ncdm ? ncdm->nspecies : 0;
     if (nsp < 0 || (nsp > 0 && !ncdm->tab)) return cp::fail(CP_EINVAL, "cp_wallish_full: bad massive-neutrino tables");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != p->device && hipSetDevice(p->device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_wallish_full: cannot select device %d", p->device);
+    cp::DeviceScope scope(p->device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_wallish_full: cannot select device %d", p->device);
     FullArgs F{};
     TailArgs& G = F.tail;
     G.nrows = ncosmo; G.coef = d_coef; G.tw = p->d_tw; G.rot = p->d_rot; G.ikx = p->d_ln_kx + 3 * (size_t)p->n;
@@ -820,8 +802,8 @@ extern "C" int cp_wallish_full(const cp_dst_plan* p, const cp_splice_plan* splic
     GenArgs& E = F.gen;
     E.dst.in = nullptr; E.dst.out = nullptr; E.dst.nrows = ncosmo; E.dst.tw = p->d_tw; E.dst.rot = p->d_rot; E.dst.kx = nullptr; E.dst.ikx = nullptr; E.dst.fused = 0; E.dst.split = 1;
     E.ncosmo = ncosmo;
-    for (int i = 0; i < CP_BG_NPARAMS; ++i) E.bg[i] = cpcosmo::Param{bg_params[i].ptr, bg_params[i].value};
-    for (int i = 0; i < CP_PK_NPARAMS; ++i) E.pw[i] = cpcosmo::Param{pk_params[i].ptr, pk_params[i].value};
+    cpcosmo::copy_params(E.bg, bg_params, CP_BG_NPARAMS);
+    cpcosmo::copy_params(E.pw, pk_params, CP_PK_NPARAMS);
     E.second_is_omega_m = second_is_omega_m;
     E.ncdm_tab = nsp ? ncdm->tab : nullptr;
     E.nsp = nsp;
@@ -839,8 +821,5 @@ extern "C" int cp_wallish_full(const cp_dst_plan* p, const cp_splice_plan* splic
     if (engine == CP_ENGINE_EH) launch_full<CP_ENGINE_EH>(F, grid, lds, s);
     else if (engine == CP_ENGINE_EH_NOWIGGLE) launch_full<CP_ENGINE_EH_NOWIGGLE>(F, grid, lds, s);
     else launch_full<CP_ENGINE_BBKS>(F, grid, lds, s);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != p->device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_wallish_full: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_wallish_full");
 }

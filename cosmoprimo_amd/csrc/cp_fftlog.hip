@@ -25,18 +25,6 @@ bool find_launcher(int npad, Launcher* out) {
            find_launcher_g4(npad, out);
 }
 
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 }  // namespace
 
 struct cp_fftlog_plan {
@@ -98,8 +86,8 @@ extern "C" int cp_fftlog_plan_create(cp_fftlog_plan** out, int n, int npad, int 
         p->d_pre = p->d_post = nullptr;
         p->d_u = p->d_tw = nullptr;
         p->large = nullptr;
-        DeviceGuard guard(device);
-        int st = guard.ok ? cp_fftlog_large_create(&p->large, n, npad, nker, pre, post, u_re_im, device)
+        cp::DeviceScope scope(device);
+        int st = scope.ok() ? cp_fftlog_large_create(&p->large, n, npad, nker, pre, post, u_re_im, device)
                           : cp::fail(CP_EDEVICE, "cp_fftlog_plan_create: cannot select device %d", device);
         if (st != CP_OK) {
             delete p;
@@ -125,9 +113,9 @@ extern "C" int cp_fftlog_plan_create(cp_fftlog_plan** out, int n, int npad, int 
     p->d_pre = p->d_post = nullptr;
     p->d_u = p->d_tw = nullptr;
     {
-        DeviceGuard guard(device);
+        cp::DeviceScope scope(device);
         std::vector<cplx> tw, u((size_t)nker * npad);
-        if (!guard.ok) {
+        if (!scope.ok()) {
             status = cp::fail(CP_EDEVICE, "cp_fftlog_plan_create: cannot select device %d", device);
             goto done;
         }
@@ -169,7 +157,7 @@ done:
 extern "C" int cp_fftlog_plan_destroy(cp_fftlog_plan* p) {
     if (!p) return CP_OK;
     {
-        DeviceGuard guard(p->device);
+        cp::DeviceScope scope(p->device);
         if (p->d_pre) (void)hipFree(p->d_pre);
         if (p->d_post) (void)hipFree(p->d_post);
         if (p->d_u) (void)hipFree(p->d_u);
@@ -209,8 +197,8 @@ static int execute_impl(const cp_fftlog_plan* p, const double* d_in, double* d_o
     if (extrap_left < CP_EXTRAP_CONSTANT || extrap_left > CP_EXTRAP_LOGLOG || extrap_right < CP_EXTRAP_CONSTANT || extrap_right > CP_EXTRAP_LOGLOG)
         return cp::fail(CP_EINVAL, "cp_fftlog_execute: unknown extrapolation mode (%d, %d)", extrap_left, extrap_right);
     if (p->large) {
-        DeviceGuard guard(p->device);
-        if (!guard.ok) return cp::fail(CP_EDEVICE, "cp_fftlog_execute: cannot select device %d", p->device);
+        cp::DeviceScope scope(p->device);
+        if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_fftlog_execute: cannot select device %d", p->device);
         return cp_fftlog_large_execute(p->large, d_in, d_out, nbatch, extrap_left, val_left, extrap_right, val_right, keep_padding,
                                        static_cast<hipStream_t>(stream));
     }
@@ -235,8 +223,8 @@ static int execute_impl(const cp_fftlog_plan* p, const double* d_in, double* d_o
     A.tw = p->d_tw;
     A.out_first = 0;
     A.out_last = A.n_out;
-    DeviceGuard guard(p->device);
-    if (!guard.ok) return cp::fail(CP_EDEVICE, "cp_fftlog_execute: cannot select device %d", p->device);
+    cp::DeviceScope scope(p->device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_fftlog_execute: cannot select device %d", p->device);
     int variant = select_variant(p->npad, p->l.p, p->n, extrap_left, val_left, extrap_right, val_right, keep_padding);
     if (variant == VAR_HALF_ZERO && out_count >= 0 && out_count < A.n_out && p->l.func[VAR_HALF_ZERO_WINDOW]) {      // other kernels store whole rows
         variant = VAR_HALF_ZERO_WINDOW;
@@ -250,9 +238,7 @@ static int execute_impl(const cp_fftlog_plan* p, const double* d_in, double* d_o
     if ((long long)p->nker * p->npad >= (1LL << 31) || 2LL * grid * p->npad >= (1LL << 31))
         return cp::fail(CP_EUNSUPPORTED, "cp_fftlog_execute: nker = %d kernels of padded size %d exceed the row-walk range", p->nker, p->npad);
     p->l.launch(variant, A, grid, static_cast<hipStream_t>(stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_fftlog_execute: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_fftlog_execute");
 }
 
 extern "C" int cp_fftlog_execute(const cp_fftlog_plan* p, const double* d_in, double* d_out, long long nbatch, int extrap_left,

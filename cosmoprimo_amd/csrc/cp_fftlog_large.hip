@@ -28,6 +28,7 @@
 #include "cp_math.h"
 #include "cp_fftlog_large.h"
 #include "cp_fftlog_tables.h"
+#include "cp_internal.h"
 
 namespace {
 
@@ -544,8 +545,7 @@ int cp_fftlog_large_execute(cp_fftlog_large* p, const double* d_in, double* d_ou
         hipLaunchKernelGGL(row_kernel, dim3((unsigned)(R.nrows < p->row_grid ? R.nrows : p->row_grid)), dim3(256), 0, st, R);
         launch_columns<false>(C, np, st);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_fftlog_execute: launch failed: %s", hipGetErrorString(e));
+    if (const int status = cp::launch_status("cp_fftlog_execute"); status != CP_OK) return status;
     if (hipEventRecord(p->done, st) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_fftlog_execute: hipEventRecord failed");
     p->has_done = true;
     return CP_OK;

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/cosmoprimo_amd.h"
+#include "cp_error.h"
 
 namespace cpfft {
 struct cplx;
@@ -57,6 +58,31 @@ bool cp_splice_plan_uniform_view(const cp_splice_plan* plan, cpsu::Tables* out, 
 // whole 160 KB of a CU the first time it is launched on the device that is current (once per (kernel, device): a multi-GPU process configures every
 // device it launches on, and a later launch with more LDS than the first finds the limit already at the maximum).
 namespace cp {
+// The calling thread on `device` for the lifetime of the scope, and back on the device it came from on every way out.  A call on the device that
+// is already current costs one hipGetDevice and nothing else; ok() is false only when a switch was needed and failed.
+class DeviceScope {
+    int prev_ = -1;
+    bool switched_ = false, ok_ = true;
+
+public:
+    explicit DeviceScope(int device) {
+        if (hipGetDevice(&prev_) != hipSuccess) prev_ = -1;
+        if (prev_ != device) ok_ = switched_ = hipSetDevice(device) == hipSuccess;
+    }
+    ~DeviceScope() {
+        if (switched_ && prev_ >= 0) (void)hipSetDevice(prev_);
+    }
+    DeviceScope(const DeviceScope&) = delete;
+    DeviceScope& operator=(const DeviceScope&) = delete;
+    bool ok() const { return ok_; }
+};
+
+// the status of entry point `who` after its launches: reads (and clears) the runtime's last error once
+inline int launch_status(const char* who, hipError_t e) {
+    return e == hipSuccess ? CP_OK : fail(CP_EDEVICE, "%s: launch failed: %s", who, hipGetErrorString(e));
+}
+inline int launch_status(const char* who) { return launch_status(who, hipGetLastError()); }
+
 template <auto KERNEL>
 inline hipError_t allow_full_lds() {
     static std::atomic<bool> configured[64];      // (zero-initialised; two threads may both set the same attribute to the same value: harmless, and no data race)

@@ -11,6 +11,7 @@
 
 #include "../../include/cosmoprimo_amd.h"
 #include "cp_error.h"
+#include "cp_internal.h"
 #include "cp_interp_table.h"
 
 // hipcc contracts a * b + c into an fma by default, also through the __dmul_rn / __dadd_rn wrappers of its headers: not in this file
@@ -73,9 +74,8 @@ extern "C" int cp_interp_linear(const double* d_xp, const double* d_fp, long lon
     if (n < 1 || nx < 0) return cp::fail(CP_EINVAL, "cp_interp_linear: need at least one table row and a non-negative sample count");
     if (nx == 0) return CP_OK;
     if (!d_xp || !d_fp || !d_x || !d_out) return cp::fail(CP_EINVAL, "cp_interp_linear: null pointer");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_interp_linear: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_interp_linear: cannot select device %d", device);
     int stride = 32;                                    // at most 4096 coarse knots (32 KB of LDS)
     while ((n + stride - 1) / stride > 4096) stride *= 2;
     const int ncoarse = (int)((n + stride - 1) / stride);
@@ -83,10 +83,7 @@ extern "C" int cp_interp_linear(const double* d_xp, const double* d_fp, long lon
     const unsigned grid = (unsigned)(blocks < 256 * 8 ? blocks : 256 * 8);
     hipLaunchKernelGGL(interp_linear_kernel, dim3(grid), dim3(256), ncoarse * sizeof(double), static_cast<hipStream_t>(stream), d_xp, d_fp, n, stride,
                        ncoarse, d_x, d_out, nx);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_interp_linear: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_interp_linear");
 }
 
 // ---- the same interpolation on a table kept as a plan: (x, f) pairs, the interval GUESSED from the sample -----------------------------------
@@ -151,9 +148,8 @@ extern "C" int cp_interp_table_create(cp_interp_table** table, long long n, cons
     t->d_xf = t->d_x = t->d_f = nullptr; t->d_flag = nullptr;
     const cpit::Law law = cpit::find_law(x, n);      // uniform in x, uniform in log x behind a few leading knots, or neither (cp_interp_table.h)
     t->law = law.law; t->first = law.first; t->a = law.a; t->b = law.b;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) { delete t; return cp::fail(CP_EDEVICE, "cp_interp_table_create: cannot select device %d", device); }
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) { delete t; return cp::fail(CP_EDEVICE, "cp_interp_table_create: cannot select device %d", device); }
     std::vector<double> pairs(2 * (size_t)n);
     for (long long i = 0; i < n; ++i) { pairs[2 * i] = x[i]; pairs[2 * i + 1] = f[i]; }
     const int zero = 0;
@@ -163,7 +159,6 @@ extern "C" int cp_interp_table_create(cp_interp_table** table, long long n, cons
          hipMemcpy(t->d_x, x, n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(t->d_f, f, n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
          hipMemcpy(t->d_flag, &zero, sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
     if (!ok) { (void)cp_interp_table_destroy(t); return cp::fail(CP_ENOMEM, "cp_interp_table_create: device allocation or upload failed"); }
     *table = t;
     return CP_OK;
@@ -187,19 +182,15 @@ int interp_table_apply(const cp_interp_table* t, const real* d_x, real* d_out, l
     if (!d_x || !d_out) return cp::fail(CP_EINVAL, "%s: null pointer", who);
     if (t->law == 0 && !std::is_same<real, double>::value)
         return cp::fail(CP_EUNSUPPORTED, "%s: single-precision samples need a table uniform in x or in log x (this one is bisected: widen the samples)", who);
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != t->device && hipSetDevice(t->device) != hipSuccess) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, t->device);
+    cp::DeviceScope scope(t->device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, t->device);
     hipStream_t hs = static_cast<hipStream_t>(stream);
     int st = CP_OK;
     // The plan has ONE flag word.  A call that does not ask (outside == NULL) hands the kernels no flag at all, so it leaves nothing behind for a
     // later call to trip over; a call that asks clears the word on its own stream in front of its kernels and reads it back behind them: calls
     // that ask must not run concurrently on two streams of one plan (the header says so), calls that do not ask may.
     int* flag = outside ? t->d_flag : nullptr;
-    if (flag && hipMemsetAsync(flag, 0, sizeof(int), hs) != hipSuccess) {
-        if (prev >= 0 && prev != t->device) (void)hipSetDevice(prev);
-        return cp::fail(CP_EDEVICE, "%s: clearing the range flag failed", who);
-    }
+    if (flag && hipMemsetAsync(flag, 0, sizeof(int), hs) != hipSuccess) return cp::fail(CP_EDEVICE, "%s: clearing the range flag failed", who);
     if (t->law == 0) {
         // irregular table: bisection (NaN outside, no flag: raised below)
         st = cp_interp_linear(t->d_x, t->d_f, t->n, reinterpret_cast<const double*>(d_x), reinterpret_cast<double*>(d_out), nx, t->device, stream);
@@ -209,12 +200,12 @@ int interp_table_apply(const cp_interp_table* t, const real* d_x, real* d_out, l
         const cpit::Pair* xf = reinterpret_cast<const cpit::Pair*>(t->d_xf);
         if (t->law == 1) hipLaunchKernelGGL((interp_table_kernel<1, real>), dim3(grid), dim3(256), 0, hs, xf, t->n, t->first, t->a, t->b, d_x, d_out, nx, flag);
         else hipLaunchKernelGGL((interp_table_kernel<2, real>), dim3(grid), dim3(256), 0, hs, xf, t->n, t->first, t->a, t->b, d_x, d_out, nx, flag);
-        if (hipGetLastError() != hipSuccess) st = cp::fail(CP_EDEVICE, "%s: launch failed", who);
+        st = cp::launch_status(who);
     }
     if (st == CP_OK && outside) {
         if (t->law == 0) {
             hipLaunchKernelGGL(flag_outside_kernel, dim3(1024), dim3(256), 0, hs, reinterpret_cast<const double*>(d_x), nx, t->x0, t->xn, t->d_flag);
-            if (hipGetLastError() != hipSuccess) st = cp::fail(CP_EDEVICE, "%s: launch failed", who);
+            st = cp::launch_status(who);
         }
         // the flag comes back with the stream drained: the caller of the reference gets its exception from the call itself (tabulated.py:33-34)
         int host = 0;
@@ -222,7 +213,6 @@ int interp_table_apply(const cp_interp_table* t, const real* d_x, real* d_out, l
             st = cp::fail(CP_EDEVICE, "%s: reading the range flag failed", who);
         if (st == CP_OK && host) *outside = 1;
     }
-    if (prev >= 0 && prev != t->device) (void)hipSetDevice(prev);
     return st;
 }
 
@@ -238,14 +228,11 @@ extern "C" int cp_interp_table_apply_f32(const cp_interp_table* t, const float* 
 
 extern "C" int cp_interp_table_destroy(cp_interp_table* t) {
     if (!t) return CP_OK;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != t->device) (void)hipSetDevice(t->device);
+    cp::DeviceScope scope(t->device);
     if (t->d_xf) (void)hipFree(t->d_xf);
     if (t->d_x) (void)hipFree(t->d_x);
     if (t->d_f) (void)hipFree(t->d_f);
     if (t->d_flag) (void)hipFree(t->d_flag);
-    if (prev >= 0 && prev != t->device) (void)hipSetDevice(prev);
     delete t;
     return CP_OK;
 }
@@ -358,9 +345,8 @@ extern "C" int cp_spline_points(const double* d_xk, const double* d_y, const dou
     if (n < 2 || ncol < 0 || nq < 0 || nu < 0 || nu > 2) return cp::fail(CP_EINVAL, "cp_spline_points: need n >= 2, nu in {0, 1, 2} and non-negative counts");
     if (nq == 0 || ncol == 0) return CP_OK;
     if (!d_xk || !d_y || !d_s || !d_xq || !d_out) return cp::fail(CP_EINVAL, "cp_spline_points: null pointer");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_spline_points: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_spline_points: cannot select device %d", device);
     int stride = 32;
     while ((n + stride - 1) / stride > 4096) stride *= 2;
     const int ncoarse = (int)((n + stride - 1) / stride);
@@ -372,17 +358,11 @@ extern "C" int cp_spline_points(const double* d_xk, const double* d_y, const dou
         const unsigned lgrid = (unsigned)(blocks < 256 * 4 ? blocks : 256 * 4);
         hipLaunchKernelGGL(spline_points_lds_kernel, dim3(lgrid), dim3(256), lds, static_cast<hipStream_t>(stream), d_xk, d_y, d_s, (int)n, d_xq, d_out, nq, nu,
                            extrapolate);
-        const hipError_t le = hipGetLastError();
-        if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-        if (le != hipSuccess) return cp::fail(CP_EDEVICE, "cp_spline_points: launch failed: %s", hipGetErrorString(le));
-        return CP_OK;
+        return cp::launch_status("cp_spline_points");
     }
     hipLaunchKernelGGL(spline_points_kernel, dim3(grid), dim3(256), ncoarse * sizeof(double), static_cast<hipStream_t>(stream), d_xk, d_y, d_s, n, ncol, stride,
                        ncoarse, d_xq, d_out, nq, nu, extrapolate);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_spline_points: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_spline_points");
 }
 
 // ---- cubic splines of many rows, each at ITS OWN queries: one lane per (row, query) --------------------------------------------------------
@@ -429,15 +409,11 @@ extern "C" int cp_spline_rows_at_queries(const double* d_xk, const double* d_y, 
     if (nrows < 0 || n < 2 || nq < 0) return cp::fail(CP_EINVAL, "cp_spline_rows_at_queries: bad sizes");
     if (nrows == 0 || nq == 0) return CP_OK;
     if (!d_xk || !d_y || !d_m || !d_xq || !d_out) return cp::fail(CP_EINVAL, "cp_spline_rows_at_queries: null pointer");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_spline_rows_at_queries: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_spline_rows_at_queries: cannot select device %d", device);
     const long long blocks = (nrows * nq + 255) / 256;
     const unsigned grid = (unsigned)(blocks < 256 * 16 ? blocks : 256 * 16);
     hipLaunchKernelGGL(spline_rows_at_queries_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), d_xk, d_y, d_m, nrows, n, d_xq, nq, d_out,
                        transposed);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_spline_rows_at_queries: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_spline_rows_at_queries");
 }

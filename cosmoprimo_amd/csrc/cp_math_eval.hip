@@ -4,6 +4,7 @@
 
 #include "../../include/cosmoprimo_amd.h"
 #include "cp_error.h"
+#include "cp_internal.h"
 #include "cp_math.h"
 
 namespace {
@@ -37,13 +38,9 @@ extern "C" int cp_math_eval(int kind, const double* d_x, double* d_y, long long 
     if (n < 0) return cp::fail(CP_EINVAL, "cp_math_eval: negative size");
     if (n == 0) return CP_OK;
     if (!d_x || !d_y) return cp::fail(CP_EINVAL, "cp_math_eval: null pointer");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_math_eval: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_math_eval: cannot select device %d", device);
     const long long blocks = (n + 255) / 256;
     hipLaunchKernelGGL(math_eval_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, static_cast<hipStream_t>(stream), kind, d_x, d_y, n);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_math_eval: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_math_eval");
 }

@@ -7,6 +7,7 @@
 
 #include "../../include/cosmoprimo_amd.h"
 #include "cp_error.h"
+#include "cp_internal.h"
 
 namespace {
 
@@ -43,12 +44,8 @@ extern "C" int cp_bilinear_pairs(const double* d_wx, const double* d_wy, const d
     if (!d_wx || !d_wy || !d_f || !d_out) return cp::fail(CP_EINVAL, "cp_bilinear_pairs: null pointer");
     const long long blocks = (nbatch * nq + 3) / 4;
     if (blocks > 2147483647LL) return cp::fail(CP_EUNSUPPORTED, "cp_bilinear_pairs: %lld x %d pairs exceed one launch", nbatch, nq);
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_bilinear_pairs: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_bilinear_pairs: cannot select device %d", device);
     hipLaunchKernelGGL(bilinear_pairs_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), d_wx, d_wy, d_f, d_out, nbatch, nq, nx, ny);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_bilinear_pairs: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_bilinear_pairs");
 }

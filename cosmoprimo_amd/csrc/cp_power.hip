@@ -334,13 +334,6 @@ __global__ __launch_bounds__(256) void variants_kernel(const VarArgs A) {
     }
 }
 
-int select_device(int device, int* prev) {
-    *prev = -1;
-    if (hipGetDevice(prev) != hipSuccess) *prev = -1;
-    if (*prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cannot select device %d", device);
-    return CP_OK;
-}
-
 }  // namespace
 
 extern "C" long long cp_power_workspace_bytes(long long ncosmo) { return ncosmo < 0 ? -1 : (long long)sizeof(CosmoConsts) * ncosmo; }
@@ -349,32 +342,25 @@ int cp_power_coefficients(int engine, long long ncosmo, const cp_param* bg_param
                           void* d_work, int device, void* stream, const double* d_k, double* d_ln_k, int n) {
     if (ncosmo <= 0) return CP_OK;
     if (!bg_params || !d_work) return cp::fail(CP_EINVAL, "cp_power_coefficients: null pointer");
-    int prev;
-    int st = select_device(device, &prev);
-    if (st != CP_OK) return st;
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_power_coefficients: cannot select device %d", device);
     Args A{};
     A.ncosmo = ncosmo;
-    for (int i = 0; i < CP_BG_NPARAMS; ++i) A.bg[i] = Param{bg_params[i].ptr, bg_params[i].value};
+    cpcosmo::copy_params(A.bg, bg_params, CP_BG_NPARAMS);
     if (pk_params)
-        for (int i = 0; i < CP_PK_NPARAMS; ++i) A.pw[i] = Param{pk_params[i].ptr, pk_params[i].value};
+        cpcosmo::copy_params(A.pw, pk_params, CP_PK_NPARAMS);
     A.second_is_omega_m = second_is_omega_m;
     A.engine = engine;
     NcdmView nu;
-    st = ncdm_view(ncdm, device, "cp_power_coefficients", &nu);
-    if (st != CP_OK) {
-        if (prev >= 0) (void)hipSetDevice(prev);
-        return st;
-    }
+    const int st = ncdm_view(ncdm, device, "cp_power_coefficients", &nu);
+    if (st != CP_OK) return st;
     A.ncdm_tab = nu.tab;
     A.ncdm_knots = nu.knots;
     A.nsp = nu.nsp;
     const int n_grid = d_k && d_ln_k ? n : 0;
     hipLaunchKernelGGL(coefficients_kernel, dim3((unsigned)((ncosmo + 63) / 64 + (n_grid + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), A,
                        static_cast<CosmoConsts*>(d_work), pk_params ? 1 : 0, d_k, d_ln_k, n_grid);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_power_coefficients: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_power_coefficients");
 }
 
 extern "C" int cp_power_eval(int engine, int what, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm,
@@ -386,13 +372,12 @@ extern "C" int cp_power_eval(int engine, int what, long long ncosmo, const cp_pa
     if (ncosmo < 0 || nk < 0 || nz < 0) return cp::fail(CP_EINVAL, "cp_power_eval: negative size");
     if (ncosmo == 0 || nk == 0) return CP_OK;
     if (!bg_params || !pk_params || !d_k || !d_out || (nz > 0 && !d_z)) return cp::fail(CP_EINVAL, "cp_power_eval: null pointer");
-    int prev;
-    int st = select_device(device, &prev);
-    if (st != CP_OK) return st;
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_power_eval: cannot select device %d", device);
     Args A;
     A.ncosmo = ncosmo;
-    for (int i = 0; i < CP_BG_NPARAMS; ++i) A.bg[i] = Param{bg_params[i].ptr, bg_params[i].value};
-    for (int i = 0; i < CP_PK_NPARAMS; ++i) A.pw[i] = Param{pk_params[i].ptr, pk_params[i].value};
+    cpcosmo::copy_params(A.bg, bg_params, CP_BG_NPARAMS);
+    cpcosmo::copy_params(A.pw, pk_params, CP_PK_NPARAMS);
     A.second_is_omega_m = second_is_omega_m;
     A.engine = engine;
     A.what = what;
@@ -404,11 +389,8 @@ extern "C" int cp_power_eval(int engine, int what, long long ncosmo, const cp_pa
     A.out = d_out;
     A.consts = nullptr;
     NcdmView nu;
-    st = ncdm_view(ncdm, device, "cp_power_eval", &nu);
-    if (st != CP_OK) {
-        if (prev >= 0) (void)hipSetDevice(prev);
-        return st;
-    }
+    const int st = ncdm_view(ncdm, device, "cp_power_eval", &nu);
+    if (st != CP_OK) return st;
     A.ncdm_tab = nu.tab;
     A.ncdm_knots = nu.knots;
     A.nsp = nu.nsp;
@@ -420,16 +402,10 @@ extern "C" int cp_power_eval(int engine, int what, long long ncosmo, const cp_pa
     while (kiter > 1 && ncosmo * ((nk + block * kiter - 1) / (block * kiter)) < 2048) kiter = (kiter + 1) / 2;
     A.kspan = block * kiter;
     A.kchunks = (nk + A.kspan - 1) / A.kspan;
-    if (ncosmo * A.kchunks > 2147483647LL) {
-        if (prev >= 0) (void)hipSetDevice(prev);
-        return cp::fail(CP_EUNSUPPORTED, "cp_power_eval: %lld cosmologies x %lld wavenumbers exceed one launch; split the batch", ncosmo, nk);
-    }
+    if (ncosmo * A.kchunks > 2147483647LL) return cp::fail(CP_EUNSUPPORTED, "cp_power_eval: %lld cosmologies x %lld wavenumbers exceed one launch; split the batch", ncosmo, nk);
     hipStream_t hs = static_cast<hipStream_t>(stream);
     {   // the constants of the cosmologies: caller-owned workspace, nothing is allocated here
-        if (!d_work) {
-            if (prev >= 0) (void)hipSetDevice(prev);
-            return cp::fail(CP_EINVAL, "cp_power_eval: needs a workspace of cp_power_workspace_bytes(ncosmo) bytes");
-        }
+        if (!d_work) return cp::fail(CP_EINVAL, "cp_power_eval: needs a workspace of cp_power_workspace_bytes(ncosmo) bytes");
         CosmoConsts* consts = static_cast<CosmoConsts*>(d_work);
         A.consts = consts;
         hipLaunchKernelGGL(coefficients_kernel, dim3((unsigned)((ncosmo + 63) / 64)), dim3(64), 0, hs, A, consts, 1, static_cast<const double*>(nullptr),
@@ -439,10 +415,7 @@ extern "C" int cp_power_eval(int engine, int what, long long ncosmo, const cp_pa
     if (engine == CP_ENGINE_EH) hipLaunchKernelGGL(power_kernel<CP_ENGINE_EH>, grid, threads, 0, hs, A);
     else if (engine == CP_ENGINE_EH_NOWIGGLE) hipLaunchKernelGGL(power_kernel<CP_ENGINE_EH_NOWIGGLE>, grid, threads, 0, hs, A);
     else hipLaunchKernelGGL(power_kernel<CP_ENGINE_BBKS>, grid, threads, 0, hs, A);
-    hipError_t e = hipGetLastError();
-    if (prev >= 0) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_power_eval: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_power_eval");
 }
 
 extern "C" int cp_power_eval_variants(int what, int of, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm,
@@ -455,13 +428,12 @@ extern "C" int cp_power_eval_variants(int what, int of, long long ncosmo, const 
     if (!bg_params || !pk_params || !d_k || !d_z || !d_out) return cp::fail(CP_EINVAL, "cp_power_eval_variants: null pointer");
     const int nsp = ncdm ? ncdm->nspecies : 0;
     if (nsp < 0 || (nsp > 0 && !ncdm->tab)) return cp::fail(CP_EINVAL, "cp_power_eval_variants: bad massive-neutrino tables");
-    int prev;
-    int st = select_device(device, &prev);
-    if (st != CP_OK) return st;
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_power_eval_variants: cannot select device %d", device);
     VarArgs A;
     A.ncosmo = ncosmo;
-    for (int i = 0; i < CP_BG_NPARAMS; ++i) A.bg[i] = Param{bg_params[i].ptr, bg_params[i].value};
-    for (int i = 0; i < CP_PK_NPARAMS; ++i) A.pw[i] = Param{pk_params[i].ptr, pk_params[i].value};
+    cpcosmo::copy_params(A.bg, bg_params, CP_BG_NPARAMS);
+    cpcosmo::copy_params(A.pw, pk_params, CP_PK_NPARAMS);
     A.second_is_omega_m = second_is_omega_m;
     A.what = what;
     A.of = of;
@@ -473,24 +445,15 @@ extern "C" int cp_power_eval_variants(int what, int of, long long ncosmo, const 
     A.nsp = nsp;
     A.ncdm_tab = nsp ? ncdm->tab : nullptr;
     A.ncdm_knots = nsp ? cpcosmo::ncdm_knots_device(device) : nullptr;
-    if (nsp && !A.ncdm_knots) {
-        if (prev >= 0) (void)hipSetDevice(prev);
-        return cp::fail(CP_ENOMEM, "cp_power_eval_variants: cannot allocate the massive-neutrino knots on device %d", device);
-    }
+    if (nsp && !A.ncdm_knots) return cp::fail(CP_ENOMEM, "cp_power_eval_variants: cannot allocate the massive-neutrino knots on device %d", device);
     const long long block = 256;
     long long kiter = (nk + block - 1) / block;
     while (kiter > 1 && ncosmo * ((nk + block * kiter - 1) / (block * kiter)) < 2048) kiter = (kiter + 1) / 2;
     A.kspan = block * kiter;
     A.kchunks = (nk + A.kspan - 1) / A.kspan;
-    if (ncosmo * A.kchunks > 2147483647LL) {
-        if (prev >= 0) (void)hipSetDevice(prev);
-        return cp::fail(CP_EUNSUPPORTED, "cp_power_eval_variants: %lld cosmologies x %lld wavenumbers exceed one launch; split the batch", ncosmo, nk);
-    }
+    if (ncosmo * A.kchunks > 2147483647LL) return cp::fail(CP_EUNSUPPORTED, "cp_power_eval_variants: %lld cosmologies x %lld wavenumbers exceed one launch; split the batch", ncosmo, nk);
     hipLaunchKernelGGL(variants_kernel, dim3((unsigned)(ncosmo * A.kchunks)), dim3((unsigned)block), 0, static_cast<hipStream_t>(stream), A);
-    hipError_t e = hipGetLastError();
-    if (prev >= 0) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_power_eval_variants: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_power_eval_variants");
 }
 
 extern "C" int cp_variants_scalars(long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, double* d_out, int device,
@@ -500,26 +463,19 @@ extern "C" int cp_variants_scalars(long long ncosmo, const cp_param* bg_params, 
     if (!bg_params || !d_out) return cp::fail(CP_EINVAL, "cp_variants_scalars: null pointer");
     const int nsp = ncdm ? ncdm->nspecies : 0;
     if (nsp < 0 || (nsp > 0 && !ncdm->tab)) return cp::fail(CP_EINVAL, "cp_variants_scalars: bad massive-neutrino tables");
-    int prev;
-    int st = select_device(device, &prev);
-    if (st != CP_OK) return st;
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_variants_scalars: cannot select device %d", device);
     VarScalArgs A;
     A.ncosmo = ncosmo;
-    for (int i = 0; i < CP_BG_NPARAMS; ++i) A.bg[i] = Param{bg_params[i].ptr, bg_params[i].value};
+    cpcosmo::copy_params(A.bg, bg_params, CP_BG_NPARAMS);
     A.second_is_omega_m = second_is_omega_m;
     A.nsp = nsp;
     A.ncdm_tab = nsp ? ncdm->tab : nullptr;
     A.ncdm_knots = nsp ? cpcosmo::ncdm_knots_device(device) : nullptr;
     A.out = d_out;
-    if (nsp && !A.ncdm_knots) {
-        if (prev >= 0) (void)hipSetDevice(prev);
-        return cp::fail(CP_ENOMEM, "cp_variants_scalars: cannot allocate the massive-neutrino knots on device %d", device);
-    }
+    if (nsp && !A.ncdm_knots) return cp::fail(CP_ENOMEM, "cp_variants_scalars: cannot allocate the massive-neutrino knots on device %d", device);
     hipLaunchKernelGGL(variants_scalars_kernel, dim3((unsigned)((ncosmo + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), A);
-    hipError_t e = hipGetLastError();
-    if (prev >= 0) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_variants_scalars: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_variants_scalars");
 }
 
 extern "C" int cp_eh_scalars(long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, double* d_out, int device,
@@ -529,19 +485,15 @@ extern "C" int cp_eh_scalars(long long ncosmo, const cp_param* bg_params, int se
     if (!bg_params || !d_out) return cp::fail(CP_EINVAL, "cp_eh_scalars: null pointer");
     const int nsp = ncdm ? ncdm->nspecies : 0;
     if (nsp < 0 || (nsp > 0 && !ncdm->tab)) return cp::fail(CP_EINVAL, "cp_eh_scalars: bad massive-neutrino tables");
-    int prev;
-    int st = select_device(device, &prev);
-    if (st != CP_OK) return st;
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_eh_scalars: cannot select device %d", device);
     ScalArgs A;
     A.ncosmo = ncosmo;
-    for (int i = 0; i < CP_BG_NPARAMS; ++i) A.bg[i] = Param{bg_params[i].ptr, bg_params[i].value};
+    cpcosmo::copy_params(A.bg, bg_params, CP_BG_NPARAMS);
     A.second_is_omega_m = second_is_omega_m;
     A.ncdm_tab = nsp ? ncdm->tab : nullptr;
     A.nsp = nsp;
     A.out = d_out;
     hipLaunchKernelGGL(eh_scalars_kernel, dim3((unsigned)((ncosmo + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), A);
-    hipError_t e = hipGetLastError();
-    if (prev >= 0) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_eh_scalars: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_eh_scalars");
 }

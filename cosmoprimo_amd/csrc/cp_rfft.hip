@@ -169,12 +169,9 @@ struct cp_rfft_plan {
 
 extern "C" int cp_rfft_plan_destroy(cp_rfft_plan* p) {
     if (!p) return CP_OK;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != p->device) (void)hipSetDevice(p->device);
+    cp::DeviceScope scope(p->device);
     if (p->d_tw) (void)hipFree(p->d_tw);
     if (p->d_rot) (void)hipFree(p->d_rot);
-    if (prev >= 0 && prev != p->device) (void)hipSetDevice(prev);
     delete p;
     return CP_OK;
 }
@@ -194,15 +191,13 @@ extern "C" int cp_rfft_plan_create(cp_rfft_plan** out, int size, int device) {
     cp_rfft_plan* p = new (std::nothrow) cp_rfft_plan();
     if (!p) return cp::fail(CP_ENOMEM, "cp_rfft_plan_create: host allocation failed");
     p->size = size; p->device = device; p->d_tw = nullptr; p->d_rot = nullptr;
-    int prev = -1, status = CP_OK;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) status = cp::fail(CP_EDEVICE, "cp_rfft_plan_create: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    int status = scope.ok() ? CP_OK : cp::fail(CP_EDEVICE, "cp_rfft_plan_create: cannot select device %d", device);
     if (status == CP_OK && (hipMalloc(&p->d_tw, tw.size() * sizeof(cplx)) != hipSuccess || hipMalloc(&p->d_rot, m * sizeof(cplx)) != hipSuccess))
         status = cp::fail(CP_ENOMEM, "cp_rfft_plan_create: device allocation failed");
     if (status == CP_OK && (hipMemcpy(p->d_tw, tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice) != hipSuccess ||
                             hipMemcpy(p->d_rot, rot.data(), m * sizeof(cplx), hipMemcpyHostToDevice) != hipSuccess))
         status = cp::fail(CP_EDEVICE, "cp_rfft_plan_create: upload failed");
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
     if (status != CP_OK) {
         cp_rfft_plan_destroy(p);
         return status;
@@ -217,9 +212,8 @@ static int rfft_run(const cp_rfft_plan* p, const double* d_in, double* d_out, lo
     if (nrows == 0) return CP_OK;
     if (!d_in || !d_out) return cp::fail(CP_EINVAL, "%s: null device pointer", what);
     if (d_in == d_out) return cp::fail(CP_EINVAL, "%s: the transform is not in place", what);
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != p->device && hipSetDevice(p->device) != hipSuccess) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", what, p->device);
+    cp::DeviceScope scope(p->device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", what, p->device);
     RArgs A;
     A.in = d_in; A.out = d_out; A.nrows = nrows; A.tw = p->d_tw; A.rot = p->d_rot; A.conj_input = conj_input;
     const int m = p->size / 2;
@@ -229,10 +223,7 @@ static int rfft_run(const cp_rfft_plan* p, const double* d_in, double* d_out, lo
     if (m == M_) rlaunch<M_, P_>(backward, A, grid, s);
     CP_RFFT_SIZES(X)
 #undef X
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != p->device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "%s: launch failed: %s", what, hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status(what);
 }
 
 extern "C" int cp_rfft_forward(const cp_rfft_plan* p, const double* d_in, double* d_out, long long nrows, void* stream) {

@@ -8,6 +8,7 @@
 
 #include "../../include/cosmoprimo_amd.h"
 #include "cp_error.h"
+#include "cp_internal.h"
 
 namespace {
 
@@ -48,13 +49,9 @@ extern "C" int cp_rows_screen(const double* d_x, long long nrows, long long n, i
     if (nrows < 0 || n < 0) return cp::fail(CP_EINVAL, "cp_rows_screen: negative size");
     if (nrows == 0) return CP_OK;
     if (!d_ok || (n > 0 && !d_x)) return cp::fail(CP_EINVAL, "cp_rows_screen: null pointer");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_rows_screen: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_rows_screen: cannot select device %d", device);
     const unsigned grid = (unsigned)(nrows < 65536 ? nrows : 65536);
     hipLaunchKernelGGL(rows_screen_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), d_x, nrows, n, require_positive, d_ok, d_scale);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_rows_screen: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_rows_screen");
 }

@@ -940,8 +940,8 @@ int sigma_rz_fused_launch(int engine, long long ncosmo, const cp_param* bg_param
     A.ext_l = A.ext_r = CP_EXTRAP_CONST; A.val_l = A.val_r = 0.; A.stream_rows = 0;
     A.pre = f.d_pre; A.post = f.d_post; A.u = f.d_u; A.tw = f.d_tw;
     S.ncosmo = ncosmo;
-    for (int i = 0; i < CP_BG_NPARAMS; ++i) S.bg[i] = Param{bg_params[i].ptr, bg_params[i].value};
-    for (int i = 0; i < CP_PK_NPARAMS; ++i) S.pw[i] = Param{pk_params[i].ptr, pk_params[i].value};
+    cpcosmo::copy_params(S.bg, bg_params, CP_BG_NPARAMS);
+    cpcosmo::copy_params(S.pw, pk_params, CP_PK_NPARAMS);
     S.second_is_omega_m = second_is_omega_m;
     S.k = d_k;
     S.consts = static_cast<const CosmoConsts*>(d_coef);
@@ -955,9 +955,8 @@ int sigma_rz_fused_launch(int engine, long long ncosmo, const cp_param* bg_param
     S.growth_sq = d_growth_sq;
     S.out = d_out;
     S.pk_out = d_pk_out;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_sigma_rz_fused: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_sigma_rz_fused: cannot select device %d", device);
     using F = Fftlog<NP, P, IN_HALF_ZERO_GEN, OUT_HALF>;
     const size_t lds = (size_t)F::LDS_BYTES + (size_t)(2 * nq + 2 * nz) * sizeof(double);
     int ncu = 0;
@@ -977,17 +976,12 @@ int sigma_rz_fused_launch(int engine, long long ncosmo, const cp_param* bg_param
         if (std::sscanf(env, "%d,%d,%d", &d, &m, &sl) == 3 && d >= 1 && m >= 1 && sl >= 0 && sl <= 4096) { S.stagger_div = d; S.stagger_mod = m; S.stagger_sleeps = sl; }
     }
     hipError_t e = hipSuccess;
-    if (lds > 160 * 1024) {
-        if (prev >= 0) (void)hipSetDevice(prev);
-        return cp::fail(CP_EUNSUPPORTED, "cp_sigma_rz_fused: %d radii x %d redshifts exceed the LDS staging", nq, nz);
-    }
+    if (lds > 160 * 1024) return cp::fail(CP_EUNSUPPORTED, "cp_sigma_rz_fused: %d radii x %d redshifts exceed the LDS staging", nq, nz);
     hipStream_t hs = static_cast<hipStream_t>(stream);
     if (engine == CP_ENGINE_EH) e = launch<CP_ENGINE_EH>(S, grid, lds, hs);
     else if (engine == CP_ENGINE_EH_NOWIGGLE) e = launch<CP_ENGINE_EH_NOWIGGLE>(S, grid, lds, hs);
     else e = launch<CP_ENGINE_BBKS>(S, grid, lds, hs);
-    if (prev >= 0) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_sigma_rz_fused: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_sigma_rz_fused", e);
 }
 }  // namespace
 
@@ -1123,22 +1117,20 @@ extern "C" int cp_sigma_rz_functional(int engine, long long ncosmo, const cp_par
     double* ln_k = reinterpret_cast<double*>(coef + ((cp_power_workspace_bytes(ncosmo) + 63) / 64) * 64);      // behind the coefficients (cp_sigma_rz_workspace_bytes)
     int st = cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, pk_params, coef, device, stream, d_k, ln_k, nk);      // (and the table of the wavenumbers)
     if (st != CP_OK) return st;
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_sigma_rz_functional: cannot select device %d", device);
     FunctionalArgs S{};
     {
-        int prev_nu = -1;
-        if (hipGetDevice(&prev_nu) != hipSuccess) prev_nu = -1;
-        if (prev_nu != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cannot select device %d", device);
         NcdmView nu;
         st = ncdm_view(ncdm, device, "cp_sigma_rz_functional / cp_sigma8_normalise", &nu);
-        if (prev_nu >= 0 && prev_nu != device) (void)hipSetDevice(prev_nu);
         if (st != CP_OK) return st;
         S.ncdm_tab = nu.tab;
         S.ncdm_knots = nu.knots;
         S.nsp = nu.nsp;
     }
     S.ncosmo = ncosmo;
-    for (int i = 0; i < CP_BG_NPARAMS; ++i) S.bg[i] = Param{bg_params[i].ptr, bg_params[i].value};
-    for (int i = 0; i < CP_PK_NPARAMS; ++i) S.pw[i] = Param{pk_params[i].ptr, pk_params[i].value};
+    cpcosmo::copy_params(S.bg, bg_params, CP_BG_NPARAMS);
+    cpcosmo::copy_params(S.pw, pk_params, CP_PK_NPARAMS);
     S.second_is_omega_m = second_is_omega_m;
     S.nk = nk; S.nq = nq; S.nz = nz;
     S.k = d_k;
@@ -1148,18 +1140,12 @@ extern "C" int cp_sigma_rz_functional(int engine, long long ncosmo, const cp_par
     S.growth_sq = d_growth_sq;
     S.out = d_out;
     S.pk_out = d_pk_out;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_sigma_rz_functional: cannot select device %d", device);
     hipStream_t hs = static_cast<hipStream_t>(stream);
     const unsigned grid = (unsigned)((ncosmo + 3) / 4);
     if (engine == CP_ENGINE_EH) hipLaunchKernelGGL(sigma_functional_kernel<CP_ENGINE_EH>, dim3(grid), dim3(256), 0, hs, S);
     else if (engine == CP_ENGINE_EH_NOWIGGLE) hipLaunchKernelGGL(sigma_functional_kernel<CP_ENGINE_EH_NOWIGGLE>, dim3(grid), dim3(256), 0, hs, S);
     else hipLaunchKernelGGL(sigma_functional_kernel<CP_ENGINE_BBKS>, dim3(grid), dim3(256), 0, hs, S);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_sigma_rz_functional: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_sigma_rz_functional");
 }
 
 extern "C" int cp_sigma8_normalise(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, const cp_param* pk_params,
@@ -1176,22 +1162,20 @@ extern "C" int cp_sigma8_normalise(int engine, long long ncosmo, const cp_param*
     double* ln_k = reinterpret_cast<double*>(coef + ((cp_power_workspace_bytes(ncosmo) + 63) / 64) * 64);      // behind the coefficients (cp_sigma_rz_workspace_bytes)
     int st = cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, pk_params, coef, device, stream, d_k, ln_k, nk);      // (and the table of the wavenumbers)
     if (st != CP_OK) return st;
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_sigma8_normalise: cannot select device %d", device);
     FunctionalArgs S{};
     {
-        int prev_nu = -1;
-        if (hipGetDevice(&prev_nu) != hipSuccess) prev_nu = -1;
-        if (prev_nu != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cannot select device %d", device);
         NcdmView nu;
         st = ncdm_view(ncdm, device, "cp_sigma_rz_functional / cp_sigma8_normalise", &nu);
-        if (prev_nu >= 0 && prev_nu != device) (void)hipSetDevice(prev_nu);
         if (st != CP_OK) return st;
         S.ncdm_tab = nu.tab;
         S.ncdm_knots = nu.knots;
         S.nsp = nu.nsp;
     }
     S.ncosmo = ncosmo;
-    for (int i = 0; i < CP_BG_NPARAMS; ++i) S.bg[i] = Param{bg_params[i].ptr, bg_params[i].value};
-    for (int i = 0; i < CP_PK_NPARAMS; ++i) S.pw[i] = Param{pk_params[i].ptr, pk_params[i].value};
+    cpcosmo::copy_params(S.bg, bg_params, CP_BG_NPARAMS);
+    cpcosmo::copy_params(S.pw, pk_params, CP_PK_NPARAMS);
     S.second_is_omega_m = second_is_omega_m;
     S.nk = nk; S.nq = 1; S.nz = 1;
     S.k = d_k;
@@ -1202,18 +1186,12 @@ extern "C" int cp_sigma8_normalise(int engine, long long ncosmo, const cp_param*
     S.target = Param{sigma8.ptr, sigma8.value};
     S.rsigma8_out = d_rsigma8;
     S.amplitude_out = d_amplitude;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_sigma8_normalise: cannot select device %d", device);
     hipStream_t hs = static_cast<hipStream_t>(stream);
     const unsigned grid = (unsigned)((ncosmo + 3) / 4);
     if (engine == CP_ENGINE_EH) hipLaunchKernelGGL(sigma8_normalise_kernel<CP_ENGINE_EH>, dim3(grid), dim3(256), 0, hs, S);
     else if (engine == CP_ENGINE_EH_NOWIGGLE) hipLaunchKernelGGL(sigma8_normalise_kernel<CP_ENGINE_EH_NOWIGGLE>, dim3(grid), dim3(256), 0, hs, S);
     else hipLaunchKernelGGL(sigma8_normalise_kernel<CP_ENGINE_BBKS>, dim3(grid), dim3(256), 0, hs, S);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_sigma8_normalise: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_sigma8_normalise");
 }
 
 // FFTLog of (nbatch, n) rows followed by the spline of every output row to the plan's queries (root taken when post_op is CP_SPLINE_POST_SQRT), as one
@@ -1237,15 +1215,11 @@ extern "C" int cp_fftlog_spline_execute(const cp_fftlog_plan* fftlog, const cp_s
     A.pre = f.d_pre; A.post = f.d_post; A.u = f.d_u; A.tw = f.d_tw;
     R.wb = b.d_wb; R.j0 = b.d_j0; R.bw = b.bw; R.nq = b.nq; R.post_sqrt = post_op == CP_SPLINE_POST_SQRT;
     R.out = d_out;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != f.device && hipSetDevice(f.device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_fftlog_spline_execute: cannot select device %d", f.device);
+    cp::DeviceScope scope(f.device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_fftlog_spline_execute: cannot select device %d", f.device);
     using F = Fftlog<NP, P, IN_HALF_ZERO, OUT_HALF>;
     const size_t lds = (size_t)F::LDS_BYTES + (size_t)(2 * b.nq) * sizeof(double);
-    if (lds > 160 * 1024) {
-        if (prev >= 0) (void)hipSetDevice(prev);
-        return cp::fail(CP_EUNSUPPORTED, "cp_fftlog_spline_execute: %d queries exceed the LDS staging", b.nq);
-    }
+    if (lds > 160 * 1024) return cp::fail(CP_EUNSUPPORTED, "cp_fftlog_spline_execute: %d queries exceed the LDS staging", b.nq);
     if (lds > 64 * 1024) (void)cp::allow_full_lds<&fftlog_spline_kernel>();
     int ncu = 0;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, f.device);
@@ -1255,10 +1229,7 @@ extern "C" int cp_fftlog_spline_execute(const cp_fftlog_plan* fftlog, const cp_s
     const long long rounds = (npairs + resident - 1) / resident;
     const int grid = (int)((npairs + rounds - 1) / rounds);
     hipLaunchKernelGGL(fftlog_spline_kernel, dim3(grid), dim3(NP / P), lds, static_cast<hipStream_t>(stream), R);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_fftlog_spline_execute: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_fftlog_spline_execute");
 }
 
 // ---- natural spline on a geometric grid, solved inside the FFTLog kernel (fftlog_geospline_kernel above) -----------------------------------------
@@ -1272,13 +1243,10 @@ struct cp_geospline_plan {
 
 extern "C" int cp_geospline_plan_destroy(cp_geospline_plan* p) {
     if (!p) return CP_OK;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != p->device) (void)hipSetDevice(p->device);
+    cp::DeviceScope scope(p->device);
     if (p->d_qe) (void)hipFree(p->d_qe);
     if (p->d_qa) (void)hipFree(p->d_qa);
     if (p->d_consts) (void)hipFree(p->d_consts);
-    if (prev >= 0 && prev != p->device) (void)hipSetDevice(prev);
     if (p->prefiltered) (void)cp_fftlog_plan_destroy(p->prefiltered);
     delete p;
     return CP_OK;
@@ -1349,9 +1317,8 @@ void geometric_bspline_pieces(long double rho, long double basis[4][4]) {
 
 int upload_geospline(cp_geospline_plan* p, const std::vector<int>& qj, const std::vector<double>& qa, const GeoConsts& consts) {
     const int nq = p->nq, device = p->device;
-    int prev = -1, status = CP_OK;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) status = cp::fail(CP_EDEVICE, "cp_geospline_plan_create: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    int status = scope.ok() ? CP_OK : cp::fail(CP_EDEVICE, "cp_geospline_plan_create: cannot select device %d", device);
     if (status == CP_OK && (hipMalloc(&p->d_qe, nq * sizeof(int)) != hipSuccess || hipMalloc(&p->d_qa, nq * sizeof(double)) != hipSuccess ||
                             hipMalloc(&p->d_consts, sizeof(GeoConsts)) != hipSuccess))
         status = cp::fail(CP_ENOMEM, "cp_geospline_plan_create: device allocation failed");
@@ -1359,7 +1326,6 @@ int upload_geospline(cp_geospline_plan* p, const std::vector<int>& qj, const std
                             hipMemcpy(p->d_qa, qa.data(), nq * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
                             hipMemcpy(p->d_consts, &consts, sizeof(GeoConsts), hipMemcpyHostToDevice) != hipSuccess))
         status = cp::fail(CP_EDEVICE, "cp_geospline_plan_create: upload failed");
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
     return status;
 }
 
@@ -1555,9 +1521,8 @@ extern "C" int cp_fftlog_geospline_execute(const cp_fftlog_plan* fftlog, const c
     R.pt = group > 0 ? group / 2 : 1;
     R.consts = spline->d_consts;
     R.qe = spline->d_qe; R.qa = spline->d_qa; R.out = d_out;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != f.device && hipSetDevice(f.device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_fftlog_geospline_execute: cannot select device %d", f.device);
+    cp::DeviceScope scope(f.device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_fftlog_geospline_execute: cannot select device %d", f.device);
     using F = Fftlog<NP, P, IN_HALF_ZERO, OUT_HALF>;
     // (prefiltered: the coefficients of the stretch behind the FFT's tables; up to 373 knots keep four workgroups on a CU)
     const size_t lds = (size_t)F::LDS_BYTES + (coef ? (((size_t)2 * (spline->ne + 2) * sizeof(double) + 15) / 16) * 16 : 0);
@@ -1582,8 +1547,5 @@ extern "C" int cp_fftlog_geospline_execute(const cp_fftlog_plan* fftlog, const c
     if (coef && few) hipLaunchKernelGGL((fftlog_geospline_kernel<true, 4>), dim3((unsigned)grid), dim3(NP / P), lds, static_cast<hipStream_t>(stream), R);
     else if (coef) hipLaunchKernelGGL((fftlog_geospline_kernel<true, GEO_QMAX>), dim3((unsigned)grid), dim3(NP / P), lds, static_cast<hipStream_t>(stream), R);
     else hipLaunchKernelGGL(fftlog_geospline_kernel<false>, dim3((unsigned)grid), dim3(NP / P), lds, static_cast<hipStream_t>(stream), R);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_fftlog_geospline_execute: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_fftlog_geospline_execute");
 }

@@ -607,15 +607,12 @@ bool cp_spline_plan_view(const cp_spline_plan* p, cp_spline_band_view* out) {
 
 extern "C" int cp_spline_plan_destroy(cp_spline_plan* p) {
     if (!p) return CP_OK;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != p->device) (void)hipSetDevice(p->device);
+    cp::DeviceScope scope(p->device);
     if (p->d_wb) (void)hipFree(p->d_wb);
     if (p->d_j0) (void)hipFree(p->d_j0);
     if (p->d_tile) (void)hipFree(p->d_tile);
     if (p->d_wdense) (void)hipFree(p->d_wdense);
     if (p->d_kwin) (void)hipFree(p->d_kwin);
-    if (prev >= 0 && prev != p->device) (void)hipSetDevice(prev);
     delete p;
     return CP_OK;
 }
@@ -844,10 +841,8 @@ static int plan_from_dense(cp_spline_plan** out, int n, int nq, const double* w,
             }
     p->col_last = std::min(p->col_last, n);
     p->col_first = std::min(p->col_first, p->col_last);
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    int status = CP_OK;
-    if (prev != device && hipSetDevice(device) != hipSuccess) status = cp::fail(CP_EDEVICE, "cp_spline_plan_create: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    int status = scope.ok() ? CP_OK : cp::fail(CP_EDEVICE, "cp_spline_plan_create: cannot select device %d", device);
     if (status == CP_OK && (hipMalloc(&p->d_wb, wb.size() * sizeof(double)) != hipSuccess || hipMalloc(&p->d_j0, nq * sizeof(int)) != hipSuccess ||
                             hipMalloc(&p->d_tile, tile.size() * sizeof(int)) != hipSuccess))
         status = cp::fail(CP_ENOMEM, "cp_spline_plan_create: device allocation failed");
@@ -861,7 +856,6 @@ static int plan_from_dense(cp_spline_plan** out, int n, int nq, const double* w,
          hipMalloc(&p->d_kwin, kwin.size() * sizeof(int)) != hipSuccess ||
          hipMemcpy(p->d_kwin, kwin.data(), kwin.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess))
         status = cp::fail(CP_ENOMEM, "cp_spline_plan_create: cannot upload the dense operator");
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
     if (status != CP_OK) {
         cp_spline_plan_destroy(p);
         return status;
@@ -933,9 +927,8 @@ extern "C" int cp_spline_apply_grouped(const cp_spline_plan* p, const double* d_
     const bool valu_fits = (size_t)4 * p->span_max * sizeof(double) <= 160 * 1024;
     if (p->d_wdense && path != CP_SPLINE_PATH_VALU &&
         ((p->prefer_dense && nrows >= 16) || path == CP_SPLINE_PATH_MFMA || !valu_fits)) {   // dense operator: GEMM on the matrix cores
-        int prev = -1;
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != p->device && hipSetDevice(p->device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_spline_apply: cannot select device %d", p->device);
+        cp::DeviceScope scope(p->device);
+        if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_spline_apply: cannot select device %d", p->device);
         DenseArgs D;
         D.y = d_y; D.out = d_out; D.nrows = nrows; D.n = p->n; D.nq = p->nq; D.n_pad = p->n_pad; D.nq_pad = p->nq_pad; D.w = p->d_wdense; D.j0 = p->d_j0;
         D.kwin = p->d_kwin; D.post_op = post_op; D.scale = scale; D.group = group;
@@ -943,10 +936,7 @@ extern "C" int cp_spline_apply_grouped(const cp_spline_plan* p, const double* d_
         const int grid = (int)(items < 256 * 2 ? items : 256 * 2);
         if (p->sub_windows) hipLaunchKernelGGL(linop_mfma_kernel<true>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), D);
         else hipLaunchKernelGGL(linop_mfma_kernel<false>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), D);
-        const hipError_t e = hipGetLastError();
-        if (prev >= 0 && prev != p->device) (void)hipSetDevice(prev);
-        if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_spline_apply: launch failed: %s", hipGetErrorString(e));
-        return CP_OK;
+        return cp::launch_status("cp_spline_apply");
     }
     // rows per work item: as many as keep the staged knots within 64 KB of LDS (two workgroups per CU), and no more than there are rows
     int rows = 16;
@@ -955,18 +945,14 @@ extern "C" int cp_spline_apply_grouped(const cp_spline_plan* p, const double* d_
     if (lds > 160 * 1024)
         return cp::fail(CP_EUNSUPPORTED, "cp_spline_apply: one query couples to %d knots, more than the LDS staging buffer holds (max %d)", p->span_max,
                         160 * 1024 / 8 / 4);
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != p->device && hipSetDevice(p->device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_spline_apply: cannot select device %d", p->device);
+    cp::DeviceScope scope(p->device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_spline_apply: cannot select device %d", p->device);
     Args A;
     A.y = d_y; A.out = d_out; A.nrows = nrows; A.n = p->n; A.nq = p->nq; A.bw = p->bw; A.wb = p->d_wb; A.j0 = p->d_j0;
     A.tile = p->d_tile; A.ntiles = p->ntiles; A.span_max = p->span_max;
     A.post_op = post_op; A.scale = scale; A.group = group;
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    const hipError_t e = rows == 16 ? launch_apply<16>(A, lds, hs) : rows == 8 ? launch_apply<8>(A, lds, hs) : launch_apply<4>(A, lds, hs);
-    if (prev >= 0 && prev != p->device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_spline_apply: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_spline_apply", rows == 16 ? launch_apply<16>(A, lds, hs) : rows == 8 ? launch_apply<8>(A, lds, hs) : launch_apply<4>(A, lds, hs));
 }
 
 
@@ -983,9 +969,8 @@ extern "C" int cp_spline_apply_outer(const cp_spline_plan* p, const double* d_y,
     while (rows > 2 && (bytes(rows) > 64 * 1024 || rows / 2 >= nrows)) rows /= 2;
     const size_t lds = bytes(rows);
     if (lds > 160 * 1024) return cp::fail(CP_EUNSUPPORTED, "cp_spline_apply_outer: %d knots per query and %d factors per row exceed the LDS staging buffer", p->span_max, nz);
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != p->device && hipSetDevice(p->device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_spline_apply_outer: cannot select device %d", p->device);
+    cp::DeviceScope scope(p->device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_spline_apply_outer: cannot select device %d", p->device);
     OuterArgs O;
     Args& A = O.a;
     A.y = d_y; A.out = d_out; A.nrows = nrows; A.n = p->n; A.nq = p->nq; A.bw = p->bw; A.wb = p->d_wb; A.j0 = p->d_j0;
@@ -993,10 +978,7 @@ extern "C" int cp_spline_apply_outer(const cp_spline_plan* p, const double* d_y,
     A.post_op = post_op; A.scale = scale; A.group = 0;
     O.g = d_g; O.nz = nz;
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    const hipError_t e = rows == 8 ? launch_outer<8>(O, lds, hs) : rows == 4 ? launch_outer<4>(O, lds, hs) : launch_outer<2>(O, lds, hs);
-    if (prev >= 0 && prev != p->device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_spline_apply_outer: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_spline_apply_outer", rows == 8 ? launch_outer<8>(O, lds, hs) : rows == 4 ? launch_outer<4>(O, lds, hs) : launch_outer<2>(O, lds, hs));
 }
 
 
@@ -1009,19 +991,15 @@ extern "C" int cp_linop_apply_mid(const cp_spline_plan* p, const double* d_y, do
     if (post_op != CP_SPLINE_POST_NONE && post_op != CP_SPLINE_POST_SQRT && post_op != CP_SPLINE_POST_EXP10)
         return cp::fail(CP_EINVAL, "cp_linop_apply_mid: unknown post op %d", post_op);
     if (!p->d_wdense) return cp::fail(CP_EUNSUPPORTED, "cp_linop_apply_mid: the plan holds no dense operator (create it with cp_linop_plan_create)");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != p->device && hipSetDevice(p->device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_linop_apply_mid: cannot select device %d", p->device);
+    cp::DeviceScope scope(p->device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_linop_apply_mid: cannot select device %d", p->device);
     MidArgs M;
     M.y = d_y; M.out = d_out; M.nbatch = nbatch; M.ninner = ninner; M.n = p->n; M.nq = p->nq; M.n_pad = p->n_pad; M.nq_pad = p->nq_pad;
     M.w = p->d_wdense; M.j0 = p->d_j0; M.post_op = post_op; M.scale = scale;
     const long long items = nbatch * ((ninner + 64 * MID_NT - 1) / (64 * MID_NT)) * (p->nq_pad / 64);
     const int grid = (int)(items < 256 * 8 ? items : 256 * 8);
     hipLaunchKernelGGL(linop_mid_mfma_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), M);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != p->device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_linop_apply_mid: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_linop_apply_mid");
 }
 
 
@@ -1391,9 +1369,8 @@ extern "C" int cp_tables_rows(const cp_spline_plan* kplan, const cp_spline_plan*
     if (post_op < CP_SPLINE_POST_NONE || post_op > CP_SPLINE_POST_EXP10) return cp::fail(CP_EINVAL, "cp_tables_rows: unknown post op %d", post_op);
     if (!cp_tables_rows_available(kplan, zplan))
         return cp::fail(CP_EUNSUPPORTED, "cp_tables_rows: needs a k operator with a dense copy and a z operator of at most 32 knots and 64 queries");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != kplan->device && hipSetDevice(kplan->device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_tables_rows: cannot select device %d", kplan->device);
+    cp::DeviceScope scope(kplan->device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_tables_rows: cannot select device %d", kplan->device);
     TablesArgs T;
     T.t = d_tables; T.out = d_out; T.nbatch = nbatch;
     T.n = kplan->n; T.nq = kplan->nq; T.n_pad = kplan->n_pad; T.nq_pad = kplan->nq_pad; T.nzin = zplan->n; T.nzq = zplan->nq;
@@ -1405,10 +1382,7 @@ extern "C" int cp_tables_rows(const cp_spline_plan* kplan, const cp_spline_plan*
     if (post_op == CP_SPLINE_POST_EXP10) hipLaunchKernelGGL(tables_rows_kernel<CP_SPLINE_POST_EXP10>, dim3(grid), dim3(256), 0, hs, T);
     else if (post_op == CP_SPLINE_POST_SQRT) hipLaunchKernelGGL(tables_rows_kernel<CP_SPLINE_POST_SQRT>, dim3(grid), dim3(256), 0, hs, T);
     else hipLaunchKernelGGL(tables_rows_kernel<CP_SPLINE_POST_NONE>, dim3(grid), dim3(256), 0, hs, T);
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != kplan->device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_tables_rows: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_tables_rows");
 }
 
 extern "C" int cp_tables_rows_direct(const cp_spline_rows_plan* kplan, const cp_spline_plan* zplan, const double* d_tables, const double* d_m, double* d_out,
@@ -1425,9 +1399,8 @@ extern "C" int cp_tables_rows_direct(const cp_spline_rows_plan* kplan, const cp_
         return cp::fail(CP_EUNSUPPORTED, "cp_tables_rows_direct: %d wavenumbers (%d knots) per row exceed the 32-bit offsets inside a table", kv.nq, kv.n);
     if (!(zplan->d_wdense && zplan->n <= 32 && zplan->nq <= 64 && zplan->n_pad <= 32 && zplan->nq_pad == 64 && zplan->device == kv.device))
         return cp::fail(CP_EUNSUPPORTED, "cp_tables_rows_direct: needs a z operator of at most 32 knots and 64 queries on the device of the k plan");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != kv.device && hipSetDevice(kv.device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_tables_rows_direct: cannot select device %d", kv.device);
+    cp::DeviceScope scope(kv.device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_tables_rows_direct: cannot select device %d", kv.device);
     TablesDirectArgs T;
     T.t = d_tables; T.m = d_m; T.out = d_out; T.nbatch = nbatch;
     T.n = kv.n; T.nq = kv.nq; T.nzin = zplan->n; T.nzq = zplan->nq;
@@ -1444,10 +1417,7 @@ extern "C" int cp_tables_rows_direct(const cp_spline_rows_plan* kplan, const cp_
     };
     if (d_m) launch(std::false_type{});
     else launch(std::true_type{});
-    const hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != kv.device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_tables_rows_direct: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_tables_rows_direct");
 }
 
 // ---- clamped cubic spline through uniformly spaced knots with one run of knots removed -------------------------------------
@@ -1541,14 +1511,10 @@ extern "C" int cp_gap_spline(const double* d_y, const int* d_box, double* d_out,
     if (ncol == 0) return CP_OK;
     if (!d_y || !d_box || !d_out) return cp::fail(CP_EINVAL, "cp_gap_spline: null device pointer");
     if (ncol > 2147483647LL) return cp::fail(CP_EUNSUPPORTED, "cp_gap_spline: too many columns for one launch");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_gap_spline: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_gap_spline: cannot select device %d", device);
     hipLaunchKernelGGL(gap_spline_kernel, dim3((unsigned)ncol), dim3(64), 0, static_cast<hipStream_t>(stream), d_y, d_box, d_out, ncol, n);
-    hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_gap_spline: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_gap_spline");
 }
 
 
@@ -1600,15 +1566,11 @@ extern "C" int cp_wallish_box(const double* d_dd, long long ncol, int n, int mar
     if (ncol == 0) return CP_OK;
     if (!d_dd || !d_box) return cp::fail(CP_EINVAL, "cp_wallish_box: null device pointer");
     if ((ncol + 3) / 4 > 2147483647LL) return cp::fail(CP_EUNSUPPORTED, "cp_wallish_box: too many columns for one launch");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_wallish_box: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_wallish_box: cannot select device %d", device);
     hipLaunchKernelGGL(wallish_box_kernel, dim3((unsigned)((ncol + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), d_dd, ncol, n, margin_first,
                        margin_second, offset_first, offset_second, d_box);
-    hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_wallish_box: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_wallish_box");
 }
 
 
@@ -1739,13 +1701,9 @@ extern "C" int cp_spline_columns(const double* d_xk, const double* d_yk, long lo
     if (ncol < 0 || n < 3 || nq < 0) return cp::fail(CP_EINVAL, "cp_spline_columns: bad sizes");
     if (ncol == 0 || nq == 0) return CP_OK;
     if (!d_xk || !d_yk || !d_xq || !d_out || !d_scratch) return cp::fail(CP_EINVAL, "cp_spline_columns: null device pointer");
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_spline_columns: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_spline_columns: cannot select device %d", device);
     hipLaunchKernelGGL(column_spline_kernel, dim3((unsigned)((ncol + 63) / 64 * column_parts(n))), dim3(64), 0, static_cast<hipStream_t>(stream), d_xk, d_yk,
                        ncol, n, d_xq, nq, d_out, d_scratch);
-    hipError_t e = hipGetLastError();
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_spline_columns: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_spline_columns");
 }

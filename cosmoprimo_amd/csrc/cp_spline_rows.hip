@@ -199,13 +199,10 @@ struct cp_spline_rows_plan {
 
 extern "C" int cp_spline_rows_plan_destroy(cp_spline_rows_plan* p) {
     if (!p) return CP_OK;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != p->device) (void)hipSetDevice(p->device);
+    cp::DeviceScope scope(p->device);
     if (p->d_tab) (void)hipFree(p->d_tab);
     if (p->d_qj) (void)hipFree(p->d_qj);
     if (p->d_qw) (void)hipFree(p->d_qw);
-    if (prev >= 0 && prev != p->device) (void)hipSetDevice(prev);
     delete p;
     return CP_OK;
 }
@@ -316,15 +313,12 @@ extern "C" int cp_spline_rows_plan_create(cp_spline_rows_plan** out, int n, cons
     p->T.fix_last = bc == CP_SPLINE_NOT_A_KNOT && w1 == n;
     for (int i = 0; i < 4; ++i) p->T.fix[i] = fix[i];
     p->T.n_src = n; p->T.w0 = w0; p->T.nw = nw; p->T.nq = nq; p->T.S = S; p->T.halo = halo; p->T.R = R; p->T.nslots = nslots;
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    bool ok = prev == device || hipSetDevice(device) == hipSuccess;
-    ok = ok && hipMalloc(&p->d_tab, tab.size() * sizeof(double)) == hipSuccess && hipMalloc(&p->d_qj, qj.size() * sizeof(int)) == hipSuccess &&
-         hipMalloc(&p->d_qw, qw.size() * sizeof(double)) == hipSuccess &&
-         hipMemcpy(p->d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(p->d_qj, qj.data(), qj.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(p->d_qw, qw.data(), qw.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-    if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
+    cp::DeviceScope scope(device);
+    const bool ok = scope.ok() && hipMalloc(&p->d_tab, tab.size() * sizeof(double)) == hipSuccess && hipMalloc(&p->d_qj, qj.size() * sizeof(int)) == hipSuccess &&
+                    hipMalloc(&p->d_qw, qw.size() * sizeof(double)) == hipSuccess &&
+                    hipMemcpy(p->d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemcpy(p->d_qj, qj.data(), qj.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemcpy(p->d_qw, qw.data(), qw.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) {
         cp_spline_rows_plan_destroy(p);
         return cp::fail(CP_ENOMEM, "cp_spline_rows_plan_create: cannot place the tables on device %d", device);
@@ -343,7 +337,7 @@ extern "C" int cp_spline_rows_plan_info(const cp_spline_rows_plan* p, int* first
     return CP_OK;
 }
 
-static int launch_rows(const cp_spline_rows_plan* p, const RowsArgs& A, long long nrows, void* stream) {
+static int launch_rows(const char* who, const cp_spline_rows_plan* p, const RowsArgs& A, long long nrows, void* stream) {
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess || ncu <= 0) ncu = 256;
     const long long blocks = ((nrows + p->T.R - 1) / p->T.R + 3) / 4;
@@ -357,9 +351,7 @@ static int launch_rows(const cp_spline_rows_plan* p, const RowsArgs& A, long lon
     if (p->T.R == 4) hipLaunchKernelGGL(spline_rows_kernel<4>, dim3(grid), dim3(256), p->lds_bytes, hs, A);
     else if (p->T.R == 2) hipLaunchKernelGGL(spline_rows_kernel<2>, dim3(grid), dim3(256), p->lds_bytes, hs, A);
     else hipLaunchKernelGGL(spline_rows_kernel<1>, dim3(grid), dim3(256), p->lds_bytes, hs, A);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_spline_rows: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status(who);
 }
 
 extern "C" int cp_spline_rows_apply(const cp_spline_rows_plan* p, const double* d_y, long long nrows, int post_op, double scale, int group, double* d_out,
@@ -370,15 +362,12 @@ extern "C" int cp_spline_rows_apply(const cp_spline_rows_plan* p, const double* 
     if (!d_y || !d_out) return cp::fail(CP_EINVAL, "cp_spline_rows_apply: null device pointer");
     if (post_op != CP_SPLINE_POST_NONE && post_op != CP_SPLINE_POST_SQRT) return cp::fail(CP_EINVAL, "cp_spline_rows_apply: post op %d (none or sqrt)", post_op);
     if (group < 0 || (group > 0 && nrows % group != 0)) return cp::fail(CP_EINVAL, "cp_spline_rows_apply: %lld rows are not whole groups of %d", nrows, group);
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != p->device && hipSetDevice(p->device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_spline_rows_apply: cannot select device %d", p->device);
+    cp::DeviceScope scope(p->device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_spline_rows_apply: cannot select device %d", p->device);
     RowsArgs A;
     A.T = p->T;
     A.y = d_y; A.nrows = nrows; A.post_op = post_op; A.group = group; A.scale = scale; A.out = d_out; A.out_m = nullptr; A.pairs = 0;
-    const int st = launch_rows(p, A, nrows, stream);
-    if (prev >= 0 && prev != p->device) (void)hipSetDevice(prev);
-    return st;
+    return launch_rows("cp_spline_rows_apply", p, A, nrows, stream);
 }
 
 static int second_derivatives(const cp_spline_rows_plan* p, const double* d_y, long long nrows, double* d_m, int pairs, void* stream);
@@ -399,15 +388,12 @@ static int second_derivatives(const cp_spline_rows_plan* p, const double* d_y, l
     if (!d_y || !d_m) return cp::fail(CP_EINVAL, "cp_spline_rows_second_derivatives: null device pointer");
     if (p->T.w0 != 0 || p->T.nw != p->T.n_src)
         return cp::fail(CP_EUNSUPPORTED, "cp_spline_rows_second_derivatives: the plan solves the knots %d .. %d only (its queries do not span the knots)", p->T.w0, p->T.w0 + p->T.nw - 1);
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != p->device && hipSetDevice(p->device) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_spline_rows_second_derivatives: cannot select device %d", p->device);
+    cp::DeviceScope scope(p->device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_spline_rows_second_derivatives: cannot select device %d", p->device);
     RowsArgs A;
     A.T = p->T;
     A.y = d_y; A.nrows = nrows; A.post_op = CP_SPLINE_POST_NONE; A.group = 0; A.scale = 1.; A.out = nullptr; A.out_m = d_m; A.pairs = pairs;
-    const int st = launch_rows(p, A, nrows, stream);
-    if (prev >= 0 && prev != p->device) (void)hipSetDevice(prev);
-    return st;
+    return launch_rows("cp_spline_rows_second_derivatives", p, A, nrows, stream);
 }
 
 // what the two-direction kernel of cp_spline.hip needs of a plan whose queries are the output wavenumbers of (z, k) tables (cp_internal.h)

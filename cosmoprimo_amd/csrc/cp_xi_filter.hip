@@ -16,6 +16,7 @@
 
 #include "../../include/cosmoprimo_amd.h"
 #include "cp_error.h"
+#include "cp_internal.h"
 
 namespace {
 
@@ -246,18 +247,6 @@ __global__ __launch_bounds__(BLOCK) void kirkby_rows_any_kernel(Args A) {
     }
 }
 
-struct DeviceScope {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceScope(int device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != device) ok = hipSetDevice(device) == hipSuccess;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
@@ -291,8 +280,8 @@ extern "C" int cp_kirkby2013_rows(const double* d_xi, double* d_xinow, long long
     A.ns = ns;
     A.fit_begin = fit_begin;
     A.fit_end = fit_end;
-    DeviceScope scope(device);
-    if (!scope.ok) return cp::fail(CP_EDEVICE, "cp_kirkby2013_rows: cannot select device %d", device);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_kirkby2013_rows: cannot select device %d", device);
     const long long blocks = (nrows + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     const unsigned grid = (unsigned)(blocks < 2048 ? blocks : 2048);      // a wave per row, 8 workgroups per CU at most; the waves walk the rest
     const bool in_registers = ns % 2 == 0 && ns <= 128 * NV && aligned16(d_xi) && aligned16(d_xinow) && aligned16(d_s);
@@ -300,7 +289,5 @@ extern "C" int cp_kirkby2013_rows(const double* d_xi, double* d_xinow, long long
         hipLaunchKernelGGL(kirkby_rows_kernel, dim3(grid), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), A);
     else
         hipLaunchKernelGGL(kirkby_rows_any_kernel, dim3(grid), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), A);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return cp::fail(CP_EDEVICE, "cp_kirkby2013_rows: launch failed: %s", hipGetErrorString(e));
-    return CP_OK;
+    return cp::launch_status("cp_kirkby2013_rows");
 }
