@@ -36,6 +36,7 @@ struct cp_fftlog_plan {
     double* d_post;
     cplx* d_u;
     cplx* d_tw;
+    unsigned* d_ticket;      // CP_CU_SLOTS arrival counters, zeroed once here and never again (cp_fftlog_kernel.h: balances_cu)
     cp_fftlog_large* large;  // Np > CP_FFTLOG_MAX_NP: the general-size path (cp_fftlog_large.hip), everything above unused
 };
 
@@ -85,6 +86,7 @@ extern "C" int cp_fftlog_plan_create(cp_fftlog_plan** out, int n, int npad, int 
         p->out_left = (npad - n) - (npad - n) / 2;
         p->d_pre = p->d_post = nullptr;
         p->d_u = p->d_tw = nullptr;
+        p->d_ticket = nullptr;
         p->large = nullptr;
         cp::DeviceScope scope(device);
         int st = scope.ok() ? cp_fftlog_large_create(&p->large, n, npad, nker, pre, post, u_re_im, device)
@@ -112,6 +114,7 @@ extern "C" int cp_fftlog_plan_create(cp_fftlog_plan** out, int n, int npad, int 
     p->l = l;
     p->d_pre = p->d_post = nullptr;
     p->d_u = p->d_tw = nullptr;
+    p->d_ticket = nullptr;
     {
         cp::DeviceScope scope(device);
         std::vector<cplx> tw, u((size_t)nker * npad);
@@ -130,14 +133,17 @@ extern "C" int cp_fftlog_plan_create(cp_fftlog_plan** out, int n, int npad, int 
         CP_HIP(hipMemcpy(p->d_post, post, tbytes, hipMemcpyHostToDevice));
         CP_HIP(hipMemcpy(p->d_u, u.data(), u.size() * sizeof(cplx), hipMemcpyHostToDevice));
         CP_HIP(hipMemcpy(p->d_tw, tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice));
+        CP_HIP(hipMalloc(&p->d_ticket, CP_CU_SLOTS * sizeof(unsigned)));
+        CP_HIP(hipMemset(p->d_ticket, 0, CP_CU_SLOTS * sizeof(unsigned)));  // before the plan exists for any caller: nothing to race with
         int ncu = 0;
         CP_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
         for (int v = 0; v < VAR_COUNT; ++v) {
             p->max_grid[v] = 0;
             if (!l.func[v]) continue;
-            if (l.lds_bytes > 64 * 1024) CP_HIP(hipFuncSetAttribute(l.func[v], hipFuncAttributeMaxDynamicSharedMemorySize, l.lds_bytes));
+            const int lds_v = l.lds_bytes + l.lds_extra[v];
+            if (lds_v > 64 * 1024) CP_HIP(hipFuncSetAttribute(l.func[v], hipFuncAttributeMaxDynamicSharedMemorySize, lds_v));
             int nblk = 0;
-            CP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, l.func[v], l.block, l.lds_bytes));
+            CP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, l.func[v], l.block, lds_v));
             if (nblk < 1) {
                 status = cp::fail(CP_EDEVICE, "cp_fftlog_plan_create: kernel variant %d for npad=%d does not fit on a CU", v, npad);
                 goto done;
@@ -162,6 +168,7 @@ extern "C" int cp_fftlog_plan_destroy(cp_fftlog_plan* p) {
         if (p->d_post) (void)hipFree(p->d_post);
         if (p->d_u) (void)hipFree(p->d_u);
         if (p->d_tw) (void)hipFree(p->d_tw);
+        if (p->d_ticket) (void)hipFree(p->d_ticket);
         cp_fftlog_large_destroy(p->large);
     }
     delete p;
@@ -181,9 +188,10 @@ extern "C" int cp_fftlog_plan_info(const cp_fftlog_plan* p, long long nbatch, in
         if (lds_bytes) *lds_bytes = 0;
         return CP_OK;
     }
-    if (grid) *grid = grid_for(p, select_variant(p->npad, p->l.p, p->n, 0, 0., 0, 0., 0), nbatch);
+    const int variant = select_variant(p->npad, p->l.p, p->n, 0, 0., 0, 0., 0);
+    if (grid) *grid = grid_for(p, variant, nbatch);
     if (block) *block = p->l.block;
-    if (lds_bytes) *lds_bytes = p->l.lds_bytes;
+    if (lds_bytes) *lds_bytes = p->l.lds_bytes + p->l.lds_extra[variant];
     return CP_OK;
 }
 
@@ -221,6 +229,7 @@ static int execute_impl(const cp_fftlog_plan* p, const double* d_in, double* d_o
     A.post = p->d_post;
     A.u = p->d_u;
     A.tw = p->d_tw;
+    A.cu_ticket = p->d_ticket;
     A.out_first = 0;
     A.out_last = A.n_out;
     cp::DeviceScope scope(p->device);

@@ -91,8 +91,11 @@ struct FftlogArgs {
     const cplx* u;      // (nker, NP) Hermitian-extended u / NP in thread layout [(i R + s) T + t]
     const cplx* tw;     // concatenated per-pass twiddles, Plan::tw_offset
     int out_first, out_last;  // OUT_HALF_WINDOW only: the columns of an output row that are stored
+    unsigned* cu_ticket;  // one arrival counter per CU (CP_CU_SLOTS entries, never reset: cp_fftlog_kernel.h, balances_cu)
 #if defined(CP_STAMPS)
     double* val_stamp;  // diagnostic builds: per-wave cycle sums
+    unsigned long long* bar_log;  // per workgroup: CU identity, start clock, two barrier clocks per pair (null: not recorded)
+    int bar_log_pairs;            // pairs per workgroup the log has room for
 #endif
 };
 

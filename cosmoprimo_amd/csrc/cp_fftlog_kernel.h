@@ -16,6 +16,7 @@ struct Launcher {
     const void* func[VAR_COUNT];
     void (*launch)(int variant, const FftlogArgs&, int grid, hipStream_t stream);
     int np, p, block, lds_bytes;
+    int lds_extra[VAR_COUNT];  // dynamic LDS a variant asks for beyond lds_bytes (the ticket word of a variant that balances its CU)
     void (*build_tw)(std::vector<cplx>&);
     void (*build_u)(const double*, cplx*);
 };
@@ -30,9 +31,10 @@ bool find_launcher_g4(int npad, Launcher* out);
 #if defined(__HIPCC__)
 #if defined(CP_STAMPS)
 // diagnostic build (tools/fftlog_microbench.hip -DCP_STAMPS): per-wave cycle sums of each phase's work and barrier wait
-// (cp_stamp: cp_fft_core.h)
-#define CP_STAMP_DECL , unsigned long long* cp_stamp_acc
-#define CP_STAMP_ARG , cp_stamp_acc
+// (cp_stamp: cp_fft_core.h), and for wave 0 of every workgroup the clock at which it left each of the pair's two workgroup
+// barriers (cp_bar_log: null in the other waves), from which the host derives the offset between the workgroups of a CU
+#define CP_STAMP_DECL , unsigned long long *cp_stamp_acc, unsigned long long *cp_bar_log
+#define CP_STAMP_ARG , cp_stamp_acc, cp_bar_log
 #else
 #define CP_STAMP_DECL
 #define CP_STAMP_ARG
@@ -59,7 +61,11 @@ __device__ __forceinline__ void run_phases(int t, const FftlogArgs& A, const dou
             __syncthreads();
         }
 #if defined(CP_STAMPS)
-        cp_stamp_acc[2 * PH + 1] += cp_stamp() - s1;
+        const unsigned long long s2 = cp_stamp();
+        cp_stamp_acc[2 * PH + 1] += s2 - s1;
+        if constexpr (!F::template barrier_free_after<PH>()) {
+            if (cp_bar_log && (threadIdx.x & 63) == 0) cp_bar_log[PH == 0 ? 0 : 1] = s2;
+        }
 #endif
         run_phases<NP, P, IM, OM, PH + 1>(t, A, ra, rb, oa, ob, has_b, ker, lds, nra, nrb, nxt_ker, st CP_STAMP_ARG);
     }
@@ -122,6 +128,36 @@ __device__ __forceinline__ void pair_walk_next(const FftlogArgs& A, PairWalk& w,
     pair_walk_flags(A, w);
 }
 
+// The CU a wave runs on: XCC_ID (bits 3:0) above the SE / SH / CU fields of HW_ID (bits 15:8); CP_CU_SLOTS values.
+#define CP_CU_SLOTS 4096
+#if defined(__HIPCC__)
+__device__ __forceinline__ unsigned cp_cu_id() {
+    unsigned hw, xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    return ((xcc & 0xfu) << 8) | ((hw >> 8) & 0xffu);
+}
+#endif
+
+// Balancing the two workgroups of a CU (profiles/headline_lockstep_before.txt).  At equal priority the hardware serves the older
+// of the two waves of a SIMD first, all the time: the workgroup that arrived first on a CU runs its pairs in two thirds of the
+// time the other needs, finishes early, and the CU spends the last quarter of the launch with one workgroup -- 1.4 times slower
+// per pair than with two.  So each workgroup takes a ticket from its CU's counter (FftlogArgs::cu_ticket) and the two trade the
+// priority once, at the same moment: the one with the odd ticket runs its first CP_BALANCE_PCT % of pairs at priority 1 and the
+// rest at 0, the one with the even ticket its first (100 - CP_BALANCE_PCT) % at 0 and the rest at 1.  Whichever of them is the
+// older, each is the fast one for half of the time and both finish together.  Only the parity of the ticket is used, so the
+// counters are never reset (two arrivals on a CU differ whatever the count was) and launches that share them on several streams
+// cannot disturb each other's results: the ticket decides when a wave is served, never what it computes.
+// CP_BALANCE_PCT: 65 measured best of 50 ... 90 (profiles/headline_stagger_ab.txt); 0 = off (the "before" of tools/mb_lockstep.sh).
+#ifndef CP_BALANCE_PCT
+#define CP_BALANCE_PCT 65
+#endif
+#define CP_BALANCE_LDS 16  // bytes behind Fftlog::LDS_BYTES that carry the ticket from thread 0 to the workgroup
+template <int NP, int P, int IM, int OM>
+constexpr bool balances_cu() {  // the headline instantiation only: nothing else is measured to gain
+    return CP_BALANCE_PCT > 0 && CP_ABLATE == 0 && NP == 4096 && P == 16 && IM == IN_HALF_ZERO && OM == OUT_HALF;
+}
+
 // One workgroup = T threads = one packed pair of rows per loop iteration (persistent over pairs).
 // Occupancy target: the LDS footprint (16 NP bytes per workgroup) allows 2 workgroups per CU at
 // NP = 4096, i.e. 2 waves per SIMD, so the register budget is 256 VGPR+AGPR per lane.
@@ -145,12 +181,24 @@ __global__ __launch_bounds__(NP / P, CP_WAVES_PER_SIMD) void fftlog_kernel(const
         const double* ra = A.in + cur.in_off;
         F::init_state(t, A, ra, ra + (cur.has_b ? walk.in_b : 0u), cur.ker, st);
     }
+    constexpr bool BALANCE = balances_cu<NP, P, IM, OM>();
+    if constexpr (BALANCE) {  // published by the barrier below (NPASS > 1)
+        if (threadIdx.x == 0) reinterpret_cast<unsigned*>(smem + F::LDS_BYTES)[0] = atomicAdd(A.cu_ticket + cp_cu_id(), 1u) & 1u;
+    }
     if constexpr (F::NPASS > 1) {
         F::fill_lds_tables(t, A, lds);
         // row screening of the first pair (HALF variants; later pairs are screened a pair ahead inside the loop)
         F::screen_prefetched(t, st.t0, A, cur.ker, lds, st);
         __syncthreads();
         if constexpr (F::SCREEN_AHEAD) st.info_nxt = F::screen_collect(lds);
+    }
+    int bal_odd = 0, bal_switch = -1, bal_k = 0;  // ticket parity; the pair in front of which the priority changes; pairs begun
+    if constexpr (BALANCE) {
+        bal_odd = __builtin_amdgcn_readfirstlane((int)reinterpret_cast<unsigned*>(smem + F::LDS_BYTES)[0]);
+        const int mine = (int)((npairs - blockIdx.x + gridDim.x - 1) / gridDim.x);  // pairs of this workgroup
+        const int first = (mine * CP_BALANCE_PCT + 50) / 100;
+        bal_switch = bal_odd ? first : mine - first;
+        if (bal_odd) __builtin_amdgcn_s_setprio(1);
     }
     // Drain the one-off loads here.  Otherwise the compiler's wait-count merge at the loop head must also cover this
     // entry path (where the row prefetch is the YOUNGEST operation) and emits vmcnt(0) at the top of every pair, which
@@ -163,8 +211,21 @@ __global__ __launch_bounds__(NP / P, CP_WAVES_PER_SIMD) void fftlog_kernel(const
     unsigned long long cp_stamp_acc[2 * F::NPH] = {0};
     for (int i = 0; i < 8; ++i) st.fs[i] = 0;
     const unsigned long long cp_t_begin = cp_stamp();
+    // barrier log of the workgroup (wave 0 writes it): [0] CU identity, [1] clock at loop entry, then two barrier clocks per pair
+    unsigned long long* cp_bar_log = nullptr;
+    if (A.bar_log && __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0) {
+        cp_bar_log = A.bar_log + (size_t)blockIdx.x * (2 + 2 * (size_t)A.bar_log_pairs);
+        if (threadIdx.x == 0) cp_bar_log[0] = cp_cu_id(), cp_bar_log[1] = cp_t_begin;
+        cp_bar_log += 2;
+    }
 #endif
     for (;;) {
+        if constexpr (BALANCE) {
+            if (bal_k++ == bal_switch) {
+                if (bal_odd) __builtin_amdgcn_s_setprio(0);
+                else __builtin_amdgcn_s_setprio(1);
+            }
+        }
         const bool more = walk.p + gridDim.x < npairs;
         if (more) pair_walk_next(A, walk, gridDim.x);
         const PairRows nxt = walk.cur;  // == cur on the last pair: its prefetch re-reads the rows it already has
@@ -181,6 +242,7 @@ __global__ __launch_bounds__(NP / P, CP_WAVES_PER_SIMD) void fftlog_kernel(const
         // its LDS reads (Fftlog::phase), where the waves have just left the previous barrier and are still in step
 #if defined(CP_STAMPS)
         cp_stamp_acc[2 * F::NPH - 1] += cp_stamp() - sb;
+        if (cp_bar_log) cp_bar_log += 2;
 #endif
         cur = nxt;
     }
@@ -206,7 +268,8 @@ void launch_impl(int variant, const FftlogArgs& A, int grid, hipStream_t stream)
     constexpr int lds = Fftlog<NP, P>::LDS_BYTES;
     if constexpr (has_half<NP, P>()) {
         if (variant == VAR_HALF_ZERO) {
-            hipLaunchKernelGGL((fftlog_kernel<NP, P, IN_HALF_ZERO, OUT_HALF>), dim3(grid), dim3(T), lds, stream, A);
+            constexpr int extra = balances_cu<NP, P, IN_HALF_ZERO, OUT_HALF>() ? CP_BALANCE_LDS : 0;
+            hipLaunchKernelGGL((fftlog_kernel<NP, P, IN_HALF_ZERO, OUT_HALF>), dim3(grid), dim3(T), lds + extra, stream, A);
             return;
         }
         if (variant == VAR_HALF) {
@@ -227,12 +290,13 @@ void launch_impl(int variant, const FftlogArgs& A, int grid, hipStream_t stream)
 template <int NP, int P>
 Launcher make_launcher() {
     Launcher l;
-    for (int v = 0; v < VAR_COUNT; ++v) l.func[v] = nullptr;
+    for (int v = 0; v < VAR_COUNT; ++v) l.func[v] = nullptr, l.lds_extra[v] = 0;
     l.func[VAR_GENERIC] = reinterpret_cast<const void*>(&fftlog_kernel<NP, P, IN_GENERIC, OUT_GENERIC>);
     l.func[VAR_LOG] = reinterpret_cast<const void*>(&fftlog_kernel<NP, P, IN_LOG, OUT_GENERIC>);
     if constexpr (has_half<NP, P>()) {
         l.func[VAR_HALF] = reinterpret_cast<const void*>(&fftlog_kernel<NP, P, IN_HALF, OUT_HALF>);
         l.func[VAR_HALF_ZERO] = reinterpret_cast<const void*>(&fftlog_kernel<NP, P, IN_HALF_ZERO, OUT_HALF>);
+        if (balances_cu<NP, P, IN_HALF_ZERO, OUT_HALF>()) l.lds_extra[VAR_HALF_ZERO] = CP_BALANCE_LDS;
         l.func[VAR_HALF_ZERO_WINDOW] = reinterpret_cast<const void*>(&fftlog_kernel<NP, P, IN_HALF_ZERO, OUT_HALF_WINDOW>);
     }
     l.launch = &launch_impl<NP, P>;

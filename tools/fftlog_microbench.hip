@@ -4,8 +4,11 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DCP_ABLATE=0 -o mb0 tools/fftlog_microbench.hip
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <map>
 #include <vector>
 
 #include "../cosmoprimo_amd/csrc/cp_fftlog_kernel.h"
@@ -41,6 +44,7 @@ int main(int argc, char** argv) {
     constexpr int NP = MB_NP, P = MB_P, N = NP / 2;
     const long long nbatch = argc > 1 ? atoll(argv[1]) : 100000;
     const int reps = argc > 2 ? atoi(argv[2]) : 20;
+    const int warm = argc > 3 ? atoi(argv[3]) : 300;  // (a counter pass needs no settled clock: 0)
     std::vector<double> in((size_t)nbatch * N), pre(NP), post(NP), u(2 * (NP / 2 + 1));
     for (size_t i = 0; i < in.size(); ++i) in[i] = 1. + 1e-3 * (double)(i % 977);
     for (int i = 0; i < NP; ++i) pre[i] = 1. + 1e-4 * i, post[i] = 1. - 1e-5 * i;
@@ -74,7 +78,17 @@ int main(int argc, char** argv) {
     int ncu = 0;
     CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0));
     const int grid = ncu * MB_WGS_PER_CU;
-    constexpr int T = Plan<NP, P>::T, lds = Fftlog<NP, P>::LDS_BYTES;
+#if defined(CP_STAMPS)
+    // barrier log (cp_fftlog_kernel.h): every launch rewrites all of it, the last one is read back
+    const int log_pairs = (int)(((nbatch + 1) / 2 + grid - 1) / grid);
+    const size_t log_stride = 2 + 2 * (size_t)log_pairs;
+    CHECK(hipMalloc(&A.bar_log, (size_t)grid * log_stride * 8));
+    CHECK(hipMemset(A.bar_log, 0, (size_t)grid * log_stride * 8));
+    A.bar_log_pairs = log_pairs;
+#endif
+    CHECK(hipMalloc(&A.cu_ticket, CP_CU_SLOTS * sizeof(unsigned)));
+    CHECK(hipMemset(A.cu_ticket, 0, CP_CU_SLOTS * sizeof(unsigned)));
+    constexpr int T = Plan<NP, P>::T, lds = Fftlog<NP, P>::LDS_BYTES + CP_BALANCE_LDS;  // (the ticket word: the headline variant uses it)
 #if MB_GENERIC == 2  // 'edge' padding through the HALF front end
     auto kern = fftlog_kernel<NP, P, IN_HALF, OUT_HALF>;
 #elif MB_GENERIC
@@ -87,7 +101,7 @@ int main(int argc, char** argv) {
     CHECK(hipEventCreate(&e0));
     CHECK(hipEventCreate(&e1));
     // reach the sustained device state first: the first tens of milliseconds of load after an idle period run ~10 % slower (clock ramp)
-    for (int i = 0; i < 300; ++i) hipLaunchKernelGGL(kern, dim3(grid), dim3(T), lds, 0, A);
+    for (int i = 0; i < warm; ++i) hipLaunchKernelGGL(kern, dim3(grid), dim3(T), lds, 0, A);
     CHECK(hipDeviceSynchronize());
     CHECK(hipEventRecord(e0));
     for (int i = 0; i < reps; ++i) hipLaunchKernelGGL(kern, dim3(grid), dim3(T), lds, 0, A);
@@ -113,6 +127,98 @@ int main(int argc, char** argv) {
         printf("fine: reads landed ph1..4 = %.0f %.0f %.0f %.0f | U applied %.0f | last twiddles applied %.0f | barrier in last phase %.0f\n",
                avg[2 * NPH + 2] / npw, avg[2 * NPH + 3] / npw, avg[2 * NPH + 4] / npw, avg[2 * NPH + 5] / npw, avg[2 * NPH + 6] / npw,
                avg[2 * NPH + 7] / npw, avg[2 * NPH + 8] / npw);
+        // ---- offset between the workgroups that share a CU (last launch) ---------------------------------------------------
+        std::vector<unsigned long long> lg((size_t)grid * log_stride);
+        CHECK(hipMemcpy(lg.data(), A.bar_log, lg.size() * 8, hipMemcpyDeviceToHost));
+        const long long npairs = (nbatch + 1) / 2;
+        auto pairs_of = [&](int b) { return (int)((npairs - b + grid - 1) / grid); };
+        std::map<unsigned long long, std::vector<int>> by_cu;
+        for (int b = 0; b < grid && b < npairs; ++b) by_cu[lg[(size_t)b * log_stride]].push_back(b);
+        int share[4] = {0, 0, 0, 0};  // CUs holding 1, 2, 3, more workgroups
+        for (auto& kv : by_cu) share[std::min<size_t>(kv.second.size(), 4) - 1]++;
+        // period of a pair and of a phase from the log itself
+        double period = 0;
+        long long nper = 0;
+        for (int b = 0; b < grid && b < npairs; ++b) {
+            const int np_b = pairs_of(b);
+            if (np_b < 2) continue;
+            const unsigned long long* q = &lg[(size_t)b * log_stride + 2];
+            period += (double)(q[2 * (np_b - 1)] - q[0]) / (np_b - 1);
+            ++nper;
+        }
+        period = nper ? period / nper : 1.;
+        const double phase_len = period / NPH;
+        constexpr int NB = 10;
+        long long h_pair[NB] = {0}, h_phase[NB] = {0}, nobs = 0;
+        const int marks[] = {0, 1, 2, 5, 10, 20, 50, 97};
+        double abs_at[8] = {0}, fold_at[8] = {0};
+        long long n_at[8] = {0};
+        for (auto& kv : by_cu) {
+            if (kv.second.size() != 2) continue;
+            const int a = kv.second[0], b = kv.second[1];
+            const int np_ab = std::min(pairs_of(a), pairs_of(b));
+            for (int k = 0; k < np_ab; ++k)
+                for (int w = 0; w < 2; ++w) {  // both barriers of the pair
+                    const double d = (double)(long long)(lg[(size_t)a * log_stride + 2 + 2 * k + w] - lg[(size_t)b * log_stride + 2 + 2 * k + w]);
+                    double fp = std::fmod(std::fabs(d), period) / period;        // in pairs, folded to [0, 1/2]
+                    if (fp > 0.5) fp = 1. - fp;
+                    double fh = std::fmod(std::fabs(d), phase_len) / phase_len;  // in phases, folded to [0, 1/2]
+                    if (fh > 0.5) fh = 1. - fh;
+                    h_pair[std::min(NB - 1, (int)(fp * 2 * NB))]++;
+                    h_phase[std::min(NB - 1, (int)(fh * 2 * NB))]++;
+                    ++nobs;
+                    if (w == 0)
+                        for (int m = 0; m < 8; ++m)
+                            if (marks[m] == k) abs_at[m] += std::fabs(d), fold_at[m] += fh, n_at[m]++;
+                }
+        }
+        // ---- do the two workgroups of a CU advance at the same rate?  (the last barrier of a workgroup's last pair = its end)
+        double alone = 0, per_fast = 0, per_slow = 0, older_first = 0, t_fast = 0, t_slow = 0;
+        long long h_alone[NB] = {0}, ncu2 = 0;
+        for (auto& kv : by_cu) {
+            if (kv.second.size() != 2) continue;
+            int a = kv.second[0], b = kv.second[1];
+            auto end_of = [&](int w) { return lg[(size_t)w * log_stride + 2 + 2 * (pairs_of(w) - 1) + 1]; };
+            auto start_of = [&](int w) { return lg[(size_t)w * log_stride + 1]; };
+            if (pairs_of(a) < 42 || pairs_of(b) < 42) continue;
+            if (end_of(a) > end_of(b)) std::swap(a, b);  // a finishes first
+            const unsigned long long t0 = std::min(start_of(a), start_of(b));
+            const double T = (double)(end_of(b) - t0), fa = (double)(end_of(b) - end_of(a)) / T;
+            alone += fa;
+            h_alone[std::min(NB - 1, (int)(fa * 2 * NB))]++;
+            auto per = [&](int w) { return (double)(lg[(size_t)w * log_stride + 2 + 2 * 40] - lg[(size_t)w * log_stride + 2 + 2 * 5]) / 35.; };
+            per_fast += per(a), per_slow += per(b);
+            t_fast += (double)(end_of(a) - t0), t_slow += T;
+            older_first += start_of(a) <= start_of(b) ? 1. : 0.;
+            ++ncu2;
+        }
+        if (ncu2) {
+            printf("rates of the two workgroups of a CU (%lld CUs): the first to finish takes %.0f ticks, the other %.0f; the CU holds ONE workgroup for %.3f of its time\n",
+                   ncu2, t_fast / ncu2, t_slow / ncu2, alone / ncu2);
+            printf("  pair period over pairs 5..40: first finisher %.0f ticks, the other %.0f; the first finisher is the one that started first on %.2f of the CUs\n",
+                   per_fast / ncu2, per_slow / ncu2, older_first / ncu2);
+            printf("  share of CUs by the fraction of time spent with one workgroup, bins of 0.05 from 0:");
+            for (int i = 0; i < NB; ++i) printf(" %.3f", (double)h_alone[i] / ncu2);
+            printf("\n");
+        }
+        printf("CU sharing: %d CUs hold 1 workgroup, %d hold 2, %d hold 3, %d more | pair period %.0f ticks, phase %.0f\n", share[0], share[1], share[2],
+               share[3], period, phase_len);
+        printf("offset between the two workgroups of a CU, same pair index and barrier, %lld observations; share per bin, uniform = %.3f\n", nobs, 1. / NB);
+        printf("  modulo a pair,  folded to [0, 1/2] pair,  bins of 1/%d:", 2 * NB);
+        for (int i = 0; i < NB; ++i) printf(" %.3f", nobs ? (double)h_pair[i] / nobs : 0.);
+        printf("\n  modulo a phase, folded to [0, 1/2] phase, bins of 1/%d:", 2 * NB);
+        for (int i = 0; i < NB; ++i) printf(" %.3f", nobs ? (double)h_phase[i] / nobs : 0.);
+        printf("\n  by pair index (first barrier): index / mean |offset| ticks / mean folded phase offset (uniform = 0.25):");
+        for (int m = 0; m < 8; ++m)
+            if (n_at[m]) printf("  %d / %.0f / %.3f", marks[m], abs_at[m] / n_at[m], fold_at[m] / n_at[m]);
+        printf("\n");
+        printf("JSON {\"ms\": %.4f, \"cus_with_2\": %d, \"first_finisher_ticks\": %.0f, \"other_ticks\": %.0f, \"one_workgroup_fraction\": %.3f, \"pair_ticks\": %.0f, \"reads_landed_ph1_3\": [%.0f, %.0f, %.0f], \"offset_mod_phase_hist\": [", ms, share[1], ncu2 ? t_fast / ncu2 : 0., ncu2 ? t_slow / ncu2 : 0.,
+               ncu2 ? alone / ncu2 : 0., period,
+               avg[2 * NPH + 2] / npw, avg[2 * NPH + 3] / npw, avg[2 * NPH + 4] / npw);
+        for (int i = 0; i < NB; ++i) printf("%s%.4f", i ? ", " : "", nobs ? (double)h_phase[i] / nobs : 0.);
+        printf("], \"offset_mod_pair_hist\": [");
+        for (int i = 0; i < NB; ++i) printf("%s%.4f", i ? ", " : "", nobs ? (double)h_pair[i] / nobs : 0.);
+        printf("]}\n");
     }
 #endif
     return 0;
