@@ -193,6 +193,11 @@ SIGNATURES['cp_kirkby2013_rows'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_voi
 SIGNATURES['cp_sigma8_normalise'] = (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
         ctypes.c_void_p, ctypes.c_void_p, cp_param, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_int, ctypes.c_void_p])
+SIGNATURES['cp_spline_tables_build'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_int, ctypes.c_void_p])
+for _name in ('cp_spline_tables_apply', 'cp_spline_tables_apply_f32'):
+    SIGNATURES[_name] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                        ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, _c_int_p, ctypes.c_int, ctypes.c_void_p])
 NCDM_NKNOTS = 119
 GROWTH_NKNOTS = 201
 

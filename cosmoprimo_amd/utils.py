@@ -4,7 +4,8 @@ Utilities with the reference's names (cosmoprimo/utils.py): :class:`LeastSquareS
 
 ``LeastSquareSolver`` is host-side numpy: it acts on <= 10 parameters x <= 1024 samples once per filter (SURVEY.md 8(a) a18:
 "negligible"); the BAO filters turn its solution into a dense operator that is applied to all columns on the device
-(:func:`cosmoprimo_amd.bao_filter._constrained_lsq_operator`).  ``DistanceToRedshift`` is a device spline (:class:`Interpolator1D`).
+(:func:`cosmoprimo_amd.bao_filter._constrained_lsq_operator`).  ``DistanceToRedshift`` is a device spline (:class:`Interpolator1D`); for a batch of cosmologies, one spline per cosmology solved and evaluated by
+``cp_spline_tables_build`` / ``cp_spline_tables_apply``.
 """
 import functools
 import inspect
@@ -177,13 +178,84 @@ class LeastSquareSolver(_Copyable):
 
 class DistanceToRedshift(_Copyable):
 
-    """Distance -> redshift conversion by spline interpolation of a tabulated redshift -> distance relation (reference utils.py:275-316)."""
+    """Distance -> redshift conversion by spline interpolation of a tabulated redshift -> distance relation (reference utils.py:275-316).
+
+    ``distance(zgrid)`` of shape ``(nz,)``: one cosmology, the reference's object.  Of shape ``(B, nz)`` (a numpy array or a device tensor, what the
+    distances of a batched cosmology return): B tables at once.  The table goes to (or stays on) the device, is never read back, and one kernel
+    solves the B splines (``cp_spline_tables_build``); ``interp_order`` 3 (natural cubic spline, the default) and 1 (linear) are available there,
+    other orders raise ``NotImplementedError``.
+
+    Deviation from a loop over the cosmologies with the reference's object: a cosmology of the batch whose distances are not
+    finite or not strictly ascending (corner cosmologies, closed models through ``comoving_transverse_distance``) gives a row of NaN and leaves
+    every other row alone, where the reference would raise or sort the table for that cosmology.
+    """
 
     def __init__(self, distance, zmax=100., nz=512, interp_order=3, device=None):
         zgrid = 1. / np.geomspace(1. / (1. + zmax), 1., nz)[::-1] - 1.
-        rgrid = np.asarray(distance(zgrid), dtype='f8')
+        rgrid = distance(zgrid)
+        self._batch = None
+        if len(getattr(rgrid, 'shape', ())) == 2:
+            self._init_batch(rgrid, zgrid, interp_order, device)
+            return
+        rgrid = np.asarray(rgrid, dtype='f8')
         self._interp = Interpolator1D(rgrid, zgrid, k=interp_order, device=device)
 
-    def __call__(self, distance, bounds_error=True):
-        """(Interpolated) redshift at ``distance`` (scalar or array)."""
+    def _init_batch(self, rgrid, zgrid, interp_order, device):
+        from . import _device as dv, _lib
+        if int(interp_order) not in (1, 3):
+            raise NotImplementedError('a batch of distance tables is interpolated linearly (interp_order=1) or by natural cubic splines (interp_order=3)')
+        torch = dv.torch()
+        self.device = dv.resolve_device(device, rgrid)
+        xk = dv.to_device(rgrid, self.device, cache=False)
+        nb, n = (int(v) for v in xk.shape)
+        if n < 2:
+            raise ValueError('at least two redshifts are needed')
+        coef = torch.empty((nb, n - 1, 4), dtype=torch.float64, device=self.device)
+        ok = torch.empty((nb,), dtype=torch.int32, device=self.device)
+        _lib.check(_lib.load().cp_spline_tables_build(xk.data_ptr(), dv.to_device(zgrid, self.device).data_ptr(), nb, n, int(interp_order), coef.data_ptr(),
+                                                      ok.data_ptr(), self.device.index, dv.stream_of(self.device)))
+        self._batch = (xk, coef, ok, torch.zeros((1,), dtype=torch.int32, device=self.device))
+
+    def _call_batch(self, distance, bounds_error, per_cosmology):
+        from . import _device as dv, _lib
+        import ctypes
+        torch = dv.torch()
+        xk, coef, ok, flag = self._batch
+        nb, n = (int(v) for v in xk.shape)
+        like_torch = _is_torch(distance)
+        single = _float_dtype(distance) == np.float32
+        tdtype = torch.float32 if single else torch.float64
+        if like_torch:
+            xq = distance.to(device=self.device, dtype=tdtype)
+        else:
+            xq = torch.from_numpy(np.array(distance, dtype='f4' if single else 'f8', ndmin=1)).to(self.device).reshape(np.shape(distance))
+        shape = tuple(xq.shape)
+        if per_cosmology:
+            if not shape or shape[0] != nb:
+                raise ValueError('per_cosmology=True takes distances of shape ({:d}, ...), one set per cosmology; got {}'.format(nb, shape))
+        else:
+            shape = (nb,) + shape
+        xq = xq.contiguous()
+        nq = xq.numel() // nb if per_cosmology else xq.numel()
+        out = torch.empty((nb, nq), dtype=tdtype, device=self.device)
+        outside = ctypes.c_int(0)
+        apply = _lib.load().cp_spline_tables_apply_f32 if single else _lib.load().cp_spline_tables_apply
+        _lib.check(apply(xk.data_ptr(), coef.data_ptr(), ok.data_ptr(), nb, n, xq.data_ptr(), int(bool(per_cosmology)), nq, out.data_ptr(), flag.data_ptr(),
+                         ctypes.byref(outside) if bounds_error else None, self.device.index, dv.stream_of(self.device)))
+        if outside.value:
+            raise ValueError('input outside of the distance table of its cosmology')
+        out = out.reshape(shape)
+        return out if like_torch else dv.to_host(out)
+
+    def __call__(self, distance, bounds_error=True, per_cosmology=False):
+        """(Interpolated) redshift at ``distance`` (scalar or array).
+
+        With a batch of B tables: distances of shape S, shared by the cosmologies, give redshifts of shape (B,) + S; ``per_cosmology=True`` takes
+        (B,) + S, one set of distances per cosmology, and returns that shape.  numpy in, numpy out; a device tensor is not read back and the result
+        stays on its device; float32 in, float32 out (computed in float64, rounded once).  ``bounds_error`` raises ``ValueError`` when a distance lies
+        outside the table of ITS cosmology (one flag is read back); without it such entries are NaN."""
+        if self._batch is not None:
+            return self._call_batch(distance, bounds_error, per_cosmology)
+        if per_cosmology:
+            raise ValueError('per_cosmology=True needs a batch of distance tables; this one holds one cosmology')
         return self._interp(distance, bounds_error=bounds_error)

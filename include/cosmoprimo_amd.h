@@ -620,6 +620,24 @@ int cp_interp_table_destroy(cp_interp_table* table);
 int cp_spline_points(const double* d_xk, const double* d_y, const double* d_s, long long n, int ncol, const double* d_xq, double* d_out, long long nq, int nu,
                      int extrapolate, int device, void* stream);
 
+/* ---- splines on per-row knots with shared values, at many points per row: the inverse of a monotonic table for a batch of cosmologies
+ *      (DistanceToRedshift over a batch, utils.py:275-316: Interpolator1D(rgrid, zgrid) per cosmology; csrc/cp_spline_tables.hip) ----
+ * build : d_xk (nrows, n) the rows' knots, d_y (n) the values all rows share, order 3 (natural cubic spline, scipy CubicSpline(bc_type='natural')) or
+ *   1 (linear, interp1d); n <= 4096 (CP_EUNSUPPORTED beyond: a row is solved in LDS).  d_coef (nrows, n - 1, 4): the polynomial coefficients
+ *   c0 .. c3 of every interval in powers of x - x_k (a query needs no division); d_ok (nrows): 0 for a row that holds a non-finite knot or is not
+ *   strictly ascending (its coefficients are not written), else 1.  No host read-back.
+ * apply : d_xq (nq) queries shared by the rows, or per_row != 0: (nrows, nq); d_out (nrows, nq).  Queries outside a row's own [x_0, x_{n-1}] and NaN
+ *   queries give NaN; rows with d_ok == 0 are NaN throughout.  outside (host, may be NULL): set to 1 when a query of a row that is ok lies outside
+ *   that row's knots or is NaN; asking for it needs d_flag (one device int the call clears and raises) and makes the call wait for the stream, NULL
+ *   leaves it asynchronous.  Rows with at least 4096 queries and at most 2048 knots are staged in LDS per workgroup; fewer queries per row (or
+ *   longer rows) are bisected in memory, one lane per (row, query); the two routes give bit-identical results.
+ *   _f32: single-precision queries and results, computed in double and rounded once. */
+int cp_spline_tables_build(const double* d_xk, const double* d_y, long long nrows, int n, int order, double* d_coef, int* d_ok, int device, void* stream);
+int cp_spline_tables_apply(const double* d_xk, const double* d_coef, const int* d_ok, long long nrows, int n, const double* d_xq, int per_row, long long nq,
+                           double* d_out, int* d_flag, int* outside, int device, void* stream);
+int cp_spline_tables_apply_f32(const double* d_xk, const double* d_coef, const int* d_ok, long long nrows, int n, const float* d_xq, int per_row,
+                               long long nq, float* d_out, int* d_flag, int* outside, int device, void* stream);
+
 /* ---- row screening utility (cp_fftlog_execute and cp_dst_execute screen their rows themselves; this pass is for callers that want
  *      the flags, e.g. to count or report the rows a batch loses) ----
  * d_x : (nrows, n) device.  d_ok[row] = 1 if every entry of the row is finite (and > 0 if require_positive: the fused log map of
