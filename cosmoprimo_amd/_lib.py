@@ -198,6 +198,9 @@ SIGNATURES['cp_spline_tables_build'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c
 for _name in ('cp_spline_tables_apply', 'cp_spline_tables_apply_f32'):
     SIGNATURES[_name] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                         ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, _c_int_p, ctypes.c_int, ctypes.c_void_p])
+SIGNATURES['cp_taylor_predict'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
+SIGNATURES['cp_taylor_fit'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
 NCDM_NKNOTS = 119
 GROWTH_NKNOTS = 201
 

@@ -1,0 +1,200 @@
+// cp_taylor.hip -- Taylor-expansion emulator of a calculator (reference emulators/tools/taylor.py:211-247) for batches of parameter points (gfx950)
+// + C ABI.  One GEMM kernel in float64 on the matrix cores (v_mfma_f64_16x16x4_f64) with two front ends for its left operand:
+//   predict : out (B, M) = monomials (B, T) . derivatives (T, M); the monomials of a tile of rows are formed in LDS, chunk of terms by chunk of terms,
+//             from x - center and the integer powers -- the (B, T) matrix never exists in memory
+//   fit     : derivatives (T, M) = S (T, npoints) . Y (npoints, M); S (the finite-difference weights of every term, built on the host) is staged
+//             through the same LDS tiles
+// Mapping.  A workgroup of four waves owns 64 rows x 256 columns of the result; the waves sit side by side in the columns on the same rows, each with
+// a tile of 64 x 64 (4 x 4 accumulator tiles of 16 x 16, 128 registers: the tile of linop_mfma_kernel, cp_spline.hip).  Fragments of the f64 form
+// (cdna_hip_programming.md): lane l supplies A[row = l & 15][k = l >> 4] and B[k = l >> 4][col = l & 15], and holds D[row = (l >> 4) + 4 r][col = l & 15]
+// in register r.  The right operand is row-major with the columns contiguous, so the 16 lanes of a k read 128 contiguous bytes; it is read straight
+// from L1 / L2 (a wave fetches 2 KB per 16 MFMAs = 8 B per matrix-core cycle, half of what linop_mfma_kernel needs, because the left operand comes
+// from LDS).  The row tiles run along grid x, which is dispatched first: the workgroups in flight share their 256 columns of the right operand in L2.
+// LDS.  The left operand of a chunk of TY_KC = 32 inner indices is stored k-major, a[k][row], with a row stride of 80 doubles: ds_read_b64 banks 32-lane
+// halves over 64 dwords, and a half holds two values of k (lanes l and l + 16), which a stride of 16 mod 32 doubles puts on opposite halves of the
+// bank row -- conflict-free reads; the writes of a term go to 64 consecutive doubles.  Two such buffers alternate, so a chunk costs one barrier;
+// 2 x 32 x 80 x 8 = 40 KB plus ndim x 64 x 8 (at most 16 KB) for x - center: two workgroups per CU at any T.
+// Monomials.  A wave forms whole terms, lane = row: the powers of a term are wave-uniform (scalar loads, uniform branches), factors with power 0 are
+// skipped -- they contribute exactly 1 whatever x - center holds (NaN, Inf: the reference's `where`, taylor.py:246) -- and a power is formed by repeated
+// multiplication.
+#include "cp_internal.h"
+
+namespace {
+
+typedef double ty_v4d __attribute__((ext_vector_type(4)));
+
+constexpr int TY_ROWS = 64, TY_COLS = 256, TY_KC = 32, TY_RS = 80, TY_MAX_NDIM = 32, TY_MAX_POWER = 15;
+
+struct TaylorArgs {
+    const double* a;        // GEN: x (R, ndim); else the left operand (R, K)
+    const double* center;   // (ndim)
+    const int* powers;      // (K, ndim)
+    const double* b;        // (K, M)
+    double* out;            // (R, M)
+    long long R;
+    int K, M, ndim;
+};
+
+// The operands of the eight inner indices k0 + 8 p .. + 7 of one chunk for one wave: two MFMA steps.  A row of the right operand past K is never read:
+// its place in the left operand is 0, and 0 x NaN would not be (row 0 is fetched in its place and masked by taylor_mask).
+__device__ __forceinline__ void taylor_load(const TaylorArgs& A, const double* buf, const int k0, const int p, const int l15, const int g, const int (&colj)[4],
+                                            double (&a)[2][4], double (&b)[2][4], bool (&keep)[2]) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int kk = 8 * p + 4 * h + g, k = k0 + kk;
+        const bool inside = k < A.K;
+        const double* br = A.b + (long long)(inside ? k : 0) * A.M;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) b[h][j] = br[colj[j]];
+        keep[h] = inside;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[h][i] = buf[kk * TY_RS + 16 * i + l15];
+    }
+}
+
+// ... and what was fetched for rows past K set to zero; kept apart from the loads so that nothing waits for them before the MFMAs they are to hide behind
+__device__ __forceinline__ void taylor_mask(double (&b)[2][4], const bool (&keep)[2]) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) b[h][j] = keep[h] ? b[h][j] : 0.;
+}
+
+template <bool GEN>
+__global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const TaylorArgs A) {
+    extern __shared__ double ty_lds[];
+    double* const abuf = ty_lds;                       // 2 x TY_KC x TY_RS
+    double* const dl = ty_lds + 2 * TY_KC * TY_RS;     // GEN: (ndim, 64) x - center of the tile's rows
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int l15 = lane & 15, g = lane >> 4;
+    const int nchunk = (A.K + TY_KC - 1) / TY_KC;
+    {      // one tile per workgroup (a loop over tiles here made the compiler keep the 64 store addresses of a lane alive through the MFMAs: spills)
+        const long long row0 = (long long)blockIdx.x * TY_ROWS;
+        const int col0 = (int)blockIdx.y * TY_COLS + wave * 64;
+        const bool active = col0 < A.M;      // (wave-uniform; an idle wave forms its share of the left operand and multiplies the last column: no branch round the MFMAs)
+        if (GEN) {
+            for (int e = threadIdx.x; e < A.ndim * TY_ROWS; e += 256) {
+                const int i = e >> 6;
+                const long long row = row0 + (e & 63);
+                dl[e] = row < A.R ? A.a[row * A.ndim + i] - A.center[i] : 0.;      // rows past the end: finite, never stored
+            }
+            __syncthreads();
+        }
+        ty_v4d acc[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = ty_v4d{0., 0., 0., 0.};
+        int colj[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int col = col0 + 16 * j + l15;
+            colj[j] = col < A.M ? col : A.M - 1;      // columns past the end repeat the last one (never stored)
+        }
+#pragma unroll 1
+        for (int c = 0; c < nchunk; ++c) {
+            double* const buf = abuf + (c & 1) * TY_KC * TY_RS;
+            const int k0 = c * TY_KC;
+            if (GEN) {
+                for (int tt = wave; tt < TY_KC; tt += 4) {      // a term per wave and step, a row per lane
+                    const int t = k0 + tt;
+                    double m = 0.;      // terms past T: zero columns of the left operand
+                    if (t < A.K) {
+                        m = 1.;
+                        const int* pw = A.powers + (long long)t * A.ndim;
+                        for (int i = 0; i < A.ndim; ++i) {
+                            int p = __builtin_amdgcn_readfirstlane(pw[i]);
+                            if (p <= 0) continue;
+                            p = p < TY_MAX_POWER ? p : TY_MAX_POWER;
+                            const double d = dl[i * TY_ROWS + lane];
+                            double v = d;
+                            for (int q = 1; q < p; ++q) v *= d;
+                            m *= v;
+                        }
+                    }
+                    buf[tt * TY_RS + lane] = m;
+                }
+            } else {
+                for (int e = threadIdx.x; e < TY_ROWS * TY_KC; e += 256) {
+                    const int r = e / TY_KC, kk = e % TY_KC;      // k along the lanes: the rows of S are contiguous in k
+                    const long long row = row0 + r;
+                    const int k = k0 + kk;
+                    buf[kk * TY_RS + r] = (row < A.R && k < A.K) ? A.a[row * A.K + k] : 0.;
+                }
+            }
+            __syncthreads();      // one barrier per chunk: the buffer written next was last read before this barrier
+            // One loop for full and partial chunks, and no branch round it: with the MFMAs on two paths the compiler kept two sets of accumulators and
+            // spilled.  Pairs of steps, the operands of the next pair fetched before the 32 MFMAs of this one (the last pair fetches itself again).
+            const int npairs = A.K - k0 >= TY_KC ? TY_KC / 8 : (A.K - k0 + 7) / 8;
+            double a0[2][4], b0[2][4];
+            bool keep[2];
+            taylor_load(A, buf, k0, 0, l15, g, colj, a0, b0, keep);
+            taylor_mask(b0, keep);
+#pragma unroll 1
+            for (int p = 0; p < npairs; ++p) {
+                double a1[2][4], b1[2][4];
+                taylor_load(A, buf, k0, p + 1 < npairs ? p + 1 : p, l15, g, colj, a1, b1, keep);
+                __builtin_amdgcn_sched_barrier(0);      // the loads are issued here, not moved below the MFMAs
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[h][i], b0[h][j], acc[i][j], 0, 0, 0);
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) a0[h][i] = a1[h][i], b0[h][i] = b1[h][i];
+                __builtin_amdgcn_sched_barrier(0);
+                taylor_mask(b0, keep);
+            }
+        }
+        if (!active) return;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int col = col0 + 16 * j + l15;
+            if (col >= A.M) continue;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const long long row = row0 + 16 * i + g + 4 * r;
+                    if (row < A.R) A.out[row * A.M + col] = acc[i][j][r];
+                }
+        }
+    }
+}
+
+template <bool GEN>
+int taylor_launch(const char* who, const TaylorArgs& A, int device, void* stream) {
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
+    // the row tiles along x: workgroups are dispatched x first, so those in flight share their 256 columns of the right operand in L2
+    const long long nrt = (A.R + TY_ROWS - 1) / TY_ROWS, nct = (A.M + TY_COLS - 1) / TY_COLS;
+    if (nrt > 0x7fffffffLL || nct > 65535) return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d results (at most 2^37 rows, 2^24 - 256 columns)", who, A.R, A.M);
+    const dim3 grid((unsigned)nrt, (unsigned)nct);
+    const size_t lds = (size_t)(2 * TY_KC * TY_RS + (GEN ? A.ndim * TY_ROWS : 0)) * sizeof(double);      // at most 56 KB
+    hipLaunchKernelGGL(taylor_gemm_kernel<GEN>, grid, dim3(256), lds, static_cast<hipStream_t>(stream), A);
+    return cp::launch_status(who);
+}
+
+}  // namespace
+
+extern "C" int cp_taylor_predict(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
+                                 const double* d_derivatives, int M, double* d_out, int device, void* stream) {
+    if (B < 0 || ndim < 1 || T < 1 || M < 1) return cp::fail(CP_EINVAL, "cp_taylor_predict: need ndim, T, M >= 1 and a non-negative count of points");
+    if (max_power < 0) return cp::fail(CP_EINVAL, "cp_taylor_predict: max_power %d is negative", max_power);
+    if (ndim > TY_MAX_NDIM) return cp::fail(CP_EUNSUPPORTED, "cp_taylor_predict: %d parameters (at most %d)", ndim, TY_MAX_NDIM);
+    if (max_power > TY_MAX_POWER) return cp::fail(CP_EUNSUPPORTED, "cp_taylor_predict: power %d (at most %d)", max_power, TY_MAX_POWER);
+    if (B == 0) return CP_OK;
+    if (!d_x || !d_center || !d_powers || !d_derivatives || !d_out) return cp::fail(CP_EINVAL, "cp_taylor_predict: null pointer");
+    const TaylorArgs A{d_x, d_center, d_powers, d_derivatives, d_out, B, T, M, ndim};
+    return taylor_launch<true>("cp_taylor_predict", A, device, stream);
+}
+
+extern "C" int cp_taylor_fit(const double* d_S, int T, int npoints, const double* d_Y, int M, double* d_derivatives, int device, void* stream) {
+    if (T < 1 || npoints < 1 || M < 1) return cp::fail(CP_EINVAL, "cp_taylor_fit: need T, npoints, M >= 1");
+    if (!d_S || !d_Y || !d_derivatives) return cp::fail(CP_EINVAL, "cp_taylor_fit: null pointer");
+    const TaylorArgs A{d_S, nullptr, nullptr, d_Y, d_derivatives, T, npoints, M, 0};
+    return taylor_launch<false>("cp_taylor_fit", A, device, stream);
+}

@@ -8,8 +8,10 @@ function params -> dictionary of arrays, keyed '<section>.<quantity>' exactly as
 Quantities follow the state dictionaries of the reference's emulated sections (cosmoprimo/emulators/emulated.py:218-223 background,
 245-251 thermodynamics, 359-361 primordial, 581-600 fourier) on the same default grids (emulated.py:13-33).  The reference's calculator
 silently drops 'fourier.pk.*' for its analytic engines (their ``pk_interpolator`` rejects the ``non_linear`` keyword and the error is
-swallowed); here the pairs the analytic engines do provide ('delta_m', 'theta_m') are returned.  The neural-network emulator classes of that
-module are out of scope (not on the hot path).
+swallowed); here the pairs the analytic engines do provide ('delta_m', 'theta_m') are returned.  The consumer of those batches is built too: the
+Taylor-expansion emulator (``Emulator``, ``TaylorEmulatorEngine``, ``DiffSampler`` of :mod:`.tools`: the whole finite-difference grid in one call of
+the calculator, fit and batched prediction on the device).  The neural-network emulator classes of that module are not (not on
+the hot path).
 """
 import numpy as np
 
@@ -111,3 +113,6 @@ def get_calculator(cosmo, section=None):
         return toret
 
     return calculator
+
+
+from .tools import Emulator, TaylorEmulatorEngine, DiffSampler  # noqa: E402,F401

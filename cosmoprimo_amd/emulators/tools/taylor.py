@@ -1,0 +1,289 @@
+"""
+Taylor-expansion emulator under the reference's names (cosmoprimo/emulators/tools/taylor.py:180-254 ``TaylorEmulatorEngine``, with the ``Emulator``
+front end of emulators/tools/base.py reduced to what the Taylor engine needs): finite differences on a grid of parameter points, then a polynomial.
+
+Fit: the derivative of every term is linear in the samples, ``derivatives (T, M) = S (T, npoints) . Y (npoints, M)``.  ``S`` -- products of 1-D
+finite-difference weights, times the 1 / alpha! of the term -- is built here on the host (T x npoints numbers); the product is one GEMM on the device
+(``cp_taylor_fit``), and ``derivatives`` stay there.  Predict: ``out (B, M) = monomials (B, T) . derivatives`` for B parameter points at once
+(``cp_taylor_predict``: the monomials are formed inside the kernel), where the reference evaluates one point per call.
+
+No x / y operations (log10, PCA, ...), no other engines.
+"""
+import itertools
+import math
+
+import numpy as np
+
+from .samples import DiffSampler, deriv_ncoeffs
+
+
+def fd_weights(order, acc, coords, idx):
+    """Finite-difference weights of the derivative of given ``order`` and accuracy ``acc`` at node ``idx`` of the (non-uniform) 1-D grid ``coords``,
+    and the offsets of the nodes they apply to: the solution of ``sum_j w_j (x_j - x_c)^i = order! delta_{i, order}`` by ``numpy.linalg.solve``, the
+    system the reference solves (taylor.py:53-88), so that the weights are bit-identical to its weights on the same coordinates.  Central where the
+    grid reaches far enough on both sides, one-sided at its ends."""
+    order, acc = int(order), int(acc)
+    if acc % 2 or acc <= 0:
+        raise ValueError('Accuracy order acc must be positive EVEN integer')
+    if order < 0:
+        raise ValueError('Derive degree must be positive integer')
+    ncoeffs = deriv_ncoeffs(order, acc=acc)
+    nside = ncoeffs // 2
+    ncoeffs += order % 2 == 0      # one-sided stencils of even derivatives take one node more
+    if idx < nside:
+        offsets = np.arange(ncoeffs)
+    elif idx >= len(coords) - nside:
+        offsets = np.arange(-ncoeffs + 1, 1)
+    else:
+        offsets = np.arange(-nside, nside + 1)
+    matrix = np.array([[1] * len(offsets)] + [[(coords[idx + j] - coords[idx])**i for j in offsets] for i in range(1, len(offsets))], dtype='f8')
+    rhs = np.zeros(len(offsets), dtype='f8')
+    rhs[order] = math.factorial(order)
+    return np.linalg.solve(matrix, rhs), offsets
+
+
+def _stencil(X, index, orders, center):
+    """Weights w (npoints,) with ``w @ Y`` the derivative of orders ``orders`` = [(axis, order, accuracy)] at ``center``, from the samples ``index`` of X:
+    the last axis is differentiated first, each of its nodes standing for the derivative along the remaining axes on the samples that share it."""
+    w = np.zeros(len(X), dtype='f8')
+    if not orders:
+        match = index[(X[index] == center).all(axis=1)]
+        if not match.size:
+            raise ValueError('Global center point not found')
+        w[match[0]] = 1.
+        return w
+    axis, order, acc = orders[-1]
+    coord = np.unique(X[index, axis])
+    if coord.size < deriv_ncoeffs(order, acc=acc):
+        raise ValueError('Grid is not large enough ({:d} < {:d}) to estimate {:d}-th order derivative'.format(coord.size, deriv_ncoeffs(order, acc=acc), order))
+    c = np.flatnonzero(coord == center[axis])
+    if not c.size:
+        raise ValueError('Global center point not found')
+    c = c[0]
+    for weight, offset in zip(*fd_weights(order, acc, coord, c)):
+        node = center.copy()
+        node[axis] = coord[c + offset]
+        w += weight * _stencil(X, index[X[index, axis] == node[axis]], orders[:-1], node)
+    return w
+
+
+def taylor_operator(X, cidx, order, accuracy):
+    """``center`` (ndim,), ``powers`` (T, ndim) and ``S`` (T, npoints) of the expansion fitted to samples at ``X`` (npoints, ndim), a grid of
+    :class:`DiffSampler` with centre ``X[cidx]`` and per-parameter maximum ``order`` and ``accuracy``: coefficient t of the expansion is ``S[t] @ Y``.
+
+    Terms in the reference's order (taylor.py:221-236): the constant, then total order 1, 2, ...; within an order, multi-indices as their first
+    appearance in ``itertools.product(range(ndim), repeat=order)``, which is the order of ``itertools.combinations_with_replacement``.  A term is skipped
+    when its total order exceeds the maximum order of any parameter it involves.  The reference adds 1 / order! once per permutation of the indices;
+    that is order! / alpha! times, i.e. the coefficient D^alpha f / alpha!."""
+    X = np.asarray(X, dtype='f8')
+    npoints, ndim = X.shape
+    cidx = int(np.ravel(cidx)[0])
+    order, accuracy = [int(o or 0) for o in order], list(accuracy)
+    center = X[cidx].copy()
+    unit = np.zeros(npoints, dtype='f8')
+    unit[cidx] = 1.
+    powers, S = [(0,) * ndim], [unit]
+    index = np.arange(npoints)
+    for total in range(1, max(order + [0]) + 1):
+        for indices in itertools.combinations_with_replacement(range(ndim), total):
+            power = tuple(np.bincount(indices, minlength=ndim).tolist())
+            if total > min(o for p, o in zip(power, order) if p):
+                continue
+            alpha = 1
+            for p in power:
+                alpha *= math.factorial(p)
+            powers.append(power)
+            S.append(_stencil(X, index, [(i, p, accuracy[i]) for i, p in enumerate(power) if p > 0], center) / alpha)
+    return center, np.array(powers, dtype='i4'), np.array(S, dtype='f8')
+
+
+class TaylorEmulatorEngine(object):
+
+    """Taylor expansion emulator engine.  State (the reference's names): ``center`` (ndim,), ``powers`` (T, ndim) int, ``derivatives`` (T, M),
+    ``sampler_options``; ``derivatives`` is the host copy of the coefficients the device holds."""
+    name = 'taylor'
+
+    def __init__(self, order=3, accuracy=2, device=None):
+        self.sampler_options = dict(order=order, accuracy=accuracy)
+        self.device = device
+        self._dev = None
+
+    def get_default_samples(self, calculator, params, **kwargs):
+        """Samples of a :class:`DiffSampler` with this engine's order and accuracy (``kwargs`` override them)."""
+        sampler = DiffSampler(calculator, params, **{**self.sampler_options, **kwargs})
+        return sampler.run()
+
+    def fit(self, X, Y, attrs, params=None):
+        """Fit to samples ``X`` (npoints, ndim), ``Y`` (npoints, M) of a :class:`DiffSampler`, ``attrs`` its ``cidx`` / ``order`` / ``accuracy`` (dictionaries
+        by parameter name, in the order of ``params``, or sequences in the order of the columns of X)."""
+        from ... import _device as dv, _lib
+        if attrs.get('cidx', None) is None:
+            raise ValueError('provide samples that are obtained with DiffSampler')
+        order, accuracy = ([item[name] for name in params] if isinstance(item, dict) else list(item) for item in (attrs['order'], attrs['accuracy']))
+        self.center, self.powers, S = taylor_operator(X, attrs['cidx'], order, accuracy)
+        torch = dv.torch()
+        device = dv.resolve_device(self.device)
+        Yd = dv.to_device(np.ascontiguousarray(Y, dtype='f8'), device, cache=False)
+        Sd = dv.to_device(S, device, cache=False)
+        (T, npoints), M = S.shape, int(Yd.shape[1])
+        if tuple(Yd.shape) != (npoints, M):
+            raise ValueError('Y must be of shape (npoints, M) = ({:d}, M), got {}'.format(npoints, tuple(Yd.shape)))
+        derivatives = torch.empty((T, M), dtype=torch.float64, device=device)
+        _lib.check(_lib.load().cp_taylor_fit(Sd.data_ptr(), T, npoints, Yd.data_ptr(), M, derivatives.data_ptr(), device.index, dv.stream_of(device)))
+        self.derivatives = dv.to_host(derivatives)
+        self._set_device(device, derivatives)
+        return self
+
+    def _set_device(self, device, derivatives=None):
+        from ... import _device as dv
+        torch = dv.torch()
+        if derivatives is None:
+            derivatives = dv.to_device(np.ascontiguousarray(self.derivatives, dtype='f8'), device, cache=False)
+        powers = np.ascontiguousarray(self.powers, dtype='i4')
+        self._dev = dict(device=device, derivatives=derivatives, center=dv.to_device(np.asarray(self.center, dtype='f8'), device, cache=False),
+                         powers=dv.upload(powers, device, cache=False), max_power=int(powers.max(initial=0)), min_power=int(powers.min(initial=0)))
+        assert self._dev['powers'].dtype == torch.int32
+
+    def predict(self, X):
+        """Expansion at the points ``X`` (B, ndim), a device tensor (or host array, uploaded): device tensor (B, M).  Nothing is read back and the call
+        does not wait for the device."""
+        from ... import _device as dv, _lib
+        if self._dev is None:
+            self._set_device(dv.resolve_device(self.device, X))
+        d = self._dev
+        torch = dv.torch()
+        X = dv.to_device(X, d['device'], cache=False)
+        T, ndim = (int(n) for n in np.shape(self.powers))
+        if X.ndim != 2 or int(X.shape[1]) != ndim:
+            raise ValueError('X must be of shape (B, {:d}), got {}'.format(ndim, tuple(X.shape)))
+        if d['min_power'] < 0:
+            raise ValueError('powers must be non-negative')
+        B, M = int(X.shape[0]), int(d['derivatives'].shape[1])
+        out = torch.empty((B, M), dtype=torch.float64, device=d['device'])
+        _lib.check(_lib.load().cp_taylor_predict(X.data_ptr(), B, d['center'].data_ptr(), d['powers'].data_ptr(), ndim, T, d['max_power'], d['derivatives'].data_ptr(),
+                                                 M, out.data_ptr(), d['device'].index, dv.stream_of(d['device'])))
+        return out
+
+    def __getstate__(self):
+        state = {'sampler_options': self.sampler_options}
+        for name in ['center', 'derivatives', 'powers']:
+            if hasattr(self, name):
+                state[name] = getattr(self, name)
+        return state
+
+    def __setstate__(self, state):
+        self.sampler_options = dict(state.get('sampler_options', {}))
+        self.device, self._dev = None, None
+        for name in ['center', 'derivatives', 'powers']:
+            if name in state:
+                setattr(self, name, np.asarray(state[name]))
+
+    @classmethod
+    def from_state(cls, state, device=None):
+        new = cls.__new__(cls)
+        new.__setstate__(state)
+        new.device = device
+        return new
+
+
+class Emulator(object):
+
+    """Emulate a calculator ``**params -> dict of arrays``: sample it (:meth:`set_samples`), :meth:`fit`, then :meth:`predict` at B parameter points at once.
+
+    .. code-block:: python
+
+        calculator = get_calculator(Cosmology(engine='eisenstein_hu'))
+        emulator = Emulator(calculator, params={'Omega_m': (0.25, 0.35), 'h': (0.6, 0.8)}, engine='taylor', order=3)
+        emulator.set_samples()       # the whole finite-difference grid in one call of the calculator
+        emulator.fit()
+        emulator.predict({'Omega_m': np.linspace(0.28, 0.32, 10000), 'h': 0.7})   # {'fourier.pk.delta_m.delta_m': (10000, 422, 30) array, ...}
+    """
+
+    def __init__(self, calculator, params=None, engine='taylor', device=None, **engine_options):
+        if isinstance(engine, str):
+            if engine != 'taylor':
+                raise NotImplementedError('engine {} (only the Taylor engine is built)'.format(engine))
+            engine = TaylorEmulatorEngine(device=device, **engine_options)
+        self.calculator = calculator
+        self.params = {name: tuple(limits) for name, limits in (params or {}).items()}
+        self.engine = engine
+        self.samples = None
+        self.varied_keys, self.varied_shapes, self.fixed = [], [], {}
+
+    def set_samples(self, samples=None, **kwargs):
+        """Set the samples to fit: those given, else the engine's default (:class:`DiffSampler` run on the calculator; ``kwargs`` override order / accuracy)."""
+        self.samples = samples if samples is not None else self.engine.get_default_samples(self.calculator, self.params, **kwargs)
+        return self.samples
+
+    def fit(self):
+        """Concatenate the flattened varied outputs into Y (npoints, M), upload it once and fit the engine on the device."""
+        if self.samples is None:
+            self.set_samples()
+        samples = self.samples
+        self.varied_keys = list(samples.varied)
+        if not self.varied_keys:
+            raise ValueError('the calculator returns nothing that varies with the parameters')
+        self.varied_shapes = [tuple(samples.varied[key].shape[1:]) for key in self.varied_keys]
+        self.fixed = dict(samples.fixed)
+        Y = np.concatenate([np.asarray(samples.varied[key], dtype='f8').reshape(len(samples.varied[key]), -1) for key in self.varied_keys], axis=1)
+        self.engine.fit(samples.matrix(), Y, samples.attrs, params=list(self.params))
+        return self
+
+    def predict(self, params, device=False):
+        """Outputs at ``params``, a dictionary of scalars or arrays of B values (host arrays or device tensors): the calculator's keys, varied ones of shape
+        ``(B,) + shape`` (no leading axis if every parameter is a scalar), fixed ones as they are.  Host arrays by default; ``device=True``: torch tensors,
+        views into one (B, M) buffer, and no synchronisation with the device."""
+        from ... import _device as dv
+        missing = [name for name in self.params if name not in params]
+        if missing:
+            raise ValueError('missing parameters {}'.format(missing))
+        values = [params[name] for name in self.params]
+        dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, *values)
+        torch = dv.torch()
+        sizes = {int(np.prod(np.shape(v))) for v in values if np.ndim(v) > 0}
+        if len(sizes) > 1:
+            raise ValueError('parameter arrays must share one length, got {}'.format(sorted(sizes)))
+        scalar = not sizes
+        B = 1 if scalar else sizes.pop()
+        if all(not dv.is_torch(v) for v in values):
+            X = np.empty((B, len(values)), dtype='f8')
+            for i, v in enumerate(values):
+                X[:, i] = np.ravel(v)
+        else:
+            X = torch.stack([dv.to_device(v, dev, cache=False).reshape(-1).expand(B) for v in values], dim=1)
+        out = self.engine.predict(X)
+        if not device:
+            out = dv.to_host(out)
+        toret, start = {}, 0
+        for key, shape in zip(self.varied_keys, self.varied_shapes):
+            size = int(np.prod(shape, dtype='i8'))
+            value = out[:, start:start + size].reshape((B,) + shape)
+            toret[key] = value[0] if scalar else value
+            start += size
+        toret.update(self.fixed)
+        return toret
+
+    def to_calculator(self, device=False):
+        """Callable ``**params -> dict`` with the contract of ``get_calculator``'s."""
+        def calculator(**params):
+            return self.predict(params, device=device)
+
+        return calculator
+
+    def __getstate__(self):
+        return {'engine': self.engine.__getstate__(), 'params': dict(self.params), 'varied_keys': list(self.varied_keys), 'varied_shapes': [tuple(s) for s in self.varied_shapes],
+                'fixed': dict(self.fixed)}
+
+    def save(self, fn):
+        """Save the state (``center``, ``powers``, ``derivatives``, ``sampler_options``, key names, shapes, fixed values) as one ``.npy`` dictionary."""
+        np.save(fn, self.__getstate__(), allow_pickle=True)
+
+    @classmethod
+    def load(cls, fn, device=None):
+        state = np.load(fn, allow_pickle=True)[()]
+        new = cls.__new__(cls)
+        new.calculator, new.samples = None, None
+        new.params = dict(state['params'])
+        new.engine = TaylorEmulatorEngine.from_state(state['engine'], device=device)
+        new.varied_keys, new.varied_shapes, new.fixed = list(state['varied_keys']), [tuple(s) for s in state['varied_shapes']], dict(state['fixed'])
+        return new

@@ -638,6 +638,18 @@ int cp_spline_tables_apply(const double* d_xk, const double* d_coef, const int* 
 int cp_spline_tables_apply_f32(const double* d_xk, const double* d_coef, const int* d_ok, long long nrows, int n, const float* d_xq, int per_row,
                                long long nq, float* d_out, int* d_flag, int* outside, int device, void* stream);
 
+/* ---- Taylor-expansion emulator of a calculator (reference emulators/tools/taylor.py:211-247; csrc/cp_taylor.hip): one float64 GEMM on the matrix
+ *      cores with two front ends.  Everything is on the device; neither call reads anything back or waits for the stream. ----
+ * predict : d_x (B, ndim) parameter points, d_center (ndim), d_powers (T, ndim) int, d_derivatives (T, M) the coefficients D^alpha f / alpha! that the fit
+ *   left on the device; d_out (B, M) = sum_t prod_i (powers[t][i] > 0 ? (x_i - center_i)^powers[t][i] : 1) * derivatives[t].  A factor with power 0 is
+ *   exactly 1 whatever x_i holds (NaN, Inf).  The (B, T) matrix of monomials is formed in LDS and never stored.  max_power: the largest entry of
+ *   d_powers, which the caller knows and the call does not read back; ndim > 32 or max_power > 15 are CP_EUNSUPPORTED (larger entries of d_powers
+ *   than declared are treated as 15).
+ * fit : d_derivatives (T, M) = d_S (T, npoints) . d_Y (npoints, M), S the finite-difference weights of every term over the samples of the grid. */
+int cp_taylor_predict(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
+                      const double* d_derivatives, int M, double* d_out, int device, void* stream);
+int cp_taylor_fit(const double* d_S, int T, int npoints, const double* d_Y, int M, double* d_derivatives, int device, void* stream);
+
 /* ---- row screening utility (cp_fftlog_execute and cp_dst_execute screen their rows themselves; this pass is for callers that want
  *      the flags, e.g. to count or report the rows a batch loses) ----
  * d_x : (nrows, n) device.  d_ok[row] = 1 if every entry of the row is finite (and > 0 if require_positive: the fused log map of
