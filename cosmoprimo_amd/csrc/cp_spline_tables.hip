@@ -8,7 +8,9 @@
 //   build : one wave per row.  The row's knots and the values go to LDS; the system for the knot first derivatives (scipy's, natural ends) is
 //           diagonally dominant, so every lane eliminates its own run of intervals plus TAB_HALO knots on either side (the scheme of
 //           column_spline_kernel, cp_spline.hip) and the row is solved in (n / 64 + 2 TAB_HALO) dependent steps instead of 2 n.  What is written
-//           are the four polynomial coefficients of every interval, so that a query is a search and a Horner form: no division.
+//           are the four polynomial coefficients of every interval, so that a query is a search and a Horner form: no division.  The LAST interval
+//           is written in a form that holds the values of both its knots (table_last below): a power form returns the value of the interval's
+//           left knot exactly and its right knot within rounding only, and the last knot of a row is the right knot of an interval alone.
 //   apply : a search plus one cubic per (row, query).  Many queries per row (a catalogue under a few hundred trial cosmologies): the workgroup
 //           stages its row in LDS and every lane bisects there (spline_points_lds_kernel's scheme, cp_interp.hip).  Very many rows with a few
 //           queries each (chain samples): one lane per (row, query) bisects in the row's knots in memory -- filling LDS would cost more than
@@ -24,7 +26,13 @@
 
 namespace {
 
-constexpr int TAB_HALO = 32;             // knots a lane eliminates beyond either end of its run: the elimination forgets its start by <= 0.31 per knot
+// Knots a lane eliminates beyond either end of its run.  What the elimination still knows of its (wrong) start after k knots is the product of its k
+// factors c_i = dx_{i-1} / (2 (dx_{i-1} + dx_i) - dx_i c_{i-1}), each < 1/2: 2 - sqrt(3) = 0.268 per knot on uniform knots, dx_{i-1} / (2 dx_{i-1} + 1.5 dx_i)
+// at least where the spacing changes, so -> 1/2 only along knots whose spacing shrinks by a large factor at EVERY step in the direction of the
+// elimination.  40 knots hold the tolerance of the tests (1e-11 relative) on every family of tests/spline_tables_cases.py, spacings that double over 39
+// consecutive knots among them (32 did not: 3 tolerances); spacings that grow geometrically over more knots than that are outside the guarantee
+// (tools/gen_spline_tables_edges_golden.py states the condition on a table, DESIGN.md section 6 the families).
+constexpr int TAB_HALO = 40;
 constexpr int TAB_MAX_KNOTS = 4096;      // build: knots, values and the run's eliminated rows in LDS, 32 n bytes = 128 KB
 constexpr int TAB_LDS_KNOTS = 2048;      // apply: knots + 4 coefficients per interval in LDS, 80 KB (SPLINE_LDS_KNOTS of cp_interp.hip)
 constexpr long long TAB_LDS_QUERIES = 4096;      // per row, from which on staging the row (5 n loads per workgroup) is cheaper than bisecting in memory
@@ -58,7 +66,8 @@ __global__ __launch_bounds__(64) void spline_tables_build_kernel(const double* _
         if (ok && a < b) {
             double4* out = reinterpret_cast<double4*>(coef + (row * (n - 1) + a) * 4);
             if (order == 1) {
-                for (int k = a; k < b; ++k) out[k - a] = double4{ys[k], (ys[k + 1] - ys[k]) / (xs[k + 1] - xs[k]), 0., 0.};
+                for (int k = a; k < b; ++k)
+                    out[k - a] = k == n - 2 ? double4{ys[k], 0., 0., ys[k + 1]} : double4{ys[k], (ys[k + 1] - ys[k]) / (xs[k + 1] - xs[k]), 0., 0.};
             } else {
                 // scipy CubicSpline, bc_type='natural': 2 s_0 + s_1 = 3 slope_0; dxp s_{i-1} + 2 (dxm + dxp) s_i + dxm s_{i+1} = 3 (dxp slm + dxm slp);
                 // s_{n-2} + 2 s_{n-1} = 3 slope_{n-2}.  From the left, knot f0 as if the spline began there: s_i + c_i s_{i+1} = d_i up to knot b - 1
@@ -91,7 +100,12 @@ __global__ __launch_bounds__(64) void spline_tables_build_kernel(const double* _
                     // PPoly coefficients of the interval as scipy's CubicSpline forms them (spline_points_kernel, cp_interp.hip)
                     const double h = xs[k + 1] - xs[k], slope = (ys[k + 1] - ys[k]) / h;
                     const double t = (s_lo + s_hi - 2. * slope) / h;
-                    out[k - a] = double4{ys[k], s_lo, (slope - s_lo) / h - t, t / h};
+                    if (k == n - 2) {      // table_last: with t = u / h, (1 - t) y_k + t y_{k+1} + t (1 - t) (A + t (B - A)), A = h s_k - dy, B = dy - h s_{k+1}
+                        const double dy = ys[k + 1] - ys[k], A = h * s_lo - dy;
+                        out[k - a] = double4{ys[k], A, (dy - h * s_hi) - A, ys[k + 1]};
+                    } else {
+                        out[k - a] = double4{ys[k], s_lo, (slope - s_lo) / h - t, t / h};
+                    }
                     s_hi = s_lo;
                 }
             }
@@ -103,6 +117,19 @@ __global__ __launch_bounds__(64) void spline_tables_build_kernel(const double* _
 // ---- apply ---------------------------------------------------------------------------------------------------------------------------------
 // the cubic of one interval at u = x - x_k; explicit fused multiply-adds: the two kernels below must round alike
 __device__ __forceinline__ double table_cubic(double c0, double c1, double c2, double c3, double u) { return fma(u, fma(u, fma(u, c3, c2), c1), c0); }
+
+// the last interval, c = (y_{n-2}, A, B - A, y_{n-1}), at t = u / h: t is exactly 0 at its left knot and exactly 1 (h / h) at the last knot of the row, where every
+// term but the knot's own value is an exact zero -- both knots return their values bit for bit.  One division, for the queries of this one interval only.
+__device__ __forceinline__ double table_last(const double4 c, double u, double h) {
+    const double t = u / h;
+    return fma(t * (1. - t), fma(t, c.z, c.y), fma(t, c.w, fma(-t, c.x, c.x)));
+}
+
+// (a branch, not a select: the division is not to be paid by the queries of the other intervals)
+__device__ __forceinline__ double table_eval(const double4 c, double u, double h, bool last) {
+    if (__builtin_expect(last, 0)) return table_last(c, u, h);
+    return table_cubic(c.x, c.y, c.z, c.w, u);
+}
 
 struct ApplyArgs {
     const double* xk;      // (nrows, n)
@@ -145,7 +172,7 @@ __global__ __launch_bounds__(256) void spline_tables_lds_kernel(const ApplyArgs 
                 if (xs[mid] <= v) lo = mid; else hi = mid;
             }
             const double4 c = *reinterpret_cast<const double4*>(cf + 4 * lo);
-            r = table_cubic(c.x, c.y, c.z, c.w, v - xs[lo]);
+            r = table_eval(c, v - xs[lo], xn - xs[n - 2], lo == n - 2);
         } else {
             outside = true;
         }
@@ -174,7 +201,7 @@ __global__ __launch_bounds__(256) void spline_tables_rows_kernel(const ApplyArgs
                     if (xr[mid] <= v) lo = mid; else hi = mid;
                 }
                 const double4 c = *reinterpret_cast<const double4*>(A.coef + (row * (n - 1) + lo) * 4);
-                r = table_cubic(c.x, c.y, c.z, c.w, v - xr[lo]);
+                r = table_eval(c, v - xr[lo], xn - xr[lo], lo == n - 2);
             } else {
                 outside = true;
             }

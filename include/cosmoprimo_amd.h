@@ -624,7 +624,9 @@ int cp_spline_points(const double* d_xk, const double* d_y, const double* d_s, l
  *      (DistanceToRedshift over a batch, utils.py:275-316: Interpolator1D(rgrid, zgrid) per cosmology; csrc/cp_spline_tables.hip) ----
  * build : d_xk (nrows, n) the rows' knots, d_y (n) the values all rows share, order 3 (natural cubic spline, scipy CubicSpline(bc_type='natural')) or
  *   1 (linear, interp1d); n <= 4096 (CP_EUNSUPPORTED beyond: a row is solved in LDS).  d_coef (nrows, n - 1, 4): the polynomial coefficients
- *   c0 .. c3 of every interval in powers of x - x_k (a query needs no division); d_ok (nrows): 0 for a row that holds a non-finite knot or is not
+ *   c0 .. c3 of every interval in powers of x - x_k (a query needs no division) -- but for the last interval, which holds (y_{n-2}, A, B - A, y_{n-1})
+ *   of the form (1 - t) y_{n-2} + t y_{n-1} + t (1 - t) (A + t (B - A)), t = (x - x_{n-2}) / h: EVERY knot returns its value bit for bit, the last one too;
+ *   the buffer is for cp_spline_tables_apply, not a PPoly to read; d_ok (nrows): 0 for a row that holds a non-finite knot or is not
  *   strictly ascending (its coefficients are not written), else 1.  No host read-back.
  * apply : d_xq (nq) queries shared by the rows, or per_row != 0: (nrows, nq); d_out (nrows, nq).  Queries outside a row's own [x_0, x_{n-1}] and NaN
  *   queries give NaN; rows with d_ok == 0 are NaN throughout.  outside (host, may be NULL): set to 1 when a query of a row that is ok lies outside
