@@ -57,6 +57,27 @@ __device__ __forceinline__ int pos_of_freq(int k) {
     return pos;
 }
 
+// Powers of two that bring a row whose largest sample has the high dword `top` (hi_abs) to the order of 1, and back: exact factors, so that the two
+// rows of a pair meet in the complex FFT at the same magnitude whatever theirs are (2^-1022 .. 2^1022: subnormal and the very largest rows end within 2)
+__device__ __forceinline__ void row_scale(unsigned top, double& to_unit, double& back) {
+    int field = 2046 - (int)(top >> 20);      // bits 30..20: the biased exponent
+    field = field < 1 ? 1 : (field > 2045 ? 2045 : field);
+    to_unit = __builtin_bit_cast(double, (unsigned long long)field << 52);
+    back = __builtin_bit_cast(double, (unsigned long long)(2046 - field) << 52);
+}
+
+// ... and then to a 2-norm in [1, 2): `sq` is the sum of the squares of the row's samples after row_scale, in units of 2^-40 (an integer sum: the same
+// in whatever order the threads add to it, so that two launches on the same rows scale them alike).  The spectra of the two rows, which is where they
+// meet, have the rows' 2-norms (the transform is orthonormal), not their largest samples: an impulse next to a constant row of the same height
+// would otherwise meet a spectrum sqrt(N) times its own.  `to_unit` and `back` of row_scale are updated; `up` is applied before `back` on the way out.
+__device__ __forceinline__ double square_2m40(double v) { return v * v * 0x1p40; }
+__device__ __forceinline__ void norm_scale(unsigned long long sq, double& to_unit, double& up) {
+    int k = sq ? ((63 - __builtin_clzll(sq)) - 40) >> 1 : 0;      // floor(log2(sum of squares) / 2)
+    k = k < -64 ? -64 : (k > 64 ? 64 : k);
+    to_unit *= __builtin_bit_cast(double, (unsigned long long)(1023 - k) << 52);      // exact: a power of two (subnormal ones included)
+    up = __builtin_bit_cast(double, (unsigned long long)(1023 + k) << 52);
+}
+
 template <int N, int P>
 __device__ __forceinline__ cplx lds_at(const cplx* lds, int pos) {
     return lds[swz<N>(pos)];
@@ -111,7 +132,13 @@ __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
     // Rows stay independent although two of them share one complex FFT (scipy transforms row by row): a row holding a sample that is
     // not finite -- or, for the fused log map, not positive -- goes into the transform as a harmless constant and is stored as NaN; its
     // partner is untouched.  The flags of the pair are raised by whichever thread meets such a sample and read behind one barrier.
+    // The two rows share the FFT's multiplications, whose rounding is relative to the larger of the two spectra: each row goes in scaled by a power of
+    // two and comes out scaled back, so that a row keeps its own accuracy whatever its partner (scipy transforms row by row).  Two stages, one LDS
+    // reduction and one barrier each: first the row's largest sample to the order of 1 (row_top: the largest hi_abs, gathered with the flags; row_scale),
+    // which makes the squares safe to sum, then its 2-norm -- the size of its spectrum -- to [1, 2) (row_sq, norm_scale).
     __shared__ int bad_row[2];
+    __shared__ unsigned row_top[2];
+    __shared__ unsigned long long row_sq[2];      // norm_scale
     __shared__ int pair_flag;   // inverse transform: some sample of the pair is not finite
     __shared__ cpmath::MathTables mt;      // the table-driven exponential of the fused inverse map (the barrier at the top of the first pair covers the fill)
     if (INVERSE) cpmath::fill_math_tables(&mt);
@@ -157,10 +184,11 @@ __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
         // position of coefficient j in its row: the wallish2018 filter treats even- and odd-indexed coefficients as two sequences
         // (bao_filter.py:373), so they can be written / read as two half rows instead of being gathered by separate copy kernels
         auto at = [&](int j) { return A.split ? ((j & 1) * (N / 2) + (j >> 1)) : j; };
-        if (t == 0) bad_row[0] = bad_row[1] = pair_flag = 0;
+        if (t == 0) bad_row[0] = bad_row[1] = pair_flag = 0, row_top[0] = row_top[1] = 0u, row_sq[0] = row_sq[1] = 0ull;
         __syncthreads();  // LDS reuse across pairs (and the table fill on the first one)
         int tt = t;
         asm volatile("" : "+v"(tt));
+        unsigned top_a = 0u, top_b = 0u;
         if constexpr (!INVERSE) {
             // Makhoul reordering with the (-1)^n sign folded in
             bool bad_a = false, bad_b = false;
@@ -170,8 +198,8 @@ __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
                 const bool lower = m < N / 2;
                 const int n = lower ? 2 * m : 2 * (N - 1 - m) + 1;
                 double a = na[r], b = nb[r];
-                bad_a |= !(fabs(a) <= 1.7976931348623157e308) || (A.fused && !(a > 0.));
-                bad_b |= !(fabs(b) <= 1.7976931348623157e308) || (A.fused && !(b > 0.));
+                bad_a |= not_finite(a) || (A.fused && !(a > 0.));
+                bad_b |= not_finite(b) || (A.fused && !(b > 0.));
                 if (A.fused) {
                     const double kk = A.kx[n];
                     a = cpmath::log_pos(kk * a);      // rows with a sample that is not positive are flagged above and left out
@@ -179,18 +207,37 @@ __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
                 }
                 x[r].re = lower ? a : -a;
                 x[r].im = has_b ? (lower ? b : -b) : 0.;
+                top_a = max(top_a, hi_abs(a));
+                top_b = max(top_b, hi_abs(b));
             }
             if (p + gridDim.x < npairs) fetch(p + gridDim.x);
             if (bad_a) bad_row[0] = 1;
             if (bad_b) bad_row[1] = 1;
+            atomicMax(&row_top[0], top_a);
+            atomicMax(&row_top[1], top_b);
             __syncthreads();
             const bool skip_a = bad_row[0] != 0, skip_b = bad_row[1] != 0;
-            if (skip_a | skip_b) {
+            double sa, sb, back_a, back_b, up_a, up_b;
+            row_scale(row_top[0], sa, back_a);
+            row_scale(row_top[1], sb, back_b);
+            unsigned long long sq_a = 0ull, sq_b = 0ull;
 #pragma unroll
-                for (int r = 0; r < P; ++r) {
-                    if (skip_a) x[r].re = 0.;
-                    if (skip_b) x[r].im = 0.;
-                }
+            for (int r = 0; r < P; ++r) {
+                x[r].re = skip_a ? 0. : x[r].re * sa;
+                x[r].im = skip_b ? 0. : x[r].im * sb;
+                sq_a += (unsigned long long)square_2m40(x[r].re);
+                sq_b += (unsigned long long)square_2m40(x[r].im);
+            }
+            atomicAdd(&row_sq[0], sq_a);
+            atomicAdd(&row_sq[1], sq_b);
+            __syncthreads();
+            sa = sb = 1.;
+            norm_scale(row_sq[0], sa, up_a);
+            norm_scale(row_sq[1], sb, up_b);
+#pragma unroll
+            for (int r = 0; r < P; ++r) {
+                x[r].re *= sa;
+                x[r].im *= sb;
             }
             dif_all<N, P>(tt, A, x, lds, ltw);
             asm volatile("" : "+v"(tt));
@@ -205,8 +252,8 @@ __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
                 // V_a = ((p + r)/2, (q - s)/2), V_b = ((q + s)/2, (r - p)/2);  C' = cos * re + sin * im
                 const double ya = 0.5 * (rot.re * (v.re + u.re) - rot.im * (v.im - u.im));
                 const double yb = 0.5 * (rot.re * (v.im + u.im) - rot.im * (u.re - v.re));
-                oa[at(N - 1 - k)] = skip_a ? nan : f * ya;
-                if (has_b) ob[at(N - 1 - k)] = skip_b ? nan : f * yb;
+                oa[at(N - 1 - k)] = skip_a ? nan : f * ya * up_a * back_a;
+                if (has_b) ob[at(N - 1 - k)] = skip_b ? nan : f * yb * up_b * back_b;
             }
         } else {
             // Hermitian-symmetrised, conjugated spectrum of the pair; a row that is skipped does not take part
@@ -215,8 +262,30 @@ __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
                 double2* w = reinterpret_cast<double2*>(lds);
 #pragma unroll
                 for (int r = 0; r < P; ++r) w[tt + T * r] = double2{na[r], nb[r]};
-                __syncthreads();
             }
+#pragma unroll
+            for (int r = 0; r < P; ++r) {      // (every coefficient of the pair is in na / nb of exactly one thread, in either order of fetch_inverse)
+                top_a = max(top_a, hi_abs(na[r]));
+                top_b = max(top_b, hi_abs(nb[r]));
+            }
+            atomicMax(&row_top[0], top_a);
+            atomicMax(&row_top[1], top_b);
+            __syncthreads();
+            double sa, sb, back_a, back_b, up_a, up_b;
+            row_scale(row_top[0], sa, back_a);
+            row_scale(row_top[1], sb, back_b);
+            unsigned long long sq_a = 0ull, sq_b = 0ull;
+#pragma unroll
+            for (int r = 0; r < P; ++r) {      // (a row that is not finite adds anything at all: it is left out below, whatever its scale)
+                const double va = na[r] * sa, vb = nb[r] * sb;
+                sq_a += fabs(va) < 4. ? (unsigned long long)square_2m40(va) : 0ull;
+                sq_b += fabs(vb) < 4. ? (unsigned long long)square_2m40(vb) : 0ull;
+            }
+            atomicAdd(&row_sq[0], sq_a);
+            atomicAdd(&row_sq[1], sq_b);
+            __syncthreads();
+            norm_scale(row_sq[0], sa, up_a);
+            norm_scale(row_sq[1], sb, up_b);
             auto spectrum = [&](bool keep_a, bool keep_b, bool prefetched) {
 #pragma unroll
                 for (int r = 0; r < P; ++r) {
@@ -227,11 +296,11 @@ __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
                     double Aa, Ab, Ba, Bb;
                     if (CP_DST_INVERSE_VIA_LDS && prefetched) {
                         const double2 va = staged[at(ia)], vb = staged[at(ib)];
-                        Aa = fa * va.x; Ab = fa * va.y;
-                        Ba = (k == 0 ? fa : fb) * vb.x; Bb = (k == 0 ? fa : fb) * vb.y;
+                        Aa = fa * (va.x * sa); Ab = fa * (va.y * sb);
+                        Ba = (k == 0 ? fa : fb) * (vb.x * sa); Bb = (k == 0 ? fa : fb) * (vb.y * sb);
                     } else {
-                        Aa = fa * (prefetched ? na[r] : ra[at(ia)]); Ab = fa * (prefetched ? nb[r] : rb[at(ia)]);
-                        Ba = (k == 0 ? fa : fb) * ((CP_DST_ABLATE & 2) ? na[r] : ra[at(ib)]); Bb = (k == 0 ? fa : fb) * ((CP_DST_ABLATE & 2) ? nb[r] : rb[at(ib)]);
+                        Aa = fa * ((prefetched ? na[r] : ra[at(ia)]) * sa); Ab = fa * ((prefetched ? nb[r] : rb[at(ia)]) * sb);
+                        Ba = (k == 0 ? fa : fb) * (((CP_DST_ABLATE & 2) ? na[r] : ra[at(ib)]) * sa); Bb = (k == 0 ? fa : fb) * (((CP_DST_ABLATE & 2) ? nb[r] : rb[at(ib)]) * sb);
                     }
                     const cplx rot = A.rot[k];
                     const double cs = rot.re, sn = -rot.im;
@@ -256,7 +325,7 @@ __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
             // (no second pass over the rows), and only a flagged pair -- rare -- reads its rows again to tell the two apart and leave the bad one out
             bool suspect = false;
 #pragma unroll
-            for (int r = 0; r < P; ++r) suspect |= !(fabs(x[r].re) <= 1.7976931348623157e308) || !(fabs(x[r].im) <= 1.7976931348623157e308);
+            for (int r = 0; r < P; ++r) suspect |= not_finite(x[r].re) || not_finite(x[r].im);
             if (suspect) pair_flag = 1;
             __syncthreads();
             bool skip_a = false, skip_b = false;
@@ -267,8 +336,8 @@ __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
                 for (int r = 0; r < P; ++r) {
                     const int k = tt + T * r;
                     const int ia = N - 1 - k, ib = k == 0 ? N - 1 : k - 1;
-                    bad_a |= !(fabs(ra[at(ia)]) <= 1.7976931348623157e308) || !(fabs(ra[at(ib)]) <= 1.7976931348623157e308);
-                    bad_b |= !(fabs(rb[at(ia)]) <= 1.7976931348623157e308) || !(fabs(rb[at(ib)]) <= 1.7976931348623157e308);
+                    bad_a |= not_finite(ra[at(ia)]) || not_finite(ra[at(ib)]);
+                    bad_b |= not_finite(rb[at(ia)]) || not_finite(rb[at(ib)]);
                 }
                 if (bad_a) bad_row[0] = 1;
                 if (bad_b) bad_row[1] = 1;
@@ -291,8 +360,8 @@ __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
                 const bool even = (n & 1) == 0;
                 const int m = even ? n / 2 : N - 1 - (n - 1) / 2;
                 const cplx g = lds_at<N, P>(lds, pos_of_freq<N, P>(m));
-                double ya = even ? g.re : -g.re;
-                double yb = even ? -g.im : g.im;
+                double ya = (even ? g.re : -g.re) * up_a * back_a;
+                double yb = (even ? -g.im : g.im) * up_b * back_b;
                 if (A.fused && !(CP_DST_ABLATE & 1)) {
                     const double ik = A.ikx ? A.ikx[n] : cpmath::recip(A.kx[n]);
                     ya = cpmath::exp_tab(ya, &mt) * ik;
@@ -445,8 +514,8 @@ __global__ __launch_bounds__(N / P, 2) void dst_generate_kernel(const GenArgs G)
             const int m = tt + T * r;
             const bool lower = m < N / 2;
             const double a = slots[2 * m], b = has_b ? slots[2 * m + 1] : 0.;
-            bad_a |= !(fabs(a) <= 1.7976931348623157e308);
-            bad_b |= !(fabs(b) <= 1.7976931348623157e308);
+            bad_a |= not_finite(a);
+            bad_b |= not_finite(b);
             x[r].re = lower ? a : -a;
             x[r].im = lower ? b : -b;
         }

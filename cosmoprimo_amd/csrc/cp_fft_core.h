@@ -257,6 +257,8 @@ CP_HD cplx cmul(const cplx a, const cplx b) {
 constexpr int cmin(int a, int b) { return a < b ? a : b; }
 
 // ---- row screening (cp_fftlog_body.h, "row independence") ----------------------------------------------------------------
+// NaN or +-Inf
+CP_HD bool not_finite(double v) { return !(__builtin_fabs(v) <= 1.7976931348623157e308); }
 // high dword of |v|: an unsigned integer that orders finite doubles by magnitude, with Inf / NaN above every finite value;
 // bits 30..20 are the biased exponent
 CP_HD unsigned hi_abs(double v) { return (unsigned)(__builtin_bit_cast(unsigned long long, v) >> 32) & 0x7fffffffu; }

@@ -8,11 +8,13 @@
 //   E_k = (Z_k + conj Z_{M-k}) / 2,  O_k = (Z_k - conj Z_{M-k}) / 2i,  X_k = E_k + e^{-2 pi i k / N} O_k,  k = 0 .. M  (Z_M = Z_0),
 // and back  Z_k = E_k + i O_k  with  E_k = (X_k + conj X_{M-k}) / 2,  O_k = (X_k - conj X_{M-k}) / 2 e^{+2 pi i k / N},  z = IFFT_M(Z) =
 // conj(FFT_M(conj Z)) / M.  A workgroup takes a row at a time: rows never share a transform, so a NaN or a huge row cannot reach another
-// (numpy transforms row by row).  The complex FFT is the pass machinery of the FFTLog kernel (cp_fft_core.h): radix-16 butterflies in
+// (numpy transforms row by row); a row that holds a NaN or an infinity is stored as NaN, every number of it, as the paired transforms of the
+// library store such a row (cp_dst.hip, cp_fftlog_body.h).  The complex FFT is the pass machinery of the FFTLog kernel (cp_fft_core.h): radix-16 butterflies in
 // registers, swizzled LDS exchanges, the twiddles of the passes behind the first resident in LDS.  The imaginary parts of the DC and Nyquist
 // bins are ignored on the way back, as numpy's c2r does.  HBM: 8 N + 16 (M + 1) bytes per row either way.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <new>
 #include <vector>
 
@@ -85,18 +87,33 @@ __global__ __launch_bounds__(M / P) void rfft_kernel(const RArgs A) {
     cplx* ltw = lds + lds_data_slots(M, P);
     const int t = threadIdx.x;
     for (int i = t; i < PL::TW_TOTAL - M; i += T) ltw[i] = A.tw[M + i];
-    for (long long row = blockIdx.x; row < A.nrows; row += gridDim.x) {
+    // A row with a sample that is not finite: left to the arithmetic, a NaN reaches every bin, but an infinity ends as +-Inf in a few (DC or
+    // Nyquist of the forward transform, the samples that only additions reach on the way back).  The thread that meets such a sample raises the
+    // row's flag before its first LDS store, the barriers of the transform publish it, and the row is stored as NaN.  Two flags taken in turn:
+    // a row's flag is cleared ahead of the row's first barrier, when its last reader (two rows back) is behind the first barrier of the row between.
+    // (ONE flag would not do: its readers sit behind the last barrier of the transform, with no barrier between them and the next row's clearing.)
+    __shared__ int bad_row[2];
+    const double nan = __builtin_nan("");
+    int turn = 0;
+    for (long long row = blockIdx.x; row < A.nrows; row += gridDim.x, turn ^= 1) {
         cplx x[P];
+        if (t == 0) bad_row[turn] = 0;
         __syncthreads();      // LDS reuse across rows (and the table fill on the first one)
+        bool bad = false;
         int tt = t;
         asm volatile("" : "+v"(tt));
         if constexpr (!BACKWARD) {
             const cplx* src = reinterpret_cast<const cplx*>(A.in + row * N);      // (x_2m, x_2m+1) is z_m
             cplx* dst = reinterpret_cast<cplx*>(A.out) + row * (M + 1);
 #pragma unroll
-            for (int r = 0; r < P; ++r) x[r] = src[tt + T * r];
+            for (int r = 0; r < P; ++r) {
+                x[r] = src[tt + T * r];
+                bad |= not_finite(x[r].re) || not_finite(x[r].im);
+            }
+            if (bad) bad_row[turn] = 1;
             rdif_all<M, P>(tt, A, x, lds, ltw);
             asm volatile("" : "+v"(tt));
+            const bool skip = bad_row[turn] != 0;
 #pragma unroll 4
             for (int s = 0; s < P; ++s) {
                 const int k = tt + T * s;
@@ -108,9 +125,9 @@ __global__ __launch_bounds__(M / P) void rfft_kernel(const RArgs A) {
                 cplx X = cplx{e.re + (w.re * o.re - w.im * o.im), e.im + (w.re * o.im + w.im * o.re)};
                 if (k == 0) {      // real bins: DC here, Nyquist = E_0 - O_0 behind the last bin
                     X.im = 0.;
-                    dst[M] = cplx{e.re - o.re, 0.};
+                    dst[M] = skip ? cplx{nan, nan} : cplx{e.re - o.re, 0.};
                 }
-                dst[k] = X;
+                dst[k] = skip ? cplx{nan, nan} : X;
             }
         } else {
             const cplx* src = reinterpret_cast<const cplx*>(A.in) + row * (M + 1);
@@ -123,6 +140,7 @@ __global__ __launch_bounds__(M / P) void rfft_kernel(const RArgs A) {
                 a.im *= sign;
                 b.im *= sign;
                 if (k == 0) a.im = b.im = 0.;      // DC and Nyquist count as real (numpy's c2r)
+                bad |= not_finite(a.re) || not_finite(a.im) || (k == 0 && not_finite(b.re));
                 const cplx w = A.rot[k];           // e^{-2 pi i k / N}: its conjugate is the factor of O_k
                 const cplx e = cplx{0.5 * (a.re + b.re), 0.5 * (a.im - b.im)};
                 const cplx d = cplx{0.5 * (a.re - b.re), 0.5 * (a.im + b.im)};
@@ -131,14 +149,16 @@ __global__ __launch_bounds__(M / P) void rfft_kernel(const RArgs A) {
                 x[r].re = e.re - o.im;
                 x[r].im = -(e.im + o.re);
             }
+            if (bad) bad_row[turn] = 1;
             rdif_all<M, P>(tt, A, x, lds, ltw);
             asm volatile("" : "+v"(tt));
+            const bool skip = bad_row[turn] != 0;
             const double scale = 1. / M;
 #pragma unroll 4
             for (int s = 0; s < P; ++s) {
                 const int m = tt + T * s;
                 const cplx g = lds[swz<M, P>(rpos_of_freq<M, P>(m))];
-                dst[m] = cplx{g.re * scale, -g.im * scale};
+                dst[m] = skip ? cplx{nan, nan} : cplx{g.re * scale, -g.im * scale};
             }
         }
     }

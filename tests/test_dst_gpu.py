@@ -54,6 +54,13 @@ def test_nonfinite_rows_stay_isolated():
     assert np.isnan(out[2]).all()
     for i in (0, 1, 3):
         np.testing.assert_allclose(out[i], fftpack.dst(np.log(kx * x[i]), type=2, norm='ortho'), rtol=1e-10, atol=1e-11)
+    # the way back: the pair is flagged from its packed spectrum and its rows are read again to tell the two apart
+    y = rng.uniform(0.5, 2., (4, 1024))
+    y[1, 3] = np.nan
+    out = d(torch.as_tensor(y, device='cuda'), inverse=True).cpu().numpy()
+    assert np.isnan(out[1]).all()
+    for i in (0, 2, 3):
+        np.testing.assert_allclose(out[i], fftpack.idst(y[i], type=2, norm='ortho'), rtol=1e-11, atol=1e-12)
 
 
 def test_rows_screen():

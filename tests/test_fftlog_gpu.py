@@ -413,7 +413,7 @@ def test_nonfinite_rows_stay_isolated(cp, golden):
     assert bool(torch.isnan(xi_t[1]).all()) and bool(torch.isfinite(xi_t[0]).all())
 
 
-@pytest.mark.parametrize('size', [8, 16, 32, 64, 256, 512, 1024, 4096, 8192, 16384])
+@pytest.mark.parametrize('size', [8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384])
 def test_engine_forward_backward_are_real_ffts(cp, size):
     """NumpyFFTEngine / FFTWEngine by name (reference fftlog.py:533-544): forward = rfft, backward = irfft(conj(.), n=size) on the package's own
     device FFTs (cp_rfft_forward / cp_rfft_backward) against numpy's, rows of very different magnitudes each on its own scale (one transform per
