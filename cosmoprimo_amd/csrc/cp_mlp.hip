@@ -1,0 +1,650 @@
+// cp_mlp.hip -- multi-layer perceptron emulator of a calculator (reference emulators/tools/mlp.py) for batches of parameter points (gfx950) + C ABI:
+// the batched prediction in one launch, the loss and its gradient for one training batch, and the Adam step (float64 throughout).
+// Network.  ndim inputs, L <= 8 hidden layers of widths 1 .. 64, M outputs; a layer is v @ kernel + bias with kernel (n_in, n_out) row-major; a hidden
+// layer is followed by silu, relu, tanh or identity-silu (two trained scalars alpha, beta per layer).  Parameters, gradients and Adam moments share ONE
+// packed layout: per layer kernel, bias, and for a hidden layer alpha, beta (always there, so that the layout depends on the widths alone).
+// Forward kernel (mlp_forward_kernel; predict and the forward pass of the training step).  The tile scheme of taylor_gemm_kernel (cp_taylor.hip): a
+// workgroup of four waves owns 64 rows x 256 columns of the result, a wave 64 x 64 (4 x 4 accumulator tiles of 16 x 16, 128 registers).  Fragments of
+// v_mfma_f64_16x16x4_f64: lane l supplies A[row = l & 15][k = l >> 4] and B[k = l >> 4][col = l & 15] and holds D[row = (l >> 4) + 4 r][col = l & 15]
+// in register r.  The hidden layers run on the vector ALUs with a row per lane, a wave taking the neurons j = wave (mod 4), four at a time (one LDS
+// read of the activation per four FMAs, the weights wave-uniform); their activations live in two LDS buffers in turn, k-major h[k][row] with a row
+// stride of 80 doubles -- the layout the MFMA's left operand is read from without bank conflicts (lanes l and l + 16 of a ds_read_b64 half on
+// opposite halves of the bank row) -- and never reach memory in predict.  The last hidden activation is multiplied by the output kernel on the matrix
+// cores, the right operand read straight from L1 / L2 (128 contiguous bytes per k), the operands of the next 32 MFMAs requested before this pair of
+// steps; rows of the left operand between H_L and the next multiple of 8 are zero and the matching rows of the kernel are masked (0 x NaN).
+// Every workgroup of a row tile forms the hidden layers again (sum of n_in n_out FMAs per row against 256 H_L per row on the matrix cores).
+// Epilogue, predict: + bias, v * yscale + yoffset per column, then 10^v or sinh(v); training: the residual against Y, scaled by 2 / (b M), to the
+// workspace and the sum of its squares per workgroup (fixed order).  Rows and columns past the end are never stored.
+// LDS.  2 x NR x 80 x 8 bytes, NR = max(ndim, widths) rounded up to 8: 40 KB at widths <= 32 (launch bounds: two workgroups per CU, the registers'
+// limit), 80 KB at widths up to 64 (two workgroups fill the 160 KB of a CU exactly).
+// Gradient.  gW_out = h^T . r (mlp_gw_out_kernel) and dh = r . W_out^T (mlp_dh_kernel) on the matrix cores, both operands straight from memory: in the
+// first both are contiguous along the 16 lanes of a k (and the column sums of r, the bias gradient, are taken from the fragments already loaded);
+// in the second both are contiguous along k, a wave takes one slice of the M inner indices of a row tile and stores a partial result, summed in
+// slice order by the kernel that applies the activation's derivative.  The hidden layers' products (at most 65 x 64 entries, sums over the batch)
+// run on the vector ALUs: a thread per entry and one of 16 phases of the batch, combined in a fixed order.  No floating-point atomics anywhere: two
+// calls give the same bits.
+#include "cp_internal.h"
+#include "cp_math.h"
+
+namespace {
+
+typedef double ml_v4d __attribute__((ext_vector_type(4)));
+
+constexpr int ML_ROWS = 64, ML_COLS = 256, ML_RS = 80, ML_MAX_NDIM = 32, ML_MAX_LAYERS = 8, ML_MAX_WIDTH = 64;
+constexpr int ML_TRAIN = 3;      // mode of the forward kernel: 0 .. 2 predict with the y function CP_MLP_Y_*, 3 the training forward pass
+enum { ACT_SILU = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_IDENTITY_SILU = 3 };
+
+struct MlpNet {
+    int ndim, L, M, nr;                 // nr: rows of an LDS buffer
+    int d[ML_MAX_LAYERS + 2];           // ndim, the widths, M
+    int act[ML_MAX_LAYERS];
+    long long off[ML_MAX_LAYERS + 1];   // start of layer l in the packed buffer (l = L: the output layer)
+    long long total;
+};
+
+// workspace of cp_mlp_loss_grad, in doubles
+struct MlpWork {
+    long long z[ML_MAX_LAYERS], h[ML_MAX_LAYERS];   // (b, d[l + 1]) pre-activations and activations of hidden layer l
+    long long resid, losspart, part, dz[2], ca, cb, total;
+    int nrt, nct, nsl, ks;                          // row tiles, column tiles; slices of the M inner indices of mlp_dh_kernel and their length
+};
+
+struct MlpFwdArgs {
+    const double* x;          // (R, ndim): raw parameters (predict), scaled ones (training)
+    const double* params;
+    const double* xoff;
+    const double* xscale;
+    const double* yoff;
+    const double* yscale;
+    const double* ytrue;      // training: (R, M)
+    double* out;              // predict: (R, M); training: the scaled residual (R, M)
+    double* work;             // training
+    long long R;
+    double rscale;            // 2 / (R M)
+    MlpNet net;
+    MlpWork ws;
+};
+
+__device__ __forceinline__ double sigmoid(double v) { return 1. / (1. + cpmath::exp_mid(-v)); }
+
+__device__ __forceinline__ double activate(int act, double v, double alpha, double beta) {
+    switch (act) {
+        case ACT_SILU: return v / (1. + cpmath::exp_mid(-v));
+        case ACT_RELU: return v > 0. ? v : (v != v ? v : 0.);      // a NaN stays one
+        case ACT_TANH: return tanh(v);
+        default: return ((1. - beta) + beta / (1. + cpmath::exp_mid(-alpha * v))) * v;
+    }
+}
+
+// The operands of the eight inner indices 8 p .. 8 p + 7 for one wave: two MFMA steps.  A row of the right operand past K is never read: its place in
+// the left operand is 0, and 0 x NaN would not be (row 0 is fetched in its place and masked by mlp_mask).
+__device__ __forceinline__ void mlp_load(const double* B, const int K, const int M, const double* buf, const int p, const int l15, const int g, const int (&colj)[4],
+                                         double (&a)[2][4], double (&b)[2][4], bool (&keep)[2]) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int k = 8 * p + 4 * h + g;
+        const bool inside = k < K;
+        const double* br = B + (long long)(inside ? k : 0) * M;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) b[h][j] = br[colj[j]];
+        keep[h] = inside;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[h][i] = buf[k * ML_RS + 16 * i + l15];
+    }
+}
+
+__device__ __forceinline__ void mlp_mask(double (&b)[2][4], const bool (&keep)[2]) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) b[h][j] = keep[h] ? b[h][j] : 0.;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256, 2) void mlp_forward_kernel(const MlpFwdArgs A) {
+    extern __shared__ double ml_lds[];
+    const MlpNet& N = A.net;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int l15 = lane & 15, g = lane >> 4;
+    const long long row0 = (long long)blockIdx.x * ML_ROWS;
+    const int col0 = (int)blockIdx.y * ML_COLS + wave * 64;
+    double* cur = ml_lds;
+    double* nxt = ml_lds + N.nr * ML_RS;
+    {      // the inputs of the tile's rows, k-major; rows past the end: finite, never stored
+        const long long row = row0 + lane;
+        for (int i = wave; i < N.ndim; i += 4) {
+            double v = 0.;
+            if (row < A.R) {
+                v = A.x[row * N.ndim + i];
+                if (MODE != ML_TRAIN) v = (v - A.xoff[i]) / A.xscale[i];
+            }
+            cur[i * ML_RS + lane] = v;
+        }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int l = 0; l < N.L; ++l) {
+        const int nin = N.d[l], nout = N.d[l + 1], act = N.act[l];
+        const double* W = A.params + N.off[l];
+        const double* bias = W + nin * nout;
+        const double alpha = bias[nout], beta = bias[nout + 1];
+        const bool record = MODE == ML_TRAIN && blockIdx.y == 0 && row0 + lane < A.R;
+#pragma unroll 1
+        for (int j0 = wave; j0 < nout; j0 += 16) {
+            int jq[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) jq[q] = j0 + 4 * q < nout ? j0 + 4 * q : j0;
+            double acc[4] = {0., 0., 0., 0.};
+#pragma unroll 2
+            for (int k = 0; k < nin; ++k) {
+                const double hv = cur[k * ML_RS + lane];
+                const double* wr = W + k * nout;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[q] = fma(hv, wr[jq[q]], acc[q]);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int j = j0 + 4 * q;
+                if (j >= nout) break;
+                const double z = acc[q] + bias[j];
+                const double hval = activate(act, z, alpha, beta);
+                nxt[j * ML_RS + lane] = hval;
+                if (record) {
+                    const long long e = (row0 + lane) * nout + j;
+                    A.work[A.ws.z[l] + e] = z;
+                    A.work[A.ws.h[l] + e] = hval;
+                }
+            }
+        }
+        for (int j = nout + wave; j < ((nout + 7) & ~7); j += 4) nxt[j * ML_RS + lane] = 0.;      // the left operand's rows up to the next pair of MFMA steps
+        __syncthreads();
+        double* const t = cur;
+        cur = nxt;
+        nxt = t;
+    }
+    // the output layer on the matrix cores
+    const int K = N.d[N.L], M = N.M;
+    const double* Wo = A.params + N.off[N.L];
+    const double* bo = Wo + (long long)K * M;
+    const bool active = col0 < M;      // (wave-uniform; an idle wave multiplies the last column: no branch round the MFMAs)
+    ml_v4d acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = ml_v4d{0., 0., 0., 0.};
+    int colj[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int col = col0 + 16 * j + l15;
+        colj[j] = col < M ? col : M - 1;      // columns past the end repeat the last one (never stored)
+    }
+    {
+        const int npairs = (K + 7) / 8;
+        double a0[2][4], b0[2][4];
+        bool keep[2];
+        mlp_load(Wo, K, M, cur, 0, l15, g, colj, a0, b0, keep);
+        mlp_mask(b0, keep);
+#pragma unroll 1
+        for (int p = 0; p < npairs; ++p) {
+            double a1[2][4], b1[2][4];
+            mlp_load(Wo, K, M, cur, p + 1 < npairs ? p + 1 : p, l15, g, colj, a1, b1, keep);
+            __builtin_amdgcn_sched_barrier(0);      // the loads are issued here, not moved below the MFMAs
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[h][i], b0[h][j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) a0[h][i] = a1[h][i], b0[h][i] = b1[h][i];
+            __builtin_amdgcn_sched_barrier(0);
+            mlp_mask(b0, keep);
+        }
+    }
+    double sq = 0.;      // training: this thread's share of sum (y_pred - y_true)^2
+    if (active) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int col = col0 + 16 * j + l15;
+            if (col >= M) continue;
+            const double bj = bo[col];
+            double ys = 1., yo = 0.;
+            if (MODE != ML_TRAIN) ys = A.yscale[col], yo = A.yoff[col];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const long long row = row0 + 16 * i + g + 4 * r;
+                    if (row >= A.R) continue;
+                    double v = acc[i][j][r] + bj;
+                    if (MODE == ML_TRAIN) {
+                        v -= A.ytrue[row * M + col];
+                        sq = fma(v, v, sq);
+                        v *= A.rscale;
+                    } else {
+                        v = fma(v, ys, yo);
+                        if (MODE == CP_MLP_Y_EXP10) v = cpmath::exp10_mid(v);
+                        if (MODE == CP_MLP_Y_SINH) v = sinh(v);
+                    }
+                    A.out[row * M + col] = v;
+                }
+        }
+    }
+    if (MODE == ML_TRAIN) {      // the workgroup's sum in thread order
+        __syncthreads();
+        ml_lds[threadIdx.x] = sq;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double s = 0.;
+            for (int t = 0; t < 256; ++t) s += ml_lds[t];
+            A.work[A.ws.losspart + (long long)blockIdx.y * gridDim.x + blockIdx.x] = s;
+        }
+    }
+}
+
+// dst[0] = scale * sum src[0 .. n): one workgroup of 1024 threads, a thread the entries t, t + 1024, ... in order, then the threads in order
+__global__ __launch_bounds__(1024) void mlp_sum_kernel(const double* src, long long n, double scale, double* dst) {
+    __shared__ double part[1024];
+    double s = 0.;
+    for (long long e = threadIdx.x; e < n; e += 1024) s += src[e];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) dst[0] = scale * part[0];
+}
+
+// gW_out (H, M) = h^T (H, b) . r (b, M) and gb_out = column sums of r.  A workgroup owns 256 columns, a wave 64 of them and all H <= 16 NI rows; the
+// inner index is the sample.  Both operands come straight from memory, contiguous along the 16 lanes of a k.
+template <int NI>
+__global__ __launch_bounds__(256, 2) void mlp_gw_out_kernel(const double* h, const double* r, const long long b, const int H, const int M, double* gW) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int l15 = lane & 15, g = lane >> 4;
+    const int col0 = (int)blockIdx.x * ML_COLS + wave * 64;
+    if (col0 >= M) return;      // (no barrier in this kernel)
+    int colj[4], rowi[NI];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int col = col0 + 16 * j + l15;
+        colj[j] = col < M ? col : M - 1;
+    }
+#pragma unroll
+    for (int i = 0; i < NI; ++i) rowi[i] = 16 * i + l15 < H ? 16 * i + l15 : H - 1;
+    ml_v4d acc[NI][4];
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = ml_v4d{0., 0., 0., 0.};
+    double cs[4] = {0., 0., 0., 0.};
+    const long long nsteps = (b + 3) / 4;
+#pragma unroll 1
+    for (long long s = 0; s < nsteps; ++s) {
+        const long long k = 4 * s + g;
+        const bool inside = k < b;
+        const double* hr = h + (inside ? k : 0) * H;
+        const double* rr = r + (inside ? k : 0) * M;
+        double a[NI], bb[4];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) a[i] = hr[rowi[i]];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bb[j] = rr[colj[j]];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) a[i] = inside ? a[i] : 0.;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            bb[j] = inside ? bb[j] : 0.;
+            cs[j] += bb[j];
+        }
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], bb[j], acc[i][j], 0, 0, 0);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {      // the four lane groups of a column, in a fixed order
+        cs[j] += __shfl_xor(cs[j], 16);
+        cs[j] += __shfl_xor(cs[j], 32);
+        const int col = col0 + 16 * j + l15;
+        if (col >= M) continue;
+        if (g == 0) gW[(long long)H * M + col] = cs[j];
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int row = 16 * i + g + 4 * q;
+                if (row < H) gW[(long long)row * M + col] = acc[i][j][q];
+            }
+    }
+}
+
+// partial dh (slice, b, H) = r (b, M) . W_out^T (M, H) over one slice of the M inner indices per wave; both operands contiguous along k.
+template <int NJ>
+__global__ __launch_bounds__(256, 2) void mlp_dh_kernel(const double* r, const double* W, const long long b, const int H, const int M, const int nsl, const int ks,
+                                                        double* part) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int l15 = lane & 15, g = lane >> 4;
+    const int sl = (int)blockIdx.y * 4 + wave;
+    if (sl >= nsl) return;      // (no barrier in this kernel)
+    const long long row0 = (long long)blockIdx.x * ML_ROWS;
+    const int kbeg = sl * ks, kend = kbeg + ks < M ? kbeg + ks : M;
+    const double* ar[4];
+    const double* br[NJ];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const long long row = row0 + 16 * i + l15;
+        ar[i] = r + (row < b ? row : b - 1) * M;
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) br[j] = W + (long long)(16 * j + l15 < H ? 16 * j + l15 : H - 1) * M;
+    ml_v4d acc[4][NJ];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[i][j] = ml_v4d{0., 0., 0., 0.};
+#pragma unroll 1
+    for (int k0 = kbeg; k0 < kend; k0 += 4) {
+        const int k = k0 + g;
+        const bool inside = k < kend;
+        const int kk = inside ? k : kbeg;
+        double a[4], bb[NJ];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] = ar[i][kk];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) bb[j] = br[j][kk];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] = inside ? a[i] : 0.;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) bb[j] = inside ? bb[j] : 0.;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], bb[j], acc[i][j], 0, 0, 0);
+    }
+    double* out = part + (long long)sl * b * H;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int col = 16 * j + l15;
+        if (col >= H) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const long long row = row0 + 16 * i + g + 4 * q;
+                if (row < b) out[row * H + col] = acc[i][j][q];
+            }
+    }
+}
+
+// dz_l (b, H) = dh_l * act'(z_l) for hidden layer l, a thread per entry.  dh_l: the sum of the nsl partial products of mlp_dh_kernel in slice order (the
+// last hidden layer), else dz_{l+1} . W_{l+1}^T.  identity-silu: the entries' contributions to the gradients of alpha and beta to ca, cb.
+__global__ __launch_bounds__(256) void mlp_dz_kernel(const double* part, const int nsl, const double* dznext, const double* Wnext, const int Hn, const double* z,
+                                                     const long long b, const int H, const int act, const double* ab, double* dz, double* ca, double* cb) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= b * H) return;
+    double dh = 0.;
+    if (part) {
+        for (int s = 0; s < nsl; ++s) dh += part[(long long)s * b * H + e];
+    } else {
+        const long long row = e / H;
+        const int i = (int)(e % H);
+        for (int j = 0; j < Hn; ++j) dh = fma(dznext[row * Hn + j], Wnext[i * Hn + j], dh);
+    }
+    const double v = z[e];
+    double d;
+    switch (act) {
+        case ACT_SILU: {
+            const double s = sigmoid(v);
+            d = s * (1. + v * (1. - s));
+            break;
+        }
+        case ACT_RELU: d = v > 0. ? 1. : 0.; break;
+        case ACT_TANH: {
+            const double t = tanh(v);
+            d = 1. - t * t;
+            break;
+        }
+        default: {
+            const double alpha = ab[0], beta = ab[1];
+            const double s = sigmoid(alpha * v), s1 = s * (1. - s);
+            d = (1. - beta) + beta * (s + alpha * v * s1);
+            ca[e] = dh * (beta * s1 * v * v);
+            cb[e] = dh * ((s - 1.) * v);
+        }
+    }
+    dz[e] = dh * d;
+}
+
+// gradient of hidden layer l: gW (nin, nout) = hprev^T . dz, gb (nout) = column sums of dz -- (nin + 1, nout) entries contiguous in the packed
+// layout -- a thread per entry and one of 16 phases of the batch (64 entries x 16 phases per workgroup), the phases combined in order.  clear_ab: the
+// layer has no alpha, beta to train (not identity-silu); their two gradients, which follow the bias's, are set to 0 here.
+__global__ __launch_bounds__(1024) void mlp_gw_hidden_kernel(const double* hprev, const double* dz, const long long b, const int nin, const int nout, double* g,
+                                                             const bool clear_ab) {
+    __shared__ double part[16][64];
+    const int t = threadIdx.x & 63, phase = threadIdx.x >> 6;
+    const int e = (int)blockIdx.x * 64 + t;
+    double s = 0.;
+    if (e < (nin + 1) * nout) {
+        const int i = e / nout, j = e % nout;
+        if (i < nin) {
+            for (long long r = phase; r < b; r += 16) s = fma(hprev[r * nin + i], dz[r * nout + j], s);
+        } else {
+            for (long long r = phase; r < b; r += 16) s += dz[r * nout + j];
+        }
+    }
+    part[phase][t] = s;
+    __syncthreads();
+    if (phase == 0 && e < (nin + 1) * nout) {
+        double total = 0.;
+        for (int p = 0; p < 16; ++p) total += part[p][t];
+        g[e] = total;
+    }
+    if (clear_ab && blockIdx.x == 0 && threadIdx.x < 2) g[(nin + 1) * nout + threadIdx.x] = 0.;
+}
+
+__global__ __launch_bounds__(256) void mlp_adam_kernel(double* p, double* m, double* v, const double* g, const long long n, const double lr, const double b1,
+                                                       const double b2, const double eps, const double c1, const double c2) {
+#pragma clang fp contract(off)      // the formula as written, every operation rounded once
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const double ge = g[e];
+    const double me = b1 * m[e] + (1. - b1) * ge;
+    const double ve = b2 * v[e] + (1. - b2) * (ge * ge);
+    m[e] = me;
+    v[e] = ve;
+    p[e] -= lr * (me / c1) / (sqrt(ve / c2) + eps);
+}
+
+int mlp_net(const char* who, int ndim, int nlayers, const int* widths, const int* activations, int M, MlpNet* net) {
+    if (ndim < 1 || nlayers < 1 || M < 1 || !widths) return cp::fail(CP_EINVAL, "%s: need ndim, M >= 1, at least one hidden layer and its widths", who);
+    if (ndim > ML_MAX_NDIM) return cp::fail(CP_EUNSUPPORTED, "%s: %d parameters (at most %d)", who, ndim, ML_MAX_NDIM);
+    if (nlayers > ML_MAX_LAYERS) return cp::fail(CP_EUNSUPPORTED, "%s: %d hidden layers (at most %d)", who, nlayers, ML_MAX_LAYERS);
+    net->ndim = ndim, net->L = nlayers, net->M = M;
+    net->d[0] = ndim;
+    int widest = ndim;
+    for (int l = 0; l < nlayers; ++l) {
+        if (widths[l] < 1) return cp::fail(CP_EINVAL, "%s: hidden layer %d has width %d", who, l, widths[l]);
+        if (widths[l] > ML_MAX_WIDTH) return cp::fail(CP_EUNSUPPORTED, "%s: hidden layer %d has width %d (at most %d)", who, l, widths[l], ML_MAX_WIDTH);
+        if (activations && (activations[l] < ACT_SILU || activations[l] > ACT_IDENTITY_SILU))
+            return cp::fail(CP_EINVAL, "%s: activation code %d of hidden layer %d (0 silu, 1 relu, 2 tanh, 3 identity-silu)", who, activations[l], l);
+        net->d[l + 1] = widths[l];
+        net->act[l] = activations ? activations[l] : 0;
+        widest = widths[l] > widest ? widths[l] : widest;
+    }
+    net->d[nlayers + 1] = M;
+    net->nr = (widest + 7) & ~7;
+    long long off = 0;
+    for (int l = 0; l <= nlayers; ++l) {
+        net->off[l] = off;
+        off += ((long long)net->d[l] + 1) * net->d[l + 1] + (l < nlayers ? 2 : 0);
+    }
+    net->total = off;
+    return CP_OK;
+}
+
+void mlp_work(const MlpNet& net, long long b, MlpWork* ws) {
+    long long off = 0, hmax = 0;
+    for (int l = 0; l < net.L; ++l) {
+        ws->z[l] = off, off += b * net.d[l + 1];
+        ws->h[l] = off, off += b * net.d[l + 1];
+        hmax = net.d[l + 1] > hmax ? net.d[l + 1] : hmax;
+    }
+    const long long nrt = (b + ML_ROWS - 1) / ML_ROWS;
+    ws->nrt = (int)nrt, ws->nct = (net.M + ML_COLS - 1) / ML_COLS;
+    // slices of mlp_dh_kernel: about 1024 waves in flight, a slice at least 64 inner indices and a multiple of 8
+    long long nsl = nrt > 0 ? (1024 + nrt - 1) / nrt : 1;
+    const long long most = (net.M + 63) / 64;
+    nsl = nsl > most ? most : nsl;
+    ws->ks = (int)((((net.M + nsl - 1) / nsl) + 7) & ~7LL);
+    ws->nsl = (net.M + ws->ks - 1) / ws->ks;
+    ws->resid = off, off += b * net.M;
+    ws->losspart = off, off += nrt * ws->nct;
+    ws->part = off, off += (long long)ws->nsl * b * net.d[net.L];
+    ws->dz[0] = off, off += b * hmax;
+    ws->dz[1] = off, off += b * hmax;
+    ws->ca = off, off += b * hmax;
+    ws->cb = off, off += b * hmax;
+    ws->total = off;
+}
+
+template <int MODE>
+int mlp_forward_launch(const char* who, const MlpFwdArgs& A, void* stream) {
+    const long long nrt = (A.R + ML_ROWS - 1) / ML_ROWS, nct = (A.net.M + ML_COLS - 1) / ML_COLS;
+    if (nrt > 0x7fffffffLL || nct > 65535) return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d results (at most 2^37 rows, 2^24 - 256 columns)", who, A.R, A.net.M);
+    const size_t lds = (size_t)2 * A.net.nr * ML_RS * sizeof(double);      // 40 KB at widths <= 32, at most 80 KB
+    if (lds > 64 * 1024) {
+        const hipError_t e = cp::allow_full_lds<mlp_forward_kernel<MODE>>();
+        if (e != hipSuccess) return cp::launch_status(who, e);
+    }
+    hipLaunchKernelGGL(mlp_forward_kernel<MODE>, dim3((unsigned)nrt, (unsigned)nct), dim3(256), lds, static_cast<hipStream_t>(stream), A);
+    return CP_OK;
+}
+
+}  // namespace
+
+extern "C" long long cp_mlp_param_count(int ndim, int nlayers, const int* widths, int M) {
+    MlpNet net;
+    const int status = mlp_net("cp_mlp_param_count", ndim, nlayers, widths, nullptr, M, &net);
+    return status == CP_OK ? net.total : -(long long)status;
+}
+
+extern "C" long long cp_mlp_workspace_doubles(long long b, int ndim, int nlayers, const int* widths, int M) {
+    MlpNet net;
+    if (b < 0) return -(long long)cp::fail(CP_EINVAL, "cp_mlp_workspace_doubles: negative batch size");
+    const int status = mlp_net("cp_mlp_workspace_doubles", ndim, nlayers, widths, nullptr, M, &net);
+    if (status != CP_OK) return -(long long)status;
+    MlpWork ws;
+    mlp_work(net, b, &ws);
+    return ws.total;
+}
+
+extern "C" int cp_mlp_predict(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
+                              const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, double* d_out,
+                              int device, void* stream) {
+    MlpFwdArgs A{};
+    if (B < 0) return cp::fail(CP_EINVAL, "cp_mlp_predict: negative count of points");
+    if (!activations) return cp::fail(CP_EINVAL, "cp_mlp_predict: no activation codes");
+    const int status = mlp_net("cp_mlp_predict", ndim, nlayers, widths, activations, M, &A.net);
+    if (status != CP_OK) return status;
+    if (yfunction < CP_MLP_Y_NONE || yfunction > CP_MLP_Y_SINH) return cp::fail(CP_EINVAL, "cp_mlp_predict: y function %d (0 none, 1 10^v, 2 sinh)", yfunction);
+    if (B == 0) return CP_OK;
+    if (!d_x || !d_params || !d_xoffset || !d_xscale || !d_yoffset || !d_yscale || !d_out) return cp::fail(CP_EINVAL, "cp_mlp_predict: null pointer");
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_mlp_predict: cannot select device %d", device);
+    A.x = d_x, A.params = d_params, A.xoff = d_xoffset, A.xscale = d_xscale, A.yoff = d_yoffset, A.yscale = d_yscale, A.out = d_out, A.R = B;
+    int launched;
+    if (yfunction == CP_MLP_Y_NONE) launched = mlp_forward_launch<CP_MLP_Y_NONE>("cp_mlp_predict", A, stream);
+    else if (yfunction == CP_MLP_Y_EXP10) launched = mlp_forward_launch<CP_MLP_Y_EXP10>("cp_mlp_predict", A, stream);
+    else launched = mlp_forward_launch<CP_MLP_Y_SINH>("cp_mlp_predict", A, stream);
+    if (launched != CP_OK) return launched;
+    return cp::launch_status("cp_mlp_predict");
+}
+
+extern "C" int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long b, int ndim, int nlayers, const int* widths, const int* activations, int M,
+                                const double* d_params, double* d_work, long long work_doubles, double* d_loss, double* d_grad, int device, void* stream) {
+    const char* who = "cp_mlp_loss_grad";
+    MlpFwdArgs A{};
+    if (b < 0) return cp::fail(CP_EINVAL, "cp_mlp_loss_grad: negative batch size");
+    if (!activations) return cp::fail(CP_EINVAL, "cp_mlp_loss_grad: no activation codes");
+    const int status = mlp_net(who, ndim, nlayers, widths, activations, M, &A.net);
+    if (status != CP_OK) return status;
+    if (b == 0) return CP_OK;
+    if (!d_X || !d_Y || !d_params || !d_work || !d_loss) return cp::fail(CP_EINVAL, "cp_mlp_loss_grad: null pointer");
+    const MlpNet& N = A.net;
+    mlp_work(N, b, &A.ws);
+    const MlpWork& ws = A.ws;
+    if (work_doubles < ws.total) return cp::fail(CP_EINVAL, "cp_mlp_loss_grad: workspace of %lld doubles, %lld needed (cp_mlp_workspace_doubles)", work_doubles, ws.total);
+    if ((long long)ws.nrt * 64 > 0x7fffffffLL || (b * ML_MAX_WIDTH + 255) / 256 > 0x7fffffffLL) return cp::fail(CP_EUNSUPPORTED, "cp_mlp_loss_grad: batch of %lld rows", b);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_mlp_loss_grad: cannot select device %d", device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    A.x = d_X, A.params = d_params, A.ytrue = d_Y, A.out = d_work + ws.resid, A.work = d_work, A.R = b;
+    A.rscale = 2. / ((double)b * (double)M);
+    const int launched = mlp_forward_launch<ML_TRAIN>(who, A, stream);
+    if (launched != CP_OK) return launched;
+    hipLaunchKernelGGL(mlp_sum_kernel, dim3(1), dim3(1024), 0, st, d_work + ws.losspart, (long long)ws.nrt * ws.nct, 1. / ((double)b * (double)M), d_loss);
+    if (!d_grad) return cp::launch_status(who);
+    const int L = N.L, H = N.d[L];
+    const double* resid = d_work + ws.resid;
+    {      // the output layer's gradient
+        const double* hL = d_work + ws.h[L - 1];
+        double* gW = d_grad + N.off[L];
+        const dim3 grid((unsigned)ws.nct);
+        switch ((H + 15) / 16) {
+            case 1: hipLaunchKernelGGL(mlp_gw_out_kernel<1>, grid, dim3(256), 0, st, hL, resid, b, H, M, gW); break;
+            case 2: hipLaunchKernelGGL(mlp_gw_out_kernel<2>, grid, dim3(256), 0, st, hL, resid, b, H, M, gW); break;
+            case 3: hipLaunchKernelGGL(mlp_gw_out_kernel<3>, grid, dim3(256), 0, st, hL, resid, b, H, M, gW); break;
+            default: hipLaunchKernelGGL(mlp_gw_out_kernel<4>, grid, dim3(256), 0, st, hL, resid, b, H, M, gW);
+        }
+    }
+    {      // dh of the last hidden layer, in slices of the outputs
+        const double* Wo = d_params + N.off[L];
+        double* part = d_work + ws.part;
+        const dim3 grid((unsigned)ws.nrt, (unsigned)((ws.nsl + 3) / 4));
+        switch ((H + 15) / 16) {
+            case 1: hipLaunchKernelGGL(mlp_dh_kernel<1>, grid, dim3(256), 0, st, resid, Wo, b, H, M, ws.nsl, ws.ks, part); break;
+            case 2: hipLaunchKernelGGL(mlp_dh_kernel<2>, grid, dim3(256), 0, st, resid, Wo, b, H, M, ws.nsl, ws.ks, part); break;
+            case 3: hipLaunchKernelGGL(mlp_dh_kernel<3>, grid, dim3(256), 0, st, resid, Wo, b, H, M, ws.nsl, ws.ks, part); break;
+            default: hipLaunchKernelGGL(mlp_dh_kernel<4>, grid, dim3(256), 0, st, resid, Wo, b, H, M, ws.nsl, ws.ks, part);
+        }
+    }
+    for (int l = L - 1; l >= 0; --l) {      // hidden layer l: d[l] -> d[l + 1]
+        const int nin = N.d[l], nout = N.d[l + 1];
+        double* dz = d_work + ws.dz[l & 1];
+        const double* ab = d_params + N.off[l] + (long long)(nin + 1) * nout;
+        double* gl = d_grad + N.off[l];
+        const unsigned nblocks = (unsigned)((b * nout + 255) / 256);
+        if (l == L - 1)
+            hipLaunchKernelGGL(mlp_dz_kernel, dim3(nblocks), dim3(256), 0, st, d_work + ws.part, ws.nsl, nullptr, nullptr, 0, d_work + ws.z[l], b, nout, N.act[l], ab,
+                               dz, d_work + ws.ca, d_work + ws.cb);
+        else
+            hipLaunchKernelGGL(mlp_dz_kernel, dim3(nblocks), dim3(256), 0, st, nullptr, 0, d_work + ws.dz[(l + 1) & 1], d_params + N.off[l + 1], N.d[l + 2],
+                               d_work + ws.z[l], b, nout, N.act[l], ab, dz, d_work + ws.ca, d_work + ws.cb);
+        const double* hprev = l == 0 ? d_X : d_work + ws.h[l - 1];
+        hipLaunchKernelGGL(mlp_gw_hidden_kernel, dim3((unsigned)(((nin + 1) * nout + 63) / 64)), dim3(1024), 0, st, hprev, dz, b, nin, nout, gl,
+                           N.act[l] != ACT_IDENTITY_SILU);
+        double* gab = gl + (long long)(nin + 1) * nout;
+        if (N.act[l] == ACT_IDENTITY_SILU) {
+            hipLaunchKernelGGL(mlp_sum_kernel, dim3(1), dim3(1024), 0, st, d_work + ws.ca, b * nout, 1., gab);
+            hipLaunchKernelGGL(mlp_sum_kernel, dim3(1), dim3(1024), 0, st, d_work + ws.cb, b * nout, 1., gab + 1);
+        }
+    }
+    return cp::launch_status(who);
+}
+
+extern "C" int cp_mlp_adam(double* d_params, double* d_m, double* d_v, const double* d_grad, long long n, double lr, double b1, double b2, double eps, double c1,
+                           double c2, int device, void* stream) {
+    if (n < 0) return cp::fail(CP_EINVAL, "cp_mlp_adam: negative count of parameters");
+    if (!(c1 > 0.) || !(c2 > 0.)) return cp::fail(CP_EINVAL, "cp_mlp_adam: bias corrections c1 = %g, c2 = %g must be positive", c1, c2);
+    if (n == 0) return CP_OK;
+    if (!d_params || !d_m || !d_v || !d_grad) return cp::fail(CP_EINVAL, "cp_mlp_adam: null pointer");
+    if ((n + 255) / 256 > 0x7fffffffLL) return cp::fail(CP_EUNSUPPORTED, "cp_mlp_adam: %lld parameters", n);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_mlp_adam: cannot select device %d", device);
+    hipLaunchKernelGGL(mlp_adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), d_params, d_m, d_v, d_grad, n, lr, b1,
+                       b2, eps, c1, c2);
+    return cp::launch_status("cp_mlp_adam");
+}

@@ -10,8 +10,8 @@ Quantities follow the state dictionaries of the reference's emulated sections (c
 silently drops 'fourier.pk.*' for its analytic engines (their ``pk_interpolator`` rejects the ``non_linear`` keyword and the error is
 swallowed); here the pairs the analytic engines do provide ('delta_m', 'theta_m') are returned.  The consumer of those batches is built too: the
 Taylor-expansion emulator (``Emulator``, ``TaylorEmulatorEngine``, ``DiffSampler`` of :mod:`.tools`: the whole finite-difference grid in one call of
-the calculator, fit and batched prediction on the device).  The neural-network emulator classes of that module are not (not on
-the hot path).
+the calculator, fit and batched prediction on the device) and the multi-layer perceptron emulator (``MLPEmulatorEngine``, ``QMCSampler``: quasi-random
+samples over the prior box in one call of the calculator, Adam training and one-launch batched prediction on the device).
 """
 import numpy as np
 
@@ -115,4 +115,4 @@ def get_calculator(cosmo, section=None):
     return calculator
 
 
-from .tools import Emulator, TaylorEmulatorEngine, DiffSampler  # noqa: E402,F401
+from .tools import Emulator, TaylorEmulatorEngine, MLPEmulatorEngine, DiffSampler, QMCSampler  # noqa: E402,F401

@@ -1,5 +1,7 @@
-"""Emulation tools under the reference's names (cosmoprimo/emulators/tools): the finite-difference sampler and the Taylor-expansion engine."""
-from .samples import DiffSampler, Samples, deriv_ncoeffs
+"""Emulation tools under the reference's names (cosmoprimo/emulators/tools): the finite-difference and quasi Monte-Carlo samplers, the Taylor-expansion
+engine and the multi-layer perceptron engine."""
+from .samples import DiffSampler, QMCSampler, Samples, deriv_ncoeffs, rqrs_points
 from .taylor import Emulator, TaylorEmulatorEngine, fd_weights, taylor_operator
+from .mlp import MLPEmulatorEngine
 
-__all__ = ['DiffSampler', 'Samples', 'Emulator', 'TaylorEmulatorEngine', 'deriv_ncoeffs', 'fd_weights', 'taylor_operator']
+__all__ = ['DiffSampler', 'QMCSampler', 'Samples', 'Emulator', 'TaylorEmulatorEngine', 'MLPEmulatorEngine', 'deriv_ncoeffs', 'fd_weights', 'taylor_operator', 'rqrs_points']

@@ -3,7 +3,9 @@ Finite-difference sampler under the reference's name (cosmoprimo/emulators/tools
 points a Taylor expansion of given order and accuracy needs, and evaluates the calculator on it.  The reference evaluates one clone per grid point;
 here the whole grid is ONE call of the calculator, every parameter an array of ``npoints`` values -- what ``get_calculator`` is made for.
 
-No MPI, no ``save_fn`` / resume, no other samplers.
+``QMCSampler`` (reference samples.py:672-714) draws quasi-random points over the box of the limits for the MLP engine and evaluates them the same way.
+
+No MPI, no ``save_fn`` / resume, no ``InputSampler`` / ``GridSampler``.
 """
 import fnmatch
 
@@ -54,6 +56,80 @@ def _pruned_grid(axes, used=0):
         nodes = coords[tags == tag]
         points += [head + (x,) for head in heads for x in nodes]
     return points
+
+
+def rqrs_points(ndim, n, seed=0.5):
+    """First ``n`` points of the R quasi-random sequence in ``ndim`` dimensions, (n, ndim) in [0, 1): point i = 1 .. n has the coordinates
+    ``(seed + i g^-k) mod 1``, k = 1 .. ndim, with g > 1 the root of ``g^(ndim + 1) = g + 1`` (the generalised golden ratio), found by Newton's method
+    from 1 until the residual is below 1e-12.  Same operations in the same order as the reference's ``RQuasiRandomSequence`` (samples.py:286-311), because
+    the points have to equal its points bit for bit (tests/test_mlp_host.py::test_qmc_points)."""
+    def residual(g):
+        return g**(ndim + 1) - g - 1
+
+    root = 1.
+    while abs(residual(root)) > 1e-12:
+        slope = (ndim + 1) * root**ndim - 1
+        root = root - residual(root) / slope
+    steps = [root**(-k) for k in range(1, ndim + 1)]
+    index = np.arange(1, n + 1).reshape(n, 1)
+    return np.mod(float(seed) + index * steps, 1.)
+
+
+class QMCSampler(object):
+
+    """Quasi Monte-Carlo samples over the box of the parameters' limits (reference samples.py:672-714; engine :class:`MLPEmulatorEngine`): 'sobol',
+    'halton', 'lhs' of :mod:`scipy.stats.qmc` or 'rqrs', the R quasi-random sequence.  The calculator is evaluated on all points in one batched call."""
+
+    def __init__(self, calculator, params, engine='rqrs', **kwargs):
+        """``kwargs``: arguments of the engine, e.g. ``seed`` (for 'rqrs' the offset of the sequence, 0.5 by default)."""
+        self.calculator = calculator
+        self.params = {name: tuple(float(v) for v in limits) for name, limits in params.items()}
+        if not self.params:
+            raise ValueError('Provide at least one parameter')
+        if engine not in ('sobol', 'halton', 'lhs', 'rqrs'):
+            raise ValueError("engine must be one of 'sobol', 'halton', 'lhs', 'rqrs', got {!r}".format(engine))
+        self.engine, self.engine_options = engine, dict(kwargs)
+        self.samples = None
+
+    def points(self, niterations=300):
+        """``niterations`` points scaled to the limits, as :class:`Samples`."""
+        from scipy.stats import qmc
+        ndim = len(self.params)
+        if self.engine == 'rqrs':
+            unit = rqrs_points(ndim, int(niterations), **self.engine_options)
+        else:
+            cls = {'sobol': qmc.Sobol, 'halton': qmc.Halton, 'lhs': qmc.LatinHypercube}[self.engine]
+            unit = cls(d=ndim, **self.engine_options).random(n=int(niterations))
+        X = qmc.scale(unit, [limits[0] for limits in self.params.values()], [limits[1] for limits in self.params.values()])
+        return Samples({name: X[:, i].copy() for i, name in enumerate(self.params)}, attrs={'params': dict(self.params)})
+
+    def run(self, niterations=300, batch_size=None):
+        """Evaluate the calculator on all points in one batched call (or in chunks of ``batch_size`` points) and once at the centre of the box (scalars:
+        the unbatched shapes, which tell *varied* from *fixed* outputs as in :meth:`DiffSampler.run`).  Points with a non-finite varied output are
+        dropped from parameters and outputs alike (the reference masks failed samples); ``attrs['ndropped']`` counts them."""
+        samples = self.points(niterations)
+        npoints = int(niterations)
+        center = self.calculator(**{name: float(np.mean(limits)) for name, limits in self.params.items()})
+        batch_size = npoints if not batch_size else int(batch_size)
+        chunks = []
+        for start in range(0, npoints, batch_size):
+            chunks.append(self.calculator(**{name: np.array(value[start:start + batch_size]) for name, value in samples.items()}))
+        good = np.ones(npoints, dtype=bool)
+        for key, first in (chunks[0] if chunks else {}).items():
+            sizes = [min(batch_size, npoints - start) for start in range(0, npoints, batch_size)]
+            if key in center and all(np.shape(chunk[key]) == (size,) + np.shape(center[key]) for chunk, size in zip(chunks, sizes)):
+                value = np.concatenate([np.asarray(chunk[key]) for chunk in chunks], axis=0)
+                good &= np.isfinite(value.reshape(npoints, -1)).all(axis=1)
+                samples.varied[key] = value
+            else:
+                samples.fixed[key] = np.asarray(first)
+        for key in samples.varied:
+            samples.varied[key] = samples.varied[key][good]
+        for name in list(samples):
+            samples[name] = samples[name][good]
+        samples.attrs['ndropped'] = int(npoints - good.sum())
+        self.samples = samples
+        return samples
 
 
 class DiffSampler(object):

@@ -201,9 +201,13 @@ class Emulator(object):
 
     def __init__(self, calculator, params=None, engine='taylor', device=None, **engine_options):
         if isinstance(engine, str):
-            if engine != 'taylor':
-                raise NotImplementedError('engine {} (only the Taylor engine is built)'.format(engine))
-            engine = TaylorEmulatorEngine(device=device, **engine_options)
+            if engine == 'mlp':
+                from .mlp import MLPEmulatorEngine
+                engine = MLPEmulatorEngine(device=device, **engine_options)
+            elif engine == 'taylor':
+                engine = TaylorEmulatorEngine(device=device, **engine_options)
+            else:
+                raise NotImplementedError('engine {} (only the Taylor and MLP engines are built)'.format(engine))
         self.calculator = calculator
         self.params = {name: tuple(limits) for name, limits in (params or {}).items()}
         self.engine = engine
@@ -211,12 +215,14 @@ class Emulator(object):
         self.varied_keys, self.varied_shapes, self.fixed = [], [], {}
 
     def set_samples(self, samples=None, **kwargs):
-        """Set the samples to fit: those given, else the engine's default (:class:`DiffSampler` run on the calculator; ``kwargs`` override order / accuracy)."""
+        """Set the samples to fit: those given, else the engine's default (Taylor: :class:`DiffSampler` run on the calculator, ``kwargs`` override order /
+        accuracy; MLP: :class:`QMCSampler`, ``kwargs`` its ``engine``, ``niterations``, ``batch_size``)."""
         self.samples = samples if samples is not None else self.engine.get_default_samples(self.calculator, self.params, **kwargs)
         return self.samples
 
-    def fit(self):
-        """Concatenate the flattened varied outputs into Y (npoints, M), upload it once and fit the engine on the device."""
+    def fit(self, **kwargs):
+        """Concatenate the flattened varied outputs into Y (npoints, M), upload it once and fit the engine on the device.  ``kwargs``: training options of
+        the engine (:meth:`MLPEmulatorEngine.fit`; the Taylor engine takes none)."""
         if self.samples is None:
             self.set_samples()
         samples = self.samples
@@ -226,7 +232,7 @@ class Emulator(object):
         self.varied_shapes = [tuple(samples.varied[key].shape[1:]) for key in self.varied_keys]
         self.fixed = dict(samples.fixed)
         Y = np.concatenate([np.asarray(samples.varied[key], dtype='f8').reshape(len(samples.varied[key]), -1) for key in self.varied_keys], axis=1)
-        self.engine.fit(samples.matrix(), Y, samples.attrs, params=list(self.params))
+        self.engine.fit(samples.matrix(), Y, samples.attrs, params=list(self.params), **kwargs)
         return self
 
     def predict(self, params, device=False):
@@ -271,11 +277,12 @@ class Emulator(object):
         return calculator
 
     def __getstate__(self):
-        return {'engine': self.engine.__getstate__(), 'params': dict(self.params), 'varied_keys': list(self.varied_keys), 'varied_shapes': [tuple(s) for s in self.varied_shapes],
+        return {'name': self.engine.name, 'engine': self.engine.__getstate__(), 'params': dict(self.params), 'varied_keys': list(self.varied_keys), 'varied_shapes': [tuple(s) for s in self.varied_shapes],
                 'fixed': dict(self.fixed)}
 
     def save(self, fn):
-        """Save the state (``center``, ``powers``, ``derivatives``, ``sampler_options``, key names, shapes, fixed values) as one ``.npy`` dictionary."""
+        """Save the state (the engine's ``name`` and state -- Taylor: ``center``, ``powers``, ``derivatives``, ``sampler_options`` -- key names, shapes, fixed
+        values) as one ``.npy`` dictionary."""
         np.save(fn, self.__getstate__(), allow_pickle=True)
 
     @classmethod
@@ -284,6 +291,13 @@ class Emulator(object):
         new = cls.__new__(cls)
         new.calculator, new.samples = None, None
         new.params = dict(state['params'])
-        new.engine = TaylorEmulatorEngine.from_state(state['engine'], device=device)
+        name = state.get('name', 'taylor')      # a file without a name is a Taylor file
+        if name == 'mlp':
+            from .mlp import MLPEmulatorEngine
+            new.engine = MLPEmulatorEngine.from_state(state['engine'], device=device)
+        elif name == 'taylor':
+            new.engine = TaylorEmulatorEngine.from_state(state['engine'], device=device)
+        else:
+            raise NotImplementedError('engine {} (only the Taylor and MLP engines are built)'.format(name))
         new.varied_keys, new.varied_shapes, new.fixed = list(state['varied_keys']), [tuple(s) for s in state['varied_shapes']], dict(state['fixed'])
         return new

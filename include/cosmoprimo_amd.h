@@ -652,6 +652,32 @@ int cp_taylor_predict(const double* d_x, long long B, const double* d_center, co
                       const double* d_derivatives, int M, double* d_out, int device, void* stream);
 int cp_taylor_fit(const double* d_S, int T, int npoints, const double* d_Y, int M, double* d_derivatives, int device, void* stream);
 
+/* ---- Multi-layer perceptron emulator of a calculator (reference emulators/tools/mlp.py; csrc/cp_mlp.hip): batched prediction, loss and gradient of
+ *      a training batch, Adam step, all float64.  Everything is on the device; no call reads anything back, allocates or waits for the stream. ----
+ * Network: ndim <= 32 inputs, nlayers <= 8 hidden layers of widths[l] in 1 .. 64 (host array), M outputs (CP_EUNSUPPORTED beyond the caps).  A layer
+ *   is v @ kernel + bias, kernel (n_in, n_out) row-major.  activations[l] (host array): 0 silu v / (1 + exp(-v)), 1 relu, 2 tanh, 3 identity-silu
+ *   ((1 - beta) + beta / (1 + exp(-alpha v))) v; the output layer has none.
+ * Packed layout (parameters, gradients, Adam moments): per layer kernel (n_in n_out), bias (n_out), and for a hidden layer alpha, beta (always
+ *   present); cp_mlp_param_count returns the length, cp_mlp_workspace_doubles the workspace of loss_grad; on an error both
+ *   return minus the status (-CP_EINVAL, -CP_EUNSUPPORTED) and set cp_last_error().
+ * predict : d_x (B, ndim) raw parameters; x' = (x - d_xoffset[i]) / d_xscale[i]; the hidden layers; d_out (B, M) = f(v d_yscale[m] + d_yoffset[m]) with v
+ *   the output layer and f = yfunction (enum cp_mlp_yfunction).  One launch; the hidden activations stay in LDS.  A NaN in a row of d_x stays in that row.
+ * loss_grad : d_X (b, ndim), d_Y (b, M) already scaled; d_loss (one device double) = mean((Y - prediction)^2); d_grad (packed layout; NULL: loss
+ *   only, with the same bits) its gradient.  d_work: work_doubles >= cp_mlp_workspace_doubles(b, ...) doubles of device workspace.  Reductions run in a
+ *   fixed order: two calls give bit-identical results.
+ * adam : m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2, p -= lr (m / c1) / (sqrt(v / c2) + eps) over n entries, every operation rounded once; c1, c2
+ *   the bias corrections 1 - b1^t, 1 - b2^t from the host. */
+enum cp_mlp_yfunction { CP_MLP_Y_NONE = 0, CP_MLP_Y_EXP10 = 1, CP_MLP_Y_SINH = 2 };
+long long cp_mlp_param_count(int ndim, int nlayers, const int* widths, int M);
+long long cp_mlp_workspace_doubles(long long b, int ndim, int nlayers, const int* widths, int M);
+int cp_mlp_predict(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
+                   const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, double* d_out,
+                   int device, void* stream);
+int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long b, int ndim, int nlayers, const int* widths, const int* activations, int M,
+                     const double* d_params, double* d_work, long long work_doubles, double* d_loss, double* d_grad, int device, void* stream);
+int cp_mlp_adam(double* d_params, double* d_m, double* d_v, const double* d_grad, long long n, double lr, double b1, double b2, double eps, double c1,
+                double c2, int device, void* stream);
+
 /* ---- row screening utility (cp_fftlog_execute and cp_dst_execute screen their rows themselves; this pass is for callers that want
  *      the flags, e.g. to count or report the rows a batch loses) ----
  * d_x : (nrows, n) device.  d_ok[row] = 1 if every entry of the row is finite (and > 0 if require_positive: the fused log map of
