@@ -6,6 +6,7 @@ from .interpolator import (PowerSpectrumInterpolator1D, PowerSpectrumInterpolato
 from .cosmology import (Cosmology, Background, Thermodynamics, Primordial, Perturbations, Transfer, Harmonic, Fourier, CosmologyError,
                         CosmologyInputError, CosmologyComputationError)
 from . import eisenstein_hu, eisenstein_hu_nowiggle, eisenstein_hu_nowiggle_variants, bbks, tabulated  # noqa: F401  (registers the engines)
+from .emulators import emulated  # noqa: F401  (registers the 'emulated' engine)
 from .bao_filter import PowerSpectrumBAOFilter, CorrelationFunctionBAOFilter
 from . import fiducial, constants  # noqa: F401
 

@@ -200,11 +200,16 @@ for _name in ('cp_spline_tables_apply', 'cp_spline_tables_apply_f32'):
                                         ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, _c_int_p, ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_taylor_predict'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
+SIGNATURES['cp_taylor_predict_columns'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                         ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong,
+                                                         ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_taylor_fit'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_mlp_param_count'] = (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int])
 SIGNATURES['cp_mlp_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int])
 SIGNATURES['cp_mlp_predict'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int] + [ctypes.c_void_p] * 5
                                               + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
+SIGNATURES['cp_mlp_predict_columns'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int] + [ctypes.c_void_p] * 5
+                                                      + [ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_mlp_loss_grad'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_mlp_adam'] = (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_longlong] + [ctypes.c_double] * 6 + [ctypes.c_int, ctypes.c_void_p])

@@ -57,9 +57,11 @@ struct MlpFwdArgs {
     const double* yoff;
     const double* yscale;
     const double* ytrue;      // training: (R, M)
-    double* out;              // predict: (R, M); training: the scaled residual (R, M)
+    double* out;              // predict: (R, ncols) with row stride ldo, the columns [c0, cend) of the (R, M) result; training: the scaled residual (R, M)
     double* work;             // training
-    long long R;
+    long long R, ldo;
+    int c0, cend;             // the column tiles start at c0 (any value: the fragments are fetched with 8-byte loads); nothing of the output layer, yoff or
+                              // yscale outside [c0, cend) is read.  Training: [0, M), ldo = M
     double rscale;            // 2 / (R M)
     MlpNet net;
     MlpWork ws;
@@ -107,7 +109,10 @@ __global__ __launch_bounds__(256, 2) void mlp_forward_kernel(const MlpFwdArgs A)
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int l15 = lane & 15, g = lane >> 4;
     const long long row0 = (long long)blockIdx.x * ML_ROWS;
-    const int col0 = (int)blockIdx.y * ML_COLS + wave * 64;
+    // the range of columns and the row stride of the result; the training pass takes every column, known at compile time (its code is what it was)
+    const int c0 = MODE == ML_TRAIN ? 0 : A.c0, cend = MODE == ML_TRAIN ? A.net.M : A.cend;
+    const long long ldo = MODE == ML_TRAIN ? (long long)A.net.M : A.ldo;
+    const int col0 = c0 + (int)blockIdx.y * ML_COLS + wave * 64;
     double* cur = ml_lds;
     double* nxt = ml_lds + N.nr * ML_RS;
     {      // the inputs of the tile's rows, k-major; rows past the end: finite, never stored
@@ -166,7 +171,7 @@ __global__ __launch_bounds__(256, 2) void mlp_forward_kernel(const MlpFwdArgs A)
     const int K = N.d[N.L], M = N.M;
     const double* Wo = A.params + N.off[N.L];
     const double* bo = Wo + (long long)K * M;
-    const bool active = col0 < M;      // (wave-uniform; an idle wave multiplies the last column: no branch round the MFMAs)
+    const bool active = col0 < cend;      // (wave-uniform; an idle wave multiplies the last column: no branch round the MFMAs)
     ml_v4d acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -176,7 +181,7 @@ __global__ __launch_bounds__(256, 2) void mlp_forward_kernel(const MlpFwdArgs A)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int col = col0 + 16 * j + l15;
-        colj[j] = col < M ? col : M - 1;      // columns past the end repeat the last one (never stored)
+        colj[j] = col < cend ? col : cend - 1;      // columns past the end of the range repeat its last one (never stored)
     }
     {
         const int npairs = (K + 7) / 8;
@@ -208,7 +213,7 @@ __global__ __launch_bounds__(256, 2) void mlp_forward_kernel(const MlpFwdArgs A)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int col = col0 + 16 * j + l15;
-            if (col >= M) continue;
+            if (col >= cend) continue;
             const double bj = bo[col];
             double ys = 1., yo = 0.;
             if (MODE != ML_TRAIN) ys = A.yscale[col], yo = A.yoff[col];
@@ -228,7 +233,7 @@ __global__ __launch_bounds__(256, 2) void mlp_forward_kernel(const MlpFwdArgs A)
                         if (MODE == CP_MLP_Y_EXP10) v = cpmath::exp10_mid(v);
                         if (MODE == CP_MLP_Y_SINH) v = sinh(v);
                     }
-                    A.out[row * M + col] = v;
+                    A.out[row * ldo + (col - c0)] = v;
                 }
         }
     }
@@ -512,7 +517,7 @@ void mlp_work(const MlpNet& net, long long b, MlpWork* ws) {
 
 template <int MODE>
 int mlp_forward_launch(const char* who, const MlpFwdArgs& A, void* stream) {
-    const long long nrt = (A.R + ML_ROWS - 1) / ML_ROWS, nct = (A.net.M + ML_COLS - 1) / ML_COLS;
+    const long long nrt = (A.R + ML_ROWS - 1) / ML_ROWS, nct = (A.cend - A.c0 + ML_COLS - 1) / ML_COLS;
     if (nrt > 0x7fffffffLL || nct > 65535) return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d results (at most 2^37 rows, 2^24 - 256 columns)", who, A.R, A.net.M);
     const size_t lds = (size_t)2 * A.net.nr * ML_RS * sizeof(double);      // 40 KB at widths <= 32, at most 80 KB
     if (lds > 64 * 1024) {
@@ -541,26 +546,44 @@ extern "C" long long cp_mlp_workspace_doubles(long long b, int ndim, int nlayers
     return ws.total;
 }
 
+// cp_mlp_predict is the range [0, M) with row stride M of the same call
+static int mlp_predict(const char* who, const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
+                       const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
+                       long long ncols, double* d_out, long long ldo, int device, void* stream) {
+    MlpFwdArgs A{};
+    if (B < 0) return cp::fail(CP_EINVAL, "%s: negative count of points", who);
+    if (!activations) return cp::fail(CP_EINVAL, "%s: no activation codes", who);
+    const int status = mlp_net(who, ndim, nlayers, widths, activations, M, &A.net);
+    if (status != CP_OK) return status;
+    if (yfunction < CP_MLP_Y_NONE || yfunction > CP_MLP_Y_SINH) return cp::fail(CP_EINVAL, "%s: y function %d (0 none, 1 10^v, 2 sinh)", who, yfunction);
+    if (col0 < 0 || ncols < 1 || ncols > (long long)M - col0) return cp::fail(CP_EINVAL, "%s: columns [%lld, %lld + %lld) of %d", who, col0, col0, ncols, M);
+    if (ldo < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the result is less than its %lld columns", who, ldo, ncols);
+    if (B == 0) return CP_OK;
+    if (!d_x || !d_params || !d_xoffset || !d_xscale || !d_yoffset || !d_yscale || !d_out) return cp::fail(CP_EINVAL, "%s: null pointer", who);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
+    A.x = d_x, A.params = d_params, A.xoff = d_xoffset, A.xscale = d_xscale, A.yoff = d_yoffset, A.yscale = d_yscale, A.out = d_out, A.R = B;
+    A.ldo = ldo, A.c0 = (int)col0, A.cend = (int)(col0 + ncols);
+    int launched;
+    if (yfunction == CP_MLP_Y_NONE) launched = mlp_forward_launch<CP_MLP_Y_NONE>(who, A, stream);
+    else if (yfunction == CP_MLP_Y_EXP10) launched = mlp_forward_launch<CP_MLP_Y_EXP10>(who, A, stream);
+    else launched = mlp_forward_launch<CP_MLP_Y_SINH>(who, A, stream);
+    if (launched != CP_OK) return launched;
+    return cp::launch_status(who);
+}
+
 extern "C" int cp_mlp_predict(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
                               const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, double* d_out,
                               int device, void* stream) {
-    MlpFwdArgs A{};
-    if (B < 0) return cp::fail(CP_EINVAL, "cp_mlp_predict: negative count of points");
-    if (!activations) return cp::fail(CP_EINVAL, "cp_mlp_predict: no activation codes");
-    const int status = mlp_net("cp_mlp_predict", ndim, nlayers, widths, activations, M, &A.net);
-    if (status != CP_OK) return status;
-    if (yfunction < CP_MLP_Y_NONE || yfunction > CP_MLP_Y_SINH) return cp::fail(CP_EINVAL, "cp_mlp_predict: y function %d (0 none, 1 10^v, 2 sinh)", yfunction);
-    if (B == 0) return CP_OK;
-    if (!d_x || !d_params || !d_xoffset || !d_xscale || !d_yoffset || !d_yscale || !d_out) return cp::fail(CP_EINVAL, "cp_mlp_predict: null pointer");
-    cp::DeviceScope scope(device);
-    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_mlp_predict: cannot select device %d", device);
-    A.x = d_x, A.params = d_params, A.xoff = d_xoffset, A.xscale = d_xscale, A.yoff = d_yoffset, A.yscale = d_yscale, A.out = d_out, A.R = B;
-    int launched;
-    if (yfunction == CP_MLP_Y_NONE) launched = mlp_forward_launch<CP_MLP_Y_NONE>("cp_mlp_predict", A, stream);
-    else if (yfunction == CP_MLP_Y_EXP10) launched = mlp_forward_launch<CP_MLP_Y_EXP10>("cp_mlp_predict", A, stream);
-    else launched = mlp_forward_launch<CP_MLP_Y_SINH>("cp_mlp_predict", A, stream);
-    if (launched != CP_OK) return launched;
-    return cp::launch_status("cp_mlp_predict");
+    return mlp_predict("cp_mlp_predict", d_x, B, ndim, nlayers, widths, activations, M, d_params, d_xoffset, d_xscale, d_yoffset, d_yscale, yfunction, 0, M, d_out, M,
+                       device, stream);
+}
+
+extern "C" int cp_mlp_predict_columns(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M,
+                                      const double* d_params, const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale,
+                                      int yfunction, long long col0, long long ncols, double* d_out, long long ldo, int device, void* stream) {
+    return mlp_predict("cp_mlp_predict_columns", d_x, B, ndim, nlayers, widths, activations, M, d_params, d_xoffset, d_xscale, d_yoffset, d_yscale, yfunction, col0,
+                       ncols, d_out, ldo, device, stream);
 }
 
 extern "C" int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long b, int ndim, int nlayers, const int* widths, const int* activations, int M,
@@ -582,6 +605,7 @@ extern "C" int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long 
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_mlp_loss_grad: cannot select device %d", device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     A.x = d_X, A.params = d_params, A.ytrue = d_Y, A.out = d_work + ws.resid, A.work = d_work, A.R = b;
+    A.ldo = M, A.c0 = 0, A.cend = M;
     A.rscale = 2. / ((double)b * (double)M);
     const int launched = mlp_forward_launch<ML_TRAIN>(who, A, stream);
     if (launched != CP_OK) return launched;

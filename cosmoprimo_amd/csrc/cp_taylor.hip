@@ -30,9 +30,10 @@ struct TaylorArgs {
     const double* center;   // (ndim)
     const int* powers;      // (K, ndim)
     const double* b;        // (K, M)
-    double* out;            // (R, M)
-    long long R;
+    double* out;            // (R, ncols) with row stride ldo: the columns [c0, cend) of the (R, M) product
+    long long R, ldo;
     int K, M, ndim;
+    int c0, cend;           // the column tiles start at c0 (any value: the fragments are fetched with 8-byte loads); nothing outside [c0, cend) of b is read
 };
 
 // The operands of the eight inner indices k0 + 8 p .. + 7 of one chunk for one wave: two MFMA steps.  A row of the right operand past K is never read:
@@ -70,8 +71,11 @@ __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const TaylorArgs A)
     const int nchunk = (A.K + TY_KC - 1) / TY_KC;
     {      // one tile per workgroup (a loop over tiles here made the compiler keep the 64 store addresses of a lane alive through the MFMAs: spills)
         const long long row0 = (long long)blockIdx.x * TY_ROWS;
-        const int col0 = (int)blockIdx.y * TY_COLS + wave * 64;
-        const bool active = col0 < A.M;      // (wave-uniform; an idle wave forms its share of the left operand and multiplies the last column: no branch round the MFMAs)
+        // the range of columns and the row stride of the result; the fit takes every column, known at compile time (its code is what it was)
+        const int c0 = GEN ? A.c0 : 0, cend = GEN ? A.cend : A.M;
+        const long long ldo = GEN ? A.ldo : (long long)A.M;
+        const int col0 = c0 + (int)blockIdx.y * TY_COLS + wave * 64;
+        const bool active = col0 < cend;      // (wave-uniform; an idle wave forms its share of the left operand and multiplies the last column: no branch round the MFMAs)
         if (GEN) {
             for (int e = threadIdx.x; e < A.ndim * TY_ROWS; e += 256) {
                 const int i = e >> 6;
@@ -89,7 +93,7 @@ __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const TaylorArgs A)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int col = col0 + 16 * j + l15;
-            colj[j] = col < A.M ? col : A.M - 1;      // columns past the end repeat the last one (never stored)
+            colj[j] = col < cend ? col : cend - 1;      // columns past the end of the range repeat its last one (never stored)
         }
 #pragma unroll 1
         for (int c = 0; c < nchunk; ++c) {
@@ -153,13 +157,13 @@ __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const TaylorArgs A)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int col = col0 + 16 * j + l15;
-            if (col >= A.M) continue;
+            if (col >= cend) continue;
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const long long row = row0 + 16 * i + g + 4 * r;
-                    if (row < A.R) A.out[row * A.M + col] = acc[i][j][r];
+                    if (row < A.R) A.out[row * ldo + (col - c0)] = acc[i][j][r];
                 }
         }
     }
@@ -170,7 +174,7 @@ int taylor_launch(const char* who, const TaylorArgs& A, int device, void* stream
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
     // the row tiles along x: workgroups are dispatched x first, so those in flight share their 256 columns of the right operand in L2
-    const long long nrt = (A.R + TY_ROWS - 1) / TY_ROWS, nct = (A.M + TY_COLS - 1) / TY_COLS;
+    const long long nrt = (A.R + TY_ROWS - 1) / TY_ROWS, nct = (A.cend - A.c0 + TY_COLS - 1) / TY_COLS;
     if (nrt > 0x7fffffffLL || nct > 65535) return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d results (at most 2^37 rows, 2^24 - 256 columns)", who, A.R, A.M);
     const dim3 grid((unsigned)nrt, (unsigned)nct);
     const size_t lds = (size_t)(2 * TY_KC * TY_RS + (GEN ? A.ndim * TY_ROWS : 0)) * sizeof(double);      // at most 56 KB
@@ -180,21 +184,35 @@ int taylor_launch(const char* who, const TaylorArgs& A, int device, void* stream
 
 }  // namespace
 
+// cp_taylor_predict is the range [0, M) with row stride M of the same call
+static int taylor_predict(const char* who, const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
+                          const double* d_derivatives, int M, long long col0, long long ncols, double* d_out, long long ldo, int device, void* stream) {
+    if (B < 0 || ndim < 1 || T < 1 || M < 1) return cp::fail(CP_EINVAL, "%s: need ndim, T, M >= 1 and a non-negative count of points", who);
+    if (max_power < 0) return cp::fail(CP_EINVAL, "%s: max_power %d is negative", who, max_power);
+    if (col0 < 0 || ncols < 1 || ncols > (long long)M - col0) return cp::fail(CP_EINVAL, "%s: columns [%lld, %lld + %lld) of %d", who, col0, col0, ncols, M);
+    if (ldo < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the result is less than its %lld columns", who, ldo, ncols);
+    if (ndim > TY_MAX_NDIM) return cp::fail(CP_EUNSUPPORTED, "%s: %d parameters (at most %d)", who, ndim, TY_MAX_NDIM);
+    if (max_power > TY_MAX_POWER) return cp::fail(CP_EUNSUPPORTED, "%s: power %d (at most %d)", who, max_power, TY_MAX_POWER);
+    if (B == 0) return CP_OK;
+    if (!d_x || !d_center || !d_powers || !d_derivatives || !d_out) return cp::fail(CP_EINVAL, "%s: null pointer", who);
+    const TaylorArgs A{d_x, d_center, d_powers, d_derivatives, d_out, B, ldo, T, M, ndim, (int)col0, (int)(col0 + ncols)};
+    return taylor_launch<true>(who, A, device, stream);
+}
+
 extern "C" int cp_taylor_predict(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                                  const double* d_derivatives, int M, double* d_out, int device, void* stream) {
-    if (B < 0 || ndim < 1 || T < 1 || M < 1) return cp::fail(CP_EINVAL, "cp_taylor_predict: need ndim, T, M >= 1 and a non-negative count of points");
-    if (max_power < 0) return cp::fail(CP_EINVAL, "cp_taylor_predict: max_power %d is negative", max_power);
-    if (ndim > TY_MAX_NDIM) return cp::fail(CP_EUNSUPPORTED, "cp_taylor_predict: %d parameters (at most %d)", ndim, TY_MAX_NDIM);
-    if (max_power > TY_MAX_POWER) return cp::fail(CP_EUNSUPPORTED, "cp_taylor_predict: power %d (at most %d)", max_power, TY_MAX_POWER);
-    if (B == 0) return CP_OK;
-    if (!d_x || !d_center || !d_powers || !d_derivatives || !d_out) return cp::fail(CP_EINVAL, "cp_taylor_predict: null pointer");
-    const TaylorArgs A{d_x, d_center, d_powers, d_derivatives, d_out, B, T, M, ndim};
-    return taylor_launch<true>("cp_taylor_predict", A, device, stream);
+    return taylor_predict("cp_taylor_predict", d_x, B, d_center, d_powers, ndim, T, max_power, d_derivatives, M, 0, M, d_out, M, device, stream);
+}
+
+extern "C" int cp_taylor_predict_columns(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
+                                         const double* d_derivatives, int M, long long col0, long long ncols, double* d_out, long long ldo, int device,
+                                         void* stream) {
+    return taylor_predict("cp_taylor_predict_columns", d_x, B, d_center, d_powers, ndim, T, max_power, d_derivatives, M, col0, ncols, d_out, ldo, device, stream);
 }
 
 extern "C" int cp_taylor_fit(const double* d_S, int T, int npoints, const double* d_Y, int M, double* d_derivatives, int device, void* stream) {
     if (T < 1 || npoints < 1 || M < 1) return cp::fail(CP_EINVAL, "cp_taylor_fit: need T, npoints, M >= 1");
     if (!d_S || !d_Y || !d_derivatives) return cp::fail(CP_EINVAL, "cp_taylor_fit: null pointer");
-    const TaylorArgs A{d_S, nullptr, nullptr, d_Y, d_derivatives, T, npoints, M, 0};
+    const TaylorArgs A{d_S, nullptr, nullptr, d_Y, d_derivatives, T, M, npoints, M, 0, 0, M};
     return taylor_launch<false>("cp_taylor_fit", A, device, stream);
 }

@@ -11,7 +11,8 @@ silently drops 'fourier.pk.*' for its analytic engines (their ``pk_interpolator`
 swallowed); here the pairs the analytic engines do provide ('delta_m', 'theta_m') are returned.  The consumer of those batches is built too: the
 Taylor-expansion emulator (``Emulator``, ``TaylorEmulatorEngine``, ``DiffSampler`` of :mod:`.tools`: the whole finite-difference grid in one call of
 the calculator, fit and batched prediction on the device) and the multi-layer perceptron emulator (``MLPEmulatorEngine``, ``QMCSampler``: quasi-random
-samples over the prior box in one call of the calculator, Adam training and one-launch batched prediction on the device).
+samples over the prior box in one call of the calculator, Adam training and one-launch batched prediction on the device).  :class:`EmulatedEngine`
+(:mod:`.emulated`) serves a :class:`Cosmology` from a saved emulator, section by section.
 """
 import numpy as np
 
@@ -106,7 +107,12 @@ def get_calculator(cosmo, section=None):
                 getstate = _states.get(section_name, None)
                 if getstate is None:
                     continue
-                for name, value in getstate(getattr(clone, 'get_{}'.format(section_name))()).items():
+                sec = getattr(clone, 'get_{}'.format(section_name))()
+                if getattr(sec, '_emulated', False):      # an emulated section holds these very quantities: its state, not a second interpolation of it
+                    state = {name: _host(value) for name, value in sec.__getstate__().items()}
+                else:
+                    state = getstate(sec)
+                for name, value in state.items():
                     toret['{}.{}'.format(section_name, name)] = value
         except CosmologyError as exc:
             raise CalculatorComputationError from exc
@@ -116,3 +122,4 @@ def get_calculator(cosmo, section=None):
 
 
 from .tools import Emulator, TaylorEmulatorEngine, MLPEmulatorEngine, DiffSampler, QMCSampler  # noqa: E402,F401
+from .emulated import EmulatedEngine  # noqa: E402,F401

@@ -328,10 +328,11 @@ class MLPEmulatorEngine(object):
         self._dev = dict(device=device, net=net, parameters=parameters, yfunction=_lib.MLP_YFUNCTIONS[first if first in ('log10', 'arcsinh') else None],
                          **{name: dv.to_device(value, device, cache=False) for name, value in dict(xoffset=xoffset, xscale=xscale, yoffset=yoffset, yscale=yscale).items()})
 
-    def predict(self, X):
+    def predict(self, X, columns=None):
         """Network at the points ``X`` (B, ndim) of raw parameters, a device tensor (or host array, uploaded): device tensor (B, M) of the calculator's
         outputs (the y operations inverted).  One launch; nothing but the result is allocated, nothing is read back and the call does not wait for the
-        device."""
+        device.  ``columns = (start, stop)``: those columns of it only, a (B, stop - start) tensor, bit for bit the same numbers
+        (``cp_mlp_predict_columns``: the hidden layers as ever, the output layer and the y operations on that range alone)."""
         from ... import _device as dv, _lib
         if self.parameters is None:
             raise ValueError('fit the engine first')
@@ -343,6 +344,13 @@ class MLPEmulatorEngine(object):
         if X.ndim != 2 or int(X.shape[1]) != net['ndim']:
             raise ValueError('X must be of shape (B, {:d}), got {}'.format(net['ndim'], tuple(X.shape)))
         B = int(X.shape[0])
+        if columns is not None:
+            start, stop = (int(c) for c in columns)
+            out = dv.torch().empty((B, max(stop - start, 0)), dtype=dv.torch().float64, device=d['device'])
+            _lib.check(_lib.load().cp_mlp_predict_columns(X.data_ptr(), B, net['ndim'], net['L'], net['widths'], net['acts'], net['M'], d['parameters'].data_ptr(),
+                                                          d['xoffset'].data_ptr(), d['xscale'].data_ptr(), d['yoffset'].data_ptr(), d['yscale'].data_ptr(), d['yfunction'],
+                                                          start, stop - start, out.data_ptr(), stop - start, d['device'].index, dv.stream_of(d['device'])))
+            return out
         out = dv.torch().empty((B, net['M']), dtype=dv.torch().float64, device=d['device'])
         _lib.check(_lib.load().cp_mlp_predict(X.data_ptr(), B, net['ndim'], net['L'], net['widths'], net['acts'], net['M'], d['parameters'].data_ptr(),
                                               d['xoffset'].data_ptr(), d['xscale'].data_ptr(), d['yoffset'].data_ptr(), d['yscale'].data_ptr(), d['yfunction'],

@@ -144,9 +144,10 @@ class TaylorEmulatorEngine(object):
                          powers=dv.upload(powers, device, cache=False), max_power=int(powers.max(initial=0)), min_power=int(powers.min(initial=0)))
         assert self._dev['powers'].dtype == torch.int32
 
-    def predict(self, X):
+    def predict(self, X, columns=None):
         """Expansion at the points ``X`` (B, ndim), a device tensor (or host array, uploaded): device tensor (B, M).  Nothing is read back and the call
-        does not wait for the device."""
+        does not wait for the device.  ``columns = (start, stop)``: those columns of it only, a (B, stop - start) tensor, bit for bit the same numbers
+        (``cp_taylor_predict_columns``: no other column of the derivatives is read, nothing else is allocated)."""
         from ... import _device as dv, _lib
         if self._dev is None:
             self._set_device(dv.resolve_device(self.device, X))
@@ -159,6 +160,13 @@ class TaylorEmulatorEngine(object):
         if d['min_power'] < 0:
             raise ValueError('powers must be non-negative')
         B, M = int(X.shape[0]), int(d['derivatives'].shape[1])
+        if columns is not None:
+            start, stop = (int(c) for c in columns)
+            out = torch.empty((B, max(stop - start, 0)), dtype=torch.float64, device=d['device'])
+            _lib.check(_lib.load().cp_taylor_predict_columns(X.data_ptr(), B, d['center'].data_ptr(), d['powers'].data_ptr(), ndim, T, d['max_power'],
+                                                             d['derivatives'].data_ptr(), M, start, stop - start, out.data_ptr(), stop - start, d['device'].index,
+                                                             dv.stream_of(d['device'])))
+            return out
         out = torch.empty((B, M), dtype=torch.float64, device=d['device'])
         _lib.check(_lib.load().cp_taylor_predict(X.data_ptr(), B, d['center'].data_ptr(), d['powers'].data_ptr(), ndim, T, d['max_power'], d['derivatives'].data_ptr(),
                                                  M, out.data_ptr(), d['device'].index, dv.stream_of(d['device'])))
@@ -184,6 +192,42 @@ class TaylorEmulatorEngine(object):
         new.__setstate__(state)
         new.device = device
         return new
+
+
+def _requested(key, keys):
+    """Is ``key`` asked for by ``keys``, a section prefix ('fourier' takes 'fourier.k', never 'fourierx.k'; 'fourier.k' takes itself, never 'fourier.kz')
+    or a list of such?"""
+    return any(key == name or key.startswith(name + '.') for name in ([keys] if isinstance(keys, str) else keys))
+
+
+def _key_columns(varied_keys, varied_shapes):
+    """(key, shape, start, stop) of every varied key in the concatenation the engine is fitted on."""
+    toret, start = [], 0
+    for key, shape in zip(varied_keys, varied_shapes):
+        size = int(np.prod(shape, dtype='i8'))
+        toret.append((key, tuple(shape), start, start + size))
+        start += size
+    return toret
+
+
+def column_runs(varied_keys, varied_shapes, keys):
+    """The maximal contiguous runs ``[(start, stop), ...]`` of columns of the (B, M) prediction that hold the varied outputs ``keys`` asks for: a list of
+    output names or section prefixes, or one such string ('background': every 'background.*').  A name matches itself and what it prefixes at a dot
+    ('fourier.k' does not take 'fourier.kz').  A name that matches no varied output raises ``KeyError``; an empty list gives no run.  Outputs without
+    columns (size 0) join no run.  The keys of one section are adjacent in the calculator's order, so a section is normally one run."""
+    names = [keys] if isinstance(keys, str) else list(keys)
+    for name in names:
+        if not any(_requested(key, [name]) for key in varied_keys):
+            raise KeyError('no varied output {}'.format(name))
+    runs = []
+    for key, shape, start, stop in _key_columns(varied_keys, varied_shapes):
+        if stop == start or not _requested(key, names):
+            continue
+        if runs and runs[-1][1] == start:
+            runs[-1] = (runs[-1][0], stop)
+        else:
+            runs.append((start, stop))
+    return runs
 
 
 class Emulator(object):
@@ -235,10 +279,15 @@ class Emulator(object):
         self.engine.fit(samples.matrix(), Y, samples.attrs, params=list(self.params), **kwargs)
         return self
 
-    def predict(self, params, device=False):
+    def predict(self, params, device=False, keys=None):
         """Outputs at ``params``, a dictionary of scalars or arrays of B values (host arrays or device tensors): the calculator's keys, varied ones of shape
         ``(B,) + shape`` (no leading axis if every parameter is a scalar), fixed ones as they are.  Host arrays by default; ``device=True``: torch tensors,
-        views into one (B, M) buffer, and no synchronisation with the device."""
+        views into one (B, M) buffer, and no synchronisation with the device.
+
+        ``keys``: a list of output names, or a section prefix such as 'background' (every 'background.*' key): these outputs only.  Their columns are
+        planned by :func:`column_runs`; each maximal contiguous run of them is one launch of the engine on that range (B, ncols) -- the keys of a section
+        are adjacent, so normally one -- and no other column is computed or stored.  The varied keys asked for and the fixed ones under the prefix (or
+        among the names) are returned."""
         from ... import _device as dv
         missing = [name for name in self.params if name not in params]
         if missing:
@@ -257,6 +306,24 @@ class Emulator(object):
                 X[:, i] = np.ravel(v)
         else:
             X = torch.stack([dv.to_device(v, dev, cache=False).reshape(-1).expand(B) for v in values], dim=1)
+        if keys is not None:
+            names = [keys] if isinstance(keys, str) else list(keys)
+            unknown = [name for name in names if not any(_requested(key, [name]) for key in list(self.varied_keys) + list(self.fixed))]
+            if unknown:
+                raise KeyError('no output {}'.format(unknown))
+            # names that match fixed outputs only need no column
+            runs = column_runs(self.varied_keys, self.varied_shapes, [name for name in names if any(_requested(key, [name]) for key in self.varied_keys)])
+            toret = {}
+            for start, stop in runs:
+                out = self.engine.predict(X, columns=(start, stop))
+                if not device:
+                    out = dv.to_host(out)
+                for key, shape, lo, hi in _key_columns(self.varied_keys, self.varied_shapes):
+                    if start <= lo and hi <= stop and _requested(key, keys):
+                        value = out[:, lo - start:hi - start].reshape((B,) + shape)
+                        toret[key] = value[0] if scalar else value
+            toret.update({key: value for key, value in self.fixed.items() if _requested(key, keys)})
+            return toret
         out = self.engine.predict(X)
         if not device:
             out = dv.to_host(out)

@@ -647,9 +647,15 @@ int cp_spline_tables_apply_f32(const double* d_xk, const double* d_coef, const i
  *   exactly 1 whatever x_i holds (NaN, Inf).  The (B, T) matrix of monomials is formed in LDS and never stored.  max_power: the largest entry of
  *   d_powers, which the caller knows and the call does not read back; ndim > 32 or max_power > 15 are CP_EUNSUPPORTED (larger entries of d_powers
  *   than declared are treated as 15).
+ * predict_columns : the columns [col0, col0 + ncols) of predict: d_out (B, ncols) with row stride ldo >= ncols, column j the column col0 + j of the full
+ *   result, bit for bit (an element's sum runs over the terms in their order whatever tile it falls in).  The column tiles cover the range only, and no
+ *   column of d_derivatives outside it is read.  col0 < 0, ncols < 1, col0 + ncols > M or ldo < ncols: CP_EINVAL before any launch.  predict is the call
+ *   with col0 = 0, ncols = M, ldo = M.
  * fit : d_derivatives (T, M) = d_S (T, npoints) . d_Y (npoints, M), S the finite-difference weights of every term over the samples of the grid. */
 int cp_taylor_predict(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                       const double* d_derivatives, int M, double* d_out, int device, void* stream);
+int cp_taylor_predict_columns(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
+                              const double* d_derivatives, int M, long long col0, long long ncols, double* d_out, long long ldo, int device, void* stream);
 int cp_taylor_fit(const double* d_S, int T, int npoints, const double* d_Y, int M, double* d_derivatives, int device, void* stream);
 
 /* ---- Multi-layer perceptron emulator of a calculator (reference emulators/tools/mlp.py; csrc/cp_mlp.hip): batched prediction, loss and gradient of
@@ -662,6 +668,10 @@ int cp_taylor_fit(const double* d_S, int T, int npoints, const double* d_Y, int 
  *   return minus the status (-CP_EINVAL, -CP_EUNSUPPORTED) and set cp_last_error().
  * predict : d_x (B, ndim) raw parameters; x' = (x - d_xoffset[i]) / d_xscale[i]; the hidden layers; d_out (B, M) = f(v d_yscale[m] + d_yoffset[m]) with v
  *   the output layer and f = yfunction (enum cp_mlp_yfunction).  One launch; the hidden activations stay in LDS.  A NaN in a row of d_x stays in that row.
+ * predict_columns : the columns [col0, col0 + ncols) of predict: d_out (B, ncols) with row stride ldo >= ncols, column j the column col0 + j of the full
+ *   result, bit for bit.  The hidden layers are formed as in predict; the column tiles cover the range only, and nothing of the output kernel and bias,
+ *   d_yoffset or d_yscale outside it is read.  col0 < 0, ncols < 1, col0 + ncols > M or ldo < ncols: CP_EINVAL before any launch.  predict is the call with
+ *   col0 = 0, ncols = M, ldo = M.
  * loss_grad : d_X (b, ndim), d_Y (b, M) already scaled; d_loss (one device double) = mean((Y - prediction)^2); d_grad (packed layout; NULL: loss
  *   only, with the same bits) its gradient.  d_work: work_doubles >= cp_mlp_workspace_doubles(b, ...) doubles of device workspace.  Reductions run in a
  *   fixed order: two calls give bit-identical results.
@@ -673,6 +683,9 @@ long long cp_mlp_workspace_doubles(long long b, int ndim, int nlayers, const int
 int cp_mlp_predict(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
                    const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, double* d_out,
                    int device, void* stream);
+int cp_mlp_predict_columns(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
+                           const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
+                           long long ncols, double* d_out, long long ldo, int device, void* stream);
 int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long b, int ndim, int nlayers, const int* widths, const int* activations, int M,
                      const double* d_params, double* d_work, long long work_doubles, double* d_loss, double* d_grad, int device, void* stream);
 int cp_mlp_adam(double* d_params, double* d_m, double* d_v, const double* d_grad, long long n, double lr, double b1, double b2, double eps, double c1,
