@@ -20,7 +20,8 @@
 // Gradient.  gW_out = h^T . r (mlp_gw_out_kernel) and dh = r . W_out^T (mlp_dh_kernel) on the matrix cores, both operands straight from memory: in the
 // first both are contiguous along the 16 lanes of a k (and the column sums of r, the bias gradient, are taken from the fragments already loaded);
 // in the second both are contiguous along k, a wave takes one slice of the M inner indices of a row tile and stores a partial result, summed in
-// slice order by the kernel that applies the activation's derivative.  The hidden layers' products (at most 65 x 64 entries, sums over the batch)
+// slice order by the kernel that applies the activation's derivative (slices of equal length, a multiple of 8 near M / min(ceil(1024 / row tiles),
+// ceil(M / 64)), the last one shorter and its last MFMA step masked: mlp_work).  The hidden layers' products (at most 65 x 64 entries, sums over the batch)
 // run on the vector ALUs: a thread per entry and one of 16 phases of the batch, combined in a fixed order.  No floating-point atomics anywhere: two
 // calls give the same bits.
 #include "cp_internal.h"
@@ -499,7 +500,9 @@ void mlp_work(const MlpNet& net, long long b, MlpWork* ws) {
     }
     const long long nrt = (b + ML_ROWS - 1) / ML_ROWS;
     ws->nrt = (int)nrt, ws->nct = (net.M + ML_COLS - 1) / ML_COLS;
-    // slices of mlp_dh_kernel: about 1024 waves in flight, a slice at least 64 inner indices and a multiple of 8
+    // slices of mlp_dh_kernel: min(ceil(1024 / row tiles), ceil(M / 64)) are wanted (about 1024 waves in flight, no more slices than M holds runs of 64); the
+    // length ks is M over that count rounded up to a multiple of 8 -- so at most 64 where M sets the count (M = 65: 40, M = 257: 56), longer where the
+    // row tiles do (b = 4033, M = 1025: 72), and 8 for M <= 8 -- and nsl = ceil(M / ks) slices are run, the last one the shorter
     long long nsl = nrt > 0 ? (1024 + nrt - 1) / nrt : 1;
     const long long most = (net.M + 63) / 64;
     nsl = nsl > most ? most : nsl;

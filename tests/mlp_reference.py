@@ -1,4 +1,4 @@
-"""Restatement of the MLP emulator's arithmetic for the tests (tests/test_mlp_host.py, test_mlp_gpu.py, test_mlp_edges_gpu.py): forward and manual
+"""Restatement of the MLP emulator's arithmetic for the tests (tests/test_mlp_host.py, test_mlp_gpu.py, test_mlp_edges_gpu.py, test_mlp_train_edges_gpu.py): forward and manual
 backward pass in any floating-point type (``np.longdouble`` is the truth, float64 the reference implementation that is not the code under test), the
 running error bound of the forward pass, and Adam.
 

@@ -7,12 +7,11 @@ level of the float64 numpy backward pass (measured against the longdouble one on
 at eps): the device sums in another order (MFMA steps of 4, tiles, slices) and has its own exp.  Adam: sqrt and division are correctly rounded and the
 kernel rounds every operation once, as numpy does, so the two differ by the rounding of ``1 - b`` products at most; allowed: 4 eps of
 ``|p| + lr |m_hat| / (sqrt(v_hat) + eps)`` for p and 4 eps of the two terms' magnitudes for m and v."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import mlp_reference as mr
+from mlp_device import device_loss_grad
 
 pytestmark = pytest.mark.gpu
 NCONFIGS = 6
@@ -31,24 +30,6 @@ def test_predict(golden, i):
     fraction, reference = float((np.abs(got - truth) / bound).max()), float((np.abs(cfg['Yq'] - truth) / bound).max())
     print('config %d: the device uses %.3g of the bound, the reference %.3g' % (i, fraction, reference))
     assert got.shape == cfg['Yq'].shape and fraction <= 1. and reference <= 1.
-
-
-def device_loss_grad(packed, dims, activations, X, Y, with_grad=True):
-    import torch
-    from cosmoprimo_amd import _device as dv, _lib
-    lib, device = _lib.load(), torch.device('cuda', 0)
-    L = len(dims) - 2
-    widths, acts = (ctypes.c_int * L)(*dims[1:-1]), (ctypes.c_int * L)(*[_lib.MLP_ACTIVATIONS[a] for a in activations])
-    Xd, Yd, pd = (torch.as_tensor(np.ascontiguousarray(a, dtype='f8'), device=device) for a in (X, Y, packed))
-    work = torch.full((int(lib.cp_mlp_workspace_doubles(len(X), dims[0], L, widths, dims[-1])),), np.nan, dtype=torch.float64, device=device)
-    loss = torch.full((1,), np.nan, dtype=torch.float64, device=device)
-    grad = torch.full((pd.numel() + 1,), -7.25, dtype=torch.float64, device=device)
-    _lib.check(lib.cp_mlp_loss_grad(Xd.data_ptr(), Yd.data_ptr(), len(X), dims[0], L, widths, acts, dims[-1], pd.data_ptr(), work.data_ptr(), work.numel(),
-                                    loss.data_ptr(), grad.data_ptr() if with_grad else None, 0, dv.stream_of(device)))
-    torch.cuda.synchronize(device)
-    grad = grad.cpu().numpy()
-    assert grad[-1] == -7.25      # nothing past the packed layout
-    return float(loss.item()), grad[:-1]
 
 
 GRADIENT_CASES = [(b, M, widths, acts) for b in (1, 64, 100) for M, widths, acts in ((8, (32, 32, 32), ['silu', 'relu', 'tanh']), (300, (5, 17), ['identity-silu', 'silu']),
@@ -204,6 +185,93 @@ def test_patience(toy):
     history = engine.history[0]
     assert history['epochs'] == 1 + 3 and len(set(history['losses'])) == 1 and history['best_loss'] == history['losses'][0]
     assert np.array_equal(engine.parameters, engine.initial_parameters(3, 8, seed=42))
+
+
+STAGE = dict(batch_frac=0.3, epochs=8, learning_rate=0.1, patience=8)      # one stage whose validation loss rises in its last epoch (test_fit_returns_the_best_state)
+DIMS, SILU = (3, 16, 16, 8), ['silu', 'silu']
+
+
+def fit_stages(X, Y, **second):
+    """The stage STAGE, then (if given) a second one."""
+    from cosmoprimo_amd.emulators import MLPEmulatorEngine
+    kwargs = {name: (value, second[name]) if second else (value,) for name, value in STAGE.items()}
+    return MLPEmulatorEngine(nhidden=(16, 16), device='cuda:0').fit(X, Y, {}, seed=42, **kwargs)
+
+
+@pytest.fixture(scope='module')
+def one_stage(toy):
+    return fit_stages(*toy)
+
+
+def scaled_splits(engine, X, Y, nstages):
+    """The scaled samples and the (validation, training) indices of the first ``nstages`` stages, drawn from one generator as ``fit`` draws them."""
+    from cosmoprimo_amd.emulators.tools import mlp
+    rng = np.random.RandomState(seed=42)
+    return mlp.apply_operations(engine.xoperations, X), mlp.apply_operations(engine.yoperations, Y), [mlp.split_indices(rng, len(X), 0.1) for _ in range(nstages)]
+
+
+def test_fit_returns_the_best_state(toy, one_stage):
+    """(d) At learning rate 0.1 the validation loss of the toy problem falls for seven epochs and rises in the eighth (0.0101 -> 0.0122 in float64 numpy from the
+    same weights, split and batches; the margins are percents, rounding moves the fourth digit at most), so the best epoch is neither the first nor the last
+    and the state ``fit`` keeps differs from the one it ends in.  The float64 loss of the returned parameters on the stage's validation split must be
+    ``best_loss`` (1e-9 relative, as test_first_three_steps compares the same two quantities); the last epoch's loss is percents away from it."""
+    X, Y = toy
+    history = one_stage.history[0]
+    losses = history['losses']
+    print('one stage: validation losses %s' % ' '.join('%.5g' % value for value in losses))
+    best = int(np.argmin(losses))
+    assert history['epochs'] == len(losses) == STAGE['epochs']
+    assert 0 < best < len(losses) - 1 and history['best_loss'] == losses[best] and losses[-1] > 1.01 * losses[best]
+    Xs, Ys, [(index1, _)] = scaled_splits(one_stage, X, Y, 1)
+    loss = mr.loss_grad(one_stage.parameters, DIMS, SILU, Xs[index1], Ys[index1])[0]
+    assert abs(history['best_loss'] - loss) <= 1e-9 * loss
+
+
+def test_next_stage_starts_from_the_best_state_with_a_fresh_split(toy, one_stage):
+    """(e) A second stage at learning rate 0 with patience 1 moves nothing and ends after its second epoch (the first improves on infinity), so the two-stage fit
+    must return, bit for bit, what the one-stage fit returns: the best state of stage one, not its last.  Its first validation loss is the float64 loss of
+    those parameters on the SECOND split drawn from the same generator, and its batch size follows ``batch_slices`` on that split's training part."""
+    from cosmoprimo_amd.emulators.tools import mlp
+    X, Y = toy
+    engine = fit_stages(X, Y, batch_frac=0.5, epochs=1000, learning_rate=0., patience=1)
+    first, second = engine.history
+    assert first['losses'] == one_stage.history[0]['losses'] and first['batch_size'] == one_stage.history[0]['batch_size']
+    assert np.array_equal(engine.parameters, one_stage.parameters)
+    assert second['epochs'] == 2 and second['losses'][0] == second['losses'][1] == second['best_loss'] and second['learning_rate'] == 0.
+    Xs, Ys, [(first1, _), (index1, index2)] = scaled_splits(engine, X, Y, 2)
+    assert not np.array_equal(np.sort(first1), np.sort(index1))      # (the two splits differ, so the loss below tells them apart)
+    loss = mr.loss_grad(engine.parameters, DIMS, SILU, Xs[index1], Ys[index1])[0]
+    other = mr.loss_grad(engine.parameters, DIMS, SILU, Xs[first1], Ys[first1])[0]
+    print('stage two: first validation loss %.6g, float64 on the second split %.6g, on the first split %.6g' % (second['losses'][0], loss, other))
+    assert abs(second['losses'][0] - loss) <= 1e-9 * loss and abs(other - loss) > 1e-6 * loss
+    slices = mlp.batch_slices(len(index2), 0.5)
+    assert second['batch_size'] == slices[0].stop - slices[0].start == 115
+
+
+def test_next_stage_has_fresh_moments(toy, one_stage):
+    """(f) A second stage of one epoch of one batch (batch_frac = 1: the 230 training samples of the second split) is ONE Adam step from the best state of stage
+    one, and ``fit`` returns its result (the only epoch improves on infinity).  Restated in float64 numpy with m = v = 0 and step = 1; allowed: the
+    propagated tolerance of test_first_three_steps for one step.  Moments carried over from stage one (24 steps at learning rate 0.1) would change
+    m_hat / (sqrt(v_hat) + eps) by order 1 and the parameters by order lr = 1e-3."""
+    from cosmoprimo_amd.emulators.tools import mlp
+    X, Y = toy
+    lr = 1e-3
+    engine = fit_stages(X, Y, batch_frac=1., epochs=1, learning_rate=lr, patience=1)
+    assert engine.history[1]['epochs'] == 1 and engine.history[1]['batch_size'] == 230
+    Xs, Ys, [_, (index1, index2)] = scaled_splits(engine, X, Y, 2)
+    [sl] = mlp.batch_slices(len(index2), 1.)
+    p0 = one_stage.parameters
+    levels, _, (_, g) = mr.gradient_levels(p0, DIMS, SILU, Xs[index2][sl], Ys[index2][sl])
+    dg = np.zeros_like(p0)
+    for name, block in mr.blocks(DIMS).items():
+        dg[block] = 2 * 16 * levels[name][0] * levels[name][1]
+    p, m, v = mr.adam(p0, np.zeros_like(p0), np.zeros_like(p0), g, lr, 1)
+    tol = lr * np.minimum(2., 3 * dg / (np.sqrt(v / (1. - 0.999)) + 1e-8))
+    difference, moved = np.abs(engine.parameters - p), np.abs(engine.parameters - p0)
+    print('one step of stage two: largest |difference| %.3g (tolerance at most %.3g), the step itself up to %.3g' % (difference.max(), tol.max(), moved.max()))
+    assert (difference <= tol).all() and tol.max() < 1e-3 * lr and moved.max() > 0.5 * lr
+    loss = mr.loss_grad(p, DIMS, SILU, Xs[index1], Ys[index1])[0]
+    assert abs(engine.history[1]['best_loss'] - loss) <= 1e-9 * loss
 
 
 @pytest.fixture(scope='module')
