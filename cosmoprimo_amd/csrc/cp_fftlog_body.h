@@ -24,6 +24,17 @@ enum { CP_EXTRAP_CONST = 0, CP_EXTRAP_EDGE = 1, CP_EXTRAP_LOG = 2 };
 #ifndef CP_INTERPAIR_BARRIER
 #define CP_INTERPAIR_BARRIER 0
 #endif
+// The four waves of a headline workgroup (NP = 4096, P = 16, zero padding) leave the barrier behind phase 0 together, do identical work and reach the CU's
+// one LDS pipe together in the three barrier-free phases that follow.  CP_WAVE_SKEW > 0: behind that barrier wave w sleeps order[w] x CP_WAVE_SKEW x 64 cycles
+// (s_sleep 1) before it issues its phase-1 reads; CP_WAVE_ORDER holds order[w] in hex digit w (0x3210: plain; 0x3120: waves 0, 2, 1, 3, i.e. SIMD order when
+// the waves sit on SIMDs 0, 2, 1, 3).  Decides when a wave runs, never what it computes.  0: off, no code is emitted.  1 (64 / 128 / 192 cycles, plain order)
+// measured best of 0 ... 12: -1.4 % on the headline, three times over (profiles/headline_wave_skew_ab.txt); 2-3 and 12 gain nothing, 7-9 about 1 %.
+#ifndef CP_WAVE_SKEW
+#define CP_WAVE_SKEW 1
+#endif
+#ifndef CP_WAVE_ORDER
+#define CP_WAVE_ORDER 0x3210
+#endif
 #ifndef CP_WIDE_IO  // 1: 16-byte row loads / stores shared by lane pairs through DPP lane transposes; 0: one 8-byte access per sample
 #define CP_WIDE_IO 0
 #endif

@@ -39,6 +39,19 @@ bool find_launcher_g4(int npad, Launcher* out);
 #define CP_STAMP_DECL
 #define CP_STAMP_ARG
 #endif
+template <int NP, int P, int IM, int OM>
+constexpr bool balances_cu();  // below
+// CP_WAVE_SKEW (cp_fftlog_body.h): the headline instantiation only, and only while the exchanges between the barrier behind phase 0
+// and the next workgroup barrier stay inside single waves -- the waves then share nothing in that span but read-only tables
+template <int NP, int P, int IM, int OM>
+constexpr bool skews_waves() {
+    using F = Fftlog<NP, P, IM, OM>;
+    if constexpr (CP_WAVE_SKEW > 0 && F::NPH == 5 && F::T == 256) {
+        return balances_cu<NP, P, IM, OM>() && F::template barrier_free_after<1>() && F::template barrier_free_after<2>();
+    }
+    return false;
+}
+
 template <int NP, int P, int IM, int OM, int PH>
 __device__ __forceinline__ void run_phases(int t, const FftlogArgs& A, const double* ra, const double* rb, double* oa, double* ob, bool has_b,
                                            int ker, cplx* lds, const double* nra, const double* nrb, int nxt_ker,
@@ -59,6 +72,13 @@ __device__ __forceinline__ void run_phases(int t, const FftlogArgs& A, const dou
             asm volatile("" ::: "memory");
         } else if (!(CP_ABLATE & 2)) {
             __syncthreads();
+            if constexpr (PH == 0 && skews_waves<NP, P, IM, OM>()) {
+                // the four waves leave this barrier together and would meet again at the LDS in each of the barrier-free phases
+                // that follow: wave w holds back CP_WAVE_ORDER[w] x CP_WAVE_SKEW sleeps of 64 cycles before its phase-1 reads
+                const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+                for (int i = 0, n = (int)((CP_WAVE_ORDER >> (4 * w)) & 0xf) * CP_WAVE_SKEW; i < n; ++i) __builtin_amdgcn_s_sleep(1);
+                asm volatile("" ::: "memory");
+            }
         }
 #if defined(CP_STAMPS)
         const unsigned long long s2 = cp_stamp();
@@ -252,6 +272,9 @@ __global__ __launch_bounds__(NP / P, CP_WAVES_PER_SIMD) void fftlog_kernel(const
                                   ((size_t)blockIdx.x * (NP / P / 64) + threadIdx.x / 64) * (2 * F::NPH + 1 + 8);
         for (int i = 0; i < 2 * F::NPH; ++i) dst[i] = cp_stamp_acc[i];
         dst[2 * F::NPH] = cp_stamp() - cp_t_begin;
+        unsigned hw;  // fs[0] is unused: it carries the SIMD the wave ran on (HW_ID bits 5:4)
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        st.fs[0] = (hw >> 4) & 3u;
         for (int i = 0; i < 8; ++i) dst[2 * F::NPH + 1 + i] = st.fs[i];
     }
 #endif

@@ -127,6 +127,31 @@ int main(int argc, char** argv) {
         printf("fine: reads landed ph1..4 = %.0f %.0f %.0f %.0f | U applied %.0f | last twiddles applied %.0f | barrier in last phase %.0f\n",
                avg[2 * NPH + 2] / npw, avg[2 * NPH + 3] / npw, avg[2 * NPH + 4] / npw, avg[2 * NPH + 5] / npw, avg[2 * NPH + 6] / npw,
                avg[2 * NPH + 7] / npw, avg[2 * NPH + 8] / npw);
+        // ---- the same by wave index within the workgroup: do the four waves of a workgroup reach the LDS together? -----------
+        if constexpr (NPH == 5) {
+            const long long npairs_all = (nbatch + 1) / 2;
+            std::vector<double> byw((size_t)W * K, 0.);
+            std::vector<double> simd((size_t)W * 4, 0.);
+            int nwg = 0;
+            for (int b = 0; b < grid && b < npairs_all; ++b) {
+                const double np_b = (double)((npairs_all - b + grid - 1) / grid);
+                for (int w = 0; w < W; ++w) {
+                    const unsigned long long* q = &h[((size_t)b * W + w) * K];
+                    for (int k = 0; k < K; ++k) byw[(size_t)w * K + k] += (double)q[k] / np_b;
+                    simd[(size_t)w * 4 + (q[2 * NPH + 1] & 3)] += 1.;
+                }
+                ++nwg;
+            }
+            printf("by wave index within the workgroup (skew=%d order=0x%x; ticks per pair, mean over %d workgroups):\n", CP_WAVE_SKEW, CP_WAVE_ORDER, nwg);
+            printf("  wave | on SIMD 0 1 2 3 [share]   | reads landed ph1   ph2   ph3   ph4 | work0 work1 work2 work3 work4 | bar0  bar3 | pair\n");
+            for (int w = 0; w < W && nwg; ++w) {
+                const double* a = &byw[(size_t)w * K];
+                printf("  %4d | %.2f %.2f %.2f %.2f             | %16.0f %5.0f %5.0f %5.0f | %5.0f %5.0f %5.0f %5.0f %5.0f | %5.0f %5.0f | %.0f\n", w,
+                       simd[w * 4] / nwg, simd[w * 4 + 1] / nwg, simd[w * 4 + 2] / nwg, simd[w * 4 + 3] / nwg, a[2 * NPH + 2] / nwg, a[2 * NPH + 3] / nwg,
+                       a[2 * NPH + 4] / nwg, a[2 * NPH + 5] / nwg, a[0] / nwg, a[2] / nwg, a[4] / nwg, a[6] / nwg, a[8] / nwg, a[1] / nwg, a[7] / nwg,
+                       a[2 * NPH] / nwg);
+            }
+        }
         // ---- offset between the workgroups that share a CU (last launch) ---------------------------------------------------
         std::vector<unsigned long long> lg((size_t)grid * log_stride);
         CHECK(hipMemcpy(lg.data(), A.bar_log, lg.size() * 8, hipMemcpyDeviceToHost));
