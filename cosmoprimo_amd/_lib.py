@@ -210,6 +210,10 @@ SIGNATURES['cp_mlp_predict'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlon
                                               + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_mlp_predict_columns'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int] + [ctypes.c_void_p] * 5
                                                       + [ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p])
+SIGNATURES['cp_taylor_jacobian'] = SIGNATURES['cp_taylor_predict_columns']      # (d_jac, ldj in the place of d_out, ldo)
+SIGNATURES['cp_mlp_jacobian'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int] + [ctypes.c_void_p] * 5
+                                               + [ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong,
+                                                  ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_mlp_loss_grad'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_mlp_adam'] = (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_longlong] + [ctypes.c_double] * 6 + [ctypes.c_int, ctypes.c_void_p])

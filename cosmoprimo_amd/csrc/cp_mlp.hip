@@ -1,5 +1,6 @@
 // cp_mlp.hip -- multi-layer perceptron emulator of a calculator (reference emulators/tools/mlp.py) for batches of parameter points (gfx950) + C ABI:
-// the batched prediction in one launch, the loss and its gradient for one training batch, and the Adam step (float64 throughout).
+// the batched prediction in one launch, its derivative with respect to the parameters, the loss and its gradient for one training batch, and the Adam
+// step (float64 throughout).
 // Network.  ndim inputs, L <= 8 hidden layers of widths 1 .. 64, M outputs; a layer is v @ kernel + bias with kernel (n_in, n_out) row-major; a hidden
 // layer is followed by silu, relu, tanh or identity-silu (two trained scalars alpha, beta per layer).  Parameters, gradients and Adam moments share ONE
 // packed layout: per layer kernel, bias, and for a hidden layer alpha, beta (always there, so that the layout depends on the widths alone).
@@ -17,6 +18,9 @@
 // workspace and the sum of its squares per workgroup (fixed order).  Rows and columns past the end are never stored.
 // LDS.  2 x NR x 80 x 8 bytes, NR = max(ndim, widths) rounded up to 8: 40 KB at widths <= 32 (launch bounds: two workgroups per CU, the registers'
 // limit), 80 KB at widths up to 64 (two workgroups fill the 160 KB of a CU exactly).
+// Jacobian (cp_mlp_jacobian: mlp_forward_kernel, then mlp_tangent_kernel).  Forward mode with a row per (point, parameter) pair in the same tile scheme; primal
+// and tangent of the hidden layers in LDS, updated in place, NR x (80 + 64) x 8 bytes: 36 KB at widths <= 32, 72 KB at widths up to 64 -- two workgroups
+// per CU at every width, the registers' limit (profiles/jacobian.txt).  Details above the kernel.
 // Gradient.  gW_out = h^T . r (mlp_gw_out_kernel) and dh = r . W_out^T (mlp_dh_kernel) on the matrix cores, both operands straight from memory: in the
 // first both are contiguous along the 16 lanes of a k (and the column sums of r, the bias gradient, are taken from the fragments already loaded);
 // in the second both are contiguous along k, a wave takes one slice of the M inner indices of a row tile and stores a partial result, summed in
@@ -247,6 +251,199 @@ __global__ __launch_bounds__(256, 2) void mlp_forward_kernel(const MlpFwdArgs A)
             for (int t = 0; t < 256; ++t) s += ml_lds[t];
             A.work[A.ws.losspart + (long long)blockIdx.y * gridDim.x + blockIdx.x] = s;
         }
+    }
+}
+
+struct MlpJacArgs {
+    const double* x;          // (B, ndim) raw parameters
+    const double* params;
+    const double* xoff;
+    const double* xscale;
+    const double* yscale;
+    const double* value;      // (B, ncols) with row stride ldv: the prediction on [c0, cend), written by the forward kernel before this one
+    double* jac;              // (R, ncols) with row stride ldj, R = B ndim: row b ndim + i is point b, parameter i
+    long long R, ldv, ldj;
+    int c0, cend;
+    MlpNet net;
+};
+
+// act(z) and act'(z) of one pre-activation: the value as activate() forms it, the derivative as mlp_dz_kernel does (relu: a NaN stays one)
+__device__ __forceinline__ void activate_tangent(int act, double v, double alpha, double beta, double& h, double& d) {
+    switch (act) {
+        case ACT_SILU: {
+            const double e = 1. + cpmath::exp_mid(-v), s = 1. / e;
+            h = v / e;
+            d = s * (1. + v * (1. - s));
+            break;
+        }
+        case ACT_RELU:
+            h = v > 0. ? v : (v != v ? v : 0.);
+            d = v > 0. ? 1. : (v != v ? v : 0.);
+            break;
+        case ACT_TANH: {
+            const double t = tanh(v);
+            h = t;
+            d = 1. - t * t;
+            break;
+        }
+        default: {
+            const double e = 1. + cpmath::exp_mid(-alpha * v), s = 1. / e;
+            h = ((1. - beta) + beta / e) * v;
+            d = (1. - beta) + beta * (s + alpha * v * (s * (1. - s)));
+        }
+    }
+}
+
+// Tangent kernel (cp_mlp_jacobian): forward mode through the network, a ROW being a (point, parameter) pair r = b ndim + i, in the tile scheme of
+// mlp_forward_kernel (64 rows x 256 columns per workgroup; 64 is no multiple of most ndim, so a point's rows may lie in two workgroups: every lane finds
+// its own b and i).  A lane carries the primal activation h and the tangent dh of its row through the hidden layers on the vector ALUs: z = h W + b,
+// dz = dh W, h = act(z), dh = act'(z) dz, from h_0 = (x - xoffset) / xscale and dh_0 = e_i / xscale[i] (one FMA each per weight and LDS read).  The last
+// tangent is multiplied by the output kernel on the matrix cores (no bias; operand fetch, masking and prefetch of the forward kernel), and the epilogue
+// multiplies by yscale[c] f'(v), f' from the prediction that the forward kernel stored before this launch: ln 10 y for 10^v, sqrt(1 + y^2) for sinh.
+// LDS.  ONE buffer of tangents, k-major with the row stride of 80 doubles (after the last layer it is the MFMA's left operand), and one of primal
+// activations, which only the vector ALUs read (64 consecutive doubles per k), with a row stride of 64: a layer is updated IN PLACE -- a wave keeps its at
+// most 16 neurons (h, dh) in registers (64, free until the MFMA accumulators are needed) until every wave has read the layer's inputs, one more barrier
+// per layer.  nr x (80 + 64) x 8 bytes = 36 KB at widths <= 32 and 72 KB at widths up to 64: two workgroups per CU at every width, the registers' limit.
+// (With two buffers each, 144 KB at widths up to 64, a CU held one workgroup and a row cost 1.8 x the forward kernel's: profiles/jacobian.txt.)
+template <int MODE>
+__global__ __launch_bounds__(256, 2) void mlp_tangent_kernel(const MlpJacArgs A) {
+    extern __shared__ double ml_lds[];
+    constexpr int PS = 64;      // row stride of the primal buffers
+    const MlpNet& N = A.net;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int l15 = lane & 15, g = lane >> 4;
+    const long long row0 = (long long)blockIdx.x * ML_ROWS;
+    const long long b0 = row0 / N.ndim;      // the tile's first point and the parameter its first row stands for: row0 + t is point b0 + (i0 + t) / ndim
+    const int i0 = (int)(row0 - b0 * N.ndim);
+    const int c0 = A.c0, cend = A.cend;
+    const int col0 = c0 + (int)blockIdx.y * ML_COLS + wave * 64;
+    double* const curt = ml_lds;                    // tangents, nr x ML_RS
+    double* const curp = ml_lds + N.nr * ML_RS;     // primal activations, nr x PS
+    {      // the inputs of the tile's rows and their tangents, k-major; rows past the end: finite, never stored
+        const bool inside = row0 + lane < A.R;
+        const long long b = b0 + (i0 + lane) / N.ndim;
+        const int mine = (i0 + lane) % N.ndim;
+        for (int i = wave; i < N.ndim; i += 4) {
+            double v = 0., t = 0.;
+            if (inside) {
+                const double xs = A.xscale[i];
+                v = (A.x[b * N.ndim + i] - A.xoff[i]) / xs;
+                t = i == mine ? 1. / xs : 0.;
+            }
+            curp[i * PS + lane] = v;
+            curt[i * ML_RS + lane] = t;
+        }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int l = 0; l < N.L; ++l) {
+        const int nin = N.d[l], nout = N.d[l + 1], act = N.act[l];
+        const double* W = A.params + N.off[l];
+        const double* bias = W + nin * nout;
+        const double alpha = bias[nout], beta = bias[nout + 1];
+        // the layer in place: a wave's neurons j = wave + 4 q (at most 16: four groups of four) stay in registers until every wave has read the inputs
+        double hn[4][4], tn[4][4];
+#pragma unroll
+        for (int grp = 0; grp < 4; ++grp) {
+            const int j0 = wave + 16 * grp;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) hn[grp][q] = tn[grp][q] = 0.;
+            if (j0 >= nout) continue;      // (wave-uniform)
+            int jq[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) jq[q] = j0 + 4 * q < nout ? j0 + 4 * q : j0;
+            double accz[4] = {0., 0., 0., 0.}, acct[4] = {0., 0., 0., 0.};
+#pragma unroll 2
+            for (int k = 0; k < nin; ++k) {
+                const double hv = curp[k * PS + lane], tv = curt[k * ML_RS + lane];
+                const double* wr = W + k * nout;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const double w = wr[jq[q]];
+                    accz[q] = fma(hv, w, accz[q]);
+                    acct[q] = fma(tv, w, acct[q]);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                double dval;
+                activate_tangent(act, accz[q] + bias[jq[q]], alpha, beta, hn[grp][q], dval);
+                tn[grp][q] = dval * acct[q];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int grp = 0; grp < 4; ++grp)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int j = wave + 16 * grp + 4 * q;
+                if (j < nout) {
+                    curp[j * PS + lane] = hn[grp][q];
+                    curt[j * ML_RS + lane] = tn[grp][q];
+                }
+            }
+        for (int j = nout + wave; j < ((nout + 7) & ~7); j += 4) curt[j * ML_RS + lane] = 0.;      // the left operand's rows up to the next pair of MFMA steps
+        __syncthreads();
+    }
+    // the output layer on the matrix cores: acc = dh_L . W_out[:, columns]
+    const int K = N.d[N.L], M = N.M;
+    const double* Wo = A.params + N.off[N.L];
+    const bool active = col0 < cend;      // (wave-uniform; an idle wave multiplies the last column: no branch round the MFMAs)
+    ml_v4d acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = ml_v4d{0., 0., 0., 0.};
+    int colj[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int col = col0 + 16 * j + l15;
+        colj[j] = col < cend ? col : cend - 1;      // columns past the end of the range repeat its last one (never stored)
+    }
+    {
+        const int npairs = (K + 7) / 8;
+        double a0[2][4], b0[2][4];
+        bool keep[2];
+        mlp_load(Wo, K, M, curt, 0, l15, g, colj, a0, b0, keep);
+        mlp_mask(b0, keep);
+#pragma unroll 1
+        for (int p = 0; p < npairs; ++p) {
+            double a1[2][4], b1[2][4];
+            mlp_load(Wo, K, M, curt, p + 1 < npairs ? p + 1 : p, l15, g, colj, a1, b1, keep);
+            __builtin_amdgcn_sched_barrier(0);      // the loads are issued here, not moved below the MFMAs
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[h][i], b0[h][j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) a0[h][i] = a1[h][i], b0[h][i] = b1[h][i];
+            __builtin_amdgcn_sched_barrier(0);
+            mlp_mask(b0, keep);
+        }
+    }
+    if (!active) return;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int col = col0 + 16 * j + l15;
+        if (col >= cend) continue;
+        const double ys = A.yscale[col];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int t = 16 * i + g + 4 * r;
+                if (row0 + t >= A.R) continue;
+                double d = ys;
+                if (MODE != CP_MLP_Y_NONE) {
+                    const double y = A.value[(b0 + (i0 + t) / N.ndim) * A.ldv + (col - c0)];
+                    d *= MODE == CP_MLP_Y_EXP10 ? 2.302585092994045684 * y : sqrt(fma(y, y, 1.));
+                }
+                A.jac[(row0 + t) * A.ldj + (col - c0)] = acc[i][j][r] * d;
+            }
     }
 }
 
@@ -531,6 +728,18 @@ int mlp_forward_launch(const char* who, const MlpFwdArgs& A, void* stream) {
     return CP_OK;
 }
 
+template <int MODE>
+int mlp_tangent_launch(const char* who, const MlpJacArgs& A, void* stream) {
+    const long long nrt = (A.R + ML_ROWS - 1) / ML_ROWS, nct = (A.cend - A.c0 + ML_COLS - 1) / ML_COLS;      // (checked by the caller)
+    const size_t lds = (size_t)A.net.nr * (ML_RS + 64) * sizeof(double);      // 36 KB at widths <= 32, at most 72 KB
+    if (lds > 64 * 1024) {
+        const hipError_t e = cp::allow_full_lds<mlp_tangent_kernel<MODE>>();
+        if (e != hipSuccess) return cp::launch_status(who, e);
+    }
+    hipLaunchKernelGGL(mlp_tangent_kernel<MODE>, dim3((unsigned)nrt, (unsigned)nct), dim3(256), lds, static_cast<hipStream_t>(stream), A);
+    return CP_OK;
+}
+
 }  // namespace
 
 extern "C" long long cp_mlp_param_count(int ndim, int nlayers, const int* widths, int M) {
@@ -587,6 +796,44 @@ extern "C" int cp_mlp_predict_columns(const double* d_x, long long B, int ndim, 
                                       int yfunction, long long col0, long long ncols, double* d_out, long long ldo, int device, void* stream) {
     return mlp_predict("cp_mlp_predict_columns", d_x, B, ndim, nlayers, widths, activations, M, d_params, d_xoffset, d_xscale, d_yoffset, d_yscale, yfunction, col0,
                        ncols, d_out, ldo, device, stream);
+}
+
+// Two launches on the stream: the forward kernel writes the prediction on the range (what cp_mlp_predict_columns writes), the tangent kernel reads it
+extern "C" int cp_mlp_jacobian(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
+                               const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
+                               long long ncols, double* d_value, long long ldv, double* d_jac, long long ldj, int device, void* stream) {
+    const char* who = "cp_mlp_jacobian";
+    MlpFwdArgs F{};
+    if (B < 0) return cp::fail(CP_EINVAL, "%s: negative count of points", who);
+    if (!activations) return cp::fail(CP_EINVAL, "%s: no activation codes", who);
+    const int status = mlp_net(who, ndim, nlayers, widths, activations, M, &F.net);
+    if (status != CP_OK) return status;
+    if (yfunction < CP_MLP_Y_NONE || yfunction > CP_MLP_Y_SINH) return cp::fail(CP_EINVAL, "%s: y function %d (0 none, 1 10^v, 2 sinh)", who, yfunction);
+    if (col0 < 0 || ncols < 1 || ncols > (long long)M - col0) return cp::fail(CP_EINVAL, "%s: columns [%lld, %lld + %lld) of %d", who, col0, col0, ncols, M);
+    if (ldv < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the value is less than its %lld columns", who, ldv, ncols);
+    if (ldj < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the Jacobian is less than its %lld columns", who, ldj, ncols);
+    if (B > 0x7fffffffLL * ML_ROWS / ndim || (ncols + ML_COLS - 1) / ML_COLS > 65535)
+        return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d x %lld results (at most 2^37 rows B ndim, 2^24 - 256 columns)", who, B, ndim, ncols);
+    if (B == 0) return CP_OK;
+    if (!d_x || !d_params || !d_xoffset || !d_xscale || !d_yoffset || !d_yscale || !d_value || !d_jac) return cp::fail(CP_EINVAL, "%s: null pointer", who);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
+    F.x = d_x, F.params = d_params, F.xoff = d_xoffset, F.xscale = d_xscale, F.yoff = d_yoffset, F.yscale = d_yscale, F.out = d_value, F.R = B;
+    F.ldo = ldv, F.c0 = (int)col0, F.cend = (int)(col0 + ncols);
+    MlpJacArgs J{d_x, d_params, d_xoffset, d_xscale, d_yscale, d_value, d_jac, B * ndim, ldv, ldj, F.c0, F.cend, F.net};
+    int launched;
+    if (yfunction == CP_MLP_Y_NONE) {
+        launched = mlp_forward_launch<CP_MLP_Y_NONE>(who, F, stream);
+        if (launched == CP_OK) launched = mlp_tangent_launch<CP_MLP_Y_NONE>(who, J, stream);
+    } else if (yfunction == CP_MLP_Y_EXP10) {
+        launched = mlp_forward_launch<CP_MLP_Y_EXP10>(who, F, stream);
+        if (launched == CP_OK) launched = mlp_tangent_launch<CP_MLP_Y_EXP10>(who, J, stream);
+    } else {
+        launched = mlp_forward_launch<CP_MLP_Y_SINH>(who, F, stream);
+        if (launched == CP_OK) launched = mlp_tangent_launch<CP_MLP_Y_SINH>(who, J, stream);
+    }
+    if (launched != CP_OK) return launched;
+    return cp::launch_status(who);
 }
 
 extern "C" int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long b, int ndim, int nlayers, const int* widths, const int* activations, int M,

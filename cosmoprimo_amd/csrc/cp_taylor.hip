@@ -1,9 +1,12 @@
 // cp_taylor.hip -- Taylor-expansion emulator of a calculator (reference emulators/tools/taylor.py:211-247) for batches of parameter points (gfx950)
-// + C ABI.  One GEMM kernel in float64 on the matrix cores (v_mfma_f64_16x16x4_f64) with two front ends for its left operand:
+// + C ABI.  One GEMM kernel in float64 on the matrix cores (v_mfma_f64_16x16x4_f64) with three front ends for its left operand:
 //   predict : out (B, M) = monomials (B, T) . derivatives (T, M); the monomials of a tile of rows are formed in LDS, chunk of terms by chunk of terms,
 //             from x - center and the integer powers -- the (B, T) matrix never exists in memory
 //   fit     : derivatives (T, M) = S (T, npoints) . Y (npoints, M); S (the finite-difference weights of every term, built on the host) is staged
 //             through the same LDS tiles
+//   jacobian: jac (B ndim, M) = d monomials / d x_i (B ndim, T) . derivatives; a row is a (point, parameter) pair r = b ndim + i (64 is no multiple of
+//             most ndim: a point's rows may lie in two workgroups, every lane finds its own b and i), its entry for term t the derivative of the
+//             monomial, p_ti (x_i - c_i)^(p_ti - 1) prod_{j != i} (x_j - c_j)^p_tj, formed in LDS chunk by chunk as the monomials are
 // Mapping.  A workgroup of four waves owns 64 rows x 256 columns of the result; the waves sit side by side in the columns on the same rows, each with
 // a tile of 64 x 64 (4 x 4 accumulator tiles of 16 x 16, 128 registers: the tile of linop_mfma_kernel, cp_spline.hip).  Fragments of the f64 form
 // (cdna_hip_programming.md): lane l supplies A[row = l & 15][k = l >> 4] and B[k = l >> 4][col = l & 15], and holds D[row = (l >> 4) + 4 r][col = l & 15]
@@ -24,9 +27,10 @@ namespace {
 typedef double ty_v4d __attribute__((ext_vector_type(4)));
 
 constexpr int TY_ROWS = 64, TY_COLS = 256, TY_KC = 32, TY_RS = 80, TY_MAX_NDIM = 32, TY_MAX_POWER = 15;
+enum { TY_FIT = 0, TY_PREDICT = 1, TY_JACOBIAN = 2 };      // the front end of the left operand
 
 struct TaylorArgs {
-    const double* a;        // GEN: x (R, ndim); else the left operand (R, K)
+    const double* a;        // predict: x (R, ndim); jacobian: x (R / ndim, ndim), row r the point r / ndim and the parameter r % ndim; fit: the left operand (R, K)
     const double* center;   // (ndim)
     const int* powers;      // (K, ndim)
     const double* b;        // (K, M)
@@ -61,8 +65,9 @@ __device__ __forceinline__ void taylor_mask(double (&b)[2][4], const bool (&keep
         for (int j = 0; j < 4; ++j) b[h][j] = keep[h] ? b[h][j] : 0.;
 }
 
-template <bool GEN>
+template <int FRONT>
 __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const TaylorArgs A) {
+    constexpr bool GEN = FRONT != TY_FIT, DER = FRONT == TY_JACOBIAN;
     extern __shared__ double ty_lds[];
     double* const abuf = ty_lds;                       // 2 x TY_KC x TY_RS
     double* const dl = ty_lds + 2 * TY_KC * TY_RS;     // GEN: (ndim, 64) x - center of the tile's rows
@@ -76,11 +81,16 @@ __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const TaylorArgs A)
         const long long ldo = GEN ? A.ldo : (long long)A.M;
         const int col0 = c0 + (int)blockIdx.y * TY_COLS + wave * 64;
         const bool active = col0 < cend;      // (wave-uniform; an idle wave forms its share of the left operand and multiplies the last column: no branch round the MFMAs)
+        // jacobian: the tile's first point and the parameter its first row stands for (row0 + t is point b0 + (i0 + t) / ndim), and this lane's parameter
+        const long long b0 = DER ? row0 / A.ndim : 0;
+        const int i0 = DER ? (int)(row0 - b0 * A.ndim) : 0;
+        const int mine = DER ? (i0 + lane) % A.ndim : 0;
         if (GEN) {
             for (int e = threadIdx.x; e < A.ndim * TY_ROWS; e += 256) {
                 const int i = e >> 6;
                 const long long row = row0 + (e & 63);
-                dl[e] = row < A.R ? A.a[row * A.ndim + i] - A.center[i] : 0.;      // rows past the end: finite, never stored
+                const long long point = DER ? b0 + (i0 + (e & 63)) / A.ndim : row;
+                dl[e] = row < A.R ? A.a[point * A.ndim + i] - A.center[i] : 0.;      // rows past the end: finite, never stored
             }
             __syncthreads();
         }
@@ -99,7 +109,37 @@ __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const TaylorArgs A)
         for (int c = 0; c < nchunk; ++c) {
             double* const buf = abuf + (c & 1) * TY_KC * TY_RS;
             const int k0 = c * TY_KC;
-            if (GEN) {
+            if (DER) {
+                // d / dx_mine of the monomial: the factor of this lane's parameter is p d^(p - 1) -- exactly 0 for p = 0 whatever the other factors hold, and
+                // without d for p = 1 --, the others d^p as in predict; the powers are wave-uniform, the lane's parameter a select
+                for (int tt = wave; tt < TY_KC; tt += 4) {
+                    const int t = k0 + tt;
+                    double m = 0.;
+                    if (t < A.K) {
+                        m = 1.;
+                        bool zero = false;
+                        const int* pw = A.powers + (long long)t * A.ndim;
+                        for (int i = 0; i < A.ndim; ++i) {
+                            int p = __builtin_amdgcn_readfirstlane(pw[i]);
+                            if (p <= 0) {
+                                zero = zero || mine == i;
+                                continue;
+                            }
+                            p = p < TY_MAX_POWER ? p : TY_MAX_POWER;
+                            const double d = dl[i * TY_ROWS + lane];
+                            if (p == 1) {
+                                m *= mine == i ? 1. : d;
+                                continue;
+                            }
+                            double v = d;      // d^(p - 1)
+                            for (int q = 2; q < p; ++q) v *= d;
+                            m *= mine == i ? (double)p * v : v * d;
+                        }
+                        m = zero ? 0. : m;
+                    }
+                    buf[tt * TY_RS + lane] = m;
+                }
+            } else if (GEN) {
                 for (int tt = wave; tt < TY_KC; tt += 4) {      // a term per wave and step, a row per lane
                     const int t = k0 + tt;
                     double m = 0.;      // terms past T: zero columns of the left operand
@@ -169,7 +209,7 @@ __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const TaylorArgs A)
     }
 }
 
-template <bool GEN>
+template <int FRONT>
 int taylor_launch(const char* who, const TaylorArgs& A, int device, void* stream) {
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
@@ -177,8 +217,8 @@ int taylor_launch(const char* who, const TaylorArgs& A, int device, void* stream
     const long long nrt = (A.R + TY_ROWS - 1) / TY_ROWS, nct = (A.cend - A.c0 + TY_COLS - 1) / TY_COLS;
     if (nrt > 0x7fffffffLL || nct > 65535) return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d results (at most 2^37 rows, 2^24 - 256 columns)", who, A.R, A.M);
     const dim3 grid((unsigned)nrt, (unsigned)nct);
-    const size_t lds = (size_t)(2 * TY_KC * TY_RS + (GEN ? A.ndim * TY_ROWS : 0)) * sizeof(double);      // at most 56 KB
-    hipLaunchKernelGGL(taylor_gemm_kernel<GEN>, grid, dim3(256), lds, static_cast<hipStream_t>(stream), A);
+    const size_t lds = (size_t)(2 * TY_KC * TY_RS + (FRONT != TY_FIT ? A.ndim * TY_ROWS : 0)) * sizeof(double);      // at most 56 KB
+    hipLaunchKernelGGL(taylor_gemm_kernel<FRONT>, grid, dim3(256), lds, static_cast<hipStream_t>(stream), A);
     return cp::launch_status(who);
 }
 
@@ -196,7 +236,7 @@ static int taylor_predict(const char* who, const double* d_x, long long B, const
     if (B == 0) return CP_OK;
     if (!d_x || !d_center || !d_powers || !d_derivatives || !d_out) return cp::fail(CP_EINVAL, "%s: null pointer", who);
     const TaylorArgs A{d_x, d_center, d_powers, d_derivatives, d_out, B, ldo, T, M, ndim, (int)col0, (int)(col0 + ncols)};
-    return taylor_launch<true>(who, A, device, stream);
+    return taylor_launch<TY_PREDICT>(who, A, device, stream);
 }
 
 extern "C" int cp_taylor_predict(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
@@ -210,9 +250,26 @@ extern "C" int cp_taylor_predict_columns(const double* d_x, long long B, const d
     return taylor_predict("cp_taylor_predict_columns", d_x, B, d_center, d_powers, ndim, T, max_power, d_derivatives, M, col0, ncols, d_out, ldo, device, stream);
 }
 
+extern "C" int cp_taylor_jacobian(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
+                                  const double* d_derivatives, int M, long long col0, long long ncols, double* d_jac, long long ldj, int device, void* stream) {
+    const char* who = "cp_taylor_jacobian";
+    if (B < 0 || ndim < 1 || T < 1 || M < 1) return cp::fail(CP_EINVAL, "%s: need ndim, T, M >= 1 and a non-negative count of points", who);
+    if (max_power < 0) return cp::fail(CP_EINVAL, "%s: max_power %d is negative", who, max_power);
+    if (col0 < 0 || ncols < 1 || ncols > (long long)M - col0) return cp::fail(CP_EINVAL, "%s: columns [%lld, %lld + %lld) of %d", who, col0, col0, ncols, M);
+    if (ldj < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the Jacobian is less than its %lld columns", who, ldj, ncols);
+    if (ndim > TY_MAX_NDIM) return cp::fail(CP_EUNSUPPORTED, "%s: %d parameters (at most %d)", who, ndim, TY_MAX_NDIM);
+    if (max_power > TY_MAX_POWER) return cp::fail(CP_EUNSUPPORTED, "%s: power %d (at most %d)", who, max_power, TY_MAX_POWER);
+    if (B > 0x7fffffffLL * TY_ROWS / ndim || (ncols + TY_COLS - 1) / TY_COLS > 65535)
+        return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d x %lld results (at most 2^37 rows B ndim, 2^24 - 256 columns)", who, B, ndim, ncols);
+    if (B == 0) return CP_OK;
+    if (!d_x || !d_center || !d_powers || !d_derivatives || !d_jac) return cp::fail(CP_EINVAL, "%s: null pointer", who);
+    const TaylorArgs A{d_x, d_center, d_powers, d_derivatives, d_jac, B * ndim, ldj, T, M, ndim, (int)col0, (int)(col0 + ncols)};
+    return taylor_launch<TY_JACOBIAN>(who, A, device, stream);
+}
+
 extern "C" int cp_taylor_fit(const double* d_S, int T, int npoints, const double* d_Y, int M, double* d_derivatives, int device, void* stream) {
     if (T < 1 || npoints < 1 || M < 1) return cp::fail(CP_EINVAL, "cp_taylor_fit: need T, npoints, M >= 1");
     if (!d_S || !d_Y || !d_derivatives) return cp::fail(CP_EINVAL, "cp_taylor_fit: null pointer");
     const TaylorArgs A{d_S, nullptr, nullptr, d_Y, d_derivatives, T, M, npoints, M, 0, 0, M};
-    return taylor_launch<false>("cp_taylor_fit", A, device, stream);
+    return taylor_launch<TY_FIT>("cp_taylor_fit", A, device, stream);
 }

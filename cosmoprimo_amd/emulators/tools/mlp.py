@@ -9,6 +9,9 @@ training split per stage from one ``RandomState(seed)``, whole batches only, val
 the next stage from the best parameters with fresh Adam moments), a training step being ``cp_mlp_loss_grad`` then ``cp_mlp_adam`` with no host
 synchronisation; the one read-back is the validation loss of an epoch.
 
+``jacobian`` is the derivative of ``predict`` with respect to the raw parameters (what ``jax.jacfwd`` gives a user of the reference), analytic, by forward
+mode through the network on the device (``cp_mlp_jacobian``).
+
 Operations are held as numbers, not as expressions: x a chain of affine maps ('scale', 'norm') folded into one (offset, scale) per parameter, y
 optionally 'log10' or 'arcsinh' first, then affine maps.  Not built: 'pca', 'chebyshev', ``model_yoperation``, batch normalisation, learning-rate
 schedules, callable losses, optimizers other than Adam (each raises ``NotImplementedError``), MPI, reading the reference's saved emulators.
@@ -356,6 +359,33 @@ class MLPEmulatorEngine(object):
                                               d['xoffset'].data_ptr(), d['xscale'].data_ptr(), d['yoffset'].data_ptr(), d['yscale'].data_ptr(), d['yfunction'],
                                               out.data_ptr(), d['device'].index, dv.stream_of(d['device'])))
         return out
+
+    def jacobian(self, X, columns=None, return_value=False):
+        """Derivative of :meth:`predict` with respect to the raw parameters at the points ``X`` (B, ndim): device tensor ``J`` (B, ndim, M),
+        ``J[b, i, c] = d predict(X)[b, c] / d X[b, i]``, computed analytically by forward mode through the network (``cp_mlp_jacobian``: the x operations
+        contribute 1 / xscale[i], the inverse y operations yscale[c] f'(v) with f' the derivative of 10^v or sinh v).  ``columns = (start, stop)``: those
+        output columns only, (B, ndim, stop - start), bit for bit the same numbers.  ``return_value=True``: ``(value, J)`` with ``value`` what
+        ``predict(X, columns=columns)`` returns, bit for bit.  Nothing is read back and the call does not wait for the device."""
+        from ... import _device as dv, _lib
+        if self.parameters is None:
+            raise ValueError('fit the engine first')
+        if self._dev is None:
+            self._set_device(dv.resolve_device(self.device, X))
+        d = self._dev
+        net = d['net']
+        torch = dv.torch()
+        X = dv.to_device(X, d['device'], cache=False)
+        if X.ndim != 2 or int(X.shape[1]) != net['ndim']:
+            raise ValueError('X must be of shape (B, {:d}), got {}'.format(net['ndim'], tuple(X.shape)))
+        B = int(X.shape[0])
+        start, stop = (int(c) for c in columns) if columns is not None else (0, net['M'])
+        ncols = max(stop - start, 0)
+        value = torch.empty((B, ncols), dtype=torch.float64, device=d['device'])
+        jac = torch.empty((B, net['ndim'], ncols), dtype=torch.float64, device=d['device'])
+        _lib.check(_lib.load().cp_mlp_jacobian(X.data_ptr(), B, net['ndim'], net['L'], net['widths'], net['acts'], net['M'], d['parameters'].data_ptr(),
+                                               d['xoffset'].data_ptr(), d['xscale'].data_ptr(), d['yoffset'].data_ptr(), d['yscale'].data_ptr(), d['yfunction'],
+                                               start, stop - start, value.data_ptr(), ncols, jac.data_ptr(), ncols, d['device'].index, dv.stream_of(d['device'])))
+        return (value, jac) if return_value else jac
 
     def __getstate__(self):
         state = {'name': self.name, 'nhidden': tuple(self.nhidden), 'activation': tuple(self.activation), 'params': self.params,

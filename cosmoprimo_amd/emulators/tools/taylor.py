@@ -5,7 +5,9 @@ front end of emulators/tools/base.py reduced to what the Taylor engine needs): f
 Fit: the derivative of every term is linear in the samples, ``derivatives (T, M) = S (T, npoints) . Y (npoints, M)``.  ``S`` -- products of 1-D
 finite-difference weights, times the 1 / alpha! of the term -- is built here on the host (T x npoints numbers); the product is one GEMM on the device
 (``cp_taylor_fit``), and ``derivatives`` stay there.  Predict: ``out (B, M) = monomials (B, T) . derivatives`` for B parameter points at once
-(``cp_taylor_predict``: the monomials are formed inside the kernel), where the reference evaluates one point per call.
+(``cp_taylor_predict``: the monomials are formed inside the kernel), where the reference evaluates one point per call.  Jacobian: the derivative of the
+polynomial with respect to the parameters, ``(B ndim, M) = d monomials / d x_i . derivatives`` by the same kernel (``cp_taylor_jacobian``);
+``Emulator.jacobian`` returns it by output key for either engine.
 
 No x / y operations (log10, PCA, ...), no other engines.
 """
@@ -172,6 +174,31 @@ class TaylorEmulatorEngine(object):
                                                  M, out.data_ptr(), d['device'].index, dv.stream_of(d['device'])))
         return out
 
+    def jacobian(self, X, columns=None, return_value=False):
+        """Derivative of :meth:`predict` with respect to the parameters at the points ``X`` (B, ndim): device tensor ``J`` (B, ndim, M),
+        ``J[b, i, :] = sum_t derivatives[t, :] p_ti (x_i - c_i)^(p_ti - 1) prod_{j != i} (x_j - c_j)^p_tj``, one launch (``cp_taylor_jacobian``: the
+        derivatives of the monomials are formed inside the kernel).  ``columns = (start, stop)``: those output columns only, (B, ndim, stop - start), bit
+        for bit the same numbers.  ``return_value=True``: ``(predict(X, columns=columns), J)``, one more launch.  Nothing is read back and the call does
+        not wait for the device."""
+        from ... import _device as dv, _lib
+        if self._dev is None:
+            self._set_device(dv.resolve_device(self.device, X))
+        d = self._dev
+        torch = dv.torch()
+        X = dv.to_device(X, d['device'], cache=False)
+        T, ndim = (int(n) for n in np.shape(self.powers))
+        if X.ndim != 2 or int(X.shape[1]) != ndim:
+            raise ValueError('X must be of shape (B, {:d}), got {}'.format(ndim, tuple(X.shape)))
+        if d['min_power'] < 0:
+            raise ValueError('powers must be non-negative')
+        B, M = int(X.shape[0]), int(d['derivatives'].shape[1])
+        start, stop = (int(c) for c in columns) if columns is not None else (0, M)
+        ncols = max(stop - start, 0)
+        jac = torch.empty((B, ndim, ncols), dtype=torch.float64, device=d['device'])
+        _lib.check(_lib.load().cp_taylor_jacobian(X.data_ptr(), B, d['center'].data_ptr(), d['powers'].data_ptr(), ndim, T, d['max_power'], d['derivatives'].data_ptr(),
+                                                  M, start, stop - start, jac.data_ptr(), ncols, d['device'].index, dv.stream_of(d['device'])))
+        return (self.predict(X, columns=columns), jac) if return_value else jac
+
     def __getstate__(self):
         state = {'sampler_options': self.sampler_options}
         for name in ['center', 'derivatives', 'powers']:
@@ -279,15 +306,8 @@ class Emulator(object):
         self.engine.fit(samples.matrix(), Y, samples.attrs, params=list(self.params), **kwargs)
         return self
 
-    def predict(self, params, device=False, keys=None):
-        """Outputs at ``params``, a dictionary of scalars or arrays of B values (host arrays or device tensors): the calculator's keys, varied ones of shape
-        ``(B,) + shape`` (no leading axis if every parameter is a scalar), fixed ones as they are.  Host arrays by default; ``device=True``: torch tensors,
-        views into one (B, M) buffer, and no synchronisation with the device.
-
-        ``keys``: a list of output names, or a section prefix such as 'background' (every 'background.*' key): these outputs only.  Their columns are
-        planned by :func:`column_runs`; each maximal contiguous run of them is one launch of the engine on that range (B, ncols) -- the keys of a section
-        are adjacent, so normally one -- and no other column is computed or stored.  The varied keys asked for and the fixed ones under the prefix (or
-        among the names) are returned."""
+    def _points(self, params):
+        """(X (B, ndim) in the order of ``self.params``, a host array unless a parameter is a device tensor; B; whether every parameter is a scalar)."""
         from ... import _device as dv
         missing = [name for name in self.params if name not in params]
         if missing:
@@ -306,6 +326,19 @@ class Emulator(object):
                 X[:, i] = np.ravel(v)
         else:
             X = torch.stack([dv.to_device(v, dev, cache=False).reshape(-1).expand(B) for v in values], dim=1)
+        return X, B, scalar
+
+    def predict(self, params, device=False, keys=None):
+        """Outputs at ``params``, a dictionary of scalars or arrays of B values (host arrays or device tensors): the calculator's keys, varied ones of shape
+        ``(B,) + shape`` (no leading axis if every parameter is a scalar), fixed ones as they are.  Host arrays by default; ``device=True``: torch tensors,
+        views into one (B, M) buffer, and no synchronisation with the device.
+
+        ``keys``: a list of output names, or a section prefix such as 'background' (every 'background.*' key): these outputs only.  Their columns are
+        planned by :func:`column_runs`; each maximal contiguous run of them is one launch of the engine on that range (B, ncols) -- the keys of a section
+        are adjacent, so normally one -- and no other column is computed or stored.  The varied keys asked for and the fixed ones under the prefix (or
+        among the names) are returned."""
+        from ... import _device as dv
+        X, B, scalar = self._points(params)
         if keys is not None:
             names = [keys] if isinstance(keys, str) else list(keys)
             unknown = [name for name in names if not any(_requested(key, [name]) for key in list(self.varied_keys) + list(self.fixed))]
@@ -335,6 +368,45 @@ class Emulator(object):
             start += size
         toret.update(self.fixed)
         return toret
+
+    def jacobian(self, params, device=False, keys=None, return_value=False):
+        """Derivatives of the varied outputs with respect to the parameters at ``params`` (as in :meth:`predict`: scalars or arrays of B values, host or
+        device), computed analytically on the device (:meth:`MLPEmulatorEngine.jacobian`, :meth:`TaylorEmulatorEngine.jacobian`):
+        ``{key: array (B, ndim) + shape}``, the ``ndim`` axis in the order of ``Emulator.params``, without the leading ``B`` axis if every parameter is a
+        scalar.  Fixed outputs are not returned: their derivative is identically zero.  Host arrays by default; ``device=True``: torch tensors, views
+        into the (B, ndim, ncols) buffer(s), and no synchronisation with the device.
+
+        ``keys``: as in :meth:`predict` -- the columns are planned by :func:`column_runs`, one call of the engine per maximal contiguous run, and no other
+        column is computed.  ``return_value=True``: ``(values, jacobian)``, ``values`` what ``predict(params, device=device, keys=keys)`` returns."""
+        from ... import _device as dv
+        X, B, scalar = self._points(params)
+        ndim = len(self.params)
+        if keys is not None:
+            names = [keys] if isinstance(keys, str) else list(keys)
+            unknown = [name for name in names if not any(_requested(key, [name]) for key in list(self.varied_keys) + list(self.fixed))]
+            if unknown:
+                raise KeyError('no output {}'.format(unknown))
+            runs = column_runs(self.varied_keys, self.varied_shapes, [name for name in names if any(_requested(key, [name]) for key in self.varied_keys)])
+        else:
+            runs = [(0, sum(int(np.prod(shape, dtype='i8')) for shape in self.varied_shapes))]
+        values, toret = {}, {}
+        for start, stop in runs:
+            out = self.engine.jacobian(X, columns=None if keys is None else (start, stop), return_value=return_value)
+            value, jac = out if return_value else (None, out)
+            if not device:
+                value, jac = (dv.to_host(a) if a is not None else None for a in (value, jac))
+            for key, shape, lo, hi in _key_columns(self.varied_keys, self.varied_shapes):
+                if not (start <= lo and hi <= stop) or (keys is not None and not _requested(key, keys)):
+                    continue
+                block = jac[:, :, lo - start:hi - start].reshape((B, ndim) + shape)
+                toret[key] = block[0] if scalar else block
+                if return_value:
+                    block = value[:, lo - start:hi - start].reshape((B,) + shape)
+                    values[key] = block[0] if scalar else block
+        if not return_value:
+            return toret
+        values.update({key: value for key, value in self.fixed.items() if keys is None or _requested(key, keys)})
+        return values, toret
 
     def to_calculator(self, device=False):
         """Callable ``**params -> dict`` with the contract of ``get_calculator``'s."""

@@ -651,12 +651,20 @@ int cp_spline_tables_apply_f32(const double* d_xk, const double* d_coef, const i
  *   result, bit for bit (an element's sum runs over the terms in their order whatever tile it falls in).  The column tiles cover the range only, and no
  *   column of d_derivatives outside it is read.  col0 < 0, ncols < 1, col0 + ncols > M or ldo < ncols: CP_EINVAL before any launch.  predict is the call
  *   with col0 = 0, ncols = M, ldo = M.
- * fit : d_derivatives (T, M) = d_S (T, npoints) . d_Y (npoints, M), S the finite-difference weights of every term over the samples of the grid. */
+ * fit : d_derivatives (T, M) = d_S (T, npoints) . d_Y (npoints, M), S the finite-difference weights of every term over the samples of the grid.
+ * jacobian : the derivative of predict_columns with respect to the parameters, one launch of the same GEMM with a third front end.  d_jac (B ndim, ncols)
+ *   with row stride ldj >= ncols; row b ndim + i holds d out[b][col0 ..] / d x[b][i] = sum_t p_ti (x_i - c_i)^(p_ti - 1) prod_{j != i} (x_j - c_j)^p_tj *
+ *   derivatives[t].  Factors of power 0 are skipped (exactly 1 for NaN, Inf), a term with p_ti = 0 contributes exactly 0 whatever x holds, p_ti = 1 drops
+ *   the factor of x_i: a NaN in x[b][j] reaches the rows of point b whose terms carry a factor of x_j, and no other point; a NaN column of
+ *   d_derivatives stays in its column.  The argument checks are those of predict_columns, plus ldj, before any device call; B = 0: CP_OK; more than
+ *   2^37 rows B ndim: CP_EUNSUPPORTED. */
 int cp_taylor_predict(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                       const double* d_derivatives, int M, double* d_out, int device, void* stream);
 int cp_taylor_predict_columns(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                               const double* d_derivatives, int M, long long col0, long long ncols, double* d_out, long long ldo, int device, void* stream);
 int cp_taylor_fit(const double* d_S, int T, int npoints, const double* d_Y, int M, double* d_derivatives, int device, void* stream);
+int cp_taylor_jacobian(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
+                       const double* d_derivatives, int M, long long col0, long long ncols, double* d_jac, long long ldj, int device, void* stream);
 
 /* ---- Multi-layer perceptron emulator of a calculator (reference emulators/tools/mlp.py; csrc/cp_mlp.hip): batched prediction, loss and gradient of
  *      a training batch, Adam step, all float64.  Everything is on the device; no call reads anything back, allocates or waits for the stream. ----
@@ -672,6 +680,14 @@ int cp_taylor_fit(const double* d_S, int T, int npoints, const double* d_Y, int 
  *   result, bit for bit.  The hidden layers are formed as in predict; the column tiles cover the range only, and nothing of the output kernel and bias,
  *   d_yoffset or d_yscale outside it is read.  col0 < 0, ncols < 1, col0 + ncols > M or ldo < ncols: CP_EINVAL before any launch.  predict is the call with
  *   col0 = 0, ncols = M, ldo = M.
+ * jacobian : the derivative of predict_columns with respect to the raw parameters, by forward mode through the network.  d_value (B, ncols) with row
+ *   stride ldv >= ncols is always written: predict_columns on that range, bit for bit (the same kernel).  d_jac (B ndim, ncols) with row stride
+ *   ldj >= ncols; row b ndim + i holds d value[b][.] / d x[b][i]: the input tangent is e_i / d_xscale[i], a hidden layer maps (h, dh) to
+ *   (act(z), act'(z) dz) with dz = dh @ kernel, the output layer (no bias) runs on the matrix cores, and the epilogue multiplies by d_yscale[m] f'(v),
+ *   f' taken from the value: ln 10 value for 10^v, sqrt(1 + value^2) for sinh.  Two launches, no atomics: two calls give the same bits, and a range
+ *   gives the bits of the same columns of the full call.  A NaN in row b of d_x makes the ndim rows of point b NaN and touches no other point; a NaN
+ *   column of the output kernel stays in its column.  The argument checks are those of predict_columns, plus ldv and ldj, before any device call;
+ *   B = 0: CP_OK; more than 2^37 rows B ndim: CP_EUNSUPPORTED.
  * loss_grad : d_X (b, ndim), d_Y (b, M) already scaled; d_loss (one device double) = mean((Y - prediction)^2); d_grad (packed layout; NULL: loss
  *   only, with the same bits) its gradient.  d_work: work_doubles >= cp_mlp_workspace_doubles(b, ...) doubles of device workspace.  Reductions run in a
  *   fixed order: two calls give bit-identical results.
@@ -686,6 +702,9 @@ int cp_mlp_predict(const double* d_x, long long B, int ndim, int nlayers, const 
 int cp_mlp_predict_columns(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
                            const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
                            long long ncols, double* d_out, long long ldo, int device, void* stream);
+int cp_mlp_jacobian(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
+                    const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
+                    long long ncols, double* d_value, long long ldv, double* d_jac, long long ldj, int device, void* stream);
 int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long b, int ndim, int nlayers, const int* widths, const int* activations, int M,
                      const double* d_params, double* d_work, long long work_doubles, double* d_loss, double* d_grad, int device, void* stream);
 int cp_mlp_adam(double* d_params, double* d_m, double* d_v, const double* d_grad, long long n, double lr, double b1, double b2, double eps, double c1,
