@@ -214,6 +214,14 @@ SIGNATURES['cp_taylor_jacobian'] = SIGNATURES['cp_taylor_predict_columns']      
 SIGNATURES['cp_mlp_jacobian'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int] + [ctypes.c_void_p] * 5
                                                + [ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong,
                                                   ctypes.c_int, ctypes.c_void_p])
+SIGNATURES['cp_taylor_vjp_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int])
+SIGNATURES['cp_taylor_vjp'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p])
+SIGNATURES['cp_mlp_vjp_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int, ctypes.c_longlong])
+SIGNATURES['cp_mlp_vjp'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int] + [ctypes.c_void_p] * 5
+                                          + [ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_mlp_loss_grad'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_mlp_adam'] = (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_longlong] + [ctypes.c_double] * 6 + [ctypes.c_int, ctypes.c_void_p])

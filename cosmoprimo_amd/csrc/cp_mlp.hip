@@ -28,6 +28,10 @@
 // ceil(M / 64)), the last one shorter and its last MFMA step masked: mlp_work).  The hidden layers' products (at most 65 x 64 entries, sums over the batch)
 // run on the vector ALUs: a thread per entry and one of 16 phases of the batch, combined in a fixed order.  No floating-point atomics anywhere: two
 // calls give the same bits.
+// Vector-Jacobian product (cp_mlp_vjp: G = cot . d predict / d x, reverse mode; three launches whatever the depth).  mlp_forward_kernel in its fourth
+// group of modes stores the pre-activations as the training pass does and, in its epilogue, the weighted cotangent w = cot yscale f'(v) beside (or
+// instead of) the prediction; mlp_dh_kernel multiplies w by the transposed columns of the output kernel; mlp_input_grad_kernel sums its slices and
+// walks the hidden layers back in LDS.  No (B, ndim, .) array exists anywhere.  Details above the kernels.
 #include "cp_internal.h"
 #include "cp_math.h"
 
@@ -36,7 +40,9 @@ namespace {
 typedef double ml_v4d __attribute__((ext_vector_type(4)));
 
 constexpr int ML_ROWS = 64, ML_COLS = 256, ML_RS = 80, ML_MAX_NDIM = 32, ML_MAX_LAYERS = 8, ML_MAX_WIDTH = 64;
-constexpr int ML_TRAIN = 3;      // mode of the forward kernel: 0 .. 2 predict with the y function CP_MLP_Y_*, 3 the training forward pass
+constexpr int ML_TRAIN = 3;      // mode of the forward kernel: 0 .. 2 predict with the y function CP_MLP_Y_*, 3 the training forward pass,
+constexpr int ML_VJP = 4;        // 4 .. 6 the forward pass of the vector-Jacobian product with the y function CP_MLP_Y_* (mode - 4)
+constexpr int ML_GS = 64;        // row stride of the LDS buffers of mlp_input_grad_kernel (the vector ALUs read them, a row per lane)
 enum { ACT_SILU = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_IDENTITY_SILU = 3 };
 
 struct MlpNet {
@@ -62,9 +68,11 @@ struct MlpFwdArgs {
     const double* yoff;
     const double* yscale;
     const double* ytrue;      // training: (R, M)
-    double* out;              // predict: (R, ncols) with row stride ldo, the columns [c0, cend) of the (R, M) result; training: the scaled residual (R, M)
-    double* work;             // training
-    long long R, ldo;
+    const double* cot;        // vjp: the cotangent (R, ncols) with row stride ldc
+    double* out;              // predict: (R, ncols) with row stride ldo, the columns [c0, cend) of the (R, M) result; training: the scaled residual (R, M);
+                              // vjp: the prediction as in predict, or null
+    double* work;             // training, vjp
+    long long R, ldo, ldc;
     int c0, cend;             // the column tiles start at c0 (any value: the fragments are fetched with 8-byte loads); nothing of the output layer, yoff or
                               // yscale outside [c0, cend) is read.  Training: [0, M), ldo = M
     double rscale;            // 2 / (R M)
@@ -109,6 +117,8 @@ __device__ __forceinline__ void mlp_mask(double (&b)[2][4], const bool (&keep)[2
 
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void mlp_forward_kernel(const MlpFwdArgs A) {
+    constexpr bool VJP = MODE >= ML_VJP;
+    constexpr int YF = VJP ? MODE - ML_VJP : MODE;      // the y function (predict, vjp)
     extern __shared__ double ml_lds[];
     const MlpNet& N = A.net;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
@@ -138,7 +148,7 @@ __global__ __launch_bounds__(256, 2) void mlp_forward_kernel(const MlpFwdArgs A)
         const double* W = A.params + N.off[l];
         const double* bias = W + nin * nout;
         const double alpha = bias[nout], beta = bias[nout + 1];
-        const bool record = MODE == ML_TRAIN && blockIdx.y == 0 && row0 + lane < A.R;
+        const bool record = (MODE == ML_TRAIN || VJP) && blockIdx.y == 0 && row0 + lane < A.R;
 #pragma unroll 1
         for (int j0 = wave; j0 < nout; j0 += 16) {
             int jq[4];
@@ -162,7 +172,7 @@ __global__ __launch_bounds__(256, 2) void mlp_forward_kernel(const MlpFwdArgs A)
                 if (record) {
                     const long long e = (row0 + lane) * nout + j;
                     A.work[A.ws.z[l] + e] = z;
-                    A.work[A.ws.h[l] + e] = hval;
+                    if (!VJP) A.work[A.ws.h[l] + e] = hval;
                 }
             }
         }
@@ -235,8 +245,14 @@ __global__ __launch_bounds__(256, 2) void mlp_forward_kernel(const MlpFwdArgs A)
                         v *= A.rscale;
                     } else {
                         v = fma(v, ys, yo);
-                        if (MODE == CP_MLP_Y_EXP10) v = cpmath::exp10_mid(v);
-                        if (MODE == CP_MLP_Y_SINH) v = sinh(v);
+                        if (YF == CP_MLP_Y_EXP10) v = cpmath::exp10_mid(v);
+                        if (YF == CP_MLP_Y_SINH) v = sinh(v);
+                    }
+                    if (VJP) {      // the weighted cotangent, f' from the prediction as mlp_tangent_kernel forms it
+                        double d = ys;
+                        if (YF != CP_MLP_Y_NONE) d *= YF == CP_MLP_Y_EXP10 ? 2.302585092994045684 * v : sqrt(fma(v, v, 1.));
+                        A.work[A.ws.resid + row * (long long)(cend - c0) + (col - c0)] = A.cot[row * A.ldc + (col - c0)] * d;
+                        if (!A.out) continue;
                     }
                     A.out[row * ldo + (col - c0)] = v;
                 }
@@ -267,7 +283,28 @@ struct MlpJacArgs {
     MlpNet net;
 };
 
-// act(z) and act'(z) of one pre-activation: the value as activate() forms it, the derivative as mlp_dz_kernel does (relu: a NaN stays one)
+// act'(z) of one pre-activation, the formulas of mlp_dz_kernel and of activate_tangent (relu: 0 at z <= 0, and a NaN stays one as in activate_tangent;
+// the training step's kernel keeps its own copy with the terms its alpha and beta gradients share, and its bits)
+__device__ __forceinline__ double activate_derivative(int act, double v, double alpha, double beta) {
+    switch (act) {
+        case ACT_SILU: {
+            const double s = sigmoid(v);
+            return s * (1. + v * (1. - s));
+        }
+        case ACT_RELU: return v > 0. ? 1. : (v != v ? v : 0.);
+        case ACT_TANH: {
+            const double t = tanh(v);
+            return 1. - t * t;
+        }
+        default: {
+            const double s = sigmoid(alpha * v);
+            return (1. - beta) + beta * (s + alpha * v * (s * (1. - s)));
+        }
+    }
+}
+
+// act(z) and act'(z) of one pre-activation: the value as activate() forms it, the derivative as activate_derivative() does, with the exponential or
+// tanh that they share taken once (written out: through the two functions the compiler took it twice, and the tangent kernel grew by half)
 __device__ __forceinline__ void activate_tangent(int act, double v, double alpha, double beta, double& h, double& d) {
     switch (act) {
         case ACT_SILU: {
@@ -524,10 +561,11 @@ __global__ __launch_bounds__(256, 2) void mlp_gw_out_kernel(const double* h, con
     }
 }
 
-// partial dh (slice, b, H) = r (b, M) . W_out^T (M, H) over one slice of the M inner indices per wave; both operands contiguous along k.
+// partial dh (slice, b, H) = r (b, M) . W_out^T (M, H) over one slice of the M inner indices per wave; both operands contiguous along k, with row
+// strides ldr and ldw (the training step: both M; the vjp: M inner indices starting at a column of the output kernel, ldw its full width).
 template <int NJ>
-__global__ __launch_bounds__(256, 2) void mlp_dh_kernel(const double* r, const double* W, const long long b, const int H, const int M, const int nsl, const int ks,
-                                                        double* part) {
+__global__ __launch_bounds__(256, 2) void mlp_dh_kernel(const double* r, const long long ldr, const double* W, const long long ldw, const long long b, const int H,
+                                                        const int M, const int nsl, const int ks, double* part) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int l15 = lane & 15, g = lane >> 4;
     const int sl = (int)blockIdx.y * 4 + wave;
@@ -539,10 +577,10 @@ __global__ __launch_bounds__(256, 2) void mlp_dh_kernel(const double* r, const d
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const long long row = row0 + 16 * i + l15;
-        ar[i] = r + (row < b ? row : b - 1) * M;
+        ar[i] = r + (row < b ? row : b - 1) * ldr;
     }
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) br[j] = W + (long long)(16 * j + l15 < H ? 16 * j + l15 : H - 1) * M;
+    for (int j = 0; j < NJ; ++j) br[j] = W + (long long)(16 * j + l15 < H ? 16 * j + l15 : H - 1) * ldw;
     ml_v4d acc[4][NJ];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -621,6 +659,74 @@ __global__ __launch_bounds__(256) void mlp_dz_kernel(const double* part, const i
     dz[e] = dh * d;
 }
 
+// Input-gradient kernel (cp_mlp_vjp): the walk back through the hidden layers for 64 points per workgroup, a row per lane, in two LDS buffers in turn,
+// k-major g[k][row] with a row stride of 64 doubles (only the vector ALUs read them).  dh of the last hidden layer is the sum of the nsl partial
+// products of mlp_dh_kernel in slice order; per layer dz = dh act'(z_l) (z_l from the workspace, a wave the neurons j = wave (mod 4)), then
+// dh_{l-1} = dz . W_l^T with a wave taking the inputs i = wave (mod 4), four at a time (one LDS read of dz per four FMAs, the weights wave-uniform and
+// contiguous along the sum), summed over j in order; at the end G[b][i] = dh_0[i] / xscale[i].  Nothing but G is stored, no atomics: two calls give the
+// same bits.  LDS: 2 x nr x 64 x 8 bytes, at most 64 KB.
+struct MlpGradArgs {
+    const double* params;
+    const double* xscale;
+    const double* work;       // z_l and the partial products, at the offsets of ws
+    double* grad;             // (B, ndim)
+    long long B;
+    MlpNet net;
+    MlpWork ws;
+};
+
+__global__ __launch_bounds__(256, 2) void mlp_input_grad_kernel(const MlpGradArgs A) {
+    extern __shared__ double ml_lds[];
+    const MlpNet& N = A.net;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const long long row0 = (long long)blockIdx.x * ML_ROWS;
+    const long long row = row0 + lane < A.B ? row0 + lane : A.B - 1;      // rows past the end repeat the last one (never stored)
+    double* cur = ml_lds;
+    double* nxt = ml_lds + N.nr * ML_GS;
+    {
+        const int H = N.d[N.L];
+        const double* part = A.work + A.ws.part;
+        for (int j = wave; j < H; j += 4) {
+            double dh = 0.;
+            for (int s = 0; s < A.ws.nsl; ++s) dh += part[((long long)s * A.B + row) * H + j];
+            cur[j * ML_GS + lane] = dh;
+        }
+    }
+#pragma unroll 1
+    for (int l = N.L - 1; l >= 0; --l) {
+        const int nin = N.d[l], nout = N.d[l + 1], act = N.act[l];
+        const double* W = A.params + N.off[l];
+        const double alpha = W[(nin + 1) * nout], beta = W[(nin + 1) * nout + 1];
+        const double* z = A.work + A.ws.z[l] + row * nout;
+        for (int j = wave; j < nout; j += 4) cur[j * ML_GS + lane] *= activate_derivative(act, z[j], alpha, beta);      // (an entry is its own thread's)
+        __syncthreads();
+#pragma unroll 1
+        for (int i0 = wave; i0 < nin; i0 += 16) {
+            const double* wr[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) wr[q] = W + (i0 + 4 * q < nin ? i0 + 4 * q : i0) * nout;
+            double acc[4] = {0., 0., 0., 0.};
+#pragma unroll 2
+            for (int j = 0; j < nout; ++j) {
+                const double dz = cur[j * ML_GS + lane];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[q] = fma(dz, wr[q][j], acc[q]);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (i0 + 4 * q < nin) nxt[(i0 + 4 * q) * ML_GS + lane] = acc[q];
+        }
+        __syncthreads();
+        double* const t = cur;
+        cur = nxt;
+        nxt = t;
+    }
+    for (int e = threadIdx.x; e < ML_ROWS * N.ndim; e += 256) {      // the tile's (64, ndim) block of G is contiguous
+        const int r = e / N.ndim, i = e - r * N.ndim;
+        if (row0 + r < A.B) A.grad[row0 * N.ndim + e] = cur[i * ML_GS + r] / A.xscale[i];
+    }
+}
+
 // gradient of hidden layer l: gW (nin, nout) = hprev^T . dz, gb (nout) = column sums of dz -- (nin + 1, nout) entries contiguous in the packed
 // layout -- a thread per entry and one of 16 phases of the batch (64 entries x 16 phases per workgroup), the phases combined in order.  clear_ab: the
 // layer has no alpha, beta to train (not identity-silu); their two gradients, which follow the bias's, are set to 0 here.
@@ -688,6 +794,15 @@ int mlp_net(const char* who, int ndim, int nlayers, const int* widths, const int
     return CP_OK;
 }
 
+// nsl slices of length ks of the M inner indices of mlp_dh_kernel for nrt row tiles (the rule is above its use in mlp_work)
+void mlp_slices(long long nrt, int M, MlpWork* ws) {
+    long long nsl = nrt > 0 ? (1024 + nrt - 1) / nrt : 1;
+    const long long most = (M + 63) / 64;
+    nsl = nsl > most ? most : nsl;
+    ws->ks = (int)((((M + nsl - 1) / nsl) + 7) & ~7LL);
+    ws->nsl = (M + ws->ks - 1) / ws->ks;
+}
+
 void mlp_work(const MlpNet& net, long long b, MlpWork* ws) {
     long long off = 0, hmax = 0;
     for (int l = 0; l < net.L; ++l) {
@@ -700,11 +815,7 @@ void mlp_work(const MlpNet& net, long long b, MlpWork* ws) {
     // slices of mlp_dh_kernel: min(ceil(1024 / row tiles), ceil(M / 64)) are wanted (about 1024 waves in flight, no more slices than M holds runs of 64); the
     // length ks is M over that count rounded up to a multiple of 8 -- so at most 64 where M sets the count (M = 65: 40, M = 257: 56), longer where the
     // row tiles do (b = 4033, M = 1025: 72), and 8 for M <= 8 -- and nsl = ceil(M / ks) slices are run, the last one the shorter
-    long long nsl = nrt > 0 ? (1024 + nrt - 1) / nrt : 1;
-    const long long most = (net.M + 63) / 64;
-    nsl = nsl > most ? most : nsl;
-    ws->ks = (int)((((net.M + nsl - 1) / nsl) + 7) & ~7LL);
-    ws->nsl = (net.M + ws->ks - 1) / ws->ks;
+    mlp_slices(nrt, net.M, ws);
     ws->resid = off, off += b * net.M;
     ws->losspart = off, off += nrt * ws->nct;
     ws->part = off, off += (long long)ws->nsl * b * net.d[net.L];
@@ -712,6 +823,19 @@ void mlp_work(const MlpNet& net, long long b, MlpWork* ws) {
     ws->dz[1] = off, off += b * hmax;
     ws->ca = off, off += b * hmax;
     ws->cb = off, off += b * hmax;
+    ws->total = off;
+}
+
+// workspace of cp_mlp_vjp over ncols columns: the pre-activations, the weighted cotangent (B, ncols) in the place of the residual, the partial products
+void mlp_vjp_work(const MlpNet& net, long long B, long long ncols, MlpWork* ws) {
+    long long off = 0;
+    for (int l = 0; l < net.L; ++l) ws->z[l] = off, ws->h[l] = 0, off += B * net.d[l + 1];
+    const long long nrt = (B + ML_ROWS - 1) / ML_ROWS;
+    ws->nrt = (int)nrt, ws->nct = (int)((ncols + ML_COLS - 1) / ML_COLS);
+    mlp_slices(nrt, (int)ncols, ws);
+    ws->resid = off, off += B * ncols;
+    ws->part = off, off += (long long)ws->nsl * B * net.d[net.L];
+    ws->losspart = ws->dz[0] = ws->dz[1] = ws->ca = ws->cb = 0;
     ws->total = off;
 }
 
@@ -836,6 +960,71 @@ extern "C" int cp_mlp_jacobian(const double* d_x, long long B, int ndim, int nla
     return cp::launch_status(who);
 }
 
+extern "C" long long cp_mlp_vjp_workspace_doubles(long long B, int ndim, int nlayers, const int* widths, int M, long long ncols) {
+    const char* who = "cp_mlp_vjp_workspace_doubles";
+    MlpNet net;
+    if (B < 0) return -(long long)cp::fail(CP_EINVAL, "%s: negative count of points", who);
+    const int status = mlp_net(who, ndim, nlayers, widths, nullptr, M, &net);
+    if (status != CP_OK) return -(long long)status;
+    if (ncols < 1 || ncols > M) return -(long long)cp::fail(CP_EINVAL, "%s: %lld columns of %d", who, ncols, M);
+    if (B > 0x7fffffffLL * ML_ROWS) return -(long long)cp::fail(CP_EUNSUPPORTED, "%s: %lld points (at most 2^37)", who, B);
+    MlpWork ws;
+    mlp_vjp_work(net, B, ncols, &ws);
+    return ws.total;
+}
+
+// Three launches on the stream: the forward kernel (pre-activations and the weighted cotangent to the workspace, the prediction to d_value if wanted),
+// mlp_dh_kernel on the weighted cotangent and the columns [col0, col0 + ncols) of the output kernel, mlp_input_grad_kernel
+extern "C" int cp_mlp_vjp(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
+                          const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
+                          long long ncols, const double* d_cot, long long ldc, double* d_value, long long ldv, double* d_grad, double* d_work,
+                          long long work_doubles, int device, void* stream) {
+    const char* who = "cp_mlp_vjp";
+    MlpFwdArgs F{};
+    if (B < 0) return cp::fail(CP_EINVAL, "%s: negative count of points", who);
+    if (!activations) return cp::fail(CP_EINVAL, "%s: no activation codes", who);
+    const int status = mlp_net(who, ndim, nlayers, widths, activations, M, &F.net);
+    if (status != CP_OK) return status;
+    if (yfunction < CP_MLP_Y_NONE || yfunction > CP_MLP_Y_SINH) return cp::fail(CP_EINVAL, "%s: y function %d (0 none, 1 10^v, 2 sinh)", who, yfunction);
+    if (col0 < 0 || ncols < 1 || ncols > (long long)M - col0) return cp::fail(CP_EINVAL, "%s: columns [%lld, %lld + %lld) of %d", who, col0, col0, ncols, M);
+    if (ldc < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the cotangent is less than its %lld columns", who, ldc, ncols);
+    if (d_value && ldv < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the value is less than its %lld columns", who, ldv, ncols);
+    if (B > 0x7fffffffLL * ML_ROWS || (ncols + ML_COLS - 1) / ML_COLS > 65535)
+        return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %lld cotangents (at most 2^37 rows, 2^24 - 256 columns)", who, B, ncols);
+    if (B == 0) return CP_OK;
+    if (!d_x || !d_params || !d_xoffset || !d_xscale || !d_yoffset || !d_yscale || !d_cot || !d_grad || !d_work) return cp::fail(CP_EINVAL, "%s: null pointer", who);
+    const MlpNet& N = F.net;
+    mlp_vjp_work(N, B, ncols, &F.ws);
+    const MlpWork& ws = F.ws;
+    if (work_doubles < ws.total) return cp::fail(CP_EINVAL, "%s: workspace of %lld doubles, %lld needed (cp_mlp_vjp_workspace_doubles)", who, work_doubles, ws.total);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    F.x = d_x, F.params = d_params, F.xoff = d_xoffset, F.xscale = d_xscale, F.yoff = d_yoffset, F.yscale = d_yscale, F.cot = d_cot, F.out = d_value, F.work = d_work;
+    F.R = B, F.ldo = ldv, F.ldc = ldc, F.c0 = (int)col0, F.cend = (int)(col0 + ncols);
+    int launched;
+    if (yfunction == CP_MLP_Y_NONE) launched = mlp_forward_launch<ML_VJP + CP_MLP_Y_NONE>(who, F, stream);
+    else if (yfunction == CP_MLP_Y_EXP10) launched = mlp_forward_launch<ML_VJP + CP_MLP_Y_EXP10>(who, F, stream);
+    else launched = mlp_forward_launch<ML_VJP + CP_MLP_Y_SINH>(who, F, stream);
+    if (launched != CP_OK) return launched;
+    const int H = N.d[N.L];
+    {      // dh of the last hidden layer, in slices of the columns
+        const double* w = d_work + ws.resid;
+        const double* Wo = d_params + N.off[N.L] + col0;
+        double* part = d_work + ws.part;
+        const dim3 grid((unsigned)ws.nrt, (unsigned)((ws.nsl + 3) / 4));
+        switch ((H + 15) / 16) {
+            case 1: hipLaunchKernelGGL(mlp_dh_kernel<1>, grid, dim3(256), 0, st, w, ncols, Wo, (long long)M, B, H, (int)ncols, ws.nsl, ws.ks, part); break;
+            case 2: hipLaunchKernelGGL(mlp_dh_kernel<2>, grid, dim3(256), 0, st, w, ncols, Wo, (long long)M, B, H, (int)ncols, ws.nsl, ws.ks, part); break;
+            case 3: hipLaunchKernelGGL(mlp_dh_kernel<3>, grid, dim3(256), 0, st, w, ncols, Wo, (long long)M, B, H, (int)ncols, ws.nsl, ws.ks, part); break;
+            default: hipLaunchKernelGGL(mlp_dh_kernel<4>, grid, dim3(256), 0, st, w, ncols, Wo, (long long)M, B, H, (int)ncols, ws.nsl, ws.ks, part);
+        }
+    }
+    const MlpGradArgs G{d_params, d_xscale, d_work, d_grad, B, N, ws};
+    hipLaunchKernelGGL(mlp_input_grad_kernel, dim3((unsigned)ws.nrt), dim3(256), (size_t)2 * N.nr * ML_GS * sizeof(double), st, G);      // at most 64 KB of LDS
+    return cp::launch_status(who);
+}
+
 extern "C" int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long b, int ndim, int nlayers, const int* widths, const int* activations, int M,
                                 const double* d_params, double* d_work, long long work_doubles, double* d_loss, double* d_grad, int device, void* stream) {
     const char* who = "cp_mlp_loss_grad";
@@ -879,10 +1068,10 @@ extern "C" int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long 
         double* part = d_work + ws.part;
         const dim3 grid((unsigned)ws.nrt, (unsigned)((ws.nsl + 3) / 4));
         switch ((H + 15) / 16) {
-            case 1: hipLaunchKernelGGL(mlp_dh_kernel<1>, grid, dim3(256), 0, st, resid, Wo, b, H, M, ws.nsl, ws.ks, part); break;
-            case 2: hipLaunchKernelGGL(mlp_dh_kernel<2>, grid, dim3(256), 0, st, resid, Wo, b, H, M, ws.nsl, ws.ks, part); break;
-            case 3: hipLaunchKernelGGL(mlp_dh_kernel<3>, grid, dim3(256), 0, st, resid, Wo, b, H, M, ws.nsl, ws.ks, part); break;
-            default: hipLaunchKernelGGL(mlp_dh_kernel<4>, grid, dim3(256), 0, st, resid, Wo, b, H, M, ws.nsl, ws.ks, part);
+            case 1: hipLaunchKernelGGL(mlp_dh_kernel<1>, grid, dim3(256), 0, st, resid, (long long)M, Wo, (long long)M, b, H, M, ws.nsl, ws.ks, part); break;
+            case 2: hipLaunchKernelGGL(mlp_dh_kernel<2>, grid, dim3(256), 0, st, resid, (long long)M, Wo, (long long)M, b, H, M, ws.nsl, ws.ks, part); break;
+            case 3: hipLaunchKernelGGL(mlp_dh_kernel<3>, grid, dim3(256), 0, st, resid, (long long)M, Wo, (long long)M, b, H, M, ws.nsl, ws.ks, part); break;
+            default: hipLaunchKernelGGL(mlp_dh_kernel<4>, grid, dim3(256), 0, st, resid, (long long)M, Wo, (long long)M, b, H, M, ws.nsl, ws.ks, part);
         }
     }
     for (int l = L - 1; l >= 0; --l) {      // hidden layer l: d[l] -> d[l + 1]

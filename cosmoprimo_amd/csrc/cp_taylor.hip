@@ -20,6 +20,10 @@
 // Monomials.  A wave forms whole terms, lane = row: the powers of a term are wave-uniform (scalar loads, uniform branches), factors with power 0 are
 // skipped -- they contribute exactly 1 whatever x - center holds (NaN, Inf: the reference's `where`, taylor.py:246) -- and a power is formed by repeated
 // multiplication.
+// Vector-Jacobian product (cp_taylor_vjp: G (B, ndim) = cot . d predict / d x).  Two launches: S (B, T) = cot (B, ncols) . D[:, columns]^T is the GEMM with
+// the front end of the fit -- both operands are then contiguous as that front end wants them, the left one (cot, row stride lda) along the contraction
+// and the right one, rows [col0, col0 + ncols) of a TRANSPOSED copy (M, T) of the derivatives that the caller keeps, along the terms -- and
+// taylor_input_grad_kernel contracts S with the derivatives of the monomials, which it forms as the jacobian front end does.  No (B, ndim, .) array exists.
 #include "cp_internal.h"
 
 namespace {
@@ -31,6 +35,7 @@ enum { TY_FIT = 0, TY_PREDICT = 1, TY_JACOBIAN = 2 };      // the front end of t
 
 struct TaylorArgs {
     const double* a;        // predict: x (R, ndim); jacobian: x (R / ndim, ndim), row r the point r / ndim and the parameter r % ndim; fit: the left operand (R, K)
+                            // with row stride lda
     const double* center;   // (ndim)
     const int* powers;      // (K, ndim)
     const double* b;        // (K, M)
@@ -38,6 +43,7 @@ struct TaylorArgs {
     long long R, ldo;
     int K, M, ndim;
     int c0, cend;           // the column tiles start at c0 (any value: the fragments are fetched with 8-byte loads); nothing outside [c0, cend) of b is read
+    long long lda;          // fit
 };
 
 // The operands of the eight inner indices k0 + 8 p .. + 7 of one chunk for one wave: two MFMA steps.  A row of the right operand past K is never read:
@@ -163,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const TaylorArgs A)
                     const int r = e / TY_KC, kk = e % TY_KC;      // k along the lanes: the rows of S are contiguous in k
                     const long long row = row0 + r;
                     const int k = k0 + kk;
-                    buf[kk * TY_RS + r] = (row < A.R && k < A.K) ? A.a[row * A.K + k] : 0.;
+                    buf[kk * TY_RS + r] = (row < A.R && k < A.K) ? A.a[row * A.lda + k] : 0.;
                 }
             }
             __syncthreads();      // one barrier per chunk: the buffer written next was last read before this barrier
@@ -209,6 +215,87 @@ __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const TaylorArgs A)
     }
 }
 
+// G[b][i] = sum_t S[b][t] d mono_t / d x_i for cp_taylor_vjp: a row per (point, parameter) pair r = b ndim + i, 64 rows per workgroup, a row per lane of
+// each of its four waves.  The derivative of a monomial as the jacobian front end of the GEMM forms it (the powers wave-uniform, the lane's own parameter a
+// select; factors of power 0 skipped), a wave the terms tt = wave (mod 4) of a chunk of TY_KC, into one of two LDS buffers m[tt][row] with a bit per term for
+// "the term holds no factor of the row's parameter"; wave 0 then adds the chunk to its rows' sums, S[b][t] m over the terms IN THEIR ORDER, while all waves
+// form the next chunk (one barrier per chunk) -- forming a term is a chain of scalar loads, branches and LDS reads that one wave per row tile left unhidden
+// (profiles/vjp.txt).  A flagged term is SKIPPED, not added as 0 x S: neither a NaN under power 0 nor a NaN of S in such a term reaches G.
+// LDS: 2 x 32 x 64 x 8 + ndim x 64 x 8 + 2 x 4 x 64 x 4 bytes, at most 50 KB.
+__global__ __launch_bounds__(256) void taylor_input_grad_kernel(const double* x, const double* center, const int* powers, const double* S, const long long R,
+                                                                const int ndim, const int T, double* grad) {
+    extern __shared__ double ty_lds[];
+    double* const mbuf = ty_lds;                                                   // 2 x TY_KC x 64
+    double* const dl = ty_lds + 2 * TY_KC * TY_ROWS;                               // (ndim, 64) x - center of the point of each row
+    unsigned* const skip = reinterpret_cast<unsigned*>(dl + ndim * TY_ROWS);       // 2 x 4 x 64: bit q of [wave][row] for the term tt = wave + 4 q
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * TY_ROWS + lane;
+    const long long point = (r < R ? r : R - 1) / ndim;      // rows past the end repeat the last one (never stored)
+    const int mine = (int)((r < R ? r : R - 1) - point * ndim);
+    for (int i = wave; i < ndim; i += 4) dl[i * TY_ROWS + lane] = x[point * ndim + i] - center[i];
+    __syncthreads();
+    const double* Sr = S + point * T;
+    const int nchunk = (T + TY_KC - 1) / TY_KC;
+    double g = 0.;
+#pragma unroll 1
+    for (int c = -1; c < nchunk; ++c) {
+        if (c + 1 < nchunk) {      // this wave's terms of chunk c + 1
+            double* const buf = mbuf + ((c + 1) & 1) * TY_KC * TY_ROWS;
+            unsigned flags = 0;
+#pragma unroll 1
+            for (int q = 0; q < TY_KC / 4; ++q) {
+                const int tt = wave + 4 * q, t = (c + 1) * TY_KC + tt;
+                double m = 0.;
+                bool zero = true;      // terms past T
+                if (t < T) {
+                    m = 1., zero = false;
+                    const int* pw = powers + (long long)t * ndim;
+                    for (int i0 = 0; i0 < ndim; i0 += 4) {      // four powers requested at a time (scalar loads: one wait for the four, not one each)
+                        int p4[4];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) p4[k] = __builtin_amdgcn_readfirstlane(pw[i0 + k < ndim ? i0 + k : ndim - 1]);
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const int i = i0 + k;
+                            int p = i < ndim ? p4[k] : 0;      // (past the last parameter: a factor of power 0 of nobody's parameter)
+                            if (p <= 0) {
+                                zero = zero || mine == i;
+                                continue;
+                            }
+                            p = p < TY_MAX_POWER ? p : TY_MAX_POWER;
+                            const double d = dl[i * TY_ROWS + lane];
+                            if (p == 1) {
+                                m *= mine == i ? 1. : d;
+                                continue;
+                            }
+                            double v = d;      // d^(p - 1)
+                            for (int e = 2; e < p; ++e) v *= d;
+                            m *= mine == i ? (double)p * v : v * d;
+                        }
+                    }
+                }
+                buf[tt * TY_ROWS + lane] = m;
+                flags |= zero ? 1u << q : 0u;
+            }
+            skip[(((c + 1) & 1) * 4 + wave) * TY_ROWS + lane] = flags;
+        }
+        if (c >= 0 && wave == 0) {      // chunk c, formed before the last barrier, in term order
+            const double* const buf = mbuf + (c & 1) * TY_KC * TY_ROWS;
+            unsigned flags[4];
+#pragma unroll
+            for (int w = 0; w < 4; ++w) flags[w] = skip[((c & 1) * 4 + w) * TY_ROWS + lane];
+            const int t0 = c * TY_KC, n = T - t0 < TY_KC ? T - t0 : TY_KC;
+            for (int tt = 0; tt < n; ++tt) {
+                const double m = buf[tt * TY_ROWS + lane], s = Sr[t0 + tt];
+                const bool zero = (flags[tt & 3] >> (tt >> 2)) & 1u;
+                g = zero ? g : fma(s, m, g);
+            }
+        }
+        __syncthreads();
+    }
+    if (wave == 0 && r < R) grad[r] = g;
+}
+
 template <int FRONT>
 int taylor_launch(const char* who, const TaylorArgs& A, int device, void* stream) {
     cp::DeviceScope scope(device);
@@ -235,7 +322,7 @@ static int taylor_predict(const char* who, const double* d_x, long long B, const
     if (max_power > TY_MAX_POWER) return cp::fail(CP_EUNSUPPORTED, "%s: power %d (at most %d)", who, max_power, TY_MAX_POWER);
     if (B == 0) return CP_OK;
     if (!d_x || !d_center || !d_powers || !d_derivatives || !d_out) return cp::fail(CP_EINVAL, "%s: null pointer", who);
-    const TaylorArgs A{d_x, d_center, d_powers, d_derivatives, d_out, B, ldo, T, M, ndim, (int)col0, (int)(col0 + ncols)};
+    const TaylorArgs A{d_x, d_center, d_powers, d_derivatives, d_out, B, ldo, T, M, ndim, (int)col0, (int)(col0 + ncols), 0};
     return taylor_launch<TY_PREDICT>(who, A, device, stream);
 }
 
@@ -263,13 +350,46 @@ extern "C" int cp_taylor_jacobian(const double* d_x, long long B, const double* 
         return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d x %lld results (at most 2^37 rows B ndim, 2^24 - 256 columns)", who, B, ndim, ncols);
     if (B == 0) return CP_OK;
     if (!d_x || !d_center || !d_powers || !d_derivatives || !d_jac) return cp::fail(CP_EINVAL, "%s: null pointer", who);
-    const TaylorArgs A{d_x, d_center, d_powers, d_derivatives, d_jac, B * ndim, ldj, T, M, ndim, (int)col0, (int)(col0 + ncols)};
+    const TaylorArgs A{d_x, d_center, d_powers, d_derivatives, d_jac, B * ndim, ldj, T, M, ndim, (int)col0, (int)(col0 + ncols), 0};
     return taylor_launch<TY_JACOBIAN>(who, A, device, stream);
+}
+
+extern "C" long long cp_taylor_vjp_workspace_doubles(long long B, int T) {
+    if (B < 0 || T < 1) return -(long long)cp::fail(CP_EINVAL, "cp_taylor_vjp_workspace_doubles: need T >= 1 and a non-negative count of points");
+    if (B > 0x7fffffffLL * TY_ROWS / TY_MAX_NDIM) return -(long long)cp::fail(CP_EUNSUPPORTED, "cp_taylor_vjp_workspace_doubles: %lld points (at most 2^32)", B);
+    return B * T;
+}
+
+extern "C" int cp_taylor_vjp(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
+                             const double* d_derivatives_t, int M, long long col0, long long ncols, const double* d_cot, long long ldc, double* d_grad,
+                             double* d_work, long long work_doubles, int device, void* stream) {
+    const char* who = "cp_taylor_vjp";
+    if (B < 0 || ndim < 1 || T < 1 || M < 1) return cp::fail(CP_EINVAL, "%s: need ndim, T, M >= 1 and a non-negative count of points", who);
+    if (max_power < 0) return cp::fail(CP_EINVAL, "%s: max_power %d is negative", who, max_power);
+    if (col0 < 0 || ncols < 1 || ncols > (long long)M - col0) return cp::fail(CP_EINVAL, "%s: columns [%lld, %lld + %lld) of %d", who, col0, col0, ncols, M);
+    if (ldc < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the cotangent is less than its %lld columns", who, ldc, ncols);
+    if (ndim > TY_MAX_NDIM) return cp::fail(CP_EUNSUPPORTED, "%s: %d parameters (at most %d)", who, ndim, TY_MAX_NDIM);
+    if (max_power > TY_MAX_POWER) return cp::fail(CP_EUNSUPPORTED, "%s: power %d (at most %d)", who, max_power, TY_MAX_POWER);
+    if (B > 0x7fffffffLL * TY_ROWS / ndim || (T + TY_COLS - 1) / TY_COLS > 65535)
+        return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d gradients of %d terms (at most 2^37 rows B ndim, 2^24 - 256 terms)", who, B, ndim, T);
+    if (B == 0) return CP_OK;
+    if (!d_x || !d_center || !d_powers || !d_derivatives_t || !d_cot || !d_grad || !d_work) return cp::fail(CP_EINVAL, "%s: null pointer", who);
+    if (work_doubles < B * T) return cp::fail(CP_EINVAL, "%s: workspace of %lld doubles, %lld needed (cp_taylor_vjp_workspace_doubles)", who, work_doubles, B * T);
+    // S (B, T) = cot (B, ncols) . Dt[col0 : col0 + ncols] (ncols, T)
+    const TaylorArgs A{d_cot, nullptr, nullptr, d_derivatives_t + col0 * T, d_work, B, T, (int)ncols, T, 0, 0, T, ldc};
+    const int status = taylor_launch<TY_FIT>(who, A, device, stream);
+    if (status != CP_OK) return status;
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
+    const long long R = B * ndim;
+    hipLaunchKernelGGL(taylor_input_grad_kernel, dim3((unsigned)((R + TY_ROWS - 1) / TY_ROWS)), dim3(256), (size_t)(2 * TY_KC + ndim) * TY_ROWS * sizeof(double) + 2 * 4 * TY_ROWS * sizeof(unsigned), static_cast<hipStream_t>(stream), d_x, d_center,
+                       d_powers, d_work, R, ndim, T, d_grad);
+    return cp::launch_status(who);
 }
 
 extern "C" int cp_taylor_fit(const double* d_S, int T, int npoints, const double* d_Y, int M, double* d_derivatives, int device, void* stream) {
     if (T < 1 || npoints < 1 || M < 1) return cp::fail(CP_EINVAL, "cp_taylor_fit: need T, npoints, M >= 1");
     if (!d_S || !d_Y || !d_derivatives) return cp::fail(CP_EINVAL, "cp_taylor_fit: null pointer");
-    const TaylorArgs A{d_S, nullptr, nullptr, d_Y, d_derivatives, T, M, npoints, M, 0, 0, M};
+    const TaylorArgs A{d_S, nullptr, nullptr, d_Y, d_derivatives, T, M, npoints, M, 0, 0, M, npoints};
     return taylor_launch<TY_FIT>("cp_taylor_fit", A, device, stream);
 }

@@ -10,7 +10,9 @@ the next stage from the best parameters with fresh Adam moments), a training ste
 synchronisation; the one read-back is the validation loss of an epoch.
 
 ``jacobian`` is the derivative of ``predict`` with respect to the raw parameters (what ``jax.jacfwd`` gives a user of the reference), analytic, by forward
-mode through the network on the device (``cp_mlp_jacobian``).
+mode through the network on the device (``cp_mlp_jacobian``).  ``vjp`` is its product with a cotangent, ``sum_c cotangent[b, c] J[b, i, c]`` (what
+``jax.vjp`` / ``jax.grad`` give: the gradient of a scalar function of the outputs for every point of a batch), by reverse mode (``cp_mlp_vjp``): one
+forward pass, one product with the transposed output kernel, one walk back through the hidden layers; the Jacobian is never formed.
 
 Operations are held as numbers, not as expressions: x a chain of affine maps ('scale', 'norm') folded into one (offset, scale) per parameter, y
 optionally 'log10' or 'arcsinh' first, then affine maps.  Not built: 'pca', 'chebyshev', ``model_yoperation``, batch normalisation, learning-rate
@@ -386,6 +388,46 @@ class MLPEmulatorEngine(object):
                                                d['xoffset'].data_ptr(), d['xscale'].data_ptr(), d['yoffset'].data_ptr(), d['yscale'].data_ptr(), d['yfunction'],
                                                start, stop - start, value.data_ptr(), ncols, jac.data_ptr(), ncols, d['device'].index, dv.stream_of(d['device'])))
         return (value, jac) if return_value else jac
+
+    def vjp(self, X, cotangent, columns=None, return_value=False):
+        """Vector-Jacobian product of :meth:`predict` at the points ``X`` (B, ndim): device tensor ``G`` (B, ndim),
+        ``G[b, i] = sum_c cotangent[b, c] d predict(X)[b, c] / d X[b, i]``, by reverse mode through the network (``cp_mlp_vjp``: three launches whatever the
+        depth, no (B, ndim, M) array anywhere).  ``cotangent``: (B, M) device tensor (or host array, uploaded), rows of any stride.
+        ``columns = (start, stop)``: the sum over those output columns only, ``cotangent`` (B, stop - start).  ``return_value=True``:
+        ``(predict(X, columns=columns), G)``, the value bit for bit, from the same forward pass.  Nothing is read back and the call does not wait for
+        the device."""
+        from ... import _device as dv, _lib
+        if self.parameters is None:
+            raise ValueError('fit the engine first')
+        if self._dev is None:
+            self._set_device(dv.resolve_device(self.device, X))
+        d = self._dev
+        net = d['net']
+        torch = dv.torch()
+        X = dv.to_device(X, d['device'], cache=False)
+        if X.ndim != 2 or int(X.shape[1]) != net['ndim']:
+            raise ValueError('X must be of shape (B, {:d}), got {}'.format(net['ndim'], tuple(X.shape)))
+        B = int(X.shape[0])
+        start, stop = (int(c) for c in columns) if columns is not None else (0, net['M'])
+        ncols = max(stop - start, 0)
+        cotangent = dv.to_device(cotangent, d['device'], cache=False)
+        if tuple(cotangent.shape) != (B, ncols):
+            raise ValueError('cotangent must be of shape ({:d}, {:d}), got {}'.format(B, ncols, tuple(cotangent.shape)))
+        if cotangent.dtype != torch.float64 or (ncols > 1 and cotangent.stride(1) != 1) or (B > 1 and cotangent.stride(0) < ncols):
+            cotangent = cotangent.to(torch.float64).contiguous()
+        ldc = int(cotangent.stride(0)) if B > 1 else ncols
+        lib = _lib.load()
+        need = int(lib.cp_mlp_vjp_workspace_doubles(B, net['ndim'], net['L'], net['widths'], net['M'], ncols))
+        if need < 0:
+            _lib.check(-need)
+        work = torch.empty((need,), dtype=torch.float64, device=d['device'])
+        value = torch.empty((B, ncols), dtype=torch.float64, device=d['device']) if return_value else None
+        grad = torch.empty((B, net['ndim']), dtype=torch.float64, device=d['device'])
+        _lib.check(lib.cp_mlp_vjp(X.data_ptr(), B, net['ndim'], net['L'], net['widths'], net['acts'], net['M'], d['parameters'].data_ptr(), d['xoffset'].data_ptr(),
+                                  d['xscale'].data_ptr(), d['yoffset'].data_ptr(), d['yscale'].data_ptr(), d['yfunction'], start, stop - start, cotangent.data_ptr(), ldc,
+                                  value.data_ptr() if return_value else None, ncols, grad.data_ptr(), work.data_ptr(), need, d['device'].index,
+                                  dv.stream_of(d['device'])))
+        return (value, grad) if return_value else grad
 
     def __getstate__(self):
         state = {'name': self.name, 'nhidden': tuple(self.nhidden), 'activation': tuple(self.activation), 'params': self.params,

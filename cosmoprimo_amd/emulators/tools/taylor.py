@@ -142,7 +142,8 @@ class TaylorEmulatorEngine(object):
         if derivatives is None:
             derivatives = dv.to_device(np.ascontiguousarray(self.derivatives, dtype='f8'), device, cache=False)
         powers = np.ascontiguousarray(self.powers, dtype='i4')
-        self._dev = dict(device=device, derivatives=derivatives, center=dv.to_device(np.asarray(self.center, dtype='f8'), device, cache=False),
+        # derivatives_t: the (M, T) transpose, the right operand of the first GEMM of vjp (contiguous along the terms), made once
+        self._dev = dict(device=device, derivatives=derivatives, derivatives_t=derivatives.t().contiguous(), center=dv.to_device(np.asarray(self.center, dtype='f8'), device, cache=False),
                          powers=dv.upload(powers, device, cache=False), max_power=int(powers.max(initial=0)), min_power=int(powers.min(initial=0)))
         assert self._dev['powers'].dtype == torch.int32
 
@@ -198,6 +199,43 @@ class TaylorEmulatorEngine(object):
         _lib.check(_lib.load().cp_taylor_jacobian(X.data_ptr(), B, d['center'].data_ptr(), d['powers'].data_ptr(), ndim, T, d['max_power'], d['derivatives'].data_ptr(),
                                                   M, start, stop - start, jac.data_ptr(), ncols, d['device'].index, dv.stream_of(d['device'])))
         return (self.predict(X, columns=columns), jac) if return_value else jac
+
+    def vjp(self, X, cotangent, columns=None, return_value=False):
+        """Vector-Jacobian product of :meth:`predict` at the points ``X`` (B, ndim): device tensor ``G`` (B, ndim),
+        ``G[b, i] = sum_c cotangent[b, c] d predict(X)[b, c] / d X[b, i]`` (``cp_taylor_vjp``: the cotangent times the transposed derivatives on the matrix
+        cores, (B, T), then its contraction with the derivatives of the monomials; no (B, ndim, M) array anywhere).  ``cotangent``: (B, M) device tensor
+        (or host array, uploaded), rows of any stride.  ``columns = (start, stop)``: the sum over those output columns only, ``cotangent``
+        (B, stop - start).  ``return_value=True``: ``(predict(X, columns=columns), G)``, one more launch.  Nothing is read back and the call does not wait
+        for the device."""
+        from ... import _device as dv, _lib
+        if self._dev is None:
+            self._set_device(dv.resolve_device(self.device, X))
+        d = self._dev
+        torch = dv.torch()
+        X = dv.to_device(X, d['device'], cache=False)
+        T, ndim = (int(n) for n in np.shape(self.powers))
+        if X.ndim != 2 or int(X.shape[1]) != ndim:
+            raise ValueError('X must be of shape (B, {:d}), got {}'.format(ndim, tuple(X.shape)))
+        if d['min_power'] < 0:
+            raise ValueError('powers must be non-negative')
+        B, M = int(X.shape[0]), int(d['derivatives'].shape[1])
+        start, stop = (int(c) for c in columns) if columns is not None else (0, M)
+        ncols = max(stop - start, 0)
+        cotangent = dv.to_device(cotangent, d['device'], cache=False)
+        if tuple(cotangent.shape) != (B, ncols):
+            raise ValueError('cotangent must be of shape ({:d}, {:d}), got {}'.format(B, ncols, tuple(cotangent.shape)))
+        if cotangent.dtype != torch.float64 or (ncols > 1 and cotangent.stride(1) != 1) or (B > 1 and cotangent.stride(0) < ncols):
+            cotangent = cotangent.to(torch.float64).contiguous()
+        ldc = int(cotangent.stride(0)) if B > 1 else ncols
+        lib = _lib.load()
+        need = int(lib.cp_taylor_vjp_workspace_doubles(B, T))
+        if need < 0:
+            _lib.check(-need)
+        work = torch.empty((need,), dtype=torch.float64, device=d['device'])
+        grad = torch.empty((B, ndim), dtype=torch.float64, device=d['device'])
+        _lib.check(lib.cp_taylor_vjp(X.data_ptr(), B, d['center'].data_ptr(), d['powers'].data_ptr(), ndim, T, d['max_power'], d['derivatives_t'].data_ptr(), M, start,
+                                     stop - start, cotangent.data_ptr(), ldc, grad.data_ptr(), work.data_ptr(), need, d['device'].index, dv.stream_of(d['device'])))
+        return (self.predict(X, columns=columns), grad) if return_value else grad
 
     def __getstate__(self):
         state = {'sampler_options': self.sampler_options}
@@ -407,6 +445,59 @@ class Emulator(object):
             return toret
         values.update({key: value for key, value in self.fixed.items() if keys is None or _requested(key, keys)})
         return values, toret
+
+    def vjp(self, params, cotangents, device=False, return_value=False):
+        """Vector-Jacobian product: the gradient with respect to the parameters of a scalar function of the outputs whose derivative with respect to
+        them is ``cotangents``, for every point of a batch -- what ``jax.vjp`` / ``jax.grad`` of the reference's ``predict`` give, and what a
+        gradient-based sampler wants of a log-likelihood.  ``params`` as in :meth:`predict`.  ``cotangents``: ``{varied key: array or tensor}``, each
+        broadcastable to ``(B,) + shape`` of that output (``shape`` alone with scalar parameters).  A fixed key is accepted and contributes nothing (its
+        derivative is zero), an unknown key raises ``KeyError``, an empty dictionary gives zeros.
+
+        Returns ``{parameter name: (B,) array}`` in the order of ``Emulator.params``, ``sum over keys and entries of cotangent * d output / d parameter``
+        (scalars if every parameter is a scalar).  Computed by reverse mode on the device (:meth:`MLPEmulatorEngine.vjp`,
+        :meth:`TaylorEmulatorEngine.vjp`) without forming the Jacobian: the columns are planned by :func:`column_runs` over the cotangents' varied keys,
+        one call of the engine per maximal contiguous run on that range only, the runs' results added in run order.  Host arrays by default;
+        ``device=True``: the views ``G[:, i]`` of one (B, ndim) tensor, and no synchronisation with the device.  ``return_value=True``:
+        ``(values, gradients)``, ``values`` what ``predict(params, device=device, keys=list(cotangents))`` returns."""
+        from ... import _device as dv
+        X, B, scalar = self._points(params)
+        torch = dv.torch()
+        names = list(cotangents)
+        unknown = [name for name in names if name not in self.varied_keys and name not in self.fixed]
+        if unknown:
+            raise KeyError('no output {}'.format(unknown))
+        runs = column_runs(self.varied_keys, self.varied_shapes, [name for name in names if name in self.varied_keys])
+        dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, *cotangents.values())
+        total, values = None, {}
+        for start, stop in runs:
+            blocks = []
+            for key, shape, lo, hi in _key_columns(self.varied_keys, self.varied_shapes):
+                if start <= lo and hi <= stop and hi > lo:      # (a run holds requested keys only)
+                    cot = dv.to_device(cotangents[key], dev, cache=False).to(torch.float64)
+                    blocks.append(torch.broadcast_to(cot, (B,) + shape).reshape(B, hi - lo))
+            out = self.engine.vjp(X, blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1), columns=(start, stop), return_value=return_value)
+            value, grad = out if return_value else (None, out)
+            total = grad if total is None else total + grad
+            if return_value:
+                if not device:
+                    value = dv.to_host(value)
+                for key, shape, lo, hi in _key_columns(self.varied_keys, self.varied_shapes):
+                    if start <= lo and hi <= stop and key in cotangents:
+                        block = value[:, lo - start:hi - start].reshape((B,) + shape)
+                        values[key] = block[0] if scalar else block
+        if total is None:
+            total = torch.zeros((B, len(self.params)), dtype=torch.float64, device=dev)
+        if not device:
+            total = dv.to_host(total)
+        grads = {name: (total[0, i] if scalar else total[:, i]) for i, name in enumerate(self.params)}
+        if not return_value:
+            return grads
+        for key in self.varied_keys:      # empty outputs hold no column and join no run
+            if key in cotangents and key not in values:
+                values[key] = self.predict(params, device=device, keys=[key])[key]
+        values = {key: values[key] for key in self.varied_keys if key in values}      # predict's order: the calculator's, then the fixed outputs
+        values.update({key: value for key, value in self.fixed.items() if key in cotangents})
+        return values, grads
 
     def to_calculator(self, device=False):
         """Callable ``**params -> dict`` with the contract of ``get_calculator``'s."""

@@ -657,7 +657,14 @@ int cp_spline_tables_apply_f32(const double* d_xk, const double* d_coef, const i
  *   derivatives[t].  Factors of power 0 are skipped (exactly 1 for NaN, Inf), a term with p_ti = 0 contributes exactly 0 whatever x holds, p_ti = 1 drops
  *   the factor of x_i: a NaN in x[b][j] reaches the rows of point b whose terms carry a factor of x_j, and no other point; a NaN column of
  *   d_derivatives stays in its column.  The argument checks are those of predict_columns, plus ldj, before any device call; B = 0: CP_OK; more than
- *   2^37 rows B ndim: CP_EUNSUPPORTED. */
+ *   2^37 rows B ndim: CP_EUNSUPPORTED.
+ * vjp : the vector-Jacobian product of predict_columns, G (B, ndim) = sum_c d_cot[b][c] d out[b][col0 + c] / d x[b][i] (what jax.vjp of the reference's
+ *   predict gives), without any (B, ndim, .) array.  d_cot (B, ncols) with row stride ldc >= ncols; d_derivatives_t (M, T): the TRANSPOSE of d_derivatives,
+ *   which the caller keeps beside it; d_work: work_doubles >= cp_taylor_vjp_workspace_doubles(B, T) = B T doubles of device workspace.  Two launches:
+ *   S (B, T) = d_cot . d_derivatives_t[col0 .. col0 + ncols) on the matrix cores (the GEMM of fit), then G[b][i] = sum_t S[b][t] d mono_t / d x_i over the terms
+ *   in their order, the derivatives of the monomials formed as in jacobian.  A term with p_ti = 0 is skipped (not added as 0): a NaN or Inf in a
+ *   parameter that only ever has power 0 leaves G finite.  No atomics: two calls give the same bits.  The argument checks are those of jacobian, plus
+ *   ldc and the workspace, before any device call; B = 0: CP_OK. */
 int cp_taylor_predict(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                       const double* d_derivatives, int M, double* d_out, int device, void* stream);
 int cp_taylor_predict_columns(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
@@ -665,6 +672,10 @@ int cp_taylor_predict_columns(const double* d_x, long long B, const double* d_ce
 int cp_taylor_fit(const double* d_S, int T, int npoints, const double* d_Y, int M, double* d_derivatives, int device, void* stream);
 int cp_taylor_jacobian(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                        const double* d_derivatives, int M, long long col0, long long ncols, double* d_jac, long long ldj, int device, void* stream);
+long long cp_taylor_vjp_workspace_doubles(long long B, int T);
+int cp_taylor_vjp(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
+                  const double* d_derivatives_t, int M, long long col0, long long ncols, const double* d_cot, long long ldc, double* d_grad, double* d_work,
+                  long long work_doubles, int device, void* stream);
 
 /* ---- Multi-layer perceptron emulator of a calculator (reference emulators/tools/mlp.py; csrc/cp_mlp.hip): batched prediction, loss and gradient of
  *      a training batch, Adam step, all float64.  Everything is on the device; no call reads anything back, allocates or waits for the stream. ----
@@ -688,6 +699,14 @@ int cp_taylor_jacobian(const double* d_x, long long B, const double* d_center, c
  *   gives the bits of the same columns of the full call.  A NaN in row b of d_x makes the ndim rows of point b NaN and touches no other point; a NaN
  *   column of the output kernel stays in its column.  The argument checks are those of predict_columns, plus ldv and ldj, before any device call;
  *   B = 0: CP_OK; more than 2^37 rows B ndim: CP_EUNSUPPORTED.
+ * vjp : the vector-Jacobian product of predict_columns by reverse mode, d_grad (B, ndim) = sum_c d_cot[b][c] d value[b][c] / d x[b][i] (what jax.vjp of the
+ *   reference's predict gives), without any (B, ndim, .) array.  d_cot (B, ncols) with row stride ldc >= ncols.  d_value: NULL, or (B, ncols) with row
+ *   stride ldv >= ncols, which receives predict_columns on that range bit for bit.  d_work: work_doubles >= cp_mlp_vjp_workspace_doubles(B, ..., ncols)
+ *   doubles of device workspace (minus the status on an error, as cp_mlp_workspace_doubles).  Three launches whatever the depth: the forward pass keeps
+ *   the pre-activations and writes w = d_cot d_yscale[m] f'(v), f' taken from the value as in jacobian; dh = w . kernel_out[:, col0 ..]^T on the matrix cores
+ *   in slices of the columns; one kernel sums the slices in their order and walks the hidden layers back in LDS (dz = dh act'(z), dh = dz . kernel^T;
+ *   relu: act' = 0 at z <= 0), ending with / d_xscale[i].  No atomics: two calls give the same bits.  A NaN in row b of d_x or of d_cot makes row b of
+ *   d_grad NaN and touches no other row.  The argument checks are those of jacobian, plus ldc and the workspace, before any device call; B = 0: CP_OK.
  * loss_grad : d_X (b, ndim), d_Y (b, M) already scaled; d_loss (one device double) = mean((Y - prediction)^2); d_grad (packed layout; NULL: loss
  *   only, with the same bits) its gradient.  d_work: work_doubles >= cp_mlp_workspace_doubles(b, ...) doubles of device workspace.  Reductions run in a
  *   fixed order: two calls give bit-identical results.
@@ -705,6 +724,11 @@ int cp_mlp_predict_columns(const double* d_x, long long B, int ndim, int nlayers
 int cp_mlp_jacobian(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
                     const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
                     long long ncols, double* d_value, long long ldv, double* d_jac, long long ldj, int device, void* stream);
+long long cp_mlp_vjp_workspace_doubles(long long B, int ndim, int nlayers, const int* widths, int M, long long ncols);
+int cp_mlp_vjp(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
+               const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
+               long long ncols, const double* d_cot, long long ldc, double* d_value, long long ldv, double* d_grad, double* d_work, long long work_doubles,
+               int device, void* stream);
 int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long b, int ndim, int nlayers, const int* widths, const int* activations, int M,
                      const double* d_params, double* d_work, long long work_doubles, double* d_loss, double* d_grad, int device, void* stream);
 int cp_mlp_adam(double* d_params, double* d_m, double* d_v, const double* d_grad, long long n, double lr, double b1, double b2, double eps, double c1,
