@@ -198,30 +198,25 @@ SIGNATURES['cp_spline_tables_build'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c
 for _name in ('cp_spline_tables_apply', 'cp_spline_tables_apply_f32'):
     SIGNATURES[_name] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                         ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, _c_int_p, ctypes.c_int, ctypes.c_void_p])
-SIGNATURES['cp_taylor_predict'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                 ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
-SIGNATURES['cp_taylor_predict_columns'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                         ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong,
-                                                         ctypes.c_int, ctypes.c_void_p])
+# the leading arguments that the emulator entry points share, and their last two
+_TAYLOR_HEAD = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]      # d_x, B, d_center, d_powers, ndim, T, max_power, d_derivatives, M
+_MLP_HEAD = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int] + [ctypes.c_void_p] * 5 + [ctypes.c_int]      # d_x, B, ndim, nlayers, widths, activations, M, d_params, the four operations, yfunction
+_RANGE = [ctypes.c_longlong, ctypes.c_longlong]            # col0, ncols
+_ARRAY = [ctypes.c_void_p, ctypes.c_longlong]              # a device array and its row stride
+_WHERE = [ctypes.c_int, ctypes.c_void_p]                   # device, stream
+SIGNATURES['cp_taylor_predict'] = (ctypes.c_int, _TAYLOR_HEAD + [ctypes.c_void_p] + _WHERE)
+SIGNATURES['cp_taylor_predict_columns'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + _WHERE)
+SIGNATURES['cp_taylor_jacobian'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + _WHERE)
+SIGNATURES['cp_taylor_vjp'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong] + _WHERE)      # d_cot, ldc; d_grad, d_work, work_doubles
+SIGNATURES['cp_mlp_predict'] = (ctypes.c_int, _MLP_HEAD + [ctypes.c_void_p] + _WHERE)
+SIGNATURES['cp_mlp_predict_columns'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _WHERE)
+SIGNATURES['cp_mlp_jacobian'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _ARRAY + _WHERE)      # d_value, ldv; d_jac, ldj
+SIGNATURES['cp_mlp_vjp'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _ARRAY + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong] + _WHERE)      # d_cot, ldc; d_value, ldv; d_grad, d_work, work_doubles
 SIGNATURES['cp_taylor_fit'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_mlp_param_count'] = (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int])
 SIGNATURES['cp_mlp_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int])
-SIGNATURES['cp_mlp_predict'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int] + [ctypes.c_void_p] * 5
-                                              + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
-SIGNATURES['cp_mlp_predict_columns'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int] + [ctypes.c_void_p] * 5
-                                                      + [ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p])
-SIGNATURES['cp_taylor_jacobian'] = SIGNATURES['cp_taylor_predict_columns']      # (d_jac, ldj in the place of d_out, ldo)
-SIGNATURES['cp_mlp_jacobian'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int] + [ctypes.c_void_p] * 5
-                                               + [ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong,
-                                                  ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_taylor_vjp_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int])
-SIGNATURES['cp_taylor_vjp'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
-                                             ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_mlp_vjp_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int, ctypes.c_longlong])
-SIGNATURES['cp_mlp_vjp'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int] + [ctypes.c_void_p] * 5
-                                          + [ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_mlp_loss_grad'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_mlp_adam'] = (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_longlong] + [ctypes.c_double] * 6 + [ctypes.c_int, ctypes.c_void_p])

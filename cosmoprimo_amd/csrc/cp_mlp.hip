@@ -32,8 +32,13 @@
 // group of modes stores the pre-activations as the training pass does and, in its epilogue, the weighted cotangent w = cot yscale f'(v) beside (or
 // instead of) the prediction; mlp_dh_kernel multiplies w by the transposed columns of the output kernel; mlp_input_grad_kernel sums its slices and
 // walks the hidden layers back in LDS.  No (B, ndim, .) array exists anywhere.  Details above the kernels.
+// Host side.  cp_mlp_predict(_columns), cp_mlp_jacobian and cp_mlp_vjp are three back ends of one front: mlp_front holds their common checks and fills the
+// forward kernel's arguments, mlp_yfunction turns the y function into a template argument, mlp_dh_launch picks mlp_dh_kernel<NJ> (vjp and training step);
+// an entry point adds its strides, grid cap, null pointers, workspace and ONE device scope, in that order.  No device function is shared between kernels
+// beyond those above: every kernel is held to its instructions.
 #include "cp_internal.h"
 #include "cp_math.h"
+#include <type_traits>
 
 namespace {
 
@@ -864,6 +869,42 @@ int mlp_tangent_launch(const char* who, const MlpJacArgs& A, void* stream) {
     return CP_OK;
 }
 
+// What cp_mlp_predict, cp_mlp_predict_columns, cp_mlp_jacobian and cp_mlp_vjp share: their checks up to the range of columns, in that order, then the
+// network, the inputs and the range in F.  What follows is the entry point's own: its strides, its grid cap, the empty batch, its null pointers, its
+// workspace, the device, and the outputs in F.
+int mlp_front(const char* who, const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
+              const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0, long long ncols,
+              MlpFwdArgs* F) {
+    if (B < 0) return cp::fail(CP_EINVAL, "%s: negative count of points", who);
+    if (!activations) return cp::fail(CP_EINVAL, "%s: no activation codes", who);
+    const int status = mlp_net(who, ndim, nlayers, widths, activations, M, &F->net);
+    if (status != CP_OK) return status;
+    if (yfunction < CP_MLP_Y_NONE || yfunction > CP_MLP_Y_SINH) return cp::fail(CP_EINVAL, "%s: y function %d (0 none, 1 10^v, 2 sinh)", who, yfunction);
+    if (col0 < 0 || ncols < 1 || ncols > (long long)M - col0) return cp::fail(CP_EINVAL, "%s: columns [%lld, %lld + %lld) of %d", who, col0, col0, ncols, M);
+    F->x = d_x, F->params = d_params, F->xoff = d_xoffset, F->xscale = d_xscale, F->yoff = d_yoffset, F->yscale = d_yscale;
+    F->R = B, F->c0 = (int)col0, F->cend = (int)(col0 + ncols);
+    return CP_OK;
+}
+
+// f(std::integral_constant<int, yfunction>): the one place where a checked y function becomes a template argument
+template <class F>
+int mlp_yfunction(int yfunction, F&& f) {
+    if (yfunction == CP_MLP_Y_NONE) return f(std::integral_constant<int, CP_MLP_Y_NONE>{});
+    if (yfunction == CP_MLP_Y_EXP10) return f(std::integral_constant<int, CP_MLP_Y_EXP10>{});
+    return f(std::integral_constant<int, CP_MLP_Y_SINH>{});
+}
+
+// mlp_dh_kernel for a last hidden layer of width H: r (b, M) with row stride ldr times the transposed W (H, M) with row stride ldw, in the slices of ws
+void mlp_dh_launch(const double* r, long long ldr, const double* W, long long ldw, long long b, int H, int M, const MlpWork& ws, double* part, hipStream_t st) {
+    const dim3 grid((unsigned)ws.nrt, (unsigned)((ws.nsl + 3) / 4));
+    switch ((H + 15) / 16) {
+        case 1: hipLaunchKernelGGL(mlp_dh_kernel<1>, grid, dim3(256), 0, st, r, ldr, W, ldw, b, H, M, ws.nsl, ws.ks, part); break;
+        case 2: hipLaunchKernelGGL(mlp_dh_kernel<2>, grid, dim3(256), 0, st, r, ldr, W, ldw, b, H, M, ws.nsl, ws.ks, part); break;
+        case 3: hipLaunchKernelGGL(mlp_dh_kernel<3>, grid, dim3(256), 0, st, r, ldr, W, ldw, b, H, M, ws.nsl, ws.ks, part); break;
+        default: hipLaunchKernelGGL(mlp_dh_kernel<4>, grid, dim3(256), 0, st, r, ldr, W, ldw, b, H, M, ws.nsl, ws.ks, part);
+    }
+}
+
 }  // namespace
 
 extern "C" long long cp_mlp_param_count(int ndim, int nlayers, const int* widths, int M) {
@@ -887,23 +928,15 @@ static int mlp_predict(const char* who, const double* d_x, long long B, int ndim
                        const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
                        long long ncols, double* d_out, long long ldo, int device, void* stream) {
     MlpFwdArgs A{};
-    if (B < 0) return cp::fail(CP_EINVAL, "%s: negative count of points", who);
-    if (!activations) return cp::fail(CP_EINVAL, "%s: no activation codes", who);
-    const int status = mlp_net(who, ndim, nlayers, widths, activations, M, &A.net);
+    const int status = mlp_front(who, d_x, B, ndim, nlayers, widths, activations, M, d_params, d_xoffset, d_xscale, d_yoffset, d_yscale, yfunction, col0, ncols, &A);
     if (status != CP_OK) return status;
-    if (yfunction < CP_MLP_Y_NONE || yfunction > CP_MLP_Y_SINH) return cp::fail(CP_EINVAL, "%s: y function %d (0 none, 1 10^v, 2 sinh)", who, yfunction);
-    if (col0 < 0 || ncols < 1 || ncols > (long long)M - col0) return cp::fail(CP_EINVAL, "%s: columns [%lld, %lld + %lld) of %d", who, col0, col0, ncols, M);
     if (ldo < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the result is less than its %lld columns", who, ldo, ncols);
     if (B == 0) return CP_OK;
     if (!d_x || !d_params || !d_xoffset || !d_xscale || !d_yoffset || !d_yscale || !d_out) return cp::fail(CP_EINVAL, "%s: null pointer", who);
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
-    A.x = d_x, A.params = d_params, A.xoff = d_xoffset, A.xscale = d_xscale, A.yoff = d_yoffset, A.yscale = d_yscale, A.out = d_out, A.R = B;
-    A.ldo = ldo, A.c0 = (int)col0, A.cend = (int)(col0 + ncols);
-    int launched;
-    if (yfunction == CP_MLP_Y_NONE) launched = mlp_forward_launch<CP_MLP_Y_NONE>(who, A, stream);
-    else if (yfunction == CP_MLP_Y_EXP10) launched = mlp_forward_launch<CP_MLP_Y_EXP10>(who, A, stream);
-    else launched = mlp_forward_launch<CP_MLP_Y_SINH>(who, A, stream);
+    A.out = d_out, A.ldo = ldo;
+    const int launched = mlp_yfunction(yfunction, [&](auto y) { return mlp_forward_launch<decltype(y)::value>(who, A, stream); });
     if (launched != CP_OK) return launched;
     return cp::launch_status(who);
 }
@@ -928,12 +961,8 @@ extern "C" int cp_mlp_jacobian(const double* d_x, long long B, int ndim, int nla
                                long long ncols, double* d_value, long long ldv, double* d_jac, long long ldj, int device, void* stream) {
     const char* who = "cp_mlp_jacobian";
     MlpFwdArgs F{};
-    if (B < 0) return cp::fail(CP_EINVAL, "%s: negative count of points", who);
-    if (!activations) return cp::fail(CP_EINVAL, "%s: no activation codes", who);
-    const int status = mlp_net(who, ndim, nlayers, widths, activations, M, &F.net);
+    const int status = mlp_front(who, d_x, B, ndim, nlayers, widths, activations, M, d_params, d_xoffset, d_xscale, d_yoffset, d_yscale, yfunction, col0, ncols, &F);
     if (status != CP_OK) return status;
-    if (yfunction < CP_MLP_Y_NONE || yfunction > CP_MLP_Y_SINH) return cp::fail(CP_EINVAL, "%s: y function %d (0 none, 1 10^v, 2 sinh)", who, yfunction);
-    if (col0 < 0 || ncols < 1 || ncols > (long long)M - col0) return cp::fail(CP_EINVAL, "%s: columns [%lld, %lld + %lld) of %d", who, col0, col0, ncols, M);
     if (ldv < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the value is less than its %lld columns", who, ldv, ncols);
     if (ldj < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the Jacobian is less than its %lld columns", who, ldj, ncols);
     if (B > 0x7fffffffLL * ML_ROWS / ndim || (ncols + ML_COLS - 1) / ML_COLS > 65535)
@@ -942,20 +971,12 @@ extern "C" int cp_mlp_jacobian(const double* d_x, long long B, int ndim, int nla
     if (!d_x || !d_params || !d_xoffset || !d_xscale || !d_yoffset || !d_yscale || !d_value || !d_jac) return cp::fail(CP_EINVAL, "%s: null pointer", who);
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
-    F.x = d_x, F.params = d_params, F.xoff = d_xoffset, F.xscale = d_xscale, F.yoff = d_yoffset, F.yscale = d_yscale, F.out = d_value, F.R = B;
-    F.ldo = ldv, F.c0 = (int)col0, F.cend = (int)(col0 + ncols);
-    MlpJacArgs J{d_x, d_params, d_xoffset, d_xscale, d_yscale, d_value, d_jac, B * ndim, ldv, ldj, F.c0, F.cend, F.net};
-    int launched;
-    if (yfunction == CP_MLP_Y_NONE) {
-        launched = mlp_forward_launch<CP_MLP_Y_NONE>(who, F, stream);
-        if (launched == CP_OK) launched = mlp_tangent_launch<CP_MLP_Y_NONE>(who, J, stream);
-    } else if (yfunction == CP_MLP_Y_EXP10) {
-        launched = mlp_forward_launch<CP_MLP_Y_EXP10>(who, F, stream);
-        if (launched == CP_OK) launched = mlp_tangent_launch<CP_MLP_Y_EXP10>(who, J, stream);
-    } else {
-        launched = mlp_forward_launch<CP_MLP_Y_SINH>(who, F, stream);
-        if (launched == CP_OK) launched = mlp_tangent_launch<CP_MLP_Y_SINH>(who, J, stream);
-    }
+    F.out = d_value, F.ldo = ldv;
+    const MlpJacArgs J{d_x, d_params, d_xoffset, d_xscale, d_yscale, d_value, d_jac, B * ndim, ldv, ldj, F.c0, F.cend, F.net};
+    const int launched = mlp_yfunction(yfunction, [&](auto y) {
+        const int forward = mlp_forward_launch<decltype(y)::value>(who, F, stream);
+        return forward != CP_OK ? forward : mlp_tangent_launch<decltype(y)::value>(who, J, stream);
+    });
     if (launched != CP_OK) return launched;
     return cp::launch_status(who);
 }
@@ -981,12 +1002,8 @@ extern "C" int cp_mlp_vjp(const double* d_x, long long B, int ndim, int nlayers,
                           long long work_doubles, int device, void* stream) {
     const char* who = "cp_mlp_vjp";
     MlpFwdArgs F{};
-    if (B < 0) return cp::fail(CP_EINVAL, "%s: negative count of points", who);
-    if (!activations) return cp::fail(CP_EINVAL, "%s: no activation codes", who);
-    const int status = mlp_net(who, ndim, nlayers, widths, activations, M, &F.net);
+    const int status = mlp_front(who, d_x, B, ndim, nlayers, widths, activations, M, d_params, d_xoffset, d_xscale, d_yoffset, d_yscale, yfunction, col0, ncols, &F);
     if (status != CP_OK) return status;
-    if (yfunction < CP_MLP_Y_NONE || yfunction > CP_MLP_Y_SINH) return cp::fail(CP_EINVAL, "%s: y function %d (0 none, 1 10^v, 2 sinh)", who, yfunction);
-    if (col0 < 0 || ncols < 1 || ncols > (long long)M - col0) return cp::fail(CP_EINVAL, "%s: columns [%lld, %lld + %lld) of %d", who, col0, col0, ncols, M);
     if (ldc < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the cotangent is less than its %lld columns", who, ldc, ncols);
     if (d_value && ldv < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the value is less than its %lld columns", who, ldv, ncols);
     if (B > 0x7fffffffLL * ML_ROWS || (ncols + ML_COLS - 1) / ML_COLS > 65535)
@@ -1000,26 +1017,11 @@ extern "C" int cp_mlp_vjp(const double* d_x, long long B, int ndim, int nlayers,
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    F.x = d_x, F.params = d_params, F.xoff = d_xoffset, F.xscale = d_xscale, F.yoff = d_yoffset, F.yscale = d_yscale, F.cot = d_cot, F.out = d_value, F.work = d_work;
-    F.R = B, F.ldo = ldv, F.ldc = ldc, F.c0 = (int)col0, F.cend = (int)(col0 + ncols);
-    int launched;
-    if (yfunction == CP_MLP_Y_NONE) launched = mlp_forward_launch<ML_VJP + CP_MLP_Y_NONE>(who, F, stream);
-    else if (yfunction == CP_MLP_Y_EXP10) launched = mlp_forward_launch<ML_VJP + CP_MLP_Y_EXP10>(who, F, stream);
-    else launched = mlp_forward_launch<ML_VJP + CP_MLP_Y_SINH>(who, F, stream);
+    F.cot = d_cot, F.out = d_value, F.work = d_work, F.ldo = ldv, F.ldc = ldc;
+    const int launched = mlp_yfunction(yfunction, [&](auto y) { return mlp_forward_launch<ML_VJP + decltype(y)::value>(who, F, stream); });
     if (launched != CP_OK) return launched;
-    const int H = N.d[N.L];
-    {      // dh of the last hidden layer, in slices of the columns
-        const double* w = d_work + ws.resid;
-        const double* Wo = d_params + N.off[N.L] + col0;
-        double* part = d_work + ws.part;
-        const dim3 grid((unsigned)ws.nrt, (unsigned)((ws.nsl + 3) / 4));
-        switch ((H + 15) / 16) {
-            case 1: hipLaunchKernelGGL(mlp_dh_kernel<1>, grid, dim3(256), 0, st, w, ncols, Wo, (long long)M, B, H, (int)ncols, ws.nsl, ws.ks, part); break;
-            case 2: hipLaunchKernelGGL(mlp_dh_kernel<2>, grid, dim3(256), 0, st, w, ncols, Wo, (long long)M, B, H, (int)ncols, ws.nsl, ws.ks, part); break;
-            case 3: hipLaunchKernelGGL(mlp_dh_kernel<3>, grid, dim3(256), 0, st, w, ncols, Wo, (long long)M, B, H, (int)ncols, ws.nsl, ws.ks, part); break;
-            default: hipLaunchKernelGGL(mlp_dh_kernel<4>, grid, dim3(256), 0, st, w, ncols, Wo, (long long)M, B, H, (int)ncols, ws.nsl, ws.ks, part);
-        }
-    }
+    // dh of the last hidden layer, in slices of the columns: the weighted cotangent times the columns [col0, col0 + ncols) of the output kernel
+    mlp_dh_launch(d_work + ws.resid, ncols, d_params + N.off[N.L] + col0, M, B, N.d[N.L], (int)ncols, ws, d_work + ws.part, st);
     const MlpGradArgs G{d_params, d_xscale, d_work, d_grad, B, N, ws};
     hipLaunchKernelGGL(mlp_input_grad_kernel, dim3((unsigned)ws.nrt), dim3(256), (size_t)2 * N.nr * ML_GS * sizeof(double), st, G);      // at most 64 KB of LDS
     return cp::launch_status(who);
@@ -1063,17 +1065,7 @@ extern "C" int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long 
             default: hipLaunchKernelGGL(mlp_gw_out_kernel<4>, grid, dim3(256), 0, st, hL, resid, b, H, M, gW);
         }
     }
-    {      // dh of the last hidden layer, in slices of the outputs
-        const double* Wo = d_params + N.off[L];
-        double* part = d_work + ws.part;
-        const dim3 grid((unsigned)ws.nrt, (unsigned)((ws.nsl + 3) / 4));
-        switch ((H + 15) / 16) {
-            case 1: hipLaunchKernelGGL(mlp_dh_kernel<1>, grid, dim3(256), 0, st, resid, (long long)M, Wo, (long long)M, b, H, M, ws.nsl, ws.ks, part); break;
-            case 2: hipLaunchKernelGGL(mlp_dh_kernel<2>, grid, dim3(256), 0, st, resid, (long long)M, Wo, (long long)M, b, H, M, ws.nsl, ws.ks, part); break;
-            case 3: hipLaunchKernelGGL(mlp_dh_kernel<3>, grid, dim3(256), 0, st, resid, (long long)M, Wo, (long long)M, b, H, M, ws.nsl, ws.ks, part); break;
-            default: hipLaunchKernelGGL(mlp_dh_kernel<4>, grid, dim3(256), 0, st, resid, (long long)M, Wo, (long long)M, b, H, M, ws.nsl, ws.ks, part);
-        }
-    }
+    mlp_dh_launch(resid, M, d_params + N.off[L], M, b, H, M, ws, d_work + ws.part, st);      // dh of the last hidden layer, in slices of the outputs
     for (int l = L - 1; l >= 0; --l) {      // hidden layer l: d[l] -> d[l + 1]
         const int nin = N.d[l], nout = N.d[l + 1];
         double* dz = d_work + ws.dz[l & 1];

@@ -296,10 +296,9 @@ __global__ __launch_bounds__(256) void taylor_input_grad_kernel(const double* x,
     if (wave == 0 && r < R) grad[r] = g;
 }
 
+// The GEMM on the stream, inside the device scope of the entry point that calls it
 template <int FRONT>
-int taylor_launch(const char* who, const TaylorArgs& A, int device, void* stream) {
-    cp::DeviceScope scope(device);
-    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
+int taylor_launch(const char* who, const TaylorArgs& A, void* stream) {
     // the row tiles along x: workgroups are dispatched x first, so those in flight share their 256 columns of the right operand in L2
     const long long nrt = (A.R + TY_ROWS - 1) / TY_ROWS, nct = (A.cend - A.c0 + TY_COLS - 1) / TY_COLS;
     if (nrt > 0x7fffffffLL || nct > 65535) return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d results (at most 2^37 rows, 2^24 - 256 columns)", who, A.R, A.M);
@@ -309,21 +308,32 @@ int taylor_launch(const char* who, const TaylorArgs& A, int device, void* stream
     return cp::launch_status(who);
 }
 
+// What cp_taylor_predict, cp_taylor_predict_columns, cp_taylor_jacobian and cp_taylor_vjp share: their checks, in that order, up to the caps of ndim and
+// of the powers; ``ld`` is the entry point's one row stride (of ``what``), which is checked between the range of columns and the caps.  What follows is
+// the entry point's own: its grid cap, the empty batch, its null pointers, its workspace, the device.
+int taylor_front(const char* who, long long B, int ndim, int T, int max_power, int M, long long col0, long long ncols, long long ld, const char* what) {
+    if (B < 0 || ndim < 1 || T < 1 || M < 1) return cp::fail(CP_EINVAL, "%s: need ndim, T, M >= 1 and a non-negative count of points", who);
+    if (max_power < 0) return cp::fail(CP_EINVAL, "%s: max_power %d is negative", who, max_power);
+    if (col0 < 0 || ncols < 1 || ncols > (long long)M - col0) return cp::fail(CP_EINVAL, "%s: columns [%lld, %lld + %lld) of %d", who, col0, col0, ncols, M);
+    if (ld < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the %s is less than its %lld columns", who, ld, what, ncols);
+    if (ndim > TY_MAX_NDIM) return cp::fail(CP_EUNSUPPORTED, "%s: %d parameters (at most %d)", who, ndim, TY_MAX_NDIM);
+    if (max_power > TY_MAX_POWER) return cp::fail(CP_EUNSUPPORTED, "%s: power %d (at most %d)", who, max_power, TY_MAX_POWER);
+    return CP_OK;
+}
+
 }  // namespace
 
 // cp_taylor_predict is the range [0, M) with row stride M of the same call
 static int taylor_predict(const char* who, const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                           const double* d_derivatives, int M, long long col0, long long ncols, double* d_out, long long ldo, int device, void* stream) {
-    if (B < 0 || ndim < 1 || T < 1 || M < 1) return cp::fail(CP_EINVAL, "%s: need ndim, T, M >= 1 and a non-negative count of points", who);
-    if (max_power < 0) return cp::fail(CP_EINVAL, "%s: max_power %d is negative", who, max_power);
-    if (col0 < 0 || ncols < 1 || ncols > (long long)M - col0) return cp::fail(CP_EINVAL, "%s: columns [%lld, %lld + %lld) of %d", who, col0, col0, ncols, M);
-    if (ldo < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the result is less than its %lld columns", who, ldo, ncols);
-    if (ndim > TY_MAX_NDIM) return cp::fail(CP_EUNSUPPORTED, "%s: %d parameters (at most %d)", who, ndim, TY_MAX_NDIM);
-    if (max_power > TY_MAX_POWER) return cp::fail(CP_EUNSUPPORTED, "%s: power %d (at most %d)", who, max_power, TY_MAX_POWER);
+    const int status = taylor_front(who, B, ndim, T, max_power, M, col0, ncols, ldo, "result");
+    if (status != CP_OK) return status;
     if (B == 0) return CP_OK;
     if (!d_x || !d_center || !d_powers || !d_derivatives || !d_out) return cp::fail(CP_EINVAL, "%s: null pointer", who);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
     const TaylorArgs A{d_x, d_center, d_powers, d_derivatives, d_out, B, ldo, T, M, ndim, (int)col0, (int)(col0 + ncols), 0};
-    return taylor_launch<TY_PREDICT>(who, A, device, stream);
+    return taylor_launch<TY_PREDICT>(who, A, stream);
 }
 
 extern "C" int cp_taylor_predict(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
@@ -340,18 +350,16 @@ extern "C" int cp_taylor_predict_columns(const double* d_x, long long B, const d
 extern "C" int cp_taylor_jacobian(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                                   const double* d_derivatives, int M, long long col0, long long ncols, double* d_jac, long long ldj, int device, void* stream) {
     const char* who = "cp_taylor_jacobian";
-    if (B < 0 || ndim < 1 || T < 1 || M < 1) return cp::fail(CP_EINVAL, "%s: need ndim, T, M >= 1 and a non-negative count of points", who);
-    if (max_power < 0) return cp::fail(CP_EINVAL, "%s: max_power %d is negative", who, max_power);
-    if (col0 < 0 || ncols < 1 || ncols > (long long)M - col0) return cp::fail(CP_EINVAL, "%s: columns [%lld, %lld + %lld) of %d", who, col0, col0, ncols, M);
-    if (ldj < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the Jacobian is less than its %lld columns", who, ldj, ncols);
-    if (ndim > TY_MAX_NDIM) return cp::fail(CP_EUNSUPPORTED, "%s: %d parameters (at most %d)", who, ndim, TY_MAX_NDIM);
-    if (max_power > TY_MAX_POWER) return cp::fail(CP_EUNSUPPORTED, "%s: power %d (at most %d)", who, max_power, TY_MAX_POWER);
+    const int status = taylor_front(who, B, ndim, T, max_power, M, col0, ncols, ldj, "Jacobian");
+    if (status != CP_OK) return status;
     if (B > 0x7fffffffLL * TY_ROWS / ndim || (ncols + TY_COLS - 1) / TY_COLS > 65535)
         return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d x %lld results (at most 2^37 rows B ndim, 2^24 - 256 columns)", who, B, ndim, ncols);
     if (B == 0) return CP_OK;
     if (!d_x || !d_center || !d_powers || !d_derivatives || !d_jac) return cp::fail(CP_EINVAL, "%s: null pointer", who);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
     const TaylorArgs A{d_x, d_center, d_powers, d_derivatives, d_jac, B * ndim, ldj, T, M, ndim, (int)col0, (int)(col0 + ncols), 0};
-    return taylor_launch<TY_JACOBIAN>(who, A, device, stream);
+    return taylor_launch<TY_JACOBIAN>(who, A, stream);
 }
 
 extern "C" long long cp_taylor_vjp_workspace_doubles(long long B, int T) {
@@ -364,23 +372,19 @@ extern "C" int cp_taylor_vjp(const double* d_x, long long B, const double* d_cen
                              const double* d_derivatives_t, int M, long long col0, long long ncols, const double* d_cot, long long ldc, double* d_grad,
                              double* d_work, long long work_doubles, int device, void* stream) {
     const char* who = "cp_taylor_vjp";
-    if (B < 0 || ndim < 1 || T < 1 || M < 1) return cp::fail(CP_EINVAL, "%s: need ndim, T, M >= 1 and a non-negative count of points", who);
-    if (max_power < 0) return cp::fail(CP_EINVAL, "%s: max_power %d is negative", who, max_power);
-    if (col0 < 0 || ncols < 1 || ncols > (long long)M - col0) return cp::fail(CP_EINVAL, "%s: columns [%lld, %lld + %lld) of %d", who, col0, col0, ncols, M);
-    if (ldc < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the cotangent is less than its %lld columns", who, ldc, ncols);
-    if (ndim > TY_MAX_NDIM) return cp::fail(CP_EUNSUPPORTED, "%s: %d parameters (at most %d)", who, ndim, TY_MAX_NDIM);
-    if (max_power > TY_MAX_POWER) return cp::fail(CP_EUNSUPPORTED, "%s: power %d (at most %d)", who, max_power, TY_MAX_POWER);
+    const int status = taylor_front(who, B, ndim, T, max_power, M, col0, ncols, ldc, "cotangent");
+    if (status != CP_OK) return status;
     if (B > 0x7fffffffLL * TY_ROWS / ndim || (T + TY_COLS - 1) / TY_COLS > 65535)
         return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d gradients of %d terms (at most 2^37 rows B ndim, 2^24 - 256 terms)", who, B, ndim, T);
     if (B == 0) return CP_OK;
     if (!d_x || !d_center || !d_powers || !d_derivatives_t || !d_cot || !d_grad || !d_work) return cp::fail(CP_EINVAL, "%s: null pointer", who);
     if (work_doubles < B * T) return cp::fail(CP_EINVAL, "%s: workspace of %lld doubles, %lld needed (cp_taylor_vjp_workspace_doubles)", who, work_doubles, B * T);
-    // S (B, T) = cot (B, ncols) . Dt[col0 : col0 + ncols] (ncols, T)
-    const TaylorArgs A{d_cot, nullptr, nullptr, d_derivatives_t + col0 * T, d_work, B, T, (int)ncols, T, 0, 0, T, ldc};
-    const int status = taylor_launch<TY_FIT>(who, A, device, stream);
-    if (status != CP_OK) return status;
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
+    // S (B, T) = cot (B, ncols) . Dt[col0 : col0 + ncols] (ncols, T)
+    const TaylorArgs A{d_cot, nullptr, nullptr, d_derivatives_t + col0 * T, d_work, B, T, (int)ncols, T, 0, 0, T, ldc};
+    const int launched = taylor_launch<TY_FIT>(who, A, stream);
+    if (launched != CP_OK) return launched;
     const long long R = B * ndim;
     hipLaunchKernelGGL(taylor_input_grad_kernel, dim3((unsigned)((R + TY_ROWS - 1) / TY_ROWS)), dim3(256), (size_t)(2 * TY_KC + ndim) * TY_ROWS * sizeof(double) + 2 * 4 * TY_ROWS * sizeof(unsigned), static_cast<hipStream_t>(stream), d_x, d_center,
                        d_powers, d_work, R, ndim, T, d_grad);
@@ -390,6 +394,8 @@ extern "C" int cp_taylor_vjp(const double* d_x, long long B, const double* d_cen
 extern "C" int cp_taylor_fit(const double* d_S, int T, int npoints, const double* d_Y, int M, double* d_derivatives, int device, void* stream) {
     if (T < 1 || npoints < 1 || M < 1) return cp::fail(CP_EINVAL, "cp_taylor_fit: need T, npoints, M >= 1");
     if (!d_S || !d_Y || !d_derivatives) return cp::fail(CP_EINVAL, "cp_taylor_fit: null pointer");
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_taylor_fit: cannot select device %d", device);
     const TaylorArgs A{d_S, nullptr, nullptr, d_Y, d_derivatives, T, M, npoints, M, 0, 0, M, npoints};
-    return taylor_launch<TY_FIT>("cp_taylor_fit", A, device, stream);
+    return taylor_launch<TY_FIT>("cp_taylor_fit", A, stream);
 }

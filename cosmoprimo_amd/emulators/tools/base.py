@@ -1,0 +1,291 @@
+"""
+The ``Emulator`` front end under the reference's name (cosmoprimo/emulators/tools/base.py ``Emulator``), reduced to what the Taylor and MLP engines need:
+sample a calculator, fit an engine on the concatenation (npoints, M) of its flattened varied outputs, and give ``predict``, ``jacobian`` and ``vjp`` back
+by output key for B parameter points at once.
+
+One front, three back ends.  The three methods share one plan (``Emulator._plan``: the keys asked for -> the maximal contiguous runs of columns of
+:func:`column_runs`, the ``(key, shape, lo, hi)`` entries each run holds, the fixed outputs to return) and one split (``_split``: a run's buffer ->
+``{key: view}``); each is then one call of the engine per run and nothing else.  What ``Emulator`` uses of an engine: ``name``, ``device``, ``_dev``
+(for its device), and ``predict`` / ``jacobian`` / ``vjp`` with ``columns=`` / ``return_value=``.
+
+The helpers that both engines' ``predict`` / ``jacobian`` / ``vjp`` open with (``_columns``, ``_cotangent``, ``_empty``) live here as well; the engines
+import this module, which imports them only where it builds one.  Nothing on the path of a call imports anything: at B = 1 a call is its Python.
+"""
+import numpy as np
+
+from ... import _device as dv
+
+
+def _columns(columns, M):
+    """``(start, ncols)`` of ``columns = (start, stop)``, of every one of the ``M`` columns for None.  ``ncols`` is as given, positive or not: the C entry
+    points refuse a bad range by name."""
+    start, stop = (int(c) for c in columns) if columns is not None else (0, M)
+    return start, stop - start
+
+
+def _empty(d, *shape):
+    """An uninitialised float64 tensor on the device of an engine's device state ``d`` (which holds the torch module: no import on the path of a call)."""
+    return d['torch'].empty(shape, dtype=d['torch'].float64, device=d['device'])
+
+
+def _cotangent(cotangent, B, ncols, device):
+    """``(cotangent, ldc)``: the cotangent (B, ncols) on ``device`` as the C entry points read it -- float64, columns contiguous, rows ``ldc >= ncols``
+    apart: the tensor itself where it is that already (rows of any stride), else a contiguous copy."""
+    torch = dv.torch()
+    cotangent = dv.to_device(cotangent, device, cache=False)
+    if tuple(cotangent.shape) != (B, ncols):
+        raise ValueError('cotangent must be of shape ({:d}, {:d}), got {}'.format(B, ncols, tuple(cotangent.shape)))
+    if cotangent.dtype != torch.float64 or (ncols > 1 and cotangent.stride(1) != 1) or (B > 1 and cotangent.stride(0) < ncols):
+        cotangent = cotangent.to(torch.float64).contiguous()
+    return cotangent, int(cotangent.stride(0)) if B > 1 else ncols
+
+
+def _requested(key, keys):
+    """Is ``key`` asked for by ``keys``, a section prefix ('fourier' takes 'fourier.k', never 'fourierx.k'; 'fourier.k' takes itself, never 'fourier.kz')
+    or a list of such?"""
+    return any(key == name or key.startswith(name + '.') for name in ([keys] if isinstance(keys, str) else keys))
+
+
+def _key_columns(varied_keys, varied_shapes):
+    """(key, shape, start, stop) of every varied key in the concatenation the engine is fitted on."""
+    toret, start = [], 0
+    for key, shape in zip(varied_keys, varied_shapes):
+        size = int(np.prod(shape, dtype='i8'))
+        toret.append((key, tuple(shape), start, start + size))
+        start += size
+    return toret
+
+
+def column_runs(varied_keys, varied_shapes, keys):
+    """The maximal contiguous runs ``[(start, stop), ...]`` of columns of the (B, M) prediction that hold the varied outputs ``keys`` asks for: a list of
+    output names or section prefixes, or one such string ('background': every 'background.*').  A name matches itself and what it prefixes at a dot
+    ('fourier.k' does not take 'fourier.kz').  A name that matches no varied output raises ``KeyError``; an empty list gives no run.  Outputs without
+    columns (size 0) join no run.  The keys of one section are adjacent in the calculator's order, so a section is normally one run."""
+    names = [keys] if isinstance(keys, str) else list(keys)
+    for name in names:
+        if not any(_requested(key, [name]) for key in varied_keys):
+            raise KeyError('no varied output {}'.format(name))
+    runs = []
+    for key, shape, start, stop in _key_columns(varied_keys, varied_shapes):
+        if stop == start or not _requested(key, names):
+            continue
+        if runs and runs[-1][1] == start:
+            runs[-1] = (runs[-1][0], stop)
+        else:
+            runs.append((start, stop))
+    return runs
+
+
+def _split(out, lead, entries, start, scalar):
+    """``{key: view}`` of the buffer ``out`` (..., ncols) of a run of columns that starts at ``start``: per entry ``(key, shape, lo, hi)`` its columns as
+    ``lead + shape``, without the leading axis if every parameter is a scalar."""
+    toret = {}
+    for key, shape, lo, hi in entries:
+        block = out[..., lo - start:hi - start].reshape(lead + shape)
+        toret[key] = block[0] if scalar else block
+    return toret
+
+
+class Emulator(object):
+
+    """Emulate a calculator ``**params -> dict of arrays``: sample it (:meth:`set_samples`), :meth:`fit`, then :meth:`predict` at B parameter points at once.
+
+    .. code-block:: python
+
+        calculator = get_calculator(Cosmology(engine='eisenstein_hu'))
+        emulator = Emulator(calculator, params={'Omega_m': (0.25, 0.35), 'h': (0.6, 0.8)}, engine='taylor', order=3)
+        emulator.set_samples()       # the whole finite-difference grid in one call of the calculator
+        emulator.fit()
+        emulator.predict({'Omega_m': np.linspace(0.28, 0.32, 10000), 'h': 0.7})   # {'fourier.pk.delta_m.delta_m': (10000, 422, 30) array, ...}
+    """
+
+    def __init__(self, calculator, params=None, engine='taylor', device=None, **engine_options):
+        if isinstance(engine, str):
+            if engine == 'mlp':
+                from .mlp import MLPEmulatorEngine
+                engine = MLPEmulatorEngine(device=device, **engine_options)
+            elif engine == 'taylor':
+                from .taylor import TaylorEmulatorEngine
+                engine = TaylorEmulatorEngine(device=device, **engine_options)
+            else:
+                raise NotImplementedError('engine {} (only the Taylor and MLP engines are built)'.format(engine))
+        self.calculator = calculator
+        self.params = {name: tuple(limits) for name, limits in (params or {}).items()}
+        self.engine = engine
+        self.samples = None
+        self.varied_keys, self.varied_shapes, self.fixed = [], [], {}
+
+    def set_samples(self, samples=None, **kwargs):
+        """Set the samples to fit: those given, else the engine's default (Taylor: :class:`DiffSampler` run on the calculator, ``kwargs`` override order /
+        accuracy; MLP: :class:`QMCSampler`, ``kwargs`` its ``engine``, ``niterations``, ``batch_size``)."""
+        self.samples = samples if samples is not None else self.engine.get_default_samples(self.calculator, self.params, **kwargs)
+        return self.samples
+
+    def fit(self, **kwargs):
+        """Concatenate the flattened varied outputs into Y (npoints, M), upload it once and fit the engine on the device.  ``kwargs``: training options of
+        the engine (:meth:`MLPEmulatorEngine.fit`; the Taylor engine takes none)."""
+        if self.samples is None:
+            self.set_samples()
+        samples = self.samples
+        self.varied_keys = list(samples.varied)
+        if not self.varied_keys:
+            raise ValueError('the calculator returns nothing that varies with the parameters')
+        self.varied_shapes = [tuple(samples.varied[key].shape[1:]) for key in self.varied_keys]
+        self.fixed = dict(samples.fixed)
+        Y = np.concatenate([np.asarray(samples.varied[key], dtype='f8').reshape(len(samples.varied[key]), -1) for key in self.varied_keys], axis=1)
+        self.engine.fit(samples.matrix(), Y, samples.attrs, params=list(self.params), **kwargs)
+        return self
+
+    def _points(self, params):
+        """(X (B, ndim) in the order of ``self.params``, a host array unless a parameter is a device tensor; B; whether every parameter is a scalar)."""
+        missing = [name for name in self.params if name not in params]
+        if missing:
+            raise ValueError('missing parameters {}'.format(missing))
+        values = [params[name] for name in self.params]
+        dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, *values)
+        torch = dv.torch()
+        sizes = {int(np.prod(np.shape(v))) for v in values if np.ndim(v) > 0}
+        if len(sizes) > 1:
+            raise ValueError('parameter arrays must share one length, got {}'.format(sorted(sizes)))
+        scalar = not sizes
+        B = 1 if scalar else sizes.pop()
+        if all(not dv.is_torch(v) for v in values):
+            X = np.empty((B, len(values)), dtype='f8')
+            for i, v in enumerate(values):
+                X[:, i] = np.ravel(v)
+        else:
+            X = torch.stack([dv.to_device(v, dev, cache=False).reshape(-1).expand(B) for v in values], dim=1)
+        return X, B, scalar
+
+    def _plan(self, keys, exact=False):
+        """What :meth:`predict`, :meth:`jacobian` and :meth:`vjp` compute for ``keys`` -- a list of output names or section prefixes, or one such string
+        (``exact``: names only, the keys of cotangents), or None for every output: ``(runs, fixed)``, ``runs = [(start, stop, entries), ...]`` the maximal
+        contiguous runs of columns of :func:`column_runs` (None: all columns as one run) with the ``(key, shape, lo, hi)`` of the varied outputs asked
+        for that each holds, ``fixed`` the fixed outputs asked for.  A name that matches no output raises ``KeyError``; one that matches fixed outputs
+        only needs no column."""
+        columns = _key_columns(self.varied_keys, self.varied_shapes)
+        if keys is None:
+            return [(0, columns[-1][3] if columns else 0, columns)], dict(self.fixed)
+        names = [keys] if isinstance(keys, str) else list(keys)
+        asked = (lambda key, names: key in names) if exact else _requested
+        unknown = [name for name in names if not any(asked(key, [name]) for key in list(self.varied_keys) + list(self.fixed))]
+        if unknown:
+            raise KeyError('no output {}'.format(unknown))
+        runs = column_runs(self.varied_keys, self.varied_shapes, [name for name in names if any(asked(key, [name]) for key in self.varied_keys)])
+        return ([(start, stop, [entry for entry in columns if start <= entry[2] and entry[3] <= stop and asked(entry[0], names)]) for start, stop in runs],
+                {key: value for key, value in self.fixed.items() if asked(key, names)})
+
+    def predict(self, params, device=False, keys=None):
+        """Outputs at ``params``, a dictionary of scalars or arrays of B values (host arrays or device tensors): the calculator's keys, varied ones of shape
+        ``(B,) + shape`` (no leading axis if every parameter is a scalar), fixed ones as they are.  Host arrays by default; ``device=True``: torch tensors,
+        views into one (B, M) buffer, and no synchronisation with the device.
+
+        ``keys``: a list of output names, or a section prefix such as 'background' (every 'background.*' key): these outputs only.  Their columns are
+        planned by :func:`column_runs`; each maximal contiguous run of them is one launch of the engine on that range (B, ncols) -- the keys of a section
+        are adjacent, so normally one -- and no other column is computed or stored.  The varied keys asked for and the fixed ones under the prefix (or
+        among the names) are returned."""
+        X, B, scalar = self._points(params)
+        runs, fixed = self._plan(keys)
+        toret = {}
+        for start, stop, entries in runs:
+            out = self.engine.predict(X, columns=None if keys is None else (start, stop))
+            toret.update(_split(out if device else dv.to_host(out), (B,), entries, start, scalar))
+        toret.update(fixed)
+        return toret
+
+    def jacobian(self, params, device=False, keys=None, return_value=False):
+        """Derivatives of the varied outputs with respect to the parameters at ``params`` (as in :meth:`predict`: scalars or arrays of B values, host or
+        device), computed analytically on the device (:meth:`MLPEmulatorEngine.jacobian`, :meth:`TaylorEmulatorEngine.jacobian`):
+        ``{key: array (B, ndim) + shape}``, the ``ndim`` axis in the order of ``Emulator.params``, without the leading ``B`` axis if every parameter is a
+        scalar.  Fixed outputs are not returned: their derivative is identically zero.  Host arrays by default; ``device=True``: torch tensors, views
+        into the (B, ndim, ncols) buffer(s), and no synchronisation with the device.
+
+        ``keys``: as in :meth:`predict` -- the columns are planned by :func:`column_runs`, one call of the engine per maximal contiguous run, and no other
+        column is computed.  ``return_value=True``: ``(values, jacobian)``, ``values`` what ``predict(params, device=device, keys=keys)`` returns."""
+        X, B, scalar = self._points(params)
+        runs, fixed = self._plan(keys)
+        values, toret = {}, {}
+        for start, stop, entries in runs:
+            out = self.engine.jacobian(X, columns=None if keys is None else (start, stop), return_value=return_value)
+            value, jac = out if return_value else (None, out)
+            toret.update(_split(jac if device else dv.to_host(jac), (B, len(self.params)), entries, start, scalar))
+            if return_value:
+                values.update(_split(value if device else dv.to_host(value), (B,), entries, start, scalar))
+        if not return_value:
+            return toret
+        values.update(fixed)
+        return values, toret
+
+    def vjp(self, params, cotangents, device=False, return_value=False):
+        """Vector-Jacobian product: the gradient with respect to the parameters of a scalar function of the outputs whose derivative with respect to
+        them is ``cotangents``, for every point of a batch -- what ``jax.vjp`` / ``jax.grad`` of the reference's ``predict`` give, and what a
+        gradient-based sampler wants of a log-likelihood.  ``params`` as in :meth:`predict`.  ``cotangents``: ``{varied key: array or tensor}``, each
+        broadcastable to ``(B,) + shape`` of that output (``shape`` alone with scalar parameters).  A fixed key is accepted and contributes nothing (its
+        derivative is zero), an unknown key raises ``KeyError``, an empty dictionary gives zeros.
+
+        Returns ``{parameter name: (B,) array}`` in the order of ``Emulator.params``, ``sum over keys and entries of cotangent * d output / d parameter``
+        (scalars if every parameter is a scalar).  Computed by reverse mode on the device (:meth:`MLPEmulatorEngine.vjp`,
+        :meth:`TaylorEmulatorEngine.vjp`) without forming the Jacobian: the columns are planned by :func:`column_runs` over the cotangents' varied keys,
+        one call of the engine per maximal contiguous run on that range only, the runs' results added in run order.  Host arrays by default;
+        ``device=True``: the views ``G[:, i]`` of one (B, ndim) tensor, and no synchronisation with the device.  ``return_value=True``:
+        ``(values, gradients)``, ``values`` what ``predict(params, device=device, keys=list(cotangents))`` returns."""
+        X, B, scalar = self._points(params)
+        torch = dv.torch()
+        runs, fixed = self._plan(list(cotangents), exact=True)
+        dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, *cotangents.values())
+        total, values = None, {}
+        for start, stop, entries in runs:
+            blocks = [torch.broadcast_to(dv.to_device(cotangents[key], dev, cache=False).to(torch.float64), (B,) + shape).reshape(B, hi - lo)
+                      for key, shape, lo, hi in entries if hi > lo]
+            out = self.engine.vjp(X, blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1), columns=(start, stop), return_value=return_value)
+            value, grad = out if return_value else (None, out)
+            total = grad if total is None else total + grad
+            if return_value:
+                values.update(_split(value if device else dv.to_host(value), (B,), entries, start, scalar))
+        if total is None:
+            total = torch.zeros((B, len(self.params)), dtype=torch.float64, device=dev)
+        if not device:
+            total = dv.to_host(total)
+        grads = {name: (total[0, i] if scalar else total[:, i]) for i, name in enumerate(self.params)}
+        if not return_value:
+            return grads
+        for key in self.varied_keys:      # empty outputs hold no column and join no run
+            if key in cotangents and key not in values:
+                values[key] = self.predict(params, device=device, keys=[key])[key]
+        values = {key: values[key] for key in self.varied_keys if key in values}      # predict's order: the calculator's, then the fixed outputs
+        values.update(fixed)
+        return values, grads
+
+    def to_calculator(self, device=False):
+        """Callable ``**params -> dict`` with the contract of ``get_calculator``'s."""
+        def calculator(**params):
+            return self.predict(params, device=device)
+
+        return calculator
+
+    def __getstate__(self):
+        return {'name': self.engine.name, 'engine': self.engine.__getstate__(), 'params': dict(self.params), 'varied_keys': list(self.varied_keys), 'varied_shapes': [tuple(s) for s in self.varied_shapes],
+                'fixed': dict(self.fixed)}
+
+    def save(self, fn):
+        """Save the state (the engine's ``name`` and state -- Taylor: ``center``, ``powers``, ``derivatives``, ``sampler_options`` -- key names, shapes, fixed
+        values) as one ``.npy`` dictionary."""
+        np.save(fn, self.__getstate__(), allow_pickle=True)
+
+    @classmethod
+    def load(cls, fn, device=None):
+        state = np.load(fn, allow_pickle=True)[()]
+        new = cls.__new__(cls)
+        new.calculator, new.samples = None, None
+        new.params = dict(state['params'])
+        name = state.get('name', 'taylor')      # a file without a name is a Taylor file
+        if name == 'mlp':
+            from .mlp import MLPEmulatorEngine
+            new.engine = MLPEmulatorEngine.from_state(state['engine'], device=device)
+        elif name == 'taylor':
+            from .taylor import TaylorEmulatorEngine
+            new.engine = TaylorEmulatorEngine.from_state(state['engine'], device=device)
+        else:
+            raise NotImplementedError('engine {} (only the Taylor and MLP engines are built)'.format(name))
+        new.varied_keys, new.varied_shapes, new.fixed = list(state['varied_keys']), [tuple(s) for s in state['varied_shapes']], dict(state['fixed'])
+        return new

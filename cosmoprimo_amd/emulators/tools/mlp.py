@@ -2,7 +2,7 @@
 Multi-layer perceptron emulator under the reference's name (cosmoprimo/emulators/tools/mlp.py ``MLPEmulatorEngine``): a network trained on quasi-random
 samples over the whole prior box, predicted for B parameter points at once.
 
-Predict is ONE launch (``cp_mlp_predict``): the affine x operation, the hidden layers in LDS, the output layer on the matrix cores, the inverse of the
+Predict is ONE launch (``cp_mlp_predict_columns``): the affine x operation, the hidden layers in LDS, the output layer on the matrix cores, the inverse of the
 y operations in its epilogue -- where the reference evaluates one point per call in Python.  Fit is written here (the reference's is jax / flax / optax,
 which this project does not depend on): the reference's procedure (mlp.py:142-147, 256-346: one stage per batch fraction, a fresh validation /
 training split per stage from one ``RandomState(seed)``, whole batches only, validation loss after each epoch, the best state kept, early stopping,
@@ -13,6 +13,8 @@ synchronisation; the one read-back is the validation loss of an epoch.
 mode through the network on the device (``cp_mlp_jacobian``).  ``vjp`` is its product with a cotangent, ``sum_c cotangent[b, c] J[b, i, c]`` (what
 ``jax.vjp`` / ``jax.grad`` give: the gradient of a scalar function of the outputs for every point of a batch), by reverse mode (``cp_mlp_vjp``): one
 forward pass, one product with the transposed output kernel, one walk back through the hidden layers; the Jacobian is never formed.
+``predict``, ``jacobian`` and ``vjp`` open with one prologue (``_enter``: fitted?, device state, upload and check of ``X``, the leading and the last
+arguments of the C entry points); the full prediction is the column range (0, M) of ``cp_mlp_predict_columns``.
 
 Operations are held as numbers, not as expressions: x a chain of affine maps ('scale', 'norm') folded into one (offset, scale) per parameter, y
 optionally 'log10' or 'arcsinh' first, then affine maps.  Not built: 'pca', 'chebyshev', ``model_yoperation``, batch normalisation, learning-rate
@@ -21,6 +23,9 @@ schedules, callable losses, optimizers other than Adam (each raises ``NotImpleme
 import ctypes
 
 import numpy as np
+
+from ... import _device as dv, _lib
+from .base import _columns, _cotangent, _empty
 
 ACTIVATIONS = ('silu', 'relu', 'tanh', 'identity-silu')
 ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-8      # optax.adam's defaults
@@ -222,7 +227,6 @@ class MLPEmulatorEngine(object):
 
     def _net(self, ndim, M):
         """The ctypes view of the network (host arrays the C ABI reads at every call), checked against the kernels' caps."""
-        from ... import _lib
         L = len(self.nhidden)
         widths = (ctypes.c_int * max(L, 1))(*self.nhidden)
         acts = (ctypes.c_int * max(L, 1))(*[_lib.MLP_ACTIVATIONS[name] for name in self.activation])
@@ -237,7 +241,6 @@ class MLPEmulatorEngine(object):
         which :class:`Emulator` hands every engine; this one reads none of them.  ``epochs``, ``learning_rate``,
         ``patience``: one value, or one per entry of ``batch_frac``.  Initial weights: :meth:`initial_parameters` -- not jax's draws, so a fit does not
         reproduce the reference's weights, only its procedure.  ``history``: per stage ``batch_size``, ``epochs`` run, ``best_loss``, ``losses``."""
-        from ... import _device as dv, _lib
         if optimizer != 'adam':
             raise NotImplementedError("optimizer {!r} is not built (only 'adam')".format(optimizer))
         if loss is not None and not (isinstance(loss, str) and loss == 'mse'):
@@ -320,7 +323,6 @@ class MLPEmulatorEngine(object):
         return self
 
     def _set_device(self, device, parameters=None):
-        from ... import _device as dv, _lib
         net = self._net(self.ndim, self.M)
         if parameters is None:
             packed = np.ascontiguousarray(self.parameters, dtype='f8')
@@ -330,15 +332,16 @@ class MLPEmulatorEngine(object):
         xoffset, xscale = (np.ascontiguousarray(np.broadcast_to(a, (self.ndim,))) for a in folded_affine(self.xoperations))
         yoffset, yscale = (np.ascontiguousarray(np.broadcast_to(a, (self.M,))) for a in folded_affine(self.yoperations))
         first = self.yoperations[0]['name']
-        self._dev = dict(device=device, net=net, parameters=parameters, yfunction=_lib.MLP_YFUNCTIONS[first if first in ('log10', 'arcsinh') else None],
+        self._dev = dict(device=device, torch=dv.torch(), net=net, parameters=parameters, yfunction=_lib.MLP_YFUNCTIONS[first if first in ('log10', 'arcsinh') else None],
                          **{name: dv.to_device(value, device, cache=False) for name, value in dict(xoffset=xoffset, xscale=xscale, yoffset=yoffset, yscale=yscale).items()})
+        # what every call of the C entry points passes after the points: the network and the operations (the tensors live as long as this dictionary)
+        d = self._dev
+        d['head'] = (net['ndim'], net['L'], net['widths'], net['acts'], net['M']) + tuple(d[name].data_ptr() for name in ('parameters', 'xoffset', 'xscale', 'yoffset', 'yscale')) \
+            + (d['yfunction'],)
 
-    def predict(self, X, columns=None):
-        """Network at the points ``X`` (B, ndim) of raw parameters, a device tensor (or host array, uploaded): device tensor (B, M) of the calculator's
-        outputs (the y operations inverted).  One launch; nothing but the result is allocated, nothing is read back and the call does not wait for the
-        device.  ``columns = (start, stop)``: those columns of it only, a (B, stop - start) tensor, bit for bit the same numbers
-        (``cp_mlp_predict_columns``: the hidden layers as ever, the output layer and the y operations on that range alone)."""
-        from ... import _device as dv, _lib
+    def _enter(self, X):
+        """The opening of :meth:`predict`, :meth:`jacobian` and :meth:`vjp`: the device state (set at the first call), ``X`` (B, ndim) on its device, B, the 13
+        leading arguments of the C entry points (the points, the network, the operations) and their last two (device, stream)."""
         if self.parameters is None:
             raise ValueError('fit the engine first')
         if self._dev is None:
@@ -349,17 +352,19 @@ class MLPEmulatorEngine(object):
         if X.ndim != 2 or int(X.shape[1]) != net['ndim']:
             raise ValueError('X must be of shape (B, {:d}), got {}'.format(net['ndim'], tuple(X.shape)))
         B = int(X.shape[0])
-        if columns is not None:
-            start, stop = (int(c) for c in columns)
-            out = dv.torch().empty((B, max(stop - start, 0)), dtype=dv.torch().float64, device=d['device'])
-            _lib.check(_lib.load().cp_mlp_predict_columns(X.data_ptr(), B, net['ndim'], net['L'], net['widths'], net['acts'], net['M'], d['parameters'].data_ptr(),
-                                                          d['xoffset'].data_ptr(), d['xscale'].data_ptr(), d['yoffset'].data_ptr(), d['yscale'].data_ptr(), d['yfunction'],
-                                                          start, stop - start, out.data_ptr(), stop - start, d['device'].index, dv.stream_of(d['device'])))
-            return out
-        out = dv.torch().empty((B, net['M']), dtype=dv.torch().float64, device=d['device'])
-        _lib.check(_lib.load().cp_mlp_predict(X.data_ptr(), B, net['ndim'], net['L'], net['widths'], net['acts'], net['M'], d['parameters'].data_ptr(),
-                                              d['xoffset'].data_ptr(), d['xscale'].data_ptr(), d['yoffset'].data_ptr(), d['yscale'].data_ptr(), d['yfunction'],
-                                              out.data_ptr(), d['device'].index, dv.stream_of(d['device'])))
+        head = (X.data_ptr(), B) + d['head']
+        return d, X, B, head, (d['device'].index, dv.stream_of(d['device']))
+
+    def predict(self, X, columns=None):
+        """Network at the points ``X`` (B, ndim) of raw parameters, a device tensor (or host array, uploaded): device tensor (B, M) of the calculator's
+        outputs (the y operations inverted).  One launch; nothing but the result is allocated, nothing is read back and the call does not wait for the
+        device.  ``columns = (start, stop)``: those columns of it only, a (B, stop - start) tensor, bit for bit the same numbers
+        (``cp_mlp_predict_columns``: the hidden layers as ever, the output layer and the y operations on that range alone; every column is the range
+        (0, M) of the same call, so a refusal names that entry point; ``cp_mlp_predict`` itself is there for C callers)."""
+        d, X, B, head, where = self._enter(X)
+        start, ncols = _columns(columns, d['net']['M'])
+        out = _empty(d, B, max(ncols, 0))
+        _lib.check(_lib.load().cp_mlp_predict_columns(*head, start, ncols, out.data_ptr(), ncols, *where))
         return out
 
     def jacobian(self, X, columns=None, return_value=False):
@@ -368,25 +373,11 @@ class MLPEmulatorEngine(object):
         contribute 1 / xscale[i], the inverse y operations yscale[c] f'(v) with f' the derivative of 10^v or sinh v).  ``columns = (start, stop)``: those
         output columns only, (B, ndim, stop - start), bit for bit the same numbers.  ``return_value=True``: ``(value, J)`` with ``value`` what
         ``predict(X, columns=columns)`` returns, bit for bit.  Nothing is read back and the call does not wait for the device."""
-        from ... import _device as dv, _lib
-        if self.parameters is None:
-            raise ValueError('fit the engine first')
-        if self._dev is None:
-            self._set_device(dv.resolve_device(self.device, X))
-        d = self._dev
-        net = d['net']
-        torch = dv.torch()
-        X = dv.to_device(X, d['device'], cache=False)
-        if X.ndim != 2 or int(X.shape[1]) != net['ndim']:
-            raise ValueError('X must be of shape (B, {:d}), got {}'.format(net['ndim'], tuple(X.shape)))
-        B = int(X.shape[0])
-        start, stop = (int(c) for c in columns) if columns is not None else (0, net['M'])
-        ncols = max(stop - start, 0)
-        value = torch.empty((B, ncols), dtype=torch.float64, device=d['device'])
-        jac = torch.empty((B, net['ndim'], ncols), dtype=torch.float64, device=d['device'])
-        _lib.check(_lib.load().cp_mlp_jacobian(X.data_ptr(), B, net['ndim'], net['L'], net['widths'], net['acts'], net['M'], d['parameters'].data_ptr(),
-                                               d['xoffset'].data_ptr(), d['xscale'].data_ptr(), d['yoffset'].data_ptr(), d['yscale'].data_ptr(), d['yfunction'],
-                                               start, stop - start, value.data_ptr(), ncols, jac.data_ptr(), ncols, d['device'].index, dv.stream_of(d['device'])))
+        d, X, B, head, where = self._enter(X)
+        start, ncols = _columns(columns, d['net']['M'])
+        width = max(ncols, 0)
+        value, jac = _empty(d, B, width), _empty(d, B, d['net']['ndim'], width)
+        _lib.check(_lib.load().cp_mlp_jacobian(*head, start, ncols, value.data_ptr(), width, jac.data_ptr(), width, *where))
         return (value, jac) if return_value else jac
 
     def vjp(self, X, cotangent, columns=None, return_value=False):
@@ -396,37 +387,19 @@ class MLPEmulatorEngine(object):
         ``columns = (start, stop)``: the sum over those output columns only, ``cotangent`` (B, stop - start).  ``return_value=True``:
         ``(predict(X, columns=columns), G)``, the value bit for bit, from the same forward pass.  Nothing is read back and the call does not wait for
         the device."""
-        from ... import _device as dv, _lib
-        if self.parameters is None:
-            raise ValueError('fit the engine first')
-        if self._dev is None:
-            self._set_device(dv.resolve_device(self.device, X))
-        d = self._dev
+        d, X, B, head, where = self._enter(X)
         net = d['net']
-        torch = dv.torch()
-        X = dv.to_device(X, d['device'], cache=False)
-        if X.ndim != 2 or int(X.shape[1]) != net['ndim']:
-            raise ValueError('X must be of shape (B, {:d}), got {}'.format(net['ndim'], tuple(X.shape)))
-        B = int(X.shape[0])
-        start, stop = (int(c) for c in columns) if columns is not None else (0, net['M'])
-        ncols = max(stop - start, 0)
-        cotangent = dv.to_device(cotangent, d['device'], cache=False)
-        if tuple(cotangent.shape) != (B, ncols):
-            raise ValueError('cotangent must be of shape ({:d}, {:d}), got {}'.format(B, ncols, tuple(cotangent.shape)))
-        if cotangent.dtype != torch.float64 or (ncols > 1 and cotangent.stride(1) != 1) or (B > 1 and cotangent.stride(0) < ncols):
-            cotangent = cotangent.to(torch.float64).contiguous()
-        ldc = int(cotangent.stride(0)) if B > 1 else ncols
+        start, ncols = _columns(columns, net['M'])
+        width = max(ncols, 0)
+        cotangent, ldc = _cotangent(cotangent, B, width, d['device'])
         lib = _lib.load()
-        need = int(lib.cp_mlp_vjp_workspace_doubles(B, net['ndim'], net['L'], net['widths'], net['M'], ncols))
+        need = int(lib.cp_mlp_vjp_workspace_doubles(B, net['ndim'], net['L'], net['widths'], net['M'], width))
         if need < 0:
             _lib.check(-need)
-        work = torch.empty((need,), dtype=torch.float64, device=d['device'])
-        value = torch.empty((B, ncols), dtype=torch.float64, device=d['device']) if return_value else None
-        grad = torch.empty((B, net['ndim']), dtype=torch.float64, device=d['device'])
-        _lib.check(lib.cp_mlp_vjp(X.data_ptr(), B, net['ndim'], net['L'], net['widths'], net['acts'], net['M'], d['parameters'].data_ptr(), d['xoffset'].data_ptr(),
-                                  d['xscale'].data_ptr(), d['yoffset'].data_ptr(), d['yscale'].data_ptr(), d['yfunction'], start, stop - start, cotangent.data_ptr(), ldc,
-                                  value.data_ptr() if return_value else None, ncols, grad.data_ptr(), work.data_ptr(), need, d['device'].index,
-                                  dv.stream_of(d['device'])))
+        work, grad = _empty(d, need), _empty(d, B, net['ndim'])
+        value = _empty(d, B, width) if return_value else None
+        _lib.check(lib.cp_mlp_vjp(*head, start, ncols, cotangent.data_ptr(), ldc, value.data_ptr() if return_value else None, width, grad.data_ptr(), work.data_ptr(), need,
+                                  *where))
         return (value, grad) if return_value else grad
 
     def __getstate__(self):

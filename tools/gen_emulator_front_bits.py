@@ -1,0 +1,46 @@
+"""Write tests/golden/emulator_front_bits.npz: the outputs of the calls of tests/test_emulator_front_bits_gpu.py, as the built library and engines give them.
+
+    python tools/gen_emulator_front_bits.py [--out tests/golden/emulator_front_bits.npz]
+
+Run on an MI355X against the build whose results are to be pinned.  The test module holds the calls (its ``mlp_entries``, ``taylor_entries``,
+``emulator_entries``) and regenerates the inputs from seeded numpy, so the file holds outputs only: per test one flat array and the names and shapes of
+its entries.  Every call is run twice; an entry whose two runs differ is not recorded: the run stops and nothing is written."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
+
+
+def toy_emulators():
+    """The two emulators of the ``emulators`` fixture of tests/test_emulator_jacobian_gpu.py, built by that fixture's own function."""
+    from test_emulator_jacobian_gpu import emulators
+    # (``__wrapped__`` of a fixture is the plain function in pytest 7 to 9 but no public contract: if an upgrade removes it, build the two emulators here)
+    return emulators.__wrapped__(lambda name: dict(np.load(os.path.join(ROOT, 'tests', 'golden', name + '.npz'))))
+
+
+def main():
+    parser = argparse.ArgumentParser()
+    parser.add_argument('--out', default=os.path.join(ROOT, 'tests', 'golden', 'emulator_front_bits.npz'))
+    args = parser.parse_args()
+    import test_emulator_front_bits_gpu as t
+    emulators = toy_emulators()
+    calls = [('mlp%d' % H, lambda H=H, y=y: t.mlp_entries(H, y)) for H, y in t.MLP_CASES] + [('taylor', t.taylor_entries)]
+    calls += [('emulator_%s' % which, lambda which=which: t.emulator_entries(emulators[which])) for which in ('taylor', 'mlp')]
+    recorded, count = {}, 0
+    for group, fn in calls:
+        first, second = fn(), fn()
+        for name, value in first.items():
+            if not (np.array_equal(value, second[name]) and np.isfinite(value).all()):
+                sys.exit('%s.%s: two runs differ (or the result is not finite); nothing written' % (group, name))
+        recorded[group + '.entries'], recorded[group] = t.flatten(first)
+        count += len(first)
+    np.savez_compressed(args.out, **recorded)
+    print('%d entries, %d bytes of arrays, written to %s (%d bytes)' % (count, sum(v.nbytes for v in recorded.values()), args.out, os.path.getsize(args.out)))
+
+
+if __name__ == '__main__':
+    main()
