@@ -195,16 +195,52 @@ def pack_params(names, params, defaults, device):
     return carr, ncosmo, keep
 
 
-def ncdm_arg(bg, ncosmo):
-    """The ``const cp_ncdm*`` argument for a background parameter block: ``bg['ncdm']`` (a :class:`cosmoprimo_amd.background.NcdmTables`, what
-    :meth:`BaseEngine.bg_params` adds for cosmologies with massive neutrinos) as (ctypes reference or None, the struct to keep alive)."""
-    ncdm = bg.get('ncdm', None) if bg else None
+def ncdm_arg(ncdm, ncosmo):
+    """The ``const cp_ncdm*`` argument for the massive-neutrino tables ``ncdm`` (a :class:`cosmoprimo_amd.background.NcdmTables`, what
+    :meth:`BaseEngine.bg_params` adds as ``bg['ncdm']`` for cosmologies with massive neutrinos, or None) as (ctypes reference or None, the struct to
+    keep alive)."""
     if ncdm is None or not ncdm.nspecies:
         return None, None
     if ncdm.ncosmo != ncosmo:
         raise ValueError('massive-neutrino tables hold {:d} cosmologies, the parameters {:d}'.format(ncdm.ncosmo, ncosmo))
     cn = ncdm.struct()
     return ctypes.byref(cn), cn
+
+
+_defaults = []      # background.DEFAULTS, power.PK_DEFAULTS: both modules import this one
+
+
+def pack_cosmologies(bg, pk, device, ncosmo=None, second_is_omega_m=False, strict=False):
+    """The cosmologies of a call of an analytic engine's entry point: background parameters ``bg``, primordial parameters ``pk`` (None: an entry
+    without them) and the massive-neutrino tables ``bg['ncdm']`` (or None), each parameter a float or an array of shape (n,).
+
+    Returns (args, n, keep).  ``n`` is the size of the batch: the one length of the arrays, which must be ``ncosmo`` where that is given; None where the
+    parameters are not such a batch (no arrays, or arrays of other lengths) -- ``args`` is then None too, unless ``strict``: one cosmology of floats is
+    a call of n = 1 then (``n`` stays None to tell), and arrays of two lengths raise ValueError.  ``args()`` is the run of C arguments
+    ``ncosmo, bg_params, second_is_omega_m, ncdm, pk_params`` (without the last for ``pk`` None); it is where the tables are held to the batch size
+    (ValueError), so a caller makes it where it makes the call, behind its own refusals.  ``keep`` is what the run points to."""
+    if not _defaults:
+        from .background import DEFAULTS
+        from .power import PK_DEFAULTS
+        _defaults.extend([DEFAULTS, PK_DEFAULTS])
+    cbg, n1, keep = pack_params(_lib.BG_PARAMS, bg, _defaults[0], device)
+    cpk, n2, keep_pk = pack_params(_lib.PK_PARAMS, pk, _defaults[1], device) if pk is not None else (None, None, [])
+    if strict and n1 is not None and n2 is not None and n1 != n2:
+        raise ValueError('parameter arrays must share one length, got {} and {}'.format(n1, n2))
+    sizes = {size for size in (n1, n2) if size is not None}
+    if ncosmo is not None:
+        n = ncosmo if not sizes - {ncosmo} else None
+    else:
+        n = next(iter(sizes)) if len(sizes) == 1 else None
+    if n is None and not strict:
+        return None, None, []
+    ncosmo = (n or 1) if strict else n      # (strict: what its callers have always passed, for arrays of length 0 too)
+    tail = (as_void_p(cpk),) if pk is not None else ()
+
+    def args():
+        nu, cn = ncdm_arg(bg.get('ncdm', None), ncosmo)      # (the reference ``nu`` holds the struct)
+        return (ncosmo, as_void_p(cbg), int(bool(second_is_omega_m)), nu) + tail
+    return args, n, [cbg, cpk, keep, keep_pk]
 
 
 def as_void_p(carr):

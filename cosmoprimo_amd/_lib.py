@@ -60,18 +60,10 @@ SIGNATURES = {
     'cp_background_eval': (ctypes.c_int, [ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     'cp_power_workspace_bytes': (ctypes.c_longlong, [ctypes.c_longlong]),
-    'cp_power_eval': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
-    'cp_power_eval_variants': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     'cp_rfft_plan_create': (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int]),
     'cp_rfft_plan_destroy': (ctypes.c_int, [ctypes.c_void_p]),
     'cp_rfft_forward': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]),
     'cp_rfft_backward': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]),
-    'cp_eh_scalars': (ctypes.c_int, [ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-        ctypes.c_void_p]),
-    'cp_variants_scalars': (ctypes.c_int, [ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     'cp_sigma_rz_workspace_bytes': (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int]),
     'cp_sigma_rz_fused_available': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     'cp_geospline_plan_create': (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int]),
@@ -83,15 +75,6 @@ SIGNATURES = {
     'cp_fftlog_geospline_execute': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
                                                   ctypes.c_int, ctypes.c_void_p]),
     'cp_fftlog_spline_execute': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]),
-    'cp_sigma_rz_analytic': (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
-    'cp_sigma_rz_analytic_prefiltered': (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
-    'cp_sigma_rz_functional': (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     'cp_spline_plan_create': (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     'cp_linop_plan_create': (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_int]),
@@ -161,16 +144,8 @@ SIGNATURES = {
                                       ctypes.c_void_p]),
     'cp_dst_plan_destroy': (ctypes.c_int, [ctypes.c_void_p]),
     'cp_dst_forward_analytic_workspace_bytes': (ctypes.c_longlong, [ctypes.c_longlong]),
-    'cp_wallish_full': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'cp_wallish_tail': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    'cp_dst_forward_analytic_box': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-        ctypes.c_int, ctypes.c_void_p]),
-    'cp_dst_forward_analytic': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     'cp_spline_operator': (ctypes.c_int, [ctypes.c_int, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p,
                                          _c_int_p]),
 }
@@ -190,9 +165,6 @@ SIGNATURES['cp_ncdm_tables'] = (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int, 
                                                _c_double_p, _c_double_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_kirkby2013_rows'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                   ctypes.c_void_p, ctypes.c_longlong, _c_double_p, _c_double_p, ctypes.c_int, ctypes.c_void_p])
-SIGNATURES['cp_sigma8_normalise'] = (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-        ctypes.c_void_p, ctypes.c_void_p, cp_param, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_spline_tables_build'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                       ctypes.c_int, ctypes.c_void_p])
 for _name in ('cp_spline_tables_apply', 'cp_spline_tables_apply_f32'):
@@ -204,6 +176,26 @@ _MLP_HEAD = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_
 _RANGE = [ctypes.c_longlong, ctypes.c_longlong]            # col0, ncols
 _ARRAY = [ctypes.c_void_p, ctypes.c_longlong]              # a device array and its row stride
 _WHERE = [ctypes.c_int, ctypes.c_void_p]                   # device, stream
+# the run that the entry points taking a batch of cosmologies share (_device.pack_cosmologies makes it): ncosmo, bg_params, second_is_omega_m, ncdm -- and pk_params
+_BG_BATCH = [ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+_BATCH = _BG_BATCH + [ctypes.c_void_p]
+_ENGINE_BATCH = [ctypes.c_int] + _BATCH                    # engine in front
+_MARGINS = [ctypes.c_int] * 4                              # margin_first, margin_second, offset_first, offset_second
+SIGNATURES['cp_power_eval'] = (ctypes.c_int, [ctypes.c_int] + _ENGINE_BATCH + [ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong] +
+                               [ctypes.c_void_p] * 3 + _WHERE)      # engine, what; nk, d_k, d_kscale, nz, d_z, d_out, d_work
+SIGNATURES['cp_power_eval_variants'] = (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + _BATCH + [ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                                                                               ctypes.c_void_p] + _WHERE)      # what, of; nk, d_k, nz, d_z, d_out
+SIGNATURES['cp_eh_scalars'] = SIGNATURES['cp_variants_scalars'] = (ctypes.c_int, _BG_BATCH + [ctypes.c_void_p] + _WHERE)
+_SIGMA_HEAD = _ENGINE_BATCH + [ctypes.c_int, ctypes.c_void_p]      # ... nk, d_k
+_SIGMA_TAIL = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3      # d_growth_sq, nz, d_out, d_pk_out, d_work
+SIGNATURES['cp_sigma_rz_analytic'] = (ctypes.c_int, _SIGMA_HEAD + [ctypes.c_void_p, ctypes.c_void_p] + _SIGMA_TAIL + [ctypes.c_int] + _WHERE)      # fftlog, spline; nblocks
+SIGNATURES['cp_sigma_rz_analytic_prefiltered'] = (ctypes.c_int, _SIGMA_HEAD + [ctypes.c_void_p] + _SIGMA_TAIL + _WHERE)      # spline
+SIGNATURES['cp_sigma_rz_functional'] = (ctypes.c_int, _SIGMA_HEAD + [ctypes.c_void_p, ctypes.c_int] + _SIGMA_TAIL + _WHERE)      # d_functional, nq
+SIGNATURES['cp_sigma8_normalise'] = (ctypes.c_int, _SIGMA_HEAD + [ctypes.c_void_p, cp_param] + [ctypes.c_void_p] * 4 + _WHERE)      # d_functional, sigma8; d_rsigma8, d_amplitude, d_pk_out, d_work
+SIGNATURES['cp_dst_forward_analytic'] = (ctypes.c_int, [ctypes.c_void_p] + _ENGINE_BATCH + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])      # plan; d_out, d_work, flags, stream
+SIGNATURES['cp_dst_forward_analytic_box'] = (ctypes.c_int, [ctypes.c_void_p] + _ENGINE_BATCH + [ctypes.c_void_p] * 3 + _MARGINS + [ctypes.c_void_p])      # plan; d_out, d_work, d_box
+SIGNATURES['cp_wallish_full'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + _ENGINE_BATCH + [ctypes.c_void_p, ctypes.c_int] + _MARGINS +
+                                 [ctypes.c_void_p] * 6)      # plans; d_pk, npk; d_tophat, d_box, d_coef, d_out, d_work, stream
 SIGNATURES['cp_taylor_predict'] = (ctypes.c_int, _TAYLOR_HEAD + [ctypes.c_void_p] + _WHERE)
 SIGNATURES['cp_taylor_predict_columns'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + _WHERE)
 SIGNATURES['cp_taylor_jacobian'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + _WHERE)

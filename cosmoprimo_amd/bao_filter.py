@@ -294,26 +294,20 @@ class Wallish2018PowerSpectrumBAOFilter(BasePowerSpectrumBAOFilter):
         """The whole filter of a batch of analytic cosmologies as one kernel (``cp_wallish_full``: the spectra evaluated into the forward transform, the
         coefficients taken through the rest on the CU); False where the plans or the parameters are not the ones the kernel is written for."""
         torch = dv.torch()
-        from .background import DEFAULTS as bg_defaults
-        from .power import PK_DEFAULTS
         ops = self._operators()
         if dst.n != 4096 or engine not in _lib.ENGINES or not isinstance(ops['splice'], SplicedClampedSpline):
             return False
         rows = self._pk_rows.contiguous()
-        cbg, n1, keep1 = dv.pack_params(_lib.BG_PARAMS, bg, bg_defaults, self.device)
-        cpk, n2, keep2 = dv.pack_params(_lib.PK_PARAMS, pk, PK_DEFAULTS, self.device)
-        sizes = {n for n in (n1, n2) if n is not None}
-        if len(sizes) != 1 or sizes.pop() != rows.shape[0]:
+        args, ncosmo, keep = dv.pack_cosmologies(bg, pk, self.device)
+        if ncosmo != rows.shape[0]:
             return False
-        ncosmo = rows.shape[0]
         lib = _lib.load()
         mf, ms, off = self._margin_first, self._margin_second, self._offset
         box = torch.empty((2 * ncosmo, 2), dtype=torch.int32, device=self.device)
         out = torch.empty_like(rows)
         work = torch.empty(int(lib.cp_dst_forward_analytic_workspace_bytes(ncosmo)), dtype=torch.uint8, device=self.device)
-        nu, keep_nu = dv.ncdm_arg(bg, ncosmo)
-        status = lib.cp_wallish_full(dst._handle, ops['splice']._handle, _lib.ENGINES[engine], ncosmo, dv.as_void_p(cbg), 0, nu, dv.as_void_p(cpk), rows.data_ptr(), rows.shape[1],
-                                     mf, ms, off[0], off[1], ops['tophat'].data_ptr(), box.data_ptr(), None, out.data_ptr(), work.data_ptr(), dv.stream_of(self.device))
+        status = lib.cp_wallish_full(dst._handle, ops['splice']._handle, _lib.ENGINES[engine], *args(), rows.data_ptr(), rows.shape[1], mf, ms, off[0], off[1],
+                                     ops['tophat'].data_ptr(), box.data_ptr(), None, out.data_ptr(), work.data_ptr(), dv.stream_of(self.device))
         if status == _lib.CP_EUNSUPPORTED:
             return False
         _lib.check(status)

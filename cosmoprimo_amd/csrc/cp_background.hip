@@ -710,8 +710,9 @@ extern "C" int cp_growth_ode_tables(long long ncosmo, const cp_param* params, in
     if (ncosmo == 0) return CP_OK;
     if (!params || !d_tab) return cp::fail(CP_EINVAL, "cp_growth_ode_tables: null pointer");
     if (mass != 0 && mass != 1) return cp::fail(CP_EINVAL, "cp_growth_ode_tables: mass must be 0 ('m') or 1 ('cb')");
-    const int nsp = ncdm ? ncdm->nspecies : 0;
-    if (nsp < 0 || (nsp > 0 && !ncdm->tab)) return cp::fail(CP_EINVAL, "cp_growth_ode_tables: bad massive-neutrino tables");
+    int nsp;
+    int st = cpcosmo::ncdm_species(ncdm, "cp_growth_ode_tables", &nsp);
+    if (st != CP_OK) return st;
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_growth_ode_tables: cannot select device %d", device);
     GrowthArgs A;
@@ -721,9 +722,9 @@ extern "C" int cp_growth_ode_tables(long long ncosmo, const cp_param* params, in
     A.mass = mass;
     A.nsp = nsp;
     A.ncdm_tab = nsp ? ncdm->tab : nullptr;
-    A.ncdm_knots = nsp ? device_ncdm_knots(device) : nullptr;
+    st = cpcosmo::ncdm_knots(nsp, device, "cp_growth_ode_tables", &A.ncdm_knots);
+    if (st != CP_OK) return st;
     A.tab = d_tab;
-    if (nsp && !A.ncdm_knots) return cp::fail(CP_ENOMEM, "cp_growth_ode_tables: cannot allocate the massive-neutrino knots on device %d", device);
     hipLaunchKernelGGL(growth_ode_kernel, dim3((unsigned)((ncosmo + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), A);
     return cp::launch_status("cp_growth_ode_tables");
 }
@@ -817,8 +818,9 @@ extern "C" int cp_background_distance(long long ncosmo, long long nz, const cp_p
 extern "C" int cp_background_eval(long long ncosmo, long long nz, const cp_param* params, int second_is_omega_m, const cp_ncdm* ncdm,
                                   const double* d_z, int z_shared, double* d_out, int kind, int device, void* stream) {
     if (ncosmo < 0 || nz < 0) return cp::fail(CP_EINVAL, "cp_background_distance: negative size");
-    const int nsp = ncdm ? ncdm->nspecies : 0;
-    if (nsp < 0 || (nsp > 0 && !ncdm->tab)) return cp::fail(CP_EINVAL, "cp_background_eval: bad massive-neutrino tables");
+    int nsp;
+    int st = cpcosmo::ncdm_species(ncdm, "cp_background_eval", &nsp);
+    if (st != CP_OK) return st;
     if (nsp > 0 && (ncdm->species < -1 || ncdm->species >= nsp)) return cp::fail(CP_EINVAL, "cp_background_eval: species %d of %d", ncdm->species, nsp);
     if (ncosmo == 0 || nz == 0) return CP_OK;
     if (!params || !d_z || !d_out) return cp::fail(CP_EINVAL, "cp_background_distance: null pointer");
@@ -845,8 +847,8 @@ extern "C" int cp_background_eval(long long ncosmo, long long nz, const cp_param
     A.nsp = nsp;
     A.species = nsp ? ncdm->species : -1;
     A.ncdm_tab = nsp ? ncdm->tab : nullptr;
-    A.ncdm_knots = nsp ? device_ncdm_knots(device) : nullptr;
-    if (nsp && !A.ncdm_knots) return cp::fail(CP_ENOMEM, "cp_background_eval: cannot allocate the massive-neutrino knots on device %d", device);
+    st = cpcosmo::ncdm_knots(nsp, device, "cp_background_eval", &A.ncdm_knots);
+    if (st != CP_OK) return st;
     const long long nsamp = ncosmo * nz;
     const int block = 256;
     const long long grid = (nsamp + block - 1) / block;

@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "../../include/cosmoprimo_amd.h"
 #include "cp_math.h"
 #include "cp_error.h"
@@ -225,23 +228,66 @@ __device__ __forceinline__ double growth_cpt(const Cosmo& c, double z) {
 // device copy of the CP_NCDM_NKNOTS massive-neutrino knots (cp_background.hip), nullptr on failure
 const double* ncdm_knots_device(int device);
 
-// the massive-neutrino tables of a call as the kernels take them (load_cosmo): nothing for ncdm == NULL or nspecies == 0.  Called with the
-// call's device current (the knots are allocated on it the first time).
-struct NcdmView {
-    const double* tab = nullptr;
-    const double* knots = nullptr;
-    int nsp = 0;
-};
-inline int ncdm_view(const cp_ncdm* ncdm, int device, const char* who, NcdmView* v) {
-    *v = NcdmView{};
-    const int nsp = ncdm ? ncdm->nspecies : 0;
-    if (nsp < 0 || (nsp > 0 && !ncdm->tab)) return cp::fail(CP_EINVAL, "%s: bad massive-neutrino tables", who);
-    if (!nsp) return CP_OK;
-    v->knots = ncdm_knots_device(device);
-    if (!v->knots) return cp::fail(CP_ENOMEM, "%s: cannot allocate the massive-neutrino knots on device %d", who, device);
-    v->tab = ncdm->tab;
-    v->nsp = nsp;
-    return CP_OK;
+// ---- the host side that the entry points taking a batch of cosmologies share -------------------------------------------------------------------------
+// An entry point of that family runs its checks in this order -- sizes and codes, the engine (engine_known), the empty batch, null pointers, the
+// massive-neutrino argument (ncdm_species): all without a device --, then opens ONE cp::DeviceScope, fetches the neutrino knots if its kernel reads them
+// (ncdm_knots), fills the cosmology block of its kernel's arguments (fill_cosmology), launches -- the coefficients first (cp_power_coefficients,
+// cp_internal.h) where its kernel reads them -- and returns ONE cp::launch_status under its public name.
+
+inline bool engine_known(int engine) { return engine >= CP_ENGINE_EH && engine <= CP_ENGINE_BBKS; }
+
+inline int unknown_engine(const char* who, int engine) { return cp::fail(CP_EINVAL, "%s: unknown engine %d", who, engine); }
+
+// f(std::integral_constant<int, engine>) for a known engine: the kernels take the engine as a template argument
+template <class F>
+inline void dispatch_engine(int engine, F&& f) {
+    if (engine == CP_ENGINE_EH) f(std::integral_constant<int, CP_ENGINE_EH>{});
+    else if (engine == CP_ENGINE_EH_NOWIGGLE) f(std::integral_constant<int, CP_ENGINE_EH_NOWIGGLE>{});
+    else f(std::integral_constant<int, CP_ENGINE_BBKS>{});
+}
+
+// the massive-neutrino argument of a call, looked at on the host: the number of species into *nsp (0 for ncdm == NULL)
+inline int ncdm_species(const cp_ncdm* ncdm, const char* who, int* nsp) {
+    *nsp = ncdm ? ncdm->nspecies : 0;
+    return *nsp < 0 || (*nsp > 0 && !ncdm->tab) ? cp::fail(CP_EINVAL, "%s: bad massive-neutrino tables", who) : CP_OK;
+}
+
+// ... and the device copy of the knots, for the entries whose kernels interpolate in the tables (null without species).  Called with the call's device
+// current (the knots are allocated on it the first time).
+inline int ncdm_knots(int nsp, int device, const char* who, const double** knots) {
+    *knots = nsp ? ncdm_knots_device(device) : nullptr;
+    return nsp && !*knots ? cp::fail(CP_ENOMEM, "%s: cannot allocate the massive-neutrino knots on device %d", who, device) : CP_OK;
+}
+
+template <class A, class = void>
+struct has_pw : std::false_type {};
+template <class A>
+struct has_pw<A, std::void_t<decltype(std::declval<A&>().pw)>> : std::true_type {};
+template <class A, class = void>
+struct has_ncdm_knots : std::false_type {};
+template <class A>
+struct has_ncdm_knots<A, std::void_t<decltype(std::declval<A&>().ncdm_knots)>> : std::true_type {};
+template <class A, class = void>
+struct has_consts : std::false_type {};
+template <class A>
+struct has_consts<A, std::void_t<decltype(std::declval<A&>().consts)>> : std::true_type {};
+
+// The cosmology block of a kernel's arguments: ncosmo, bg, pw, second_is_omega_m, ncdm_tab, ncdm_knots, nsp, consts -- those of them the struct has (the
+// structs share the names, not a sub-struct: the kernels are tuned to their layouts).  nsp from ncdm_species, knots from ncdm_knots (null for a struct
+// without them), consts the workspace cp_power_coefficients fills (null for a struct without them).
+template <class A>
+inline void fill_cosmology(A& a, long long ncosmo, const cp_param* bg_params, const cp_param* pk_params, int second_is_omega_m, const cp_ncdm* ncdm, int nsp,
+                           const double* knots = nullptr, const void* consts = nullptr) {
+    a.ncosmo = ncosmo;
+    copy_params(a.bg, bg_params, CP_BG_NPARAMS);
+    if constexpr (has_pw<A>::value) {
+        if (pk_params) copy_params(a.pw, pk_params, CP_PK_NPARAMS);
+    }
+    a.second_is_omega_m = second_is_omega_m;
+    a.ncdm_tab = nsp ? ncdm->tab : nullptr;
+    a.nsp = nsp;
+    if constexpr (has_ncdm_knots<A>::value) a.ncdm_knots = knots;
+    if constexpr (has_consts<A>::value) a.consts = static_cast<decltype(a.consts)>(consts);
 }
 
 }  // namespace cpcosmo

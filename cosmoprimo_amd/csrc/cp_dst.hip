@@ -721,11 +721,83 @@ void launch_generate(const GenArgs& G, int grid, hipStream_t stream) {
 
 }  // namespace
 
-extern "C" long long cp_dst_forward_analytic_workspace_bytes(long long ncosmo) { return ncosmo < 0 ? -1 : cp_power_workspace_bytes(ncosmo) + 64; }
+extern "C" long long cp_dst_forward_analytic_workspace_bytes(long long ncosmo) { return ncosmo < 0 ? -1 : cp::coef_workspace_bytes(ncosmo, 0); }
 
-static int dst_forward_analytic(const cp_dst_plan* p, int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm,
-                                const cp_param* pk_params, double* d_out, void* d_work, int flags, int* d_box, int margin_first, int margin_second, int offset_first, int offset_second,
-                                void* stream);
+namespace {
+
+constexpr int WALLISH_LDS = (4096 + Plan<4096, 16>::TW_TOTAL - 4096) * (int)sizeof(cplx) + 2 * cpdd::DD_NTAB * (int)sizeof(double);
+
+bool bad_margins(int margin_first, int margin_second) { return margin_first < 0 || 2 * margin_first >= 2048 || margin_second < 0 || margin_second >= 2048; }
+
+// two workgroups per CU are resident (LDS): every workgroup the same number of pairs
+int wallish_grid(long long nrows, int device) { return cp::balanced_grid((nrows + 1) / 2, 2LL * cp::cu_count(device)); }
+
+// The forward side of wallish2018 for a batch of analytic cosmologies (dst_generate_kernel, wallish_full_kernel): the transform's tables, the cosmology
+// block, the plan's wavenumbers.  d_out null: the coefficients stay on the CU.
+void fill_generate(GenArgs& G, const cp_dst_plan* p, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, int nsp,
+                   const cp_param* pk_params, double* d_out, bool split, const void* consts) {
+    G.dst.in = nullptr; G.dst.out = d_out; G.dst.nrows = ncosmo; G.dst.tw = p->d_tw; G.dst.rot = p->d_rot; G.dst.kx = nullptr; G.dst.ikx = nullptr; G.dst.fused = 0;
+    G.dst.split = split;
+    cpcosmo::fill_cosmology(G, ncosmo, bg_params, pk_params, second_is_omega_m, ncdm, nsp, nullptr, consts);
+    G.k = p->d_kx;
+    G.ln_k = p->d_ln_kx;
+}
+
+// What cp_wallish_tail and cp_wallish_full ask of their plans (the splice plan's tables into *U); npk: the columns of P
+int wallish_plans(const char* who, const cp_dst_plan* p, const cp_splice_plan* splice, int npk, cpsu::Tables* U) {
+    if (p->n != 4096 || !p->d_kx || !p->d_ln_kx)
+        return cp::fail(CP_EUNSUPPORTED, "%s: needs a transform plan of length 4096 made with its abscissa (wallish2018's linear grid)", who);
+    int device = -1;
+    if (!cp_splice_plan_uniform_view(splice, U, &device) || device != p->device)
+        return cp::fail(CP_EUNSUPPORTED, "%s: the splice plan does not run the uniform-stretch scheme on the transform's device", who);
+    // the stretch comes from the transformed rows, everything else from the rows of P; the stretch, the slot in front of it and the 64 S knots the
+    // lanes own lie inside a row of the transform; one query per column of P
+    if (U->src_u != 1 || (U->wl > 0 && U->src_l != 0) || (U->wr > 0 && U->src_r != 0) || U->col_u < 1 || U->col_u + 64 * U->S + 1 > 4096 || U->nq != npk ||
+        U->ngb > cpsu::NGB || U->S != 49 || U->col_l + U->wl > npk || U->col_r + U->wr > npk)
+        return cp::fail(CP_EUNSUPPORTED, "%s: the splice plan is not the filter's (stretch of %d knots at column %d of array %d, %d queries)", who, U->nm, U->col_u,
+                        U->src_u, U->nq);
+    return CP_OK;
+}
+
+// everything of wallish2018 behind its forward transform (wallish_tail_kernel, the tail of wallish_full_kernel)
+void fill_tail(TailArgs& G, const cp_dst_plan* p, const cpsu::Tables& U, long long nrows, double* d_coef, const double* d_pk, int margin_first, int margin_second,
+               int offset_first, int offset_second, const double* d_tophat, int* d_box, double* d_out) {
+    G.nrows = nrows; G.coef = d_coef; G.tw = p->d_tw; G.rot = p->d_rot; G.ikx = p->d_ln_kx + 3 * (size_t)p->n;
+    G.U = U;
+    G.pk = d_pk; G.tophat = d_tophat; G.out = d_out; G.box = d_box;
+    G.margin_first = margin_first; G.margin_second = margin_second; G.off0 = offset_first; G.off1 = offset_second;
+}
+
+int dst_forward_analytic(const cp_dst_plan* p, int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm,
+                         const cp_param* pk_params, double* d_out, void* d_work, int flags, int* d_box, int margin_first, int margin_second, int offset_first,
+                         int offset_second, void* stream) {
+    const char* who = "cp_dst_forward_analytic";
+    if (!p) return cp::fail(CP_EINVAL, "cp_dst_forward_analytic: null plan");
+    if (flags & ~CP_DST_SPLIT) return cp::fail(CP_EINVAL, "cp_dst_forward_analytic: unknown flags %d", flags);
+    if (p->n != 4096 || !p->d_kx) return cp::fail(CP_EUNSUPPORTED, "cp_dst_forward_analytic: needs a plan of length 4096 made with its abscissa (wallish2018's linear grid)");
+    if (!cpcosmo::engine_known(engine)) return cpcosmo::unknown_engine(who, engine);
+    if (ncosmo < 0) return cp::fail(CP_EINVAL, "cp_dst_forward_analytic: negative batch");
+    if (ncosmo == 0) return CP_OK;
+    if (!bg_params || !pk_params || !d_out || !d_work) return cp::fail(CP_EINVAL, "cp_dst_forward_analytic: null pointer");
+    int nsp;
+    int st = cpcosmo::ncdm_species(ncdm, who, &nsp);
+    if (st != CP_OK) return st;
+    cp::DeviceScope scope(p->device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_dst_forward_analytic: cannot select device %d", p->device);
+    const double* knots;
+    st = cpcosmo::ncdm_knots(nsp, p->device, who, &knots);
+    if (st != CP_OK) return st;
+    char* coef = cp::coef_workspace(d_work, ncosmo).coef;
+    cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, knots, pk_params, coef, stream);
+    GenArgs G{};
+    fill_generate(G, p, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, pk_params, d_out, (flags & CP_DST_SPLIT) != 0, coef);
+    G.box = d_box; G.margin_first = margin_first; G.margin_second = margin_second; G.off0 = offset_first; G.off1 = offset_second;
+    const int grid = wallish_grid(ncosmo, p->device);
+    cpcosmo::dispatch_engine(engine, [&](auto e) { launch_generate<decltype(e)::value>(G, grid, static_cast<hipStream_t>(stream)); });
+    return cp::launch_status(who);
+}
+
+}  // namespace
 
 extern "C" int cp_dst_forward_analytic(const cp_dst_plan* p, int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m,
                                        const cp_ncdm* ncdm, const cp_param* pk_params, double* d_out, void* d_work, int flags, void* stream) {
@@ -736,95 +808,30 @@ extern "C" int cp_dst_forward_analytic_box(const cp_dst_plan* p, int engine, lon
                                            const cp_ncdm* ncdm, const cp_param* pk_params, double* d_out, void* d_work, int* d_box, int margin_first, int margin_second,
                                            int offset_first, int offset_second, void* stream) {
     if (!d_box) return cp::fail(CP_EINVAL, "cp_dst_forward_analytic_box: null box pointer");
-    if (margin_first < 0 || 2 * margin_first >= 2048 || margin_second < 0 || margin_second >= 2048)
-        return cp::fail(CP_EINVAL, "cp_dst_forward_analytic_box: bad margins");
+    if (bad_margins(margin_first, margin_second)) return cp::fail(CP_EINVAL, "cp_dst_forward_analytic_box: bad margins");
     return dst_forward_analytic(p, engine, ncosmo, bg_params, second_is_omega_m, ncdm, pk_params, d_out, d_work, CP_DST_SPLIT, d_box, margin_first, margin_second,
                                 offset_first, offset_second, stream);
 }
-
-static int dst_forward_analytic(const cp_dst_plan* p, int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm,
-                                const cp_param* pk_params, double* d_out, void* d_work, int flags, int* d_box, int margin_first, int margin_second, int offset_first, int offset_second,
-                                void* stream) {
-    if (!p) return cp::fail(CP_EINVAL, "cp_dst_forward_analytic: null plan");
-    if (flags & ~CP_DST_SPLIT) return cp::fail(CP_EINVAL, "cp_dst_forward_analytic: unknown flags %d", flags);
-    if (p->n != 4096 || !p->d_kx) return cp::fail(CP_EUNSUPPORTED, "cp_dst_forward_analytic: needs a plan of length 4096 made with its abscissa (wallish2018's linear grid)");
-    if (engine != CP_ENGINE_EH && engine != CP_ENGINE_EH_NOWIGGLE && engine != CP_ENGINE_BBKS) return cp::fail(CP_EINVAL, "cp_dst_forward_analytic: unknown engine %d", engine);
-    if (ncosmo < 0) return cp::fail(CP_EINVAL, "cp_dst_forward_analytic: negative batch");
-    if (ncosmo == 0) return CP_OK;
-    if (!bg_params || !pk_params || !d_out || !d_work) return cp::fail(CP_EINVAL, "cp_dst_forward_analytic: null pointer");
-    char* coef = static_cast<char*>(d_work);
-    coef += (64 - (reinterpret_cast<unsigned long long>(coef) & 63u)) & 63u;
-    int st = cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, pk_params, coef, p->device, stream);      // (validates the massive-neutrino tables)
-    if (st != CP_OK) return st;
-    const int nsp = ncdm ? ncdm->nspecies : 0;
-    if (nsp < 0 || (nsp > 0 && !ncdm->tab)) return cp::fail(CP_EINVAL, "cp_dst_forward_analytic: bad massive-neutrino tables");
-    cp::DeviceScope scope(p->device);
-    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_dst_forward_analytic: cannot select device %d", p->device);
-    GenArgs G{};
-    G.dst.in = nullptr; G.dst.out = d_out; G.dst.nrows = ncosmo; G.dst.tw = p->d_tw; G.dst.rot = p->d_rot; G.dst.kx = nullptr; G.dst.ikx = nullptr; G.dst.fused = 0;
-    G.dst.split = (flags & CP_DST_SPLIT) != 0;
-    G.ncosmo = ncosmo;
-    cpcosmo::copy_params(G.bg, bg_params, CP_BG_NPARAMS);
-    cpcosmo::copy_params(G.pw, pk_params, CP_PK_NPARAMS);
-    G.second_is_omega_m = second_is_omega_m;
-    G.ncdm_tab = nsp ? ncdm->tab : nullptr;
-    G.nsp = nsp;
-    G.k = p->d_kx;
-    G.ln_k = p->d_ln_kx;
-    G.consts = reinterpret_cast<const cppower::CosmoConsts*>(coef);
-    G.box = d_box; G.margin_first = margin_first; G.margin_second = margin_second; G.off0 = offset_first; G.off1 = offset_second;
-    const long long npairs = (ncosmo + 1) / 2;
-    int ncu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess || ncu <= 0) ncu = 256;
-    // two workgroups per CU are resident (LDS): every workgroup the same number of pairs
-    const long long resident = 2LL * ncu, rounds = (npairs + resident - 1) / resident;
-    const int grid = (int)((npairs + rounds - 1) / rounds);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (engine == CP_ENGINE_EH) launch_generate<CP_ENGINE_EH>(G, grid, s);
-    else if (engine == CP_ENGINE_EH_NOWIGGLE) launch_generate<CP_ENGINE_EH_NOWIGGLE>(G, grid, s);
-    else launch_generate<CP_ENGINE_BBKS>(G, grid, s);
-    return cp::launch_status("cp_dst_forward_analytic");
-}
-
 
 // ---- cp_wallish_tail: everything of wallish2018 behind its forward transform, one kernel (wallish_tail_kernel above) ----
 extern "C" int cp_wallish_tail(const cp_dst_plan* p, const cp_splice_plan* splice, double* d_coef, const double* d_pk, int npk, long long nrows, int margin_first,
                                int margin_second, int offset_first, int offset_second, const double* d_tophat, int* d_box, double* d_out, void* stream) {
     if (!p || !splice) return cp::fail(CP_EINVAL, "cp_wallish_tail: null plan");
     if (nrows < 0) return cp::fail(CP_EINVAL, "cp_wallish_tail: negative batch");
-    if (margin_first < 0 || 2 * margin_first >= 2048 || margin_second < 0 || margin_second >= 2048) return cp::fail(CP_EINVAL, "cp_wallish_tail: bad margins");
-    if (p->n != 4096 || !p->d_kx || !p->d_ln_kx)
-        return cp::fail(CP_EUNSUPPORTED, "cp_wallish_tail: needs a transform plan of length 4096 made with its abscissa (wallish2018's linear grid)");
+    if (bad_margins(margin_first, margin_second)) return cp::fail(CP_EINVAL, "cp_wallish_tail: bad margins");
     cpsu::Tables U;
-    int device = -1;
-    if (!cp_splice_plan_uniform_view(splice, &U, &device) || device != p->device)
-        return cp::fail(CP_EUNSUPPORTED, "cp_wallish_tail: the splice plan does not run the uniform-stretch scheme on the transform's device");
-    // the stretch comes from the transformed rows, everything else from the rows of P; the stretch, the slot in front of it and the 64 S knots the
-    // lanes own lie inside a row of the transform; one query per column of P
-    if (U.src_u != 1 || (U.wl > 0 && U.src_l != 0) || (U.wr > 0 && U.src_r != 0) || U.col_u < 1 || U.col_u + 64 * U.S + 1 > 4096 || U.nq != npk || U.ngb > cpsu::NGB ||
-        U.S != 49 || U.col_l + U.wl > npk || U.col_r + U.wr > npk)
-        return cp::fail(CP_EUNSUPPORTED, "cp_wallish_tail: the splice plan is not the filter's (stretch of %d knots at column %d of array %d, %d queries)", U.nm, U.col_u,
-                        U.src_u, U.nq);
+    const int st = wallish_plans("cp_wallish_tail", p, splice, npk, &U);
+    if (st != CP_OK) return st;
     if (nrows == 0) return CP_OK;
     if (!d_coef || !d_pk || !d_box || !d_out) return cp::fail(CP_EINVAL, "cp_wallish_tail: null device pointer");
     cp::DeviceScope scope(p->device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_wallish_tail: cannot select device %d", p->device);
     TailArgs G{};
-    G.nrows = nrows; G.coef = d_coef; G.tw = p->d_tw; G.rot = p->d_rot; G.ikx = p->d_ln_kx + 3 * (size_t)p->n;
-    G.U = U;
-    G.pk = d_pk; G.tophat = d_tophat; G.out = d_out; G.box = d_box;
-    G.margin_first = margin_first; G.margin_second = margin_second; G.off0 = offset_first; G.off1 = offset_second;
-    const long long npairs = (nrows + 1) / 2;
-    int ncu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess || ncu <= 0) ncu = 256;
-    const long long resident = 2LL * ncu, rounds = (npairs + resident - 1) / resident;      // two workgroups per CU are resident (LDS): every workgroup the same number of pairs
-    const int grid = (int)((npairs + rounds - 1) / rounds);
-    constexpr int lds = (4096 + Plan<4096, 16>::TW_TOTAL - 4096) * (int)sizeof(cplx) + 2 * cpdd::DD_NTAB * (int)sizeof(double);
+    fill_tail(G, p, U, nrows, d_coef, d_pk, margin_first, margin_second, offset_first, offset_second, d_tophat, d_box, d_out);
     (void)cp::allow_full_lds<&wallish_tail_kernel<49>>();
-    hipLaunchKernelGGL(wallish_tail_kernel<49>, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), G);
+    hipLaunchKernelGGL(wallish_tail_kernel<49>, dim3(wallish_grid(nrows, p->device)), dim3(256), WALLISH_LDS, static_cast<hipStream_t>(stream), G);
     return cp::launch_status("cp_wallish_tail");
 }
-
 
 // ---- cp_wallish_full: wallish2018 of a batch of analytic cosmologies, one kernel (wallish_full_kernel, cp_wallish_tail.h) ----
 namespace {
@@ -838,57 +845,30 @@ void launch_full(const FullArgs& F, int grid, int lds, hipStream_t stream) {
 extern "C" int cp_wallish_full(const cp_dst_plan* p, const cp_splice_plan* splice, int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m,
                                const cp_ncdm* ncdm, const cp_param* pk_params, const double* d_pk, int npk, int margin_first, int margin_second, int offset_first,
                                int offset_second, const double* d_tophat, int* d_box, double* d_coef, double* d_out, void* d_work, void* stream) {
+    const char* who = "cp_wallish_full";
     if (!p || !splice) return cp::fail(CP_EINVAL, "cp_wallish_full: null plan");
     if (ncosmo < 0) return cp::fail(CP_EINVAL, "cp_wallish_full: negative batch");
-    if (engine != CP_ENGINE_EH && engine != CP_ENGINE_EH_NOWIGGLE && engine != CP_ENGINE_BBKS) return cp::fail(CP_EINVAL, "cp_wallish_full: unknown engine %d", engine);
-    if (margin_first < 0 || 2 * margin_first >= 2048 || margin_second < 0 || margin_second >= 2048) return cp::fail(CP_EINVAL, "cp_wallish_full: bad margins");
-    if (p->n != 4096 || !p->d_kx || !p->d_ln_kx)
-        return cp::fail(CP_EUNSUPPORTED, "cp_wallish_full: needs a transform plan of length 4096 made with its abscissa (wallish2018's linear grid)");
+    if (!cpcosmo::engine_known(engine)) return cpcosmo::unknown_engine(who, engine);
+    if (bad_margins(margin_first, margin_second)) return cp::fail(CP_EINVAL, "cp_wallish_full: bad margins");
     cpsu::Tables U;
-    int device = -1;
-    if (!cp_splice_plan_uniform_view(splice, &U, &device) || device != p->device)
-        return cp::fail(CP_EUNSUPPORTED, "cp_wallish_full: the splice plan does not run the uniform-stretch scheme on the transform's device");
-    if (U.src_u != 1 || (U.wl > 0 && U.src_l != 0) || (U.wr > 0 && U.src_r != 0) || U.col_u < 1 || U.col_u + 64 * U.S + 1 > 4096 || U.nq != npk || U.ngb > cpsu::NGB ||
-        U.S != 49 || U.col_l + U.wl > npk || U.col_r + U.wr > npk)
-        return cp::fail(CP_EUNSUPPORTED, "cp_wallish_full: the splice plan is not the filter's (stretch of %d knots at column %d of array %d, %d queries)", U.nm, U.col_u,
-                        U.src_u, U.nq);
+    int st = wallish_plans(who, p, splice, npk, &U);
+    if (st != CP_OK) return st;
     if (ncosmo == 0) return CP_OK;
     if (!bg_params || !pk_params || !d_pk || !d_box || !d_out || !d_work) return cp::fail(CP_EINVAL, "cp_wallish_full: null pointer");
-    char* coef = static_cast<char*>(d_work);
-    coef += (64 - (reinterpret_cast<unsigned long long>(coef) & 63u)) & 63u;
-    int st = cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, pk_params, coef, p->device, stream);      // (validates the massive-neutrino tables)
+    int nsp;
+    st = cpcosmo::ncdm_species(ncdm, who, &nsp);
     if (st != CP_OK) return st;
-    const int nsp = ncdm ? ncdm->nspecies : 0;
-    if (nsp < 0 || (nsp > 0 && !ncdm->tab)) return cp::fail(CP_EINVAL, "cp_wallish_full: bad massive-neutrino tables");
     cp::DeviceScope scope(p->device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_wallish_full: cannot select device %d", p->device);
+    const double* knots;
+    st = cpcosmo::ncdm_knots(nsp, p->device, who, &knots);
+    if (st != CP_OK) return st;
+    char* coef = cp::coef_workspace(d_work, ncosmo).coef;
+    cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, knots, pk_params, coef, stream);
     FullArgs F{};
-    TailArgs& G = F.tail;
-    G.nrows = ncosmo; G.coef = d_coef; G.tw = p->d_tw; G.rot = p->d_rot; G.ikx = p->d_ln_kx + 3 * (size_t)p->n;
-    G.U = U;
-    G.pk = d_pk; G.tophat = d_tophat; G.out = d_out; G.box = d_box;
-    G.margin_first = margin_first; G.margin_second = margin_second; G.off0 = offset_first; G.off1 = offset_second;
-    GenArgs& E = F.gen;
-    E.dst.in = nullptr; E.dst.out = nullptr; E.dst.nrows = ncosmo; E.dst.tw = p->d_tw; E.dst.rot = p->d_rot; E.dst.kx = nullptr; E.dst.ikx = nullptr; E.dst.fused = 0; E.dst.split = 1;
-    E.ncosmo = ncosmo;
-    cpcosmo::copy_params(E.bg, bg_params, CP_BG_NPARAMS);
-    cpcosmo::copy_params(E.pw, pk_params, CP_PK_NPARAMS);
-    E.second_is_omega_m = second_is_omega_m;
-    E.ncdm_tab = nsp ? ncdm->tab : nullptr;
-    E.nsp = nsp;
-    E.k = p->d_kx;
-    E.ln_k = p->d_ln_kx;
-    E.consts = reinterpret_cast<const cppower::CosmoConsts*>(coef);
-    E.box = nullptr;
-    const long long npairs = (ncosmo + 1) / 2;
-    int ncu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess || ncu <= 0) ncu = 256;
-    const long long resident = 2LL * ncu, rounds = (npairs + resident - 1) / resident;
-    const int grid = (int)((npairs + rounds - 1) / rounds);
-    constexpr int lds = (4096 + Plan<4096, 16>::TW_TOTAL - 4096) * (int)sizeof(cplx) + 2 * cpdd::DD_NTAB * (int)sizeof(double);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (engine == CP_ENGINE_EH) launch_full<CP_ENGINE_EH>(F, grid, lds, s);
-    else if (engine == CP_ENGINE_EH_NOWIGGLE) launch_full<CP_ENGINE_EH_NOWIGGLE>(F, grid, lds, s);
-    else launch_full<CP_ENGINE_BBKS>(F, grid, lds, s);
-    return cp::launch_status("cp_wallish_full");
+    fill_tail(F.tail, p, U, ncosmo, d_coef, d_pk, margin_first, margin_second, offset_first, offset_second, d_tophat, d_box, d_out);
+    fill_generate(F.gen, p, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, pk_params, nullptr, true, coef);
+    const int grid = wallish_grid(ncosmo, p->device);
+    cpcosmo::dispatch_engine(engine, [&](auto e) { launch_full<decltype(e)::value>(F, grid, WALLISH_LDS, static_cast<hipStream_t>(stream)); });
+    return cp::launch_status(who);
 }

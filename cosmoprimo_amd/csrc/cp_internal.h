@@ -30,13 +30,19 @@ struct cp_spline_band_view {
 };
 bool cp_spline_plan_view(const cp_spline_plan* plan, cp_spline_band_view* out);
 
-// the constants of a batch of cosmologies for the evaluation of engine `engine` (cppower::CosmoConsts: fit coefficients of EH98 / no-wiggle, Gamma of
+// The constants of a batch of cosmologies for the evaluation of engine `engine` (cppower::CosmoConsts: fit coefficients of EH98 / no-wiggle, Gamma of
 // BBKS, the primordial constants of pk_params -- NULL: transfer functions only) into d_work (cp_power_workspace_bytes(ncosmo) bytes): the first of
-// the two kernels cp_power_eval launches
+// the two kernels cp_power_eval launches.  A launch and nothing else: its caller (a public entry point) has validated the arguments (nsp from
+// cpcosmo::ncdm_species), holds the cp::DeviceScope, has fetched the knots (cpcosmo::ncdm_knots) and reads the launch status once, behind its own kernel.
 // d_k / d_ln_k (n wavenumbers; optional): extra workgroups of the same launch write the (3, n) table log k, k^1.08, k^1.4 of the kernels that evaluate on
 // a shared grid (cp_power_eval.h: powers_of_wavenumber) -- a launch of their own for 1024 values was 3 % of the fused sigma(r, z) call
-int cp_power_coefficients(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, const cp_param* pk_params,
-                          void* d_work, int device, void* stream, const double* d_k = nullptr, double* d_ln_k = nullptr, int n = 0);
+void cp_power_coefficients(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, int nsp, const double* knots,
+                           const cp_param* pk_params, void* d_work, void* stream, const double* d_k = nullptr, double* d_ln_k = nullptr, int n = 0);
+
+// the one-kernel route of cp_sigma_rz_analytic (cp_sigma.hip), called by it with its arguments checked (nsp from cpcosmo::ncdm_species): opens the scope and reads the launch status under its name
+int cp_sigma_rz_fused(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, int nsp, const cp_param* pk_params,
+                      const double* d_k, const cp_fftlog_plan* fftlog, const cp_spline_plan* spline, const double* d_growth_sq, int nz, double* d_out,
+                      double* d_pk_out, void* d_work, int device, void* stream);
 
 // a cp_spline_rows plan seen from cp_spline.hip: its queries as (interval, four weights) per query -- A y_j + B y_{j+1} + wM0 M_j + wM1 M_{j+1}, the
 // second derivatives M from cp_spline_rows_second_derivatives -- for the kernel that evaluates the k direction of (z, k) tables itself
@@ -76,6 +82,39 @@ public:
     DeviceScope& operator=(const DeviceScope&) = delete;
     bool ok() const { return ok_; }
 };
+
+// The workspace of the entries that evaluate spectra themselves: the cosmologies' constants, 64-byte aligned, and -- for the kernels that evaluate on a
+// shared grid of nk wavenumbers -- the (3, nk) table cp_power_coefficients writes, 64-byte aligned behind them.
+inline char* align64(void* p) {
+    char* c = static_cast<char*>(p);
+    return c + ((64 - (reinterpret_cast<unsigned long long>(c) & 63u)) & 63u);
+}
+struct CoefWorkspace {
+    char* coef;
+    double* ln_k;
+};
+inline CoefWorkspace coef_workspace(void* d_work, long long ncosmo) {
+    char* coef = align64(d_work);
+    return CoefWorkspace{coef, reinterpret_cast<double*>(coef + ((cp_power_workspace_bytes(ncosmo) + 63) / 64) * 64)};
+}
+inline long long coef_workspace_bytes(long long ncosmo, long long nk) {      // what coef_workspace() may touch of a workspace that starts anywhere
+    return 64 + ((cp_power_workspace_bytes(ncosmo) + 63) / 64) * 64 + 3 * nk * (long long)sizeof(double);
+}
+
+// compute units of `device` (256 where the runtime does not say)
+inline int cu_count(int device) {
+    int ncu = 0;
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu <= 0) ncu = 256;
+    return ncu;
+}
+
+// The grid of a persistent kernel that takes a pair of rows per iteration, `resident` workgroups fitting on the chip: every workgroup the same number of
+// pairs (5000 pairs on 1024 resident workgroups would leave a fifth of the chip idle in the last round).  *rounds: pairs per workgroup.
+inline int balanced_grid(long long npairs, long long resident, long long* rounds = nullptr) {
+    const long long r = (npairs + resident - 1) / resident;
+    if (rounds) *rounds = r;
+    return (int)((npairs + r - 1) / r);
+}
 
 // the status of entry point `who` after its launches: reads (and clears) the runtime's last error once
 inline int launch_status(const char* who, hipError_t e) {

@@ -12,14 +12,9 @@
 #include <mutex>
 
 #include "../../include/cosmoprimo_amd.h"
+#include "cp_cosmo_common.h"
 #include "cp_error.h"
 #include "cp_internal.h"
-
-extern "C" int cp_sigma_rz_fused_available(const cp_fftlog_plan* fftlog, const cp_spline_plan* spline);
-int cp_sigma_rz_fused(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, const cp_param* pk_params,
-                      const double* d_k,
-                      const cp_fftlog_plan* fftlog, const cp_spline_plan* spline, const double* d_growth_sq, int nz, double* d_out, double* d_pk_out,
-                      void* d_coef, int device, void* stream);
 
 namespace {
 
@@ -61,7 +56,8 @@ void offset_params(const cp_param* in, cp_param* out, int n, long long first) {
 
 extern "C" long long cp_sigma_rz_workspace_bytes(long long ncosmo, int nk) {
     if (ncosmo < 0 || nk < 0) return -1;
-    return 2 * ncosmo * (long long)nk * (long long)sizeof(double) + cp_power_workspace_bytes(ncosmo) + 192 + 3 * (long long)nk * (long long)sizeof(double);      // ... + log k, k^1.08, k^1.4
+    // the block route: spectra and variances in front of the coefficients; the one-kernel routes: coefficients and log k, k^1.08, k^1.4
+    return 2 * ncosmo * (long long)nk * (long long)sizeof(double) + cp::coef_workspace_bytes(ncosmo, nk);
 }
 
 extern "C" int cp_sigma_rz_analytic(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm,
@@ -69,19 +65,20 @@ extern "C" int cp_sigma_rz_analytic(int engine, long long ncosmo, const cp_param
                                     const double* d_k, const cp_fftlog_plan* fftlog, const cp_spline_plan* spline, const double* d_growth_sq, int nz,
                                     double* d_out, double* d_pk_out, void* d_work, int nblocks, int device, void* stream) {
     if (ncosmo < 0 || nk <= 0 || nz <= 0) return cp::fail(CP_EINVAL, "cp_sigma_rz_analytic: bad sizes");
+    if (!cpcosmo::engine_known(engine)) return cpcosmo::unknown_engine("cp_sigma_rz_analytic", engine);
     if (ncosmo == 0) return CP_OK;
     if (!bg_params || !pk_params || !d_k || !fftlog || !spline || !d_growth_sq || !d_out || !d_work)
         return cp::fail(CP_EINVAL, "cp_sigma_rz_analytic: null pointer");
+    int nsp;
+    int st = cpcosmo::ncdm_species(ncdm, "cp_sigma_rz_analytic", &nsp);
+    if (st != CP_OK) return st;
     int n_spline = 0, nq = 0;
-    int st = cp_spline_plan_info(spline, &n_spline, &nq, nullptr);
+    st = cp_spline_plan_info(spline, &n_spline, &nq, nullptr);
     if (st != CP_OK) return st;
     if (n_spline != nk) return cp::fail(CP_EINVAL, "cp_sigma_rz_analytic: the spline plan has %d knots, the spectra %d samples", n_spline, nk);
     if (nblocks <= 0) {      // the one-kernel route (cp_sigma.hip) where the plans are the ones it is written for, else one block on one stream
-        if (cp_sigma_rz_fused_available(fftlog, spline)) {
-            char* coef = static_cast<char*>(d_work);
-            coef += (64 - (reinterpret_cast<unsigned long long>(coef) & 63u)) & 63u;
-            return cp_sigma_rz_fused(engine, ncosmo, bg_params, second_is_omega_m, ncdm, pk_params, d_k, fftlog, spline, d_growth_sq, nz, d_out, d_pk_out, coef, device, stream);
-        }
+        if (cp_sigma_rz_fused_available(fftlog, spline))
+            return cp_sigma_rz_fused(engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, pk_params, d_k, fftlog, spline, d_growth_sq, nz, d_out, d_pk_out, d_work, device, stream);
         nblocks = 1;
     }
     if (nblocks > MAX_BLOCKS) nblocks = MAX_BLOCKS;
@@ -92,8 +89,7 @@ extern "C" int cp_sigma_rz_analytic(int engine, long long ncosmo, const cp_param
     double* work = static_cast<double*>(d_work);
     double* rows = d_pk_out ? d_pk_out : work;      // the spectra are kept where the caller wants them: (ncosmo, nk), nothing behind them is the callee's
     double* var = d_pk_out ? work : work + ncosmo * (long long)nk;      // variances and coefficients always live in the workspace
-    char* coef = reinterpret_cast<char*>(var + ncosmo * (long long)nk);
-    coef += (64 - (reinterpret_cast<unsigned long long>(coef) & 63u)) & 63u;
+    char* coef = cp::align64(var + ncosmo * (long long)nk);
     if (side) {  // what the caller queued before this call (growth factors, the result buffer) is ready once its stream gets here
         if (hipEventRecord(side->begin, main) != hipSuccess || hipStreamWaitEvent(side->stream, side->begin, 0) != hipSuccess)
             return cp::fail(CP_EDEVICE, "cp_sigma_rz_analytic: cannot order the second stream");

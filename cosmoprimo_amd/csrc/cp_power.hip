@@ -338,47 +338,58 @@ __global__ __launch_bounds__(256) void variants_kernel(const VarArgs A) {
 
 extern "C" long long cp_power_workspace_bytes(long long ncosmo) { return ncosmo < 0 ? -1 : (long long)sizeof(CosmoConsts) * ncosmo; }
 
-int cp_power_coefficients(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, const cp_param* pk_params,
-                          void* d_work, int device, void* stream, const double* d_k, double* d_ln_k, int n) {
-    if (ncosmo <= 0) return CP_OK;
-    if (!bg_params || !d_work) return cp::fail(CP_EINVAL, "cp_power_coefficients: null pointer");
-    cp::DeviceScope scope(device);
-    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_power_coefficients: cannot select device %d", device);
+void cp_power_coefficients(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, int nsp, const double* knots,
+                           const cp_param* pk_params, void* d_work, void* stream, const double* d_k, double* d_ln_k, int n) {
     Args A{};
-    A.ncosmo = ncosmo;
-    cpcosmo::copy_params(A.bg, bg_params, CP_BG_NPARAMS);
-    if (pk_params)
-        cpcosmo::copy_params(A.pw, pk_params, CP_PK_NPARAMS);
-    A.second_is_omega_m = second_is_omega_m;
+    cpcosmo::fill_cosmology(A, ncosmo, bg_params, pk_params, second_is_omega_m, ncdm, nsp, knots);
     A.engine = engine;
-    NcdmView nu;
-    const int st = ncdm_view(ncdm, device, "cp_power_coefficients", &nu);
-    if (st != CP_OK) return st;
-    A.ncdm_tab = nu.tab;
-    A.ncdm_knots = nu.knots;
-    A.nsp = nu.nsp;
     const int n_grid = d_k && d_ln_k ? n : 0;
     hipLaunchKernelGGL(coefficients_kernel, dim3((unsigned)((ncosmo + 63) / 64 + (n_grid + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), A,
                        static_cast<CosmoConsts*>(d_work), pk_params ? 1 : 0, d_k, d_ln_k, n_grid);
-    return cp::launch_status("cp_power_coefficients");
 }
+
+namespace {
+
+// wavenumbers per workgroup of `block` threads: all of a cosmology's when the batch alone fills the chip, fewer for small batches; false when the grid
+// exceeds one launch
+template <class A>
+bool split_wavenumbers(A& a, long long ncosmo, long long nk, long long block) {
+    long long kiter = (nk + block - 1) / block;
+    while (kiter > 1 && ncosmo * ((nk + block * kiter - 1) / (block * kiter)) < 2048) kiter = (kiter + 1) / 2;
+    a.kspan = block * kiter;
+    a.kchunks = (nk + a.kspan - 1) / a.kspan;
+    return ncosmo * a.kchunks <= 2147483647LL;
+}
+
+}  // namespace
 
 extern "C" int cp_power_eval(int engine, int what, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm,
                              const cp_param* pk_params, long long nk, const double* d_k, const double* d_kscale, long long nz, const double* d_z, double* d_out, void* d_work,
                              int device, void* stream) {
-    if (engine < CP_ENGINE_EH || engine > CP_ENGINE_BBKS) return cp::fail(CP_EINVAL, "cp_power_eval: unknown engine %d", engine);
+    const char* who = "cp_power_eval";
+    if (!cpcosmo::engine_known(engine)) return cpcosmo::unknown_engine(who, engine);
     if (what < CP_PK_MATTER || what > CP_PK_LOG_K_MATTER) return cp::fail(CP_EINVAL, "cp_power_eval: unknown quantity %d", what);
     if (what == CP_PK_LOG_K_MATTER && nz > 0) return cp::fail(CP_EINVAL, "cp_power_eval: log(k P) is without growth factor (nz = 0)");
     if (ncosmo < 0 || nk < 0 || nz < 0) return cp::fail(CP_EINVAL, "cp_power_eval: negative size");
     if (ncosmo == 0 || nk == 0) return CP_OK;
     if (!bg_params || !pk_params || !d_k || !d_out || (nz > 0 && !d_z)) return cp::fail(CP_EINVAL, "cp_power_eval: null pointer");
+    int nsp;
+    int st = cpcosmo::ncdm_species(ncdm, who, &nsp);
+    if (st != CP_OK) return st;
+    Args A{};
+    // A batch that fills the chip with one WAVE per cosmology (12 waves per CU) takes that shape: a thread's per-cosmology part is amortised over nk / 64
+    // wavenumbers instead of nk / 256 (brieden2022 evaluates 341 per cosmology: 2 282 -> ~900 instructions per spectrum for the no-wiggle form)
+    const long long block = ncosmo >= 256 * 12 ? 64 : 256;
+    if (!split_wavenumbers(A, ncosmo, nk, block)) return cp::fail(CP_EUNSUPPORTED, "cp_power_eval: %lld cosmologies x %lld wavenumbers exceed one launch; split the batch", ncosmo, nk);
+    // the constants of the cosmologies: caller-owned workspace, nothing is allocated here
+    if (!d_work) return cp::fail(CP_EINVAL, "cp_power_eval: needs a workspace of cp_power_workspace_bytes(ncosmo) bytes");
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_power_eval: cannot select device %d", device);
-    Args A;
-    A.ncosmo = ncosmo;
-    cpcosmo::copy_params(A.bg, bg_params, CP_BG_NPARAMS);
-    cpcosmo::copy_params(A.pw, pk_params, CP_PK_NPARAMS);
-    A.second_is_omega_m = second_is_omega_m;
+    const double* knots;
+    st = cpcosmo::ncdm_knots(nsp, device, who, &knots);
+    if (st != CP_OK) return st;
+    cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, knots, pk_params, d_work, stream);
+    cpcosmo::fill_cosmology(A, ncosmo, bg_params, pk_params, second_is_omega_m, ncdm, nsp, knots, d_work);
     A.engine = engine;
     A.what = what;
     A.nk = nk;
@@ -387,54 +398,30 @@ extern "C" int cp_power_eval(int engine, int what, long long ncosmo, const cp_pa
     A.kscale = d_kscale;
     A.z = d_z;
     A.out = d_out;
-    A.consts = nullptr;
-    NcdmView nu;
-    const int st = ncdm_view(ncdm, device, "cp_power_eval", &nu);
-    if (st != CP_OK) return st;
-    A.ncdm_tab = nu.tab;
-    A.ncdm_knots = nu.knots;
-    A.nsp = nu.nsp;
-    // wavenumbers per workgroup: all of a cosmology's when the batch alone fills the chip (>= 8 workgroups per CU), fewer for small batches.  A batch
-    // that fills the chip with one WAVE per cosmology (12 waves per CU) takes that shape: a thread's per-cosmology part is amortised over nk / 64
-    // wavenumbers instead of nk / 256 (brieden2022 evaluates 341 per cosmology: 2 282 -> ~900 instructions per spectrum for the no-wiggle form)
-    const long long block = ncosmo >= 256 * 12 ? 64 : 256;
-    long long kiter = (nk + block - 1) / block;
-    while (kiter > 1 && ncosmo * ((nk + block * kiter - 1) / (block * kiter)) < 2048) kiter = (kiter + 1) / 2;
-    A.kspan = block * kiter;
-    A.kchunks = (nk + A.kspan - 1) / A.kspan;
-    if (ncosmo * A.kchunks > 2147483647LL) return cp::fail(CP_EUNSUPPORTED, "cp_power_eval: %lld cosmologies x %lld wavenumbers exceed one launch; split the batch", ncosmo, nk);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    {   // the constants of the cosmologies: caller-owned workspace, nothing is allocated here
-        if (!d_work) return cp::fail(CP_EINVAL, "cp_power_eval: needs a workspace of cp_power_workspace_bytes(ncosmo) bytes");
-        CosmoConsts* consts = static_cast<CosmoConsts*>(d_work);
-        A.consts = consts;
-        hipLaunchKernelGGL(coefficients_kernel, dim3((unsigned)((ncosmo + 63) / 64)), dim3(64), 0, hs, A, consts, 1, static_cast<const double*>(nullptr),
-                           static_cast<double*>(nullptr), 0);
-    }
     const dim3 grid((unsigned)(ncosmo * A.kchunks)), threads((unsigned)block);
-    if (engine == CP_ENGINE_EH) hipLaunchKernelGGL(power_kernel<CP_ENGINE_EH>, grid, threads, 0, hs, A);
-    else if (engine == CP_ENGINE_EH_NOWIGGLE) hipLaunchKernelGGL(power_kernel<CP_ENGINE_EH_NOWIGGLE>, grid, threads, 0, hs, A);
-    else hipLaunchKernelGGL(power_kernel<CP_ENGINE_BBKS>, grid, threads, 0, hs, A);
-    return cp::launch_status("cp_power_eval");
+    cpcosmo::dispatch_engine(engine, [&](auto e) { hipLaunchKernelGGL((power_kernel<decltype(e)::value>), grid, threads, 0, static_cast<hipStream_t>(stream), A); });
+    return cp::launch_status(who);
 }
 
 extern "C" int cp_power_eval_variants(int what, int of, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm,
                                       const cp_param* pk_params, long long nk, const double* d_k, long long nz, const double* d_z, double* d_out,
                                       int device, void* stream) {
+    const char* who = "cp_power_eval_variants";
     if (what != CP_PK_MATTER && what != CP_PK_TRANSFER) return cp::fail(CP_EINVAL, "cp_power_eval_variants: unknown quantity %d", what);
     if (of != 0 && of != 1) return cp::fail(CP_EINVAL, "cp_power_eval_variants: of must be 0 (delta_m) or 1 (delta_cb)");
     if (ncosmo < 0 || nk < 0 || nz < 0) return cp::fail(CP_EINVAL, "cp_power_eval_variants: negative size");
     if (ncosmo == 0 || nk == 0 || nz == 0) return CP_OK;
     if (!bg_params || !pk_params || !d_k || !d_z || !d_out) return cp::fail(CP_EINVAL, "cp_power_eval_variants: null pointer");
-    const int nsp = ncdm ? ncdm->nspecies : 0;
-    if (nsp < 0 || (nsp > 0 && !ncdm->tab)) return cp::fail(CP_EINVAL, "cp_power_eval_variants: bad massive-neutrino tables");
+    int nsp;
+    int st = cpcosmo::ncdm_species(ncdm, who, &nsp);
+    if (st != CP_OK) return st;
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_power_eval_variants: cannot select device %d", device);
+    const double* knots;
+    st = cpcosmo::ncdm_knots(nsp, device, who, &knots);
+    if (st != CP_OK) return st;
     VarArgs A;
-    A.ncosmo = ncosmo;
-    cpcosmo::copy_params(A.bg, bg_params, CP_BG_NPARAMS);
-    cpcosmo::copy_params(A.pw, pk_params, CP_PK_NPARAMS);
-    A.second_is_omega_m = second_is_omega_m;
+    cpcosmo::fill_cosmology(A, ncosmo, bg_params, pk_params, second_is_omega_m, ncdm, nsp, knots);
     A.what = what;
     A.of = of;
     A.nk = nk;
@@ -442,58 +429,47 @@ extern "C" int cp_power_eval_variants(int what, int of, long long ncosmo, const 
     A.k = d_k;
     A.z = d_z;
     A.out = d_out;
-    A.nsp = nsp;
-    A.ncdm_tab = nsp ? ncdm->tab : nullptr;
-    A.ncdm_knots = nsp ? cpcosmo::ncdm_knots_device(device) : nullptr;
-    if (nsp && !A.ncdm_knots) return cp::fail(CP_ENOMEM, "cp_power_eval_variants: cannot allocate the massive-neutrino knots on device %d", device);
     const long long block = 256;
-    long long kiter = (nk + block - 1) / block;
-    while (kiter > 1 && ncosmo * ((nk + block * kiter - 1) / (block * kiter)) < 2048) kiter = (kiter + 1) / 2;
-    A.kspan = block * kiter;
-    A.kchunks = (nk + A.kspan - 1) / A.kspan;
-    if (ncosmo * A.kchunks > 2147483647LL) return cp::fail(CP_EUNSUPPORTED, "cp_power_eval_variants: %lld cosmologies x %lld wavenumbers exceed one launch; split the batch", ncosmo, nk);
+    if (!split_wavenumbers(A, ncosmo, nk, block)) return cp::fail(CP_EUNSUPPORTED, "cp_power_eval_variants: %lld cosmologies x %lld wavenumbers exceed one launch; split the batch", ncosmo, nk);
     hipLaunchKernelGGL(variants_kernel, dim3((unsigned)(ncosmo * A.kchunks)), dim3((unsigned)block), 0, static_cast<hipStream_t>(stream), A);
-    return cp::launch_status("cp_power_eval_variants");
+    return cp::launch_status(who);
 }
 
 extern "C" int cp_variants_scalars(long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, double* d_out, int device,
                                    void* stream) {
+    const char* who = "cp_variants_scalars";
     if (ncosmo < 0) return cp::fail(CP_EINVAL, "cp_variants_scalars: negative size");
     if (ncosmo == 0) return CP_OK;
     if (!bg_params || !d_out) return cp::fail(CP_EINVAL, "cp_variants_scalars: null pointer");
-    const int nsp = ncdm ? ncdm->nspecies : 0;
-    if (nsp < 0 || (nsp > 0 && !ncdm->tab)) return cp::fail(CP_EINVAL, "cp_variants_scalars: bad massive-neutrino tables");
+    int nsp;
+    int st = cpcosmo::ncdm_species(ncdm, who, &nsp);
+    if (st != CP_OK) return st;
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_variants_scalars: cannot select device %d", device);
+    const double* knots;
+    st = cpcosmo::ncdm_knots(nsp, device, who, &knots);
+    if (st != CP_OK) return st;
     VarScalArgs A;
-    A.ncosmo = ncosmo;
-    cpcosmo::copy_params(A.bg, bg_params, CP_BG_NPARAMS);
-    A.second_is_omega_m = second_is_omega_m;
-    A.nsp = nsp;
-    A.ncdm_tab = nsp ? ncdm->tab : nullptr;
-    A.ncdm_knots = nsp ? cpcosmo::ncdm_knots_device(device) : nullptr;
+    cpcosmo::fill_cosmology(A, ncosmo, bg_params, nullptr, second_is_omega_m, ncdm, nsp, knots);
     A.out = d_out;
-    if (nsp && !A.ncdm_knots) return cp::fail(CP_ENOMEM, "cp_variants_scalars: cannot allocate the massive-neutrino knots on device %d", device);
     hipLaunchKernelGGL(variants_scalars_kernel, dim3((unsigned)((ncosmo + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), A);
-    return cp::launch_status("cp_variants_scalars");
+    return cp::launch_status(who);
 }
 
 extern "C" int cp_eh_scalars(long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, double* d_out, int device,
                              void* stream) {
+    const char* who = "cp_eh_scalars";
     if (ncosmo < 0) return cp::fail(CP_EINVAL, "cp_eh_scalars: negative size");
     if (ncosmo == 0) return CP_OK;
     if (!bg_params || !d_out) return cp::fail(CP_EINVAL, "cp_eh_scalars: null pointer");
-    const int nsp = ncdm ? ncdm->nspecies : 0;
-    if (nsp < 0 || (nsp > 0 && !ncdm->tab)) return cp::fail(CP_EINVAL, "cp_eh_scalars: bad massive-neutrino tables");
+    int nsp;
+    const int st = cpcosmo::ncdm_species(ncdm, who, &nsp);
+    if (st != CP_OK) return st;
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_eh_scalars: cannot select device %d", device);
     ScalArgs A;
-    A.ncosmo = ncosmo;
-    cpcosmo::copy_params(A.bg, bg_params, CP_BG_NPARAMS);
-    A.second_is_omega_m = second_is_omega_m;
-    A.ncdm_tab = nsp ? ncdm->tab : nullptr;
-    A.nsp = nsp;
+    cpcosmo::fill_cosmology(A, ncosmo, bg_params, nullptr, second_is_omega_m, ncdm, nsp);      // (the kernel reads today's densities only: no knots)
     A.out = d_out;
     hipLaunchKernelGGL(eh_scalars_kernel, dim3((unsigned)((ncosmo + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), A);
-    return cp::launch_status("cp_eh_scalars");
+    return cp::launch_status(who);
 }

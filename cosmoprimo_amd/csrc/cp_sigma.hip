@@ -897,9 +897,69 @@ struct GeoTail {
     const GeoBasis* basis;
 };
 
-int sigma_rz_fused_launch(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, const cp_param* pk_params,
-                          const double* d_k, const cp_fftlog_tables_view& f, const cp_spline_band_view* band, const GeoTail* geo, const double* d_growth_sq,
-                          int nz, double* d_out, double* d_pk_out, void* d_coef, int device, void* stream);
+// the FftlogArgs of the fused kernels' shape (1024 samples padded to 2048, one kernel, zero padding, cropped output) on the tables of plan view f.
+// in == null: the rows are formed inside the kernel.
+FftlogArgs fused_fftlog_args(const cp_fftlog_tables_view& f, const double* in, long long nbatch) {
+    FftlogArgs A{};
+    A.in = in; A.out = nullptr; A.nbatch = nbatch; A.nker = 1; A.n = f.n; A.in_left = f.in_left; A.out_off = f.out_left; A.n_out = f.n;
+    A.ext_l = A.ext_r = CP_EXTRAP_CONST; A.val_l = A.val_r = 0.;
+    A.stream_rows = in && (double)nbatch * f.n * 8. > 512. * 1024. * 1024. ? 3 : 0;
+    A.pre = f.d_pre; A.post = f.d_post; A.u = f.d_u; A.tw = f.d_tw;
+    return A;
+}
+
+// workgroups with `lds` bytes each that share a CU (at most 4: the kernels' launch bounds), and the grid of a kernel that takes pairs of rows
+int workgroups_per_cu(size_t lds) {
+    const size_t per_cu = lds ? (160 * 1024) / lds : 4;
+    return (int)(per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu));
+}
+int pairs_grid(long long nrows, size_t lds, int device) { return cp::balanced_grid((nrows + 1) / 2, (long long)cp::cu_count(device) * workgroups_per_cu(lds)); }
+
+// the fused sigma(r, z) kernel for entry point `who`, which has checked sizes, engine, pointers and the massive-neutrino argument (nsp): ONE scope,
+// the coefficients, the kernel, ONE launch status
+int sigma_rz_fused_launch(const char* who, int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, int nsp,
+                          const cp_param* pk_params, const double* d_k, const cp_fftlog_tables_view& f, const cp_spline_band_view* band, const GeoTail* geo,
+                          const double* d_growth_sq, int nz, double* d_out, double* d_pk_out, void* d_work, int device, void* stream) {
+    const int nq = geo ? geo->nq : band->nq;
+    using F = Fftlog<NP, P, IN_HALF_ZERO_GEN, OUT_HALF>;
+    const size_t lds = (size_t)F::LDS_BYTES + (size_t)(2 * nq + 2 * nz) * sizeof(double);
+    if (lds > 160 * 1024) return cp::fail(CP_EUNSUPPORTED, "cp_sigma_rz_fused: %d radii x %d redshifts exceed the LDS staging", nq, nz);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
+    const double* knots;
+    const int st = cpcosmo::ncdm_knots(nsp, device, who, &knots);
+    if (st != CP_OK) return st;
+    const cp::CoefWorkspace w = cp::coef_workspace(d_work, ncosmo);
+    cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, knots, pk_params, w.coef, stream, d_k, w.ln_k, f.n);      // (and the table of the wavenumbers)
+    SigmaArgs S{};
+    S.fft = fused_fftlog_args(f, nullptr, ncosmo);
+    cpcosmo::fill_cosmology(S, ncosmo, bg_params, pk_params, second_is_omega_m, ncdm, nsp, nullptr, w.coef);
+    S.k = d_k;
+    S.ln_k = w.ln_k;
+    S.nq = nq; S.nz = nz;
+    if (geo) {
+        S.qe = geo->qe; S.qx = geo->qx; S.basis = geo->basis; S.ws = geo->ws;
+    } else {
+        S.wb = band->d_wb; S.j0 = band->d_j0; S.bw = band->bw;
+    }
+    S.growth_sq = d_growth_sq;
+    S.out = d_out;
+    S.pk_out = d_pk_out;
+    const int ncu = cp::cu_count(device), per_cu = workgroups_per_cu(lds);
+    long long rounds;
+    const int grid = cp::balanced_grid((ncosmo + 1) / 2, (long long)ncu * per_cu, &rounds);
+    // The workgroups that share a CU (b, b + ncu, b + 2 ncu, ...: the dispatcher deals them out in order) start two s_sleep(127) apart: the first of them
+    // has its first results in memory while the others still evaluate, instead of all four storing at once behind a first evaluation at a quarter of the
+    // CU each (0.327 -> 0.317 ms per 10 000 cosmologies, profiles/r5_sigma_stagger.txt; larger offsets only delay the last workgroup).  Same results.
+    S.stagger_div = ncu; S.stagger_mod = per_cu; S.stagger_sleeps = rounds >= 2 ? 2 : 0;
+    if (const char* env = std::getenv("CP_SIGMA_STAGGER")) {      // "div,mod,sleeps": measurements (tools/ab_sigma_stagger.py)
+        int d = 1, m = 1, sl = 0;
+        if (std::sscanf(env, "%d,%d,%d", &d, &m, &sl) == 3 && d >= 1 && m >= 1 && sl >= 0 && sl <= 4096) { S.stagger_div = d; S.stagger_mod = m; S.stagger_sleeps = sl; }
+    }
+    hipError_t e = hipSuccess;
+    cpcosmo::dispatch_engine(engine, [&](auto en) { e = launch<decltype(en)::value>(S, grid, lds, static_cast<hipStream_t>(stream)); });
+    return cp::launch_status(who, e);
+}
 
 }  // namespace
 
@@ -911,79 +971,15 @@ extern "C" int cp_sigma_rz_fused_available(const cp_fftlog_plan* fftlog, const c
     return f.npad == NP && f.n == NP / 2 && f.nker == 1 && f.in_left == NP / 4 && f.out_left == NP / 4 && b.n == f.n && b.device == f.device;
 }
 
-int cp_sigma_rz_fused(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, const cp_param* pk_params,
-                      const double* d_k,
-                      const cp_fftlog_plan* fftlog, const cp_spline_plan* spline, const double* d_growth_sq, int nz, double* d_out, double* d_pk_out,
-                      void* d_coef, int device, void* stream) {
+int cp_sigma_rz_fused(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, int nsp, const cp_param* pk_params,
+                      const double* d_k, const cp_fftlog_plan* fftlog, const cp_spline_plan* spline, const double* d_growth_sq, int nz, double* d_out,
+                      double* d_pk_out, void* d_work, int device, void* stream) {
     cp_fftlog_tables_view f;
     cp_spline_band_view b;
     if (!cp_fftlog_plan_view(fftlog, &f) || !cp_spline_plan_view(spline, &b)) return cp::fail(CP_EINVAL, "cp_sigma_rz_fused: plans without device tables");
-    return sigma_rz_fused_launch(engine, ncosmo, bg_params, second_is_omega_m, ncdm, pk_params, d_k, f, &b, nullptr, d_growth_sq, nz, d_out, d_pk_out, d_coef, device,
-                                 stream);
+    return sigma_rz_fused_launch("cp_sigma_rz_analytic", engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, pk_params, d_k, f, &b, nullptr, d_growth_sq, nz, d_out,
+                                 d_pk_out, d_work, device, stream);
 }
-
-namespace {
-int sigma_rz_fused_launch(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, const cp_param* pk_params,
-                          const double* d_k, const cp_fftlog_tables_view& f, const cp_spline_band_view* band, const GeoTail* geo, const double* d_growth_sq,
-                          int nz, double* d_out, double* d_pk_out, void* d_coef, int device, void* stream) {
-    const int nq = geo ? geo->nq : band->nq;
-    double* ln_k = reinterpret_cast<double*>(static_cast<char*>(d_coef) + ((cp_power_workspace_bytes(ncosmo) + 63) / 64) * 64);      // behind the coefficients
-    // (validates the massive-neutrino tables; the same launch writes the table of the wavenumbers)
-    int st = cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, pk_params, d_coef, device, stream, d_k, ln_k, f.n);
-    if (st != CP_OK) return st;
-    SigmaArgs S{};
-    S.nsp = ncdm ? ncdm->nspecies : 0;
-    if (S.nsp < 0 || (S.nsp > 0 && !ncdm->tab)) return cp::fail(CP_EINVAL, "cp_sigma_rz_fused: bad massive-neutrino tables");
-    S.ncdm_tab = S.nsp ? ncdm->tab : nullptr;
-    FftlogArgs& A = S.fft;
-    A.in = nullptr; A.out = nullptr; A.nbatch = ncosmo; A.nker = 1; A.n = f.n; A.in_left = f.in_left; A.out_off = f.out_left; A.n_out = f.n;
-    A.ext_l = A.ext_r = CP_EXTRAP_CONST; A.val_l = A.val_r = 0.; A.stream_rows = 0;
-    A.pre = f.d_pre; A.post = f.d_post; A.u = f.d_u; A.tw = f.d_tw;
-    S.ncosmo = ncosmo;
-    cpcosmo::copy_params(S.bg, bg_params, CP_BG_NPARAMS);
-    cpcosmo::copy_params(S.pw, pk_params, CP_PK_NPARAMS);
-    S.second_is_omega_m = second_is_omega_m;
-    S.k = d_k;
-    S.consts = static_cast<const CosmoConsts*>(d_coef);
-    S.ln_k = ln_k;
-    S.nq = nq; S.nz = nz;
-    if (geo) {
-        S.qe = geo->qe; S.qx = geo->qx; S.basis = geo->basis; S.ws = geo->ws;
-    } else {
-        S.wb = band->d_wb; S.j0 = band->d_j0; S.bw = band->bw;
-    }
-    S.growth_sq = d_growth_sq;
-    S.out = d_out;
-    S.pk_out = d_pk_out;
-    cp::DeviceScope scope(device);
-    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_sigma_rz_fused: cannot select device %d", device);
-    using F = Fftlog<NP, P, IN_HALF_ZERO_GEN, OUT_HALF>;
-    const size_t lds = (size_t)F::LDS_BYTES + (size_t)(2 * nq + 2 * nz) * sizeof(double);
-    int ncu = 0;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
-    const long long npairs = (ncosmo + 1) / 2;
-    const size_t per_cu = lds ? (160 * 1024) / lds : 4;
-    const long long resident = (long long)(ncu > 0 ? ncu : 256) * (long long)(per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu));
-    // every workgroup the same number of pairs (5000 pairs on 1024 resident workgroups would leave a fifth of the chip idle in the last round)
-    const long long rounds = (npairs + resident - 1) / resident;
-    const int grid = (int)((npairs + rounds - 1) / rounds);
-    // The workgroups that share a CU (b, b + ncu, b + 2 ncu, ...: the dispatcher deals them out in order) start two s_sleep(127) apart: the first of them
-    // has its first results in memory while the others still evaluate, instead of all four storing at once behind a first evaluation at a quarter of the
-    // CU each (0.327 -> 0.317 ms per 10 000 cosmologies, profiles/r5_sigma_stagger.txt; larger offsets only delay the last workgroup).  Same results.
-    S.stagger_div = ncu > 0 ? ncu : 256; S.stagger_mod = (int)(per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu)); S.stagger_sleeps = rounds >= 2 ? 2 : 0;
-    if (const char* env = std::getenv("CP_SIGMA_STAGGER")) {      // "div,mod,sleeps": measurements (tools/ab_sigma_stagger.py)
-        int d = 1, m = 1, sl = 0;
-        if (std::sscanf(env, "%d,%d,%d", &d, &m, &sl) == 3 && d >= 1 && m >= 1 && sl >= 0 && sl <= 4096) { S.stagger_div = d; S.stagger_mod = m; S.stagger_sleeps = sl; }
-    }
-    hipError_t e = hipSuccess;
-    if (lds > 160 * 1024) return cp::fail(CP_EUNSUPPORTED, "cp_sigma_rz_fused: %d radii x %d redshifts exceed the LDS staging", nq, nz);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    if (engine == CP_ENGINE_EH) e = launch<CP_ENGINE_EH>(S, grid, lds, hs);
-    else if (engine == CP_ENGINE_EH_NOWIGGLE) e = launch<CP_ENGINE_EH_NOWIGGLE>(S, grid, lds, hs);
-    else e = launch<CP_ENGINE_BBKS>(S, grid, lds, hs);
-    return cp::launch_status("cp_sigma_rz_fused", e);
-}
-}  // namespace
 
 // ---- few radii: sigma^2(r_q) as a linear functional of the spectrum --------------------------------------------------------------------------
 // The transform and the spline are linear in P(k): for fixed wavenumbers and radii sigma^2(r_q) = sum_j F[q, j] P(k_j), with F the rows that
@@ -1103,95 +1099,72 @@ __global__ __launch_bounds__(256) void sigma_functional_kernel(const FunctionalA
 
 }  // namespace
 
+namespace {
+
+// What cp_sigma_rz_functional and cp_sigma8_normalise (`normalise`) do behind their own checks of sizes, engine and pointers.  S holds what differs
+// between the two: radii, redshifts and results, or the target and the three results of the normalisation.
+int functional_launch(const char* who, bool normalise, FunctionalArgs& S, int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m,
+                      const cp_ncdm* ncdm, const cp_param* pk_params, int nk, const double* d_k, const double* d_functional, double* d_pk_out, void* d_work,
+                      int device, void* stream) {
+    int nsp;
+    int st = cpcosmo::ncdm_species(ncdm, who, &nsp);
+    if (st != CP_OK) return st;
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
+    const double* knots;
+    st = cpcosmo::ncdm_knots(nsp, device, who, &knots);
+    if (st != CP_OK) return st;
+    const cp::CoefWorkspace w = cp::coef_workspace(d_work, ncosmo);
+    cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, knots, pk_params, w.coef, stream, d_k, w.ln_k, nk);      // (and the table of the wavenumbers)
+    cpcosmo::fill_cosmology(S, ncosmo, bg_params, pk_params, second_is_omega_m, ncdm, nsp, knots, w.coef);
+    S.nk = nk;
+    S.k = d_k;
+    S.ln_k = w.ln_k;
+    S.functional = d_functional;
+    S.pk_out = d_pk_out;
+    const dim3 grid((unsigned)((ncosmo + 3) / 4));
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    cpcosmo::dispatch_engine(engine, [&](auto e) {
+        constexpr int ENGINE = decltype(e)::value;
+        if (normalise) hipLaunchKernelGGL(sigma8_normalise_kernel<ENGINE>, grid, dim3(256), 0, hs, S);
+        else hipLaunchKernelGGL(sigma_functional_kernel<ENGINE>, grid, dim3(256), 0, hs, S);
+    });
+    return cp::launch_status(who);
+}
+
+}  // namespace
+
 extern "C" int cp_sigma_rz_functional(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, const cp_param* pk_params,
-        int nk,
-                                      const double* d_k, const double* d_functional, int nq, const double* d_growth_sq, int nz, double* d_out,
+                                      int nk, const double* d_k, const double* d_functional, int nq, const double* d_growth_sq, int nz, double* d_out,
                                       double* d_pk_out, void* d_work, int device, void* stream) {
     if (ncosmo < 0 || nk <= 0 || nz <= 0 || nq <= 0) return cp::fail(CP_EINVAL, "cp_sigma_rz_functional: bad sizes");
     if (nq > FUNCTIONAL_MAX_NQ) return cp::fail(CP_EUNSUPPORTED, "cp_sigma_rz_functional: %d radii (at most %d: use cp_sigma_rz_analytic)", nq, FUNCTIONAL_MAX_NQ);
-    if (engine != CP_ENGINE_EH && engine != CP_ENGINE_EH_NOWIGGLE && engine != CP_ENGINE_BBKS) return cp::fail(CP_EINVAL, "cp_sigma_rz_functional: unknown engine %d", engine);
+    if (!cpcosmo::engine_known(engine)) return cpcosmo::unknown_engine("cp_sigma_rz_functional", engine);
     if (ncosmo == 0) return CP_OK;
     if (!bg_params || !pk_params || !d_k || !d_functional || !d_growth_sq || !d_out || !d_work) return cp::fail(CP_EINVAL, "cp_sigma_rz_functional: null pointer");
-    char* coef = static_cast<char*>(d_work);
-    coef += (64 - (reinterpret_cast<unsigned long long>(coef) & 63u)) & 63u;
-    double* ln_k = reinterpret_cast<double*>(coef + ((cp_power_workspace_bytes(ncosmo) + 63) / 64) * 64);      // behind the coefficients (cp_sigma_rz_workspace_bytes)
-    int st = cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, pk_params, coef, device, stream, d_k, ln_k, nk);      // (and the table of the wavenumbers)
-    if (st != CP_OK) return st;
-    cp::DeviceScope scope(device);
-    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_sigma_rz_functional: cannot select device %d", device);
     FunctionalArgs S{};
-    {
-        NcdmView nu;
-        st = ncdm_view(ncdm, device, "cp_sigma_rz_functional / cp_sigma8_normalise", &nu);
-        if (st != CP_OK) return st;
-        S.ncdm_tab = nu.tab;
-        S.ncdm_knots = nu.knots;
-        S.nsp = nu.nsp;
-    }
-    S.ncosmo = ncosmo;
-    cpcosmo::copy_params(S.bg, bg_params, CP_BG_NPARAMS);
-    cpcosmo::copy_params(S.pw, pk_params, CP_PK_NPARAMS);
-    S.second_is_omega_m = second_is_omega_m;
-    S.nk = nk; S.nq = nq; S.nz = nz;
-    S.k = d_k;
-    S.consts = reinterpret_cast<const CosmoConsts*>(coef);
-    S.ln_k = ln_k;
-    S.functional = d_functional;
+    S.nq = nq; S.nz = nz;
     S.growth_sq = d_growth_sq;
     S.out = d_out;
-    S.pk_out = d_pk_out;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    const unsigned grid = (unsigned)((ncosmo + 3) / 4);
-    if (engine == CP_ENGINE_EH) hipLaunchKernelGGL(sigma_functional_kernel<CP_ENGINE_EH>, dim3(grid), dim3(256), 0, hs, S);
-    else if (engine == CP_ENGINE_EH_NOWIGGLE) hipLaunchKernelGGL(sigma_functional_kernel<CP_ENGINE_EH_NOWIGGLE>, dim3(grid), dim3(256), 0, hs, S);
-    else hipLaunchKernelGGL(sigma_functional_kernel<CP_ENGINE_BBKS>, dim3(grid), dim3(256), 0, hs, S);
-    return cp::launch_status("cp_sigma_rz_functional");
+    return functional_launch("cp_sigma_rz_functional", false, S, engine, ncosmo, bg_params, second_is_omega_m, ncdm, pk_params, nk, d_k, d_functional, d_pk_out, d_work,
+                             device, stream);
 }
 
 extern "C" int cp_sigma8_normalise(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, const cp_param* pk_params,
-        int nk,
-                                   const double* d_k, const double* d_functional, cp_param sigma8, double* d_rsigma8, double* d_amplitude, double* d_pk_out,
+                                   int nk, const double* d_k, const double* d_functional, cp_param sigma8, double* d_rsigma8, double* d_amplitude, double* d_pk_out,
                                    void* d_work, int device, void* stream) {
     if (ncosmo < 0) return cp::fail(CP_EINVAL, "cp_sigma8_normalise: negative size");
     if (nk != 1024) return cp::fail(CP_EUNSUPPORTED, "cp_sigma8_normalise: %d wavenumbers (built for the 1024 of the default transform)", nk);
-    if (engine != CP_ENGINE_EH && engine != CP_ENGINE_EH_NOWIGGLE && engine != CP_ENGINE_BBKS) return cp::fail(CP_EINVAL, "cp_sigma8_normalise: unknown engine %d", engine);
+    if (!cpcosmo::engine_known(engine)) return cpcosmo::unknown_engine("cp_sigma8_normalise", engine);
     if (ncosmo == 0) return CP_OK;
     if (!bg_params || !pk_params || !d_k || !d_functional || !d_rsigma8 || !d_work) return cp::fail(CP_EINVAL, "cp_sigma8_normalise: null pointer");
-    char* coef = static_cast<char*>(d_work);
-    coef += (64 - (reinterpret_cast<unsigned long long>(coef) & 63u)) & 63u;
-    double* ln_k = reinterpret_cast<double*>(coef + ((cp_power_workspace_bytes(ncosmo) + 63) / 64) * 64);      // behind the coefficients (cp_sigma_rz_workspace_bytes)
-    int st = cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, pk_params, coef, device, stream, d_k, ln_k, nk);      // (and the table of the wavenumbers)
-    if (st != CP_OK) return st;
-    cp::DeviceScope scope(device);
-    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_sigma8_normalise: cannot select device %d", device);
     FunctionalArgs S{};
-    {
-        NcdmView nu;
-        st = ncdm_view(ncdm, device, "cp_sigma_rz_functional / cp_sigma8_normalise", &nu);
-        if (st != CP_OK) return st;
-        S.ncdm_tab = nu.tab;
-        S.ncdm_knots = nu.knots;
-        S.nsp = nu.nsp;
-    }
-    S.ncosmo = ncosmo;
-    cpcosmo::copy_params(S.bg, bg_params, CP_BG_NPARAMS);
-    cpcosmo::copy_params(S.pw, pk_params, CP_PK_NPARAMS);
-    S.second_is_omega_m = second_is_omega_m;
-    S.nk = nk; S.nq = 1; S.nz = 1;
-    S.k = d_k;
-    S.consts = reinterpret_cast<const CosmoConsts*>(coef);
-    S.ln_k = ln_k;
-    S.functional = d_functional;
-    S.pk_out = d_pk_out;
+    S.nq = 1; S.nz = 1;
     S.target = Param{sigma8.ptr, sigma8.value};
     S.rsigma8_out = d_rsigma8;
     S.amplitude_out = d_amplitude;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    const unsigned grid = (unsigned)((ncosmo + 3) / 4);
-    if (engine == CP_ENGINE_EH) hipLaunchKernelGGL(sigma8_normalise_kernel<CP_ENGINE_EH>, dim3(grid), dim3(256), 0, hs, S);
-    else if (engine == CP_ENGINE_EH_NOWIGGLE) hipLaunchKernelGGL(sigma8_normalise_kernel<CP_ENGINE_EH_NOWIGGLE>, dim3(grid), dim3(256), 0, hs, S);
-    else hipLaunchKernelGGL(sigma8_normalise_kernel<CP_ENGINE_BBKS>, dim3(grid), dim3(256), 0, hs, S);
-    return cp::launch_status("cp_sigma8_normalise");
+    return functional_launch("cp_sigma8_normalise", true, S, engine, ncosmo, bg_params, second_is_omega_m, ncdm, pk_params, nk, d_k, d_functional, d_pk_out, d_work, device,
+                             stream);
 }
 
 // FFTLog of (nbatch, n) rows followed by the spline of every output row to the plan's queries (root taken when post_op is CP_SPLINE_POST_SQRT), as one
@@ -1208,11 +1181,7 @@ extern "C" int cp_fftlog_spline_execute(const cp_fftlog_plan* fftlog, const cp_s
     (void)cp_fftlog_plan_view(fftlog, &f);
     (void)cp_spline_plan_view(spline, &b);
     RowsArgs R{};
-    FftlogArgs& A = R.fft;
-    A.in = d_in; A.out = nullptr; A.nbatch = nbatch; A.nker = 1; A.n = f.n; A.in_left = f.in_left; A.out_off = f.out_left; A.n_out = f.n;
-    A.ext_l = A.ext_r = CP_EXTRAP_CONST; A.val_l = A.val_r = 0.;
-    A.stream_rows = (double)nbatch * f.n * 8. > 512. * 1024. * 1024. ? 3 : 0;
-    A.pre = f.d_pre; A.post = f.d_post; A.u = f.d_u; A.tw = f.d_tw;
+    R.fft = fused_fftlog_args(f, d_in, nbatch);
     R.wb = b.d_wb; R.j0 = b.d_j0; R.bw = b.bw; R.nq = b.nq; R.post_sqrt = post_op == CP_SPLINE_POST_SQRT;
     R.out = d_out;
     cp::DeviceScope scope(f.device);
@@ -1221,14 +1190,7 @@ extern "C" int cp_fftlog_spline_execute(const cp_fftlog_plan* fftlog, const cp_s
     const size_t lds = (size_t)F::LDS_BYTES + (size_t)(2 * b.nq) * sizeof(double);
     if (lds > 160 * 1024) return cp::fail(CP_EUNSUPPORTED, "cp_fftlog_spline_execute: %d queries exceed the LDS staging", b.nq);
     if (lds > 64 * 1024) (void)cp::allow_full_lds<&fftlog_spline_kernel>();
-    int ncu = 0;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, f.device);
-    const long long npairs = (nbatch + 1) / 2;
-    const size_t per_cu = (160 * 1024) / lds;
-    const long long resident = (long long)(ncu > 0 ? ncu : 256) * (long long)(per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu));
-    const long long rounds = (npairs + resident - 1) / resident;
-    const int grid = (int)((npairs + rounds - 1) / rounds);
-    hipLaunchKernelGGL(fftlog_spline_kernel, dim3(grid), dim3(NP / P), lds, static_cast<hipStream_t>(stream), R);
+    hipLaunchKernelGGL(fftlog_spline_kernel, dim3(pairs_grid(nbatch, lds, f.device)), dim3(NP / P), lds, static_cast<hipStream_t>(stream), R);
     return cp::launch_status("cp_fftlog_spline_execute");
 }
 
@@ -1471,18 +1433,20 @@ extern "C" int cp_sigma_rz_analytic_prefiltered(int engine, long long ncosmo, co
                                                 const cp_param* pk_params, int nk, const double* d_k, const cp_geospline_plan* spline,
                                                 const double* d_growth_sq, int nz, double* d_out, double* d_pk_out, void* d_work, int device, void* stream) {
     if (ncosmo < 0 || nk <= 0 || nz <= 0) return cp::fail(CP_EINVAL, "cp_sigma_rz_analytic_prefiltered: bad sizes");
+    if (!cpcosmo::engine_known(engine)) return cpcosmo::unknown_engine("cp_sigma_rz_analytic_prefiltered", engine);
     if (ncosmo == 0) return CP_OK;
     if (!bg_params || !pk_params || !d_k || !spline || !d_growth_sq || !d_out || !d_work) return cp::fail(CP_EINVAL, "cp_sigma_rz_analytic_prefiltered: null pointer");
+    int nsp;
+    const int st = cpcosmo::ncdm_species(ncdm, "cp_sigma_rz_analytic_prefiltered", &nsp);
+    if (st != CP_OK) return st;
     if (!spline->prefiltered) return cp::fail(CP_EINVAL, "cp_sigma_rz_analytic_prefiltered: the spline plan carries no transform (cp_geospline_plan_create_prefiltered)");
     if (spline->n != nk) return cp::fail(CP_EINVAL, "cp_sigma_rz_analytic_prefiltered: the spline plan has %d knots, the spectra %d samples", spline->n, nk);
     if (spline->device != device) return cp::fail(CP_EINVAL, "cp_sigma_rz_analytic_prefiltered: the spline plan lives on device %d", spline->device);
     cp_fftlog_tables_view f;
     if (!cp_fftlog_plan_view(spline->prefiltered, &f)) return cp::fail(CP_EINVAL, "cp_sigma_rz_analytic_prefiltered: plan without device tables");
     const GeoTail geo{spline->nq, spline->ws, spline->d_qe, spline->d_qa, &spline->d_consts->basis};
-    char* coef = static_cast<char*>(d_work);
-    coef += (64 - (reinterpret_cast<unsigned long long>(coef) & 63u)) & 63u;
-    return sigma_rz_fused_launch(engine, ncosmo, bg_params, second_is_omega_m, ncdm, pk_params, d_k, f, nullptr, &geo, d_growth_sq, nz, d_out, d_pk_out, coef, device,
-                                 stream);
+    return sigma_rz_fused_launch("cp_sigma_rz_analytic_prefiltered", engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, pk_params, d_k, f, nullptr, &geo, d_growth_sq, nz,
+                                 d_out, d_pk_out, d_work, device, stream);
 }
 
 extern "C" int cp_geospline_plan_info(const cp_geospline_plan* p, int* first_knot, int* nknots, int* nq) {
@@ -1511,11 +1475,7 @@ extern "C" int cp_fftlog_geospline_execute(const cp_fftlog_plan* fftlog, const c
         return cp::fail(CP_EUNSUPPORTED, "cp_fftlog_geospline_execute: transform outside the fused kernel's shape (1024 samples padded to 2048, one kernel)");
     if (spline->n != f.n || spline->device != f.device) return cp::fail(CP_EINVAL, "cp_fftlog_geospline_execute: the spline plan is for %d knots on device %d", spline->n, spline->device);
     GeoArgs R{};
-    FftlogArgs& A = R.fft;
-    A.in = d_in; A.out = nullptr; A.nbatch = nbatch; A.nker = 1; A.n = f.n; A.in_left = f.in_left; A.out_off = f.out_left; A.n_out = f.n;
-    A.ext_l = A.ext_r = CP_EXTRAP_CONST; A.val_l = A.val_r = 0.;
-    A.stream_rows = (double)nbatch * f.n * 8. > 512. * 1024. * 1024. ? 3 : 0;
-    A.pre = f.d_pre; A.post = f.d_post; A.u = f.d_u; A.tw = f.d_tw;
+    R.fft = fused_fftlog_args(f, d_in, nbatch);
     R.ws = spline->ws; R.ne = spline->ne; R.S = spline->S; R.nq = spline->nq; R.post_sqrt = post_op == CP_SPLINE_POST_SQRT; R.group = group;
     R.ntables = group > 0 ? (int)(nbatch / group) : (int)((nbatch + 1) / 2);
     R.pt = group > 0 ? group / 2 : 1;
@@ -1530,19 +1490,14 @@ extern "C" int cp_fftlog_geospline_execute(const cp_fftlog_plan* fftlog, const c
     if (lds > 64 * 1024)
         (void)(!coef ? cp::allow_full_lds<&fftlog_geospline_kernel<false>>()
                      : few ? cp::allow_full_lds<&fftlog_geospline_kernel<true, 4>>() : cp::allow_full_lds<&fftlog_geospline_kernel<true, GEO_QMAX>>());
-    int ncu = 0;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, f.device);
-    const long long npairs = (nbatch + 1) / 2;
-    const size_t per_cu = (160 * 1024) / lds;
-    const long long resident = (long long)(ncu > 0 ? ncu : 256) * (long long)(per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu));
+    const long long resident = (long long)cp::cu_count(f.device) * workgroups_per_cu(lds);
     long long grid;
     if (group > 0) {      // a multiple of 8 (one share per XCD), every workgroup of an XCD the same number of rounds
         const long long per_xcd = ((nbatch / group + 7) / 8) * (group / 2), slots = std::max(1LL, resident / 8);
         const long long rounds = (per_xcd + slots - 1) / slots;
         grid = 8 * ((per_xcd + rounds - 1) / rounds);
     } else {
-        const long long rounds = (npairs + resident - 1) / resident;
-        grid = (npairs + rounds - 1) / rounds;
+        grid = cp::balanced_grid((nbatch + 1) / 2, resident);
     }
     if (coef && few) hipLaunchKernelGGL((fftlog_geospline_kernel<true, 4>), dim3((unsigned)grid), dim3(NP / P), lds, static_cast<hipStream_t>(stream), R);
     else if (coef) hipLaunchKernelGGL((fftlog_geospline_kernel<true, GEO_QMAX>), dim3((unsigned)grid), dim3(NP / P), lds, static_cast<hipStream_t>(stream), R);

@@ -46,27 +46,22 @@ class DST(object):
         box = (margin_first, margin_second, offset_first, offset_second): also the next step of the filter in the kernel's epilogue
         (``cp_dst_forward_analytic_box``: split layout, boxes rewritten); returns (coefficients, boxes (2 ncosmo, 2) int32)."""
         torch = dv.torch()
-        from .background import DEFAULTS as bg_defaults
-        from .power import PK_DEFAULTS
         if self.n != 4096 or engine not in _lib.ENGINES:
             return None
-        cbg, n1, keep1 = dv.pack_params(_lib.BG_PARAMS, bg, bg_defaults, self.device)
-        cpk, n2, keep2 = dv.pack_params(_lib.PK_PARAMS, pk, PK_DEFAULTS, self.device)
-        sizes = {n for n in (n1, n2) if n is not None}
-        if len(sizes) != 1:
+        args, ncosmo, keep = dv.pack_cosmologies(bg, pk, self.device)
+        if ncosmo is None:
             return None
-        ncosmo = sizes.pop()
         lib = _lib.load()
         out = torch.empty((ncosmo, self.n), dtype=torch.float64, device=self.device)
         work = torch.empty(int(lib.cp_dst_forward_analytic_workspace_bytes(ncosmo)), dtype=torch.uint8, device=self.device)
-        nu, keep_nu = dv.ncdm_arg(bg, ncosmo)
+        args = args()
         if box is not None:
             boxes = torch.empty((2 * ncosmo, 2), dtype=torch.int32, device=self.device)
-            _lib.check(lib.cp_dst_forward_analytic_box(self._handle, _lib.ENGINES[engine], ncosmo, dv.as_void_p(cbg), 0, nu, dv.as_void_p(cpk), out.data_ptr(),
-                                                       work.data_ptr(), boxes.data_ptr(), int(box[0]), int(box[1]), int(box[2]), int(box[3]), dv.stream_of(self.device)))
+            _lib.check(lib.cp_dst_forward_analytic_box(self._handle, _lib.ENGINES[engine], *args, out.data_ptr(), work.data_ptr(), boxes.data_ptr(),
+                                                       int(box[0]), int(box[1]), int(box[2]), int(box[3]), dv.stream_of(self.device)))
             return out, boxes
-        _lib.check(lib.cp_dst_forward_analytic(self._handle, _lib.ENGINES[engine], ncosmo, dv.as_void_p(cbg), 0, nu, dv.as_void_p(cpk), out.data_ptr(), work.data_ptr(),
-                                               2 if split else 0, dv.stream_of(self.device)))
+        _lib.check(lib.cp_dst_forward_analytic(self._handle, _lib.ENGINES[engine], *args, out.data_ptr(), work.data_ptr(), 2 if split else 0,
+                                               dv.stream_of(self.device)))
         return out
 
     def __del__(self):

@@ -1208,12 +1208,9 @@ def sigma_rz_analytic(engine, bg, pk, r, growth_sq, device, kmin=1e-7, kmax=1e2,
     (batch, 1024) (the sigma8 normalisation keeps them: the filters ask for P on the same wavenumbers next).  None when the parameter arrays do
     not match the batch of ``growth_sq`` (batch, nz)."""
     torch = dv.torch()
-    from .background import DEFAULTS as bg_defaults
-    from .power import PK_DEFAULTS
     nb, nz = growth_sq.shape
-    cbg, n1, keep1 = dv.pack_params(_lib.BG_PARAMS, bg, bg_defaults, device)
-    cpk, n2, keep2 = dv.pack_params(_lib.PK_PARAMS, pk, PK_DEFAULTS, device)
-    if {n for n in (n1, n2) if n is not None} - {nb}:
+    args, n, keep = dv.pack_cosmologies(bg, pk, device, ncosmo=nb)
+    if n is None:
         return None
     nk = 1024
     k = np.geomspace(kmin, kmax, nk)
@@ -1227,13 +1224,13 @@ def sigma_rz_analytic(engine, bg, pk, r, growth_sq, device, kmin=1e-7, kmax=1e2,
     spectra = torch.empty((nb, nk), dtype=torch.float64, device=device) if keep_spectra else None
     work = torch.empty(int(lib.cp_sigma_rz_workspace_bytes(nb, nk)), dtype=torch.uint8, device=device)
     growth_sq = growth_sq.contiguous()
-    nu, keep_nu = dv.ncdm_arg(bg, nb)
+    args = args()
     if 1 <= rr.size <= _FUNCTIONAL_RADII and blocks == 0:
         # few radii (sigma8: one): transform and spline are linear in P(k) -- sigma^2(r_q) = sum_j F[q, j] P(k_j), F = what the two return for unit
         # spectra, computed once per (grid, radii) -- and the kernel is the evaluation of P(k) with a dot product behind it
         functional = _cached_operator(('sigma_functional', key, rr.tobytes()),
                                       lambda: op(fft(torch.eye(nk, dtype=torch.float64, device=device))[1]).transpose(0, 1).contiguous())
-        _lib.check(lib.cp_sigma_rz_functional(_lib.ENGINES[engine], nb, dv.as_void_p(cbg), 0, nu, dv.as_void_p(cpk), nk, dv.upload(k, device).data_ptr(),
+        _lib.check(lib.cp_sigma_rz_functional(_lib.ENGINES[engine], *args, nk, dv.upload(k, device).data_ptr(),
                                               functional.data_ptr(), rr.size, growth_sq.data_ptr(), nz, out.data_ptr(),
                                               spectra.data_ptr() if keep_spectra else None, work.data_ptr(), device.index, dv.stream_of(device)))
         return out, spectra, k
@@ -1242,11 +1239,11 @@ def sigma_rz_analytic(engine, bg, pk, r, growth_sq, device, kmin=1e-7, kmax=1e2,
         native = fft._get_plan(device)
         geo = _cached_operator(('geospline', id(native), True, s.tobytes(), rr.tobytes(), device.index), lambda: _GeoSpline(s, rr, device, fft=fft, keep=native))
         if geo.prefiltered:
-            _lib.check(lib.cp_sigma_rz_analytic_prefiltered(_lib.ENGINES[engine], nb, dv.as_void_p(cbg), 0, nu, dv.as_void_p(cpk), nk,
-                                                            dv.upload(k, device).data_ptr(), geo.handle, growth_sq.data_ptr(), nz, out.data_ptr(),
-                                                            spectra.data_ptr() if keep_spectra else None, work.data_ptr(), device.index, dv.stream_of(device)))
+            _lib.check(lib.cp_sigma_rz_analytic_prefiltered(_lib.ENGINES[engine], *args, nk, dv.upload(k, device).data_ptr(), geo.handle,
+                                                            growth_sq.data_ptr(), nz, out.data_ptr(), spectra.data_ptr() if keep_spectra else None,
+                                                            work.data_ptr(), device.index, dv.stream_of(device)))
             return out, spectra, k
-    _lib.check(lib.cp_sigma_rz_analytic(_lib.ENGINES[engine], nb, dv.as_void_p(cbg), 0, nu, dv.as_void_p(cpk), nk, dv.upload(k, device).data_ptr(),
+    _lib.check(lib.cp_sigma_rz_analytic(_lib.ENGINES[engine], *args, nk, dv.upload(k, device).data_ptr(),
                                         fft._get_plan(device).handle, op._handle, growth_sq.data_ptr(), nz, out.data_ptr(),
                                         spectra.data_ptr() if keep_spectra else None, work.data_ptr(), blocks, device.index, dv.stream_of(device)))
     return out, spectra, k
@@ -1258,14 +1255,10 @@ def sigma8_normalise(engine, bg, pk, sigma8, device, kmin=1e-7, kmax=1e2):
     (rsigma8 (batch,), A_s rsigma8^2 (batch,), spectra without growth at the normalised amplitude (batch, 1024), their wavenumbers), or None when
     the parameters are not a batch."""
     torch = dv.torch()
-    from .background import DEFAULTS as bg_defaults
-    from .power import PK_DEFAULTS
-    cbg, n1, keep1 = dv.pack_params(_lib.BG_PARAMS, bg, bg_defaults, device)
-    cpk, n2, keep2 = dv.pack_params(_lib.PK_PARAMS, pk, PK_DEFAULTS, device)
-    sizes = {n for n in (n1, n2) if n is not None}
-    if len(sizes) != 1:
+    args, nb, keep = dv.pack_cosmologies(bg, pk, device)
+    if nb is None:
         return None
-    nb, nk = sizes.pop(), 1024
+    nk = 1024
     k = np.geomspace(kmin, kmax, nk)
     key = (float(kmin), float(kmax), nk, device.index)
     fft = _tophat_plan(key, k, device)
@@ -1286,8 +1279,7 @@ def sigma8_normalise(engine, bg, pk, sigma8, device, kmin=1e-7, kmax=1e2):
     amplitude = torch.empty(nb, dtype=torch.float64, device=device)
     spectra = torch.empty((nb, nk), dtype=torch.float64, device=device)
     work = torch.empty(int(lib.cp_sigma_rz_workspace_bytes(nb, nk)), dtype=torch.uint8, device=device)
-    nu, keep_nu = dv.ncdm_arg(bg, nb)
-    _lib.check(lib.cp_sigma8_normalise(_lib.ENGINES[engine], nb, dv.as_void_p(cbg), 0, nu, dv.as_void_p(cpk), nk, dv.upload(k, device).data_ptr(),
+    _lib.check(lib.cp_sigma8_normalise(_lib.ENGINES[engine], *args(), nk, dv.upload(k, device).data_ptr(),
                                        functional.data_ptr(), target, rsigma8.data_ptr(), amplitude.data_ptr(), spectra.data_ptr(), work.data_ptr(),
                                        device.index, dv.stream_of(device)))
     return rsigma8, amplitude, spectra, k
