@@ -200,10 +200,12 @@ SIGNATURES['cp_taylor_predict'] = (ctypes.c_int, _TAYLOR_HEAD + [ctypes.c_void_p
 SIGNATURES['cp_taylor_predict_columns'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + _WHERE)
 SIGNATURES['cp_taylor_jacobian'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + _WHERE)
 SIGNATURES['cp_taylor_vjp'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong] + _WHERE)      # d_cot, ldc; d_grad, d_work, work_doubles
+SIGNATURES['cp_taylor_jvp'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + _ARRAY + _WHERE)      # d_tan, K; d_out, ldo
 SIGNATURES['cp_mlp_predict'] = (ctypes.c_int, _MLP_HEAD + [ctypes.c_void_p] + _WHERE)
 SIGNATURES['cp_mlp_predict_columns'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _WHERE)
 SIGNATURES['cp_mlp_jacobian'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _ARRAY + _WHERE)      # d_value, ldv; d_jac, ldj
 SIGNATURES['cp_mlp_vjp'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _ARRAY + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong] + _WHERE)      # d_cot, ldc; d_value, ldv; d_grad, d_work, work_doubles
+SIGNATURES['cp_mlp_jvp'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _ARRAY + _ARRAY + _WHERE)      # d_tan, K; d_value, ldv; d_out, ldo
 SIGNATURES['cp_taylor_fit'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_mlp_param_count'] = (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int])
 SIGNATURES['cp_mlp_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int])

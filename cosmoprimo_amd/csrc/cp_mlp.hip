@@ -32,7 +32,10 @@
 // group of modes stores the pre-activations as the training pass does and, in its epilogue, the weighted cotangent w = cot yscale f'(v) beside (or
 // instead of) the prediction; mlp_dh_kernel multiplies w by the transposed columns of the output kernel; mlp_input_grad_kernel sums its slices and
 // walks the hidden layers back in LDS.  No (B, ndim, .) array exists anywhere.  Details above the kernels.
-// Host side.  cp_mlp_predict(_columns), cp_mlp_jacobian and cp_mlp_vjp are three back ends of one front: mlp_front holds their common checks and fills the
+// Jacobian-vector product (cp_mlp_jvp: out (B K, .) = tan . d predict / d x along K directions per point; mlp_forward_kernel, then mlp_jvp_kernel).  The
+// tangent kernel with a row per (point, direction) pair and the input tangent tan[b][k][i] / xscale[i]: the same LDS, registers and occupancy, and with
+// K = ndim identity tangents the same bits.  No (B, ndim, .) array exists anywhere.
+// Host side.  cp_mlp_predict(_columns), cp_mlp_jacobian, cp_mlp_vjp and cp_mlp_jvp are back ends of one front: mlp_front holds their common checks and fills the
 // forward kernel's arguments, mlp_yfunction turns the y function into a template argument, mlp_dh_launch picks mlp_dh_kernel<NJ> (vjp and training step);
 // an entry point adds its strides, grid cap, null pointers, workspace and ONE device scope, in that order.  No device function is shared between kernels
 // beyond those above: every kernel is held to its instructions.
@@ -489,6 +492,160 @@ __global__ __launch_bounds__(256, 2) void mlp_tangent_kernel(const MlpJacArgs A)
     }
 }
 
+// Directional derivatives (cp_mlp_jvp): mlp_tangent_kernel with a row per (point, direction) pair r = b K + k and dh_0[i] = tan[b][k][i] / xscale[i] in the
+// place of e_i / xscale[i] -- the same tile, LDS buffers, in-place layer update, MFMA sequence and epilogue, operation for operation, so that K = ndim
+// identity tangents give the bits of cp_mlp_jacobian.  J.R = B K rows, J.jac the (B K, ncols) result.  (Written out, not shared with the tangent kernel
+// through a device function: that changed the tangent kernel's instructions.)
+struct MlpJvpArgs {
+    MlpJacArgs J;
+    const double* tan;        // (B, K, ndim), raw-parameter units
+    int K;
+};
+
+template <int MODE>
+__global__ __launch_bounds__(256, 2) void mlp_jvp_kernel(const MlpJvpArgs P) {
+    const MlpJacArgs& A = P.J;
+    const int nd = P.K;
+    extern __shared__ double ml_lds[];
+    constexpr int PS = 64;      // row stride of the primal buffers
+    const MlpNet& N = A.net;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int l15 = lane & 15, g = lane >> 4;
+    const long long row0 = (long long)blockIdx.x * ML_ROWS;
+    const long long b0 = row0 / nd;      // the tile's first point and the direction its first row stands for: row0 + t is point b0 + (k0 + t) / K
+    const int i0 = (int)(row0 - b0 * nd);
+    const int c0 = A.c0, cend = A.cend;
+    const int col0 = c0 + (int)blockIdx.y * ML_COLS + wave * 64;
+    double* const curt = ml_lds;                    // tangents, nr x ML_RS
+    double* const curp = ml_lds + N.nr * ML_RS;     // primal activations, nr x PS
+    {      // the inputs of the tile's rows and their tangents, k-major; rows past the end: finite, never stored
+        const bool inside = row0 + lane < A.R;
+        const long long b = b0 + (i0 + lane) / nd;
+        const double* tan = P.tan + (row0 + lane) * N.ndim;      // row r = b K + k: tan[b][k] is row r of the (B K, ndim) array
+        for (int i = wave; i < N.ndim; i += 4) {
+            double v = 0., t = 0.;
+            if (inside) {
+                const double xs = A.xscale[i];
+                v = (A.x[b * N.ndim + i] - A.xoff[i]) / xs;
+                t = tan[i] / xs;
+            }
+            curp[i * PS + lane] = v;
+            curt[i * ML_RS + lane] = t;
+        }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int l = 0; l < N.L; ++l) {
+        const int nin = N.d[l], nout = N.d[l + 1], act = N.act[l];
+        const double* W = A.params + N.off[l];
+        const double* bias = W + nin * nout;
+        const double alpha = bias[nout], beta = bias[nout + 1];
+        // the layer in place: a wave's neurons j = wave + 4 q (at most 16: four groups of four) stay in registers until every wave has read the inputs
+        double hn[4][4], tn[4][4];
+#pragma unroll
+        for (int grp = 0; grp < 4; ++grp) {
+            const int j0 = wave + 16 * grp;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) hn[grp][q] = tn[grp][q] = 0.;
+            if (j0 >= nout) continue;      // (wave-uniform)
+            int jq[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) jq[q] = j0 + 4 * q < nout ? j0 + 4 * q : j0;
+            double accz[4] = {0., 0., 0., 0.}, acct[4] = {0., 0., 0., 0.};
+#pragma unroll 2
+            for (int k = 0; k < nin; ++k) {
+                const double hv = curp[k * PS + lane], tv = curt[k * ML_RS + lane];
+                const double* wr = W + k * nout;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const double w = wr[jq[q]];
+                    accz[q] = fma(hv, w, accz[q]);
+                    acct[q] = fma(tv, w, acct[q]);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                double dval;
+                activate_tangent(act, accz[q] + bias[jq[q]], alpha, beta, hn[grp][q], dval);
+                tn[grp][q] = dval * acct[q];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int grp = 0; grp < 4; ++grp)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int j = wave + 16 * grp + 4 * q;
+                if (j < nout) {
+                    curp[j * PS + lane] = hn[grp][q];
+                    curt[j * ML_RS + lane] = tn[grp][q];
+                }
+            }
+        for (int j = nout + wave; j < ((nout + 7) & ~7); j += 4) curt[j * ML_RS + lane] = 0.;      // the left operand's rows up to the next pair of MFMA steps
+        __syncthreads();
+    }
+    // the output layer on the matrix cores: acc = dh_L . W_out[:, columns]
+    const int K = N.d[N.L], M = N.M;
+    const double* Wo = A.params + N.off[N.L];
+    const bool active = col0 < cend;      // (wave-uniform; an idle wave multiplies the last column: no branch round the MFMAs)
+    ml_v4d acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = ml_v4d{0., 0., 0., 0.};
+    int colj[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int col = col0 + 16 * j + l15;
+        colj[j] = col < cend ? col : cend - 1;      // columns past the end of the range repeat its last one (never stored)
+    }
+    {
+        const int npairs = (K + 7) / 8;
+        double a0[2][4], b0[2][4];
+        bool keep[2];
+        mlp_load(Wo, K, M, curt, 0, l15, g, colj, a0, b0, keep);
+        mlp_mask(b0, keep);
+#pragma unroll 1
+        for (int p = 0; p < npairs; ++p) {
+            double a1[2][4], b1[2][4];
+            mlp_load(Wo, K, M, curt, p + 1 < npairs ? p + 1 : p, l15, g, colj, a1, b1, keep);
+            __builtin_amdgcn_sched_barrier(0);      // the loads are issued here, not moved below the MFMAs
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[h][i], b0[h][j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) a0[h][i] = a1[h][i], b0[h][i] = b1[h][i];
+            __builtin_amdgcn_sched_barrier(0);
+            mlp_mask(b0, keep);
+        }
+    }
+    if (!active) return;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int col = col0 + 16 * j + l15;
+        if (col >= cend) continue;
+        const double ys = A.yscale[col];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int t = 16 * i + g + 4 * r;
+                if (row0 + t >= A.R) continue;
+                double d = ys;
+                if (MODE != CP_MLP_Y_NONE) {
+                    const double y = A.value[(b0 + (i0 + t) / nd) * A.ldv + (col - c0)];
+                    d *= MODE == CP_MLP_Y_EXP10 ? 2.302585092994045684 * y : sqrt(fma(y, y, 1.));
+                }
+                A.jac[(row0 + t) * A.ldj + (col - c0)] = acc[i][j][r] * d;
+            }
+    }
+}
+
 // dst[0] = scale * sum src[0 .. n): one workgroup of 1024 threads, a thread the entries t, t + 1024, ... in order, then the threads in order
 __global__ __launch_bounds__(1024) void mlp_sum_kernel(const double* src, long long n, double scale, double* dst) {
     __shared__ double part[1024];
@@ -869,7 +1026,19 @@ int mlp_tangent_launch(const char* who, const MlpJacArgs& A, void* stream) {
     return CP_OK;
 }
 
-// What cp_mlp_predict, cp_mlp_predict_columns, cp_mlp_jacobian and cp_mlp_vjp share: their checks up to the range of columns, in that order, then the
+template <int MODE>
+int mlp_jvp_launch(const char* who, const MlpJvpArgs& A, void* stream) {
+    const long long nrt = (A.J.R + ML_ROWS - 1) / ML_ROWS, nct = (A.J.cend - A.J.c0 + ML_COLS - 1) / ML_COLS;      // (checked by the caller)
+    const size_t lds = (size_t)A.J.net.nr * (ML_RS + 64) * sizeof(double);      // 36 KB at widths <= 32, at most 72 KB
+    if (lds > 64 * 1024) {
+        const hipError_t e = cp::allow_full_lds<mlp_jvp_kernel<MODE>>();
+        if (e != hipSuccess) return cp::launch_status(who, e);
+    }
+    hipLaunchKernelGGL(mlp_jvp_kernel<MODE>, dim3((unsigned)nrt, (unsigned)nct), dim3(256), lds, static_cast<hipStream_t>(stream), A);
+    return CP_OK;
+}
+
+// What cp_mlp_predict, cp_mlp_predict_columns, cp_mlp_jacobian, cp_mlp_vjp and cp_mlp_jvp share: their checks up to the range of columns, in that order, then the
 // network, the inputs and the range in F.  What follows is the entry point's own: its strides, its grid cap, the empty batch, its null pointers, its
 // workspace, the device, and the outputs in F.
 int mlp_front(const char* who, const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
@@ -976,6 +1145,34 @@ extern "C" int cp_mlp_jacobian(const double* d_x, long long B, int ndim, int nla
     const int launched = mlp_yfunction(yfunction, [&](auto y) {
         const int forward = mlp_forward_launch<decltype(y)::value>(who, F, stream);
         return forward != CP_OK ? forward : mlp_tangent_launch<decltype(y)::value>(who, J, stream);
+    });
+    if (launched != CP_OK) return launched;
+    return cp::launch_status(who);
+}
+
+// Two launches on the stream as in cp_mlp_jacobian: the forward kernel writes the prediction on the range, mlp_jvp_kernel reads it
+extern "C" int cp_mlp_jvp(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
+                          const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
+                          long long ncols, const double* d_tan, long long K, double* d_value, long long ldv, double* d_out, long long ldo, int device,
+                          void* stream) {
+    const char* who = "cp_mlp_jvp";
+    MlpFwdArgs F{};
+    const int status = mlp_front(who, d_x, B, ndim, nlayers, widths, activations, M, d_params, d_xoffset, d_xscale, d_yoffset, d_yscale, yfunction, col0, ncols, &F);
+    if (status != CP_OK) return status;
+    if (ldv < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the value is less than its %lld columns", who, ldv, ncols);
+    if (ldo < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the result is less than its %lld columns", who, ldo, ncols);
+    if (K < 1) return cp::fail(CP_EINVAL, "%s: %lld directions per point (at least 1)", who, K);
+    if (K > 0x7fffffffLL || B > 0x7fffffffLL * ML_ROWS / K || (ncols + ML_COLS - 1) / ML_COLS > 65535)
+        return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %lld x %lld results (at most 2^37 rows B K, 2^31 - 1 directions, 2^24 - 256 columns)", who, B, K, ncols);
+    if (B == 0) return CP_OK;
+    if (!d_x || !d_params || !d_xoffset || !d_xscale || !d_yoffset || !d_yscale || !d_tan || !d_value || !d_out) return cp::fail(CP_EINVAL, "%s: null pointer", who);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
+    F.out = d_value, F.ldo = ldv;
+    const MlpJvpArgs J{{d_x, d_params, d_xoffset, d_xscale, d_yscale, d_value, d_out, B * K, ldv, ldo, F.c0, F.cend, F.net}, d_tan, (int)K};
+    const int launched = mlp_yfunction(yfunction, [&](auto y) {
+        const int forward = mlp_forward_launch<decltype(y)::value>(who, F, stream);
+        return forward != CP_OK ? forward : mlp_jvp_launch<decltype(y)::value>(who, J, stream);
     });
     if (launched != CP_OK) return launched;
     return cp::launch_status(who);

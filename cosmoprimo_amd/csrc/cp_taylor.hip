@@ -24,6 +24,8 @@
 // the front end of the fit -- both operands are then contiguous as that front end wants them, the left one (cot, row stride lda) along the contraction
 // and the right one, rows [col0, col0 + ncols) of a TRANSPOSED copy (M, T) of the derivatives that the caller keeps, along the terms -- and
 // taylor_input_grad_kernel contracts S with the derivatives of the monomials, which it forms as the jacobian front end does.  No (B, ndim, .) array exists.
+// Jacobian-vector product (cp_taylor_jvp: out (B K, M) = [tan . d monomials / d x] (B K, T) . derivatives along K directions per point).  One launch of
+// taylor_jvp_kernel, the GEMM with a fourth front end of its left operand as a kernel of its own; details above it.  No (B, ndim, .) array exists.
 #include "cp_internal.h"
 
 namespace {
@@ -215,6 +217,145 @@ __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const TaylorArgs A)
     }
 }
 
+// Directional derivatives (cp_taylor_jvp): out (B K, M) = [sum_i tan[b][k][i] d mono_t / d x_i] (B K, T) . derivatives -- the tile, chunks, operand fetch and
+// MFMA sequence of taylor_gemm_kernel with one more front end of its left operand (a kernel of its own: TaylorArgs, and with it every symbol of the GEMM,
+// stays what it is).  A row is a (point, direction) pair r = b K + k; 64 is no multiple of most K, so a point's rows may lie in two workgroups and every
+// lane finds its own b.  A wave forms whole terms, lane = row: one pass over the powers of the term (wave-uniform) marks the parameters with p_ti > 0 in
+// a mask and packs their powers into scalar registers; then, per marked i in parameter order, d mono_t / d x_i is the product over the marked j IN THEIR ORDER of p d^(p - 1) (j = i) or d^p (else),
+// each factor formed as the jacobian front end forms it, and is added as fma(tan_i, ., sum).  A parameter with p_ti = 0 is skipped, not added as 0 x: a
+// NaN or Inf in a parameter, or in its tangent component, that only ever has power 0 never reaches the result; with K = ndim identity tangents the
+// entry is fma(1, m_i, 0 + 0 x m_j ...) = the jacobian front end's m_i, bit for bit on finite inputs.
+// LDS: the two operand buffers, x - center (ndim, 64) and the tangents (ndim, 64): 40 KB + 2 x ndim x 512 bytes, at most 72 KB -- two workgroups per CU.
+struct TaylorJvpArgs {
+    TaylorArgs G;           // a: x (B, ndim); R = B K rows of the result
+    const double* tan;      // (B, K, ndim)
+    int Kdir;               // K directions per point
+};
+
+__global__ __launch_bounds__(256, 2) void taylor_jvp_kernel(const TaylorJvpArgs P) {
+    const TaylorArgs& A = P.G;
+    extern __shared__ double ty_lds[];
+    double* const abuf = ty_lds;                       // 2 x TY_KC x TY_RS
+    double* const dl = ty_lds + 2 * TY_KC * TY_RS;     // (ndim, 64) x - center of the point of each row
+    double* const tl = dl + A.ndim * TY_ROWS;          // (ndim, 64) the tangent of each row
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int l15 = lane & 15, g = lane >> 4;
+    const int nchunk = (A.K + TY_KC - 1) / TY_KC;
+    const long long row0 = (long long)blockIdx.x * TY_ROWS;
+    const int c0 = A.c0, cend = A.cend;
+    const int col0 = c0 + (int)blockIdx.y * TY_COLS + wave * 64;
+    const bool active = col0 < cend;      // (wave-uniform; an idle wave forms its share of the left operand and multiplies the last column: no branch round the MFMAs)
+    // the tile's first point and the direction its first row stands for: row0 + t is point b0 + (k0 + t) / K
+    const long long b0 = row0 / P.Kdir;
+    const int kd0 = (int)(row0 - b0 * P.Kdir);
+    for (int e = threadIdx.x; e < A.ndim * TY_ROWS; e += 256) {
+        const int i = e >> 6;
+        const long long row = row0 + (e & 63);
+        const long long point = b0 + (kd0 + (e & 63)) / P.Kdir;
+        const bool inside = row < A.R;      // rows past the end: finite, never stored
+        dl[e] = inside ? A.a[point * A.ndim + i] - A.center[i] : 0.;
+        tl[e] = inside ? P.tan[row * A.ndim + i] : 0.;
+    }
+    __syncthreads();
+    ty_v4d acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = ty_v4d{0., 0., 0., 0.};
+    int colj[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int col = col0 + 16 * j + l15;
+        colj[j] = col < cend ? col : cend - 1;      // columns past the end of the range repeat its last one (never stored)
+    }
+#pragma unroll 1
+    for (int c = 0; c < nchunk; ++c) {
+        double* const buf = abuf + (c & 1) * TY_KC * TY_RS;
+        const int k0 = c * TY_KC;
+        for (int tt = wave; tt < TY_KC; tt += 4) {      // a term per wave and step, a row per lane
+            const int t = k0 + tt;
+            double s = 0.;      // terms past T: zero columns of the left operand
+            if (t < A.K) {
+                const int* pw = A.powers + (long long)t * A.ndim;
+                // one pass over the powers, four scalar loads in flight: bit i of marked for p_ti > 0 (ndim <= 32), the powers themselves (at most 15) in four
+                // bits each of two scalar registers -- the loops below read no memory but the lanes' LDS
+                unsigned marked = 0;
+                unsigned long long plo = 0, phi = 0;
+                for (int i0 = 0; i0 < A.ndim; i0 += 4) {
+                    int p4[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) p4[k] = __builtin_amdgcn_readfirstlane(pw[i0 + k < A.ndim ? i0 + k : A.ndim - 1]);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int i = i0 + k;
+                        int p = i < A.ndim ? p4[k] : 0;
+                        if (p <= 0) continue;
+                        p = p < TY_MAX_POWER ? p : TY_MAX_POWER;
+                        marked |= 1u << i;
+                        if (i < 16) plo |= (unsigned long long)p << (4 * i);
+                        else phi |= (unsigned long long)p << (4 * (i - 16));
+                    }
+                }
+                for (unsigned mi = marked; mi; mi &= mi - 1) {
+                    const int i = __builtin_ctz(mi);
+                    double m = 1.;
+                    for (unsigned mj = marked; mj; mj &= mj - 1) {
+                        const int j = __builtin_ctz(mj);
+                        const int p = (int)((j < 16 ? plo >> (4 * j) : phi >> (4 * (j - 16))) & 15);
+                        const double d = dl[j * TY_ROWS + lane];
+                        if (p == 1) {
+                            if (j != i) m *= d;
+                            continue;
+                        }
+                        double v = d;      // d^(p - 1)
+                        for (int q = 2; q < p; ++q) v *= d;
+                        m *= j == i ? (double)p * v : v * d;
+                    }
+                    s = fma(tl[i * TY_ROWS + lane], m, s);
+                }
+            }
+            buf[tt * TY_RS + lane] = s;
+        }
+        __syncthreads();      // one barrier per chunk: the buffer written next was last read before this barrier
+        const int npairs = A.K - k0 >= TY_KC ? TY_KC / 8 : (A.K - k0 + 7) / 8;
+        double a0[2][4], b0r[2][4];
+        bool keep[2];
+        taylor_load(A, buf, k0, 0, l15, g, colj, a0, b0r, keep);
+        taylor_mask(b0r, keep);
+#pragma unroll 1
+        for (int p = 0; p < npairs; ++p) {
+            double a1[2][4], b1[2][4];
+            taylor_load(A, buf, k0, p + 1 < npairs ? p + 1 : p, l15, g, colj, a1, b1, keep);
+            __builtin_amdgcn_sched_barrier(0);      // the loads are issued here, not moved below the MFMAs
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[h][i], b0r[h][j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) a0[h][i] = a1[h][i], b0r[h][i] = b1[h][i];
+            __builtin_amdgcn_sched_barrier(0);
+            taylor_mask(b0r, keep);
+        }
+    }
+    if (!active) return;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int col = col0 + 16 * j + l15;
+        if (col >= cend) continue;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long long row = row0 + 16 * i + g + 4 * r;
+                if (row < A.R) A.out[row * A.ldo + (col - c0)] = acc[i][j][r];
+            }
+    }
+}
+
 // G[b][i] = sum_t S[b][t] d mono_t / d x_i for cp_taylor_vjp: a row per (point, parameter) pair r = b ndim + i, 64 rows per workgroup, a row per lane of
 // each of its four waves.  The derivative of a monomial as the jacobian front end of the GEMM forms it (the powers wave-uniform, the lane's own parameter a
 // select; factors of power 0 skipped), a wave the terms tt = wave (mod 4) of a chunk of TY_KC, into one of two LDS buffers m[tt][row] with a bit per term for
@@ -308,7 +449,7 @@ int taylor_launch(const char* who, const TaylorArgs& A, void* stream) {
     return cp::launch_status(who);
 }
 
-// What cp_taylor_predict, cp_taylor_predict_columns, cp_taylor_jacobian and cp_taylor_vjp share: their checks, in that order, up to the caps of ndim and
+// What cp_taylor_predict, cp_taylor_predict_columns, cp_taylor_jacobian, cp_taylor_vjp and cp_taylor_jvp share: their checks, in that order, up to the caps of ndim and
 // of the powers; ``ld`` is the entry point's one row stride (of ``what``), which is checked between the range of columns and the caps.  What follows is
 // the entry point's own: its grid cap, the empty batch, its null pointers, its workspace, the device.
 int taylor_front(const char* who, long long B, int ndim, int T, int max_power, int M, long long col0, long long ncols, long long ld, const char* what) {
@@ -360,6 +501,31 @@ extern "C" int cp_taylor_jacobian(const double* d_x, long long B, const double* 
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
     const TaylorArgs A{d_x, d_center, d_powers, d_derivatives, d_jac, B * ndim, ldj, T, M, ndim, (int)col0, (int)(col0 + ncols), 0};
     return taylor_launch<TY_JACOBIAN>(who, A, stream);
+}
+
+// One launch: taylor_jvp_kernel on the B K rows (b, k)
+extern "C" int cp_taylor_jvp(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
+                             const double* d_derivatives, int M, long long col0, long long ncols, const double* d_tan, long long K, double* d_out,
+                             long long ldo, int device, void* stream) {
+    const char* who = "cp_taylor_jvp";
+    const int status = taylor_front(who, B, ndim, T, max_power, M, col0, ncols, ldo, "result");
+    if (status != CP_OK) return status;
+    if (K < 1) return cp::fail(CP_EINVAL, "%s: %lld directions per point (at least 1)", who, K);
+    if (K > 0x7fffffffLL || B > 0x7fffffffLL * TY_ROWS / K || (ncols + TY_COLS - 1) / TY_COLS > 65535)
+        return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %lld x %lld results (at most 2^37 rows B K, 2^31 - 1 directions, 2^24 - 256 columns)", who, B, K, ncols);
+    if (B == 0) return CP_OK;
+    if (!d_x || !d_center || !d_powers || !d_derivatives || !d_tan || !d_out) return cp::fail(CP_EINVAL, "%s: null pointer", who);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
+    const TaylorJvpArgs A{{d_x, d_center, d_powers, d_derivatives, d_out, B * K, ldo, T, M, ndim, (int)col0, (int)(col0 + ncols), 0}, d_tan, (int)K};
+    const long long nrt = (B * K + TY_ROWS - 1) / TY_ROWS, nct = (ncols + TY_COLS - 1) / TY_COLS;
+    const size_t lds = (size_t)(2 * TY_KC * TY_RS + 2 * ndim * TY_ROWS) * sizeof(double);      // at most 72 KB
+    if (lds > 64 * 1024) {
+        const hipError_t e = cp::allow_full_lds<taylor_jvp_kernel>();
+        if (e != hipSuccess) return cp::launch_status(who, e);
+    }
+    hipLaunchKernelGGL(taylor_jvp_kernel, dim3((unsigned)nrt, (unsigned)nct), dim3(256), lds, static_cast<hipStream_t>(stream), A);
+    return cp::launch_status(who);
 }
 
 extern "C" long long cp_taylor_vjp_workspace_doubles(long long B, int T) {

@@ -1,14 +1,14 @@
 """
 The ``Emulator`` front end under the reference's name (cosmoprimo/emulators/tools/base.py ``Emulator``), reduced to what the Taylor and MLP engines need:
-sample a calculator, fit an engine on the concatenation (npoints, M) of its flattened varied outputs, and give ``predict``, ``jacobian`` and ``vjp`` back
+sample a calculator, fit an engine on the concatenation (npoints, M) of its flattened varied outputs, and give ``predict``, ``jacobian``, ``vjp`` and ``jvp`` back
 by output key for B parameter points at once.
 
-One front, three back ends.  The three methods share one plan (``Emulator._plan``: the keys asked for -> the maximal contiguous runs of columns of
+One front, four back ends.  The four methods share one plan (``Emulator._plan``: the keys asked for -> the maximal contiguous runs of columns of
 :func:`column_runs`, the ``(key, shape, lo, hi)`` entries each run holds, the fixed outputs to return) and one split (``_split``: a run's buffer ->
 ``{key: view}``); each is then one call of the engine per run and nothing else.  What ``Emulator`` uses of an engine: ``name``, ``device``, ``_dev``
-(for its device), and ``predict`` / ``jacobian`` / ``vjp`` with ``columns=`` / ``return_value=``.
+(for its device), and ``predict`` / ``jacobian`` / ``vjp`` / ``jvp`` with ``columns=`` / ``return_value=``.
 
-The helpers that both engines' ``predict`` / ``jacobian`` / ``vjp`` open with (``_columns``, ``_cotangent``, ``_empty``) live here as well; the engines
+The helpers that both engines' ``predict`` / ``jacobian`` / ``vjp`` open with (``_columns``, ``_cotangent``, ``_tangent``, ``_empty``) live here as well; the engines
 import this module, which imports them only where it builds one.  Nothing on the path of a call imports anything: at B = 1 a call is its Python.
 """
 import numpy as np
@@ -38,6 +38,19 @@ def _cotangent(cotangent, B, ncols, device):
     if cotangent.dtype != torch.float64 or (ncols > 1 and cotangent.stride(1) != 1) or (B > 1 and cotangent.stride(0) < ncols):
         cotangent = cotangent.to(torch.float64).contiguous()
     return cotangent, int(cotangent.stride(0)) if B > 1 else ncols
+
+
+def _tangent(tangents, B, ndim, device):
+    """``(tangents (B, K, ndim), K, single)``: the directions on ``device`` as the C entry points read them -- float64, contiguous; ``single``: they were
+    given as (B, ndim), one direction per point."""
+    torch = dv.torch()
+    tangents = dv.to_device(tangents, device, cache=False)
+    single = tangents.ndim == 2
+    if single:
+        tangents = tangents[:, None, :]
+    if tangents.ndim != 3 or int(tangents.shape[0]) != B or int(tangents.shape[2]) != ndim:
+        raise ValueError('tangents must be of shape ({0:d}, {1:d}) or ({0:d}, K, {1:d}), got {2}'.format(B, ndim, tuple(tangents.shape)))
+    return tangents.to(torch.float64).contiguous(), int(tangents.shape[1]), single
 
 
 def _requested(key, keys):
@@ -158,7 +171,7 @@ class Emulator(object):
         return X, B, scalar
 
     def _plan(self, keys, exact=False):
-        """What :meth:`predict`, :meth:`jacobian` and :meth:`vjp` compute for ``keys`` -- a list of output names or section prefixes, or one such string
+        """What :meth:`predict`, :meth:`jacobian`, :meth:`vjp` and :meth:`jvp` compute for ``keys`` -- a list of output names or section prefixes, or one such string
         (``exact``: names only, the keys of cotangents), or None for every output: ``(runs, fixed)``, ``runs = [(start, stop, entries), ...]`` the maximal
         contiguous runs of columns of :func:`column_runs` (None: all columns as one run) with the ``(key, shape, lo, hi)`` of the varied outputs asked
         for that each holds, ``fixed`` the fixed outputs asked for.  A name that matches no output raises ``KeyError``; one that matches fixed outputs
@@ -255,6 +268,60 @@ class Emulator(object):
         values = {key: values[key] for key in self.varied_keys if key in values}      # predict's order: the calculator's, then the fixed outputs
         values.update(fixed)
         return values, grads
+
+    def _directions(self, tangents, B):
+        """(T (B, ndim) or (B, K, ndim) float64, K or None) of ``tangents = {parameter name: value}``, a host array unless a tangent is a device tensor: a
+        value of dimension <= 1 broadcasts against (B,) and is one direction, one of dimension 2 is (B or 1, K); a missing name is a zero component."""
+        unknown = [name for name in tangents if name not in self.params]
+        if unknown:
+            raise KeyError('no parameter {}'.format(unknown))
+        if all(not dv.is_torch(v) for v in tangents.values()):
+            xp, values = np, {name: np.asarray(value, dtype='f8') for name, value in tangents.items()}
+        else:
+            xp = dv.torch()
+            dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, *tangents.values())
+            values = {name: dv.to_device(value, dev, cache=False) for name, value in tangents.items()}
+            values[None] = xp.zeros((), dtype=xp.float64, device=dev)
+        if any(v.ndim > 2 for v in values.values()):
+            raise ValueError('a tangent is a scalar, (B,) or (B or 1, K)')
+        counts = {int(v.shape[1]) for v in values.values() if v.ndim == 2}
+        if len(counts) > 1:
+            raise ValueError('tangents must share one count of directions, got {}'.format(sorted(counts)))
+        K = counts.pop() if counts else None
+        columns = []
+        for name in self.params:
+            v = values.get(name, values.get(None, np.zeros(())))
+            columns.append(xp.broadcast_to(v.reshape(-1, 1) if K is not None and v.ndim == 1 else v, (B,) if K is None else (B, K)))
+        return xp.stack(columns, -1), K
+
+    def jvp(self, params, tangents, device=False, keys=None, return_value=False):
+        """Jacobian-vector product: the derivative of the varied outputs along given directions in parameter space, for every point of a batch -- what
+        ``jax.jvp`` / ``jax.linearize`` of the reference's ``predict`` give.  ``params`` as in :meth:`predict`.  ``tangents``:
+        ``{parameter name: value}`` in raw-parameter units; a value of dimension <= 1 broadcasts against ``(B,)`` and gives one direction, a value of
+        dimension 2 is ``(B or 1, K)``, K directions per point (all such values share one K).  A name that is no parameter raises ``KeyError``, a missing
+        name is a zero component, an empty dictionary gives zeros.
+
+        Returns ``{varied key: (B,) + shape}``, or ``{varied key: (B, K) + shape}`` with K directions,
+        ``sum_i tangent_i d output / d parameter_i``, without the leading ``B`` axis if every parameter is a scalar.  Fixed outputs are not returned:
+        their derivative is identically zero.  Computed by forward mode on the device (:meth:`MLPEmulatorEngine.jvp`,
+        :meth:`TaylorEmulatorEngine.jvp`) without forming the Jacobian.  ``keys``: as in :meth:`predict` -- one call of the engine per maximal
+        contiguous run of columns, and no other column is computed.  Host arrays by default; ``device=True``: torch tensors, views into the run's
+        buffer, and no synchronisation with the device.  ``return_value=True``: ``(values, tangents_out)``, ``values`` what
+        ``predict(params, device=device, keys=keys)`` returns."""
+        X, B, scalar = self._points(params)
+        runs, fixed = self._plan(keys)
+        T, K = self._directions(tangents, B)
+        values, toret = {}, {}
+        for start, stop, entries in runs:
+            out = self.engine.jvp(X, T, columns=None if keys is None else (start, stop), return_value=return_value)
+            value, tan = out if return_value else (None, out)
+            toret.update(_split(tan if device else dv.to_host(tan), (B,) if K is None else (B, K), entries, start, scalar))
+            if return_value:
+                values.update(_split(value if device else dv.to_host(value), (B,), entries, start, scalar))
+        if not return_value:
+            return toret
+        values.update(fixed)
+        return values, toret
 
     def to_calculator(self, device=False):
         """Callable ``**params -> dict`` with the contract of ``get_calculator``'s."""

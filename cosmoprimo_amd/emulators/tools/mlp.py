@@ -13,8 +13,10 @@ synchronisation; the one read-back is the validation loss of an epoch.
 mode through the network on the device (``cp_mlp_jacobian``).  ``vjp`` is its product with a cotangent, ``sum_c cotangent[b, c] J[b, i, c]`` (what
 ``jax.vjp`` / ``jax.grad`` give: the gradient of a scalar function of the outputs for every point of a batch), by reverse mode (``cp_mlp_vjp``): one
 forward pass, one product with the transposed output kernel, one walk back through the hidden layers; the Jacobian is never formed.
-``predict``, ``jacobian`` and ``vjp`` open with one prologue (``_enter``: fitted?, device state, upload and check of ``X``, the leading and the last
-arguments of the C entry points); the full prediction is the column range (0, M) of ``cp_mlp_predict_columns``.
+``jvp`` is its product with tangents, ``sum_i tangent[b, k, i] J[b, i, c]`` (what ``jax.jvp`` / ``jax.linearize`` give), by forward mode with a row per
+(point, direction) pair (``cp_mlp_jvp``).
+``predict``, ``jacobian``, ``vjp`` and ``jvp`` open with one prologue (``_enter``: fitted?, device state, upload and check of ``X``, the leading and the
+last arguments of the C entry points); the full prediction is the column range (0, M) of ``cp_mlp_predict_columns``.
 
 Operations are held as numbers, not as expressions: x a chain of affine maps ('scale', 'norm') folded into one (offset, scale) per parameter, y
 optionally 'log10' or 'arcsinh' first, then affine maps.  Not built: 'pca', 'chebyshev', ``model_yoperation``, batch normalisation, learning-rate
@@ -25,7 +27,7 @@ import ctypes
 import numpy as np
 
 from ... import _device as dv, _lib
-from .base import _columns, _cotangent, _empty
+from .base import _columns, _cotangent, _empty, _tangent
 
 ACTIVATIONS = ('silu', 'relu', 'tanh', 'identity-silu')
 ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-8      # optax.adam's defaults
@@ -401,6 +403,22 @@ class MLPEmulatorEngine(object):
         _lib.check(lib.cp_mlp_vjp(*head, start, ncols, cotangent.data_ptr(), ldc, value.data_ptr() if return_value else None, width, grad.data_ptr(), work.data_ptr(), need,
                                   *where))
         return (value, grad) if return_value else grad
+
+    def jvp(self, X, tangents, columns=None, return_value=False):
+        """Jacobian-vector product of :meth:`predict` at the points ``X`` (B, ndim) along ``tangents`` (B, ndim) -- device tensor (B, M),
+        ``out[b, c] = sum_i tangents[b, i] d predict(X)[b, c] / d X[b, i]`` -- or (B, K, ndim), K directions per point -- (B, K, M) --, a device tensor or
+        host array (uploaded), in raw-parameter units; by forward mode through the network with a row per (point, direction) pair (``cp_mlp_jvp``: the
+        kernel of :meth:`jacobian` with ``tangents / xscale`` as the input tangent; no (B, ndim, M) array anywhere, and ndim identity tangents give the
+        bits of :meth:`jacobian`).  ``columns = (start, stop)``: those output columns only, bit for bit the same numbers.  ``return_value=True``:
+        ``(predict(X, columns=columns), out)``, the value bit for bit.  Nothing is read back and the call does not wait for the device."""
+        d, X, B, head, where = self._enter(X)
+        start, ncols = _columns(columns, d['net']['M'])
+        width = max(ncols, 0)
+        tangents, K, single = _tangent(tangents, B, d['net']['ndim'], d['device'])
+        value, out = _empty(d, B, width), _empty(d, B, K, width)
+        _lib.check(_lib.load().cp_mlp_jvp(*head, start, ncols, tangents.data_ptr(), K, value.data_ptr(), width, out.data_ptr(), width, *where))
+        out = out[:, 0] if single else out
+        return (value, out) if return_value else out
 
     def __getstate__(self):
         state = {'name': self.name, 'nhidden': tuple(self.nhidden), 'activation': tuple(self.activation), 'params': self.params,

@@ -7,8 +7,8 @@ finite-difference weights, times the 1 / alpha! of the term -- is built here on 
 (``cp_taylor_fit``), and ``derivatives`` stay there.  Predict: ``out (B, M) = monomials (B, T) . derivatives`` for B parameter points at once
 (``cp_taylor_predict_columns``: the monomials are formed inside the kernel), where the reference evaluates one point per call.  Jacobian: the derivative
 of the polynomial with respect to the parameters, ``(B ndim, M) = d monomials / d x_i . derivatives`` by the same kernel (``cp_taylor_jacobian``).  Vjp: its
-product with a cotangent, without forming it (``cp_taylor_vjp``).  The three open with one prologue (``_enter``: device state, upload and check of ``X``,
-the nine leading C arguments).
+product with a cotangent, without forming it (``cp_taylor_vjp``).  Jvp: its product with tangents, without forming it (``cp_taylor_jvp``).  They open
+with one prologue (``_enter``: device state, upload and check of ``X``, the nine leading C arguments).
 
 No x / y operations (log10, PCA, ...).
 """
@@ -18,7 +18,7 @@ import math
 import numpy as np
 
 from ... import _device as dv, _lib
-from .base import _columns, _cotangent, _empty
+from .base import _columns, _cotangent, _empty, _tangent
 from .samples import DiffSampler, deriv_ncoeffs
 
 
@@ -207,6 +207,22 @@ class TaylorEmulatorEngine(object):
         work, grad = _empty(d, need), _empty(d, B, ndim)
         _lib.check(lib.cp_taylor_vjp(*head, start, ncols, cotangent.data_ptr(), ldc, grad.data_ptr(), work.data_ptr(), need, *where))
         return (self.predict(X, columns=columns), grad) if return_value else grad
+
+    def jvp(self, X, tangents, columns=None, return_value=False):
+        """Jacobian-vector product of :meth:`predict` at the points ``X`` (B, ndim) along ``tangents`` (B, ndim) -- device tensor (B, M),
+        ``out[b, c] = sum_i tangents[b, i] d predict(X)[b, c] / d X[b, i]`` -- or (B, K, ndim), K directions per point -- (B, K, M) --, a device tensor or
+        host array (uploaded); one launch (``cp_taylor_jvp``: the derivatives of the monomials contracted with the tangent inside the kernel, a parameter
+        that a term does not hold skipped; no (B, ndim, M) array anywhere, and ndim identity tangents give the bits of :meth:`jacobian`).
+        ``columns = (start, stop)``: those output columns only, bit for bit the same numbers.  ``return_value=True``:
+        ``(predict(X, columns=columns), out)``, one more launch.  Nothing is read back and the call does not wait for the device."""
+        d, X, (B, ndim, T, M), head, where = self._enter(X)
+        start, ncols = _columns(columns, M)
+        width = max(ncols, 0)
+        tangents, K, single = _tangent(tangents, B, ndim, d['device'])
+        out = _empty(d, B, K, width)
+        _lib.check(_lib.load().cp_taylor_jvp(*head, start, ncols, tangents.data_ptr(), K, out.data_ptr(), width, *where))
+        out = out[:, 0] if single else out
+        return (self.predict(X, columns=columns), out) if return_value else out
 
     def __getstate__(self):
         state = {'sampler_options': self.sampler_options}

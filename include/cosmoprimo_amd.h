@@ -664,7 +664,15 @@ int cp_spline_tables_apply_f32(const double* d_xk, const double* d_coef, const i
  *   S (B, T) = d_cot . d_derivatives_t[col0 .. col0 + ncols) on the matrix cores (the GEMM of fit), then G[b][i] = sum_t S[b][t] d mono_t / d x_i over the terms
  *   in their order, the derivatives of the monomials formed as in jacobian.  A term with p_ti = 0 is skipped (not added as 0): a NaN or Inf in a
  *   parameter that only ever has power 0 leaves G finite.  No atomics: two calls give the same bits.  The argument checks are those of jacobian, plus
- *   ldc and the workspace, before any device call; B = 0: CP_OK. */
+ *   ldc and the workspace, before any device call; B = 0: CP_OK.
+ * jvp : the Jacobian-vector product of predict_columns along K >= 1 directions per point (what jax.jvp / jax.linearize of the reference's predict give),
+ *   without any (B, ndim, .) array.  d_tan (B, K, ndim) contiguous, raw-parameter units; d_out (B K, ncols) with row stride ldo >= ncols, row b K + k =
+ *   sum_i d_tan[b][k][i] d out[b][col0 ..] / d x[b][i].  One launch: the GEMM with the left-operand entry sum_i tan_i p_ti (x_i - c_i)^(p_ti - 1)
+ *   prod_{j != i} (x_j - c_j)^p_tj formed in LDS, summed over i in parameter order; a parameter with p_ti = 0 is skipped (not added as 0): a NaN or Inf
+ *   in a parameter, or in its tangent component, that only ever has power 0 leaves the result finite.  No atomics: two calls give the same bits, a range
+ *   gives the bits of the same columns of the full call, and K = ndim identity tangents give the bits of jacobian on finite inputs.  The argument checks
+ *   are those of jacobian (ldo in the place of ldj), then K < 1: CP_EINVAL, before any device call; more than 2^37 rows B K or K > 2^31 - 1:
+ *   CP_EUNSUPPORTED; B = 0: CP_OK. */
 int cp_taylor_predict(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                       const double* d_derivatives, int M, double* d_out, int device, void* stream);
 int cp_taylor_predict_columns(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
@@ -676,6 +684,9 @@ long long cp_taylor_vjp_workspace_doubles(long long B, int T);
 int cp_taylor_vjp(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                   const double* d_derivatives_t, int M, long long col0, long long ncols, const double* d_cot, long long ldc, double* d_grad, double* d_work,
                   long long work_doubles, int device, void* stream);
+int cp_taylor_jvp(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
+                  const double* d_derivatives, int M, long long col0, long long ncols, const double* d_tan, long long K, double* d_out, long long ldo,
+                  int device, void* stream);
 
 /* ---- Multi-layer perceptron emulator of a calculator (reference emulators/tools/mlp.py; csrc/cp_mlp.hip): batched prediction, loss and gradient of
  *      a training batch, Adam step, all float64.  Everything is on the device; no call reads anything back, allocates or waits for the stream. ----
@@ -707,6 +718,14 @@ int cp_taylor_vjp(const double* d_x, long long B, const double* d_center, const 
  *   in slices of the columns; one kernel sums the slices in their order and walks the hidden layers back in LDS (dz = dh act'(z), dh = dz . kernel^T;
  *   relu: act' = 0 at z <= 0), ending with / d_xscale[i].  No atomics: two calls give the same bits.  A NaN in row b of d_x or of d_cot makes row b of
  *   d_grad NaN and touches no other row.  The argument checks are those of jacobian, plus ldc and the workspace, before any device call; B = 0: CP_OK.
+ * jvp : the Jacobian-vector product of predict_columns along K >= 1 directions per point by forward mode (what jax.jvp / jax.linearize of the reference's
+ *   predict give), without any (B, ndim, .) array.  d_tan (B, K, ndim) contiguous, raw-parameter units; d_value as in jacobian (always written,
+ *   predict_columns bit for bit); d_out (B K, ncols) with row stride ldo >= ncols, row b K + k = sum_i d_tan[b][k][i] d value[b][.] / d x[b][i]: the
+ *   kernel of jacobian with the input tangent d_tan[b][k][i] / d_xscale[i] in the place of e_i / d_xscale[i].  Two launches, no atomics: two calls give
+ *   the same bits, a range gives the bits of the same columns of the full call, and K = ndim identity tangents give the bits of jacobian on finite
+ *   inputs.  A NaN in row b of d_x makes the K rows of point b NaN, a NaN in d_tan[b][k] row b K + k, and touches no other row.  The argument checks
+ *   are those of jacobian (ldo in the place of ldj), then K < 1: CP_EINVAL, before any device call; more than 2^37 rows B K or K > 2^31 - 1:
+ *   CP_EUNSUPPORTED; B = 0: CP_OK.
  * loss_grad : d_X (b, ndim), d_Y (b, M) already scaled; d_loss (one device double) = mean((Y - prediction)^2); d_grad (packed layout; NULL: loss
  *   only, with the same bits) its gradient.  d_work: work_doubles >= cp_mlp_workspace_doubles(b, ...) doubles of device workspace.  Reductions run in a
  *   fixed order: two calls give bit-identical results.
@@ -729,6 +748,9 @@ int cp_mlp_vjp(const double* d_x, long long B, int ndim, int nlayers, const int*
                const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
                long long ncols, const double* d_cot, long long ldc, double* d_value, long long ldv, double* d_grad, double* d_work, long long work_doubles,
                int device, void* stream);
+int cp_mlp_jvp(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
+               const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
+               long long ncols, const double* d_tan, long long K, double* d_value, long long ldv, double* d_out, long long ldo, int device, void* stream);
 int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long b, int ndim, int nlayers, const int* widths, const int* activations, int M,
                      const double* d_params, double* d_work, long long work_doubles, double* d_loss, double* d_grad, int device, void* stream);
 int cp_mlp_adam(double* d_params, double* d_m, double* d_v, const double* d_grad, long long n, double lr, double b1, double b2, double eps, double c1,
