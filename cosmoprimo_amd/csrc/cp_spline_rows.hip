@@ -278,13 +278,19 @@ extern "C" int cp_spline_rows_plan_create(cp_spline_rows_plan** out, int n, cons
         if (worst < 1e-18 || halo >= n) break;
     }
     const int w0 = std::max(0, jmin - halo), w1 = std::min(n, jmax + 2 + halo), nw = w1 - w0;
+    // rows per wave: as many as the window's length suggests, fewer where their buffers do not fit (4 R row buffers per workgroup: with a halo of 32
+    // two rows per wave end at 1632 knots, not at the 32 x 59 of their lanes)
     int R = nw <= 16 * 27 ? 4 : (nw <= 32 * 59 ? 2 : 1);
-    const int lpr = 64 / R;
-    const int S = ((nw + lpr - 1) / lpr) | 1;
-    const int pad = halo + 1;
-    const int nslots = lpr * S + pad;
-    const int rstride = lpr * S + 2 * pad + 1;
-    const size_t lds = ((size_t)((4 * R * rstride + 3) & ~3) + 4 * (size_t)nslots) * sizeof(double);
+    int S, nslots;
+    size_t lds;
+    for (;; R /= 2) {
+        const int lpr = 64 / R, pad = halo + 1;
+        S = ((nw + lpr - 1) / lpr) | 1;
+        nslots = lpr * S + pad;
+        const int rstride = lpr * S + 2 * pad + 1;
+        lds = ((size_t)((4 * R * rstride + 3) & ~3) + 4 * (size_t)nslots) * sizeof(double);
+        if (lds <= 160 * 1024 || R == 1) break;
+    }
     if (lds > 160 * 1024) return cp::fail(CP_EUNSUPPORTED, "cp_spline_rows_plan_create: a window of %d knots exceeds the LDS budget of the kernel", nw);
     std::vector<double> tab((size_t)4 * nslots), qw((size_t)4 * nq, 0.);
     for (int s = 0; s < nslots; ++s) {
