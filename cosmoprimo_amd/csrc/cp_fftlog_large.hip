@@ -6,7 +6,8 @@
 // second transform runs the transposed network back), so that no transposition pass exists:
 //
 //   screen   per row: the largest |sample x prefactor| (its exponent) -- rows are scaled to [1, 2) and back by exact powers of two, a row that
-//            is not finite is transformed as zeros and stored as NaN: the two rows of a pair stay independent, as numpy's row-by-row FFTs are
+//            is not finite is transformed as zeros and stored as NaN, a row of zeros is stored as zeros: the two rows of a pair stay independent,
+//            as numpy's row-by-row FFTs are
 //   columns  A[k1][n2] = sum_n1 z[n1 4096 + n2] w_N1^(n1 k1): pad + prefactor + pack on the way in, N1-point FFTs down the columns of a
 //            (N1 x C) tile in LDS, written to the scratch at row k1
 //   rows     for each k1: x w_Np^(k1 n2), 4096-point FFT (radix 16 x 3 in registers, exchanges through swizzled LDS), x U[k1 + N1 k2],
@@ -107,7 +108,9 @@ __global__ __launch_bounds__(256) void screen_kernel(const ScreenArgs A) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {       // (the padded length is a multiple of the 4096 samples of a workgroup)
             const int j = seg * 4096 + i * 256 + threadIdx.x;
-            const unsigned h = cpfft::hi_abs(padded_sample(a, j, A.S) * pre[j]);
+            const double v = padded_sample(a, j, A.S) * pre[j];
+            unsigned h = cpfft::hi_abs(v);
+            h = (h == 0u && v != 0.) ? 1u : h;      // (a subnormal below 2^-1042 has an empty high dword: a magnitude of 0 is kept for rows that ARE zero)
             m = h > m ? h : m;
         }
     }
@@ -137,6 +140,7 @@ __device__ __forceinline__ RowScale row_scale(unsigned mag) {
     if (!r.finite || mag == 0u) sh = 0;
     r.down = __builtin_bit_cast(double, (unsigned long long)(1023 + sh) << 52);
     r.up = __builtin_bit_cast(double, (unsigned long long)(1023 - sh) << 52);
+    if (mag == 0u) r.up = 0.;      // a row of zeros is stored as zeros: what its partner's rounding leaves in its half of the packed transform is not its result
     return r;
 }
 

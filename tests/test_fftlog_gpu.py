@@ -343,7 +343,8 @@ def test_mixed_magnitude_batch_pointwise(cp, golden):
 def test_large_sizes(cp, n):
     """Padded sizes beyond the LDS-resident kernel (Np = 16384, 16384, 65536, 262144, 1048576: column transforms of 4, 16, 64 and 256 points
     around the 4096-point row kernel, csrc/cp_fftlog_large.hip) follow the same reference arithmetic: every extrap mode, keep_padding,
-    multi-kernel, odd batch."""
+    multi-kernel, odd batch.  The remaining column plans (8, 32, 128 points and 512 ... 4096, the three-pass ones), a second chunk of the scratch and
+    two streams on one plan: tests/test_fftlog_large_truth_gpu.py, against longdouble truth."""
     rng = np.random.default_rng(n)
     k = np.logspace(-4, 2, n)
     t = ofl.power_to_correlation(k, ell=[0, 2])
