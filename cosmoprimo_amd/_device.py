@@ -17,6 +17,27 @@ class Copyable(object):
         return copy.copy(self)
 
 
+class PlanOwner(object):
+
+    """Owner of plans of the C library.  The attribute named ``_handle_attr`` holds one handle (a ``ctypes.c_void_p``, null or None when there is no
+    plan) or a dict of them; ``_destroy`` names the entry point that frees one.  The plans die with the object: the library frees their device
+    tables on the device they were created on."""
+
+    _destroy = None
+    _handle_attr = '_handle'
+
+    def __del__(self):
+        try:
+            held = self.__dict__.get(self._handle_attr)
+            several = isinstance(held, dict)
+            for handle in (held.values() if several else [held]):
+                if handle:
+                    getattr(_lib.load(), self._destroy)(handle)
+            setattr(self, self._handle_attr, {} if several else None)
+        except Exception:
+            pass
+
+
 def torch():
     import torch as _torch
     return _torch

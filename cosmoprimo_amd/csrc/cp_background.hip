@@ -437,7 +437,7 @@ void build_tables(TablesN<NK_TIME>& t) {
 }
 
 // one device copy of the grid tables per device and grid: created by cp_background_init(device), or -- for callers that did not ask -- by the first
-// entry point that needs it (a hipMalloc and a synchronous upload inside that one call; the mutex keeps two host threads from both doing it)
+// entry point that needs it (an allocation and a synchronous upload inside that one call; the mutex keeps two host threads from both doing it)
 std::mutex& table_mutex() {
     static std::mutex m;
     return m;
@@ -454,11 +454,9 @@ TablesN<NK>* device_tables(int device) {
     if (!d) {
         std::vector<TablesN<NK>> h(1);
         build_tables(h[0]);
-        if (hipMalloc(&d, sizeof(TablesN<NK>)) != hipSuccess) return nullptr;
-        if (hipMemcpy(d, h.data(), sizeof(TablesN<NK>), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            return nullptr;
-        }
+        cp::DeviceArray<TablesN<NK>> placed;
+        if (placed.upload(h.data(), 1) != hipSuccess) return nullptr;
+        d = placed.release();      // the cache's from here on, for the life of the process
         cache[device].store(d, std::memory_order_release);
     }
     return d;
@@ -596,11 +594,9 @@ double* device_ncdm_knots(int device) {
     if (!d) {
         double h[CP_NCDM_NKNOTS];
         build_ncdm_knots(h);
-        if (hipMalloc(&d, sizeof(h)) != hipSuccess) return nullptr;
-        if (hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            return nullptr;
-        }
+        cp::DeviceArray<double> placed;
+        if (placed.upload(h, CP_NCDM_NKNOTS) != hipSuccess) return nullptr;
+        d = placed.release();
         cache[device].store(d, std::memory_order_release);
     }
     return d;

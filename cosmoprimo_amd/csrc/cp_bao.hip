@@ -920,35 +920,19 @@ __global__ __launch_bounds__(256) void splice_kernel(const SpliceArgs A) {
 struct cp_splice_plan {
     SpliceTables T;
     int device;
-    double* d_tab;
-    int* d_qj;
-    int* d_qcol;
-    double* d_qw;
+    cp::DeviceArray<double> d_tab;
+    cp::DeviceArray<int> d_qj, d_qcol;
+    cp::DeviceArray<double> d_qw;
     size_t lds_bytes;
     // the scheme for knots on a long uniform stretch (cp_splice_uniform.h), where it fits
     bool has_uniform, use_uniform;
     cpsu::Tables U;
-    double* d_uwin;
-    double* d_uqw;
-    int* d_uqe;
+    cp::DeviceArray<double> d_uwin, d_uqw;
+    cp::DeviceArray<int> d_uqe;
     size_t uniform_lds_bytes;
 };
 
-extern "C" int cp_splice_plan_destroy(cp_splice_plan* p) {
-    if (!p) return CP_OK;
-    {
-        cp::DeviceScope scope(p->device);
-        if (p->d_tab) (void)hipFree(p->d_tab);
-        if (p->d_qj) (void)hipFree(p->d_qj);
-        if (p->d_qcol) (void)hipFree(p->d_qcol);
-        if (p->d_qw) (void)hipFree(p->d_qw);
-        if (p->d_uwin) (void)hipFree(p->d_uwin);
-        if (p->d_uqw) (void)hipFree(p->d_uqw);
-        if (p->d_uqe) (void)hipFree(p->d_uqe);
-    }
-    delete p;
-    return CP_OK;
-}
+extern "C" int cp_splice_plan_destroy(cp_splice_plan* p) { return cp::destroy_plan(p); }
 
 extern "C" int cp_splice_plan_create(cp_splice_plan** out, int nknots, const double* x, int npieces, const int* piece_src, const int* piece_start,
                                      const int* piece_count, int nq, const double* xq, int device) {
@@ -1041,8 +1025,9 @@ extern "C" int cp_splice_plan_create(cp_splice_plan** out, int nknots, const dou
     // queries: interval, source columns of its two knots, weights
     std::vector<int> first(3, n), qj(nq), qcol((size_t)2 * nq);
     std::vector<double> qw((size_t)4 * nq);
-    cp_splice_plan* p = new (std::nothrow) cp_splice_plan();
+    cp::PlanPtr<cp_splice_plan> p(new (std::nothrow) cp_splice_plan());
     if (!p) return cp::fail(CP_ENOMEM, "cp_splice_plan_create: host allocation failed");
+    p->device = device;
     for (int k = 0, f = 0; k < 3; ++k) {
         p->T.piece_src[k] = k < npieces ? piece_src[k] : 0;
         p->T.piece_start[k] = k < npieces ? piece_start[k] : 0;
@@ -1083,9 +1068,6 @@ extern "C" int cp_splice_plan_create(cp_splice_plan** out, int nknots, const dou
     if (generic_end <= generic_first) generic_first = generic_end = 0;
     p->T.generic_first = generic_first;
     p->T.generic_end = generic_end;
-    p->device = device;
-    p->d_tab = nullptr; p->d_qj = nullptr; p->d_qcol = nullptr; p->d_qw = nullptr;
-    p->d_uwin = nullptr; p->d_uqw = nullptr; p->d_uqe = nullptr;
     p->has_uniform = p->use_uniform = false;
     p->uniform_lds_bytes = 0;
     p->lds_bytes = lds;
@@ -1093,37 +1075,28 @@ extern "C" int cp_splice_plan_create(cp_splice_plan** out, int nknots, const dou
     p->T.ntab_left = ntab_left; p->T.uniform_end = uniform_end;
     p->T.h0 = h0; p->T.rh0 = 1. / h0; p->T.inv0 = inv0;
     cp::DeviceScope scope(device);
-    bool ok = scope.ok() && hipMalloc(&p->d_tab, tab.size() * sizeof(double)) == hipSuccess && hipMalloc(&p->d_qj, qj.size() * sizeof(int)) == hipSuccess &&
-              hipMalloc(&p->d_qcol, qcol.size() * sizeof(int)) == hipSuccess && hipMalloc(&p->d_qw, qw.size() * sizeof(double)) == hipSuccess;
-    ok = ok && hipMemcpy(p->d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(p->d_qj, qj.data(), qj.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(p->d_qcol, qcol.data(), qcol.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(p->d_qw, qw.data(), qw.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-        cp_splice_plan_destroy(p);
-        return cp::fail(CP_ENOMEM, "cp_splice_plan_create: cannot place the tables on device %d", device);
-    }
-    p->T.tab = p->d_tab; p->T.qj = p->d_qj; p->T.qcol = p->d_qcol; p->T.qw = p->d_qw;
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_splice_plan_create: cannot select device %d", device);
+    hipError_t e = p->d_tab.upload(tab.data(), tab.size());
+    if (e == hipSuccess) e = p->d_qj.upload(qj.data(), qj.size());
+    if (e == hipSuccess) e = p->d_qcol.upload(qcol.data(), qcol.size());
+    if (e == hipSuccess) e = p->d_qw.upload(qw.data(), qw.size());
+    if (e != hipSuccess) return cp::place_status("cp_splice_plan_create", device, e);
+    p->T.tab = p->d_tab.get(); p->T.qj = p->d_qj.get(); p->T.qcol = p->d_qcol.get(); p->T.qw = p->d_qw.get();
     if (best_hi - best_lo + 1 >= 256) {
         cpsu::Built built = cpsu::build(n, x, p->T.piece_first, p->T.piece_src, p->T.piece_start, npieces, nq, xq, qj.data(), best_lo, best_hi, generic_first,
                                         generic_end);
         if (built.ok) {
-            ok = hipMalloc(&p->d_uwin, built.win.size() * sizeof(double)) == hipSuccess && hipMalloc(&p->d_uqw, built.qw.size() * sizeof(double)) == hipSuccess &&
-                 hipMalloc(&p->d_uqe, built.qe.size() * sizeof(int)) == hipSuccess &&
-                 hipMemcpy(p->d_uwin, built.win.data(), built.win.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-                 hipMemcpy(p->d_uqw, built.qw.data(), built.qw.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-                 hipMemcpy(p->d_uqe, built.qe.data(), built.qe.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-            if (!ok) {
-                cp_splice_plan_destroy(p);
-                return cp::fail(CP_ENOMEM, "cp_splice_plan_create: cannot place the tables on device %d", device);
-            }
+            e = p->d_uwin.upload(built.win.data(), built.win.size());
+            if (e == hipSuccess) e = p->d_uqw.upload(built.qw.data(), built.qw.size());
+            if (e == hipSuccess) e = p->d_uqe.upload(built.qe.data(), built.qe.size());
+            if (e != hipSuccess) return cp::place_status("cp_splice_plan_create", device, e);
             p->U = built.T;
-            p->U.win = p->d_uwin; p->U.qw = p->d_uqw; p->U.qe = p->d_uqe;
+            p->U.win = p->d_uwin.get(); p->U.qw = p->d_uqw.get(); p->U.qe = p->d_uqe.get();
             p->uniform_lds_bytes = built.lds_bytes;
             p->has_uniform = p->use_uniform = true;
         }
     }
-    *out = p;
+    *out = p.release();
     return CP_OK;
 }
 
@@ -1161,8 +1134,7 @@ extern "C" int cp_splice_apply(const cp_splice_plan* p, const double* d_src0, in
     if ((nrows + 3) / 4 > 2147483647LL) return cp::fail(CP_EUNSUPPORTED, "cp_splice_apply: too many rows for one launch");
     cp::DeviceScope scope(p->device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_splice_apply: cannot select device %d", p->device);
-    int ncu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess || ncu <= 0) ncu = 256;
+    const int ncu = cp::cu_count(p->device);
     const long long blocks = (nrows + 3) / 4;
     if (p->use_uniform) {
         cpsu::Args U;

@@ -638,22 +638,12 @@ void launch(bool inverse, const Args& A, int grid, hipStream_t stream) {
 
 struct cp_dst_plan {
     int n, device;
-    cplx* d_tw;
-    cplx* d_rot;
-    double* d_kx;
-    double* d_ln_kx;      // log of the abscissa, filled at the first cp_dst_forward_analytic (device kernel: the bits of power_kernel's own logarithm)
+    cp::DeviceArray<cplx> d_tw, d_rot;
+    cp::DeviceArray<double> d_kx;
+    cp::DeviceArray<double> d_ln_kx;      // log of the abscissa, filled at the first cp_dst_forward_analytic (device kernel: the bits of power_kernel's own logarithm)
 };
 
-extern "C" int cp_dst_plan_destroy(cp_dst_plan* p) {
-    if (!p) return CP_OK;
-    cp::DeviceScope scope(p->device);
-    if (p->d_tw) (void)hipFree(p->d_tw);
-    if (p->d_rot) (void)hipFree(p->d_rot);
-    if (p->d_kx) (void)hipFree(p->d_kx);
-    if (p->d_ln_kx) (void)hipFree(p->d_ln_kx);
-    delete p;
-    return CP_OK;
-}
+extern "C" int cp_dst_plan_destroy(cp_dst_plan* p) { return cp::destroy_plan(p); }
 
 extern "C" int cp_dst_plan_create(cp_dst_plan** out, int n, const double* kx, int device) {
     if (!out) return cp::fail(CP_EINVAL, "cp_dst_plan_create: null plan pointer");
@@ -664,27 +654,21 @@ extern "C" int cp_dst_plan_create(cp_dst_plan** out, int n, const double* kx, in
     else if (n == 1024) build_twiddles<1024, 16>(tw);
     else build_twiddles<4096, 16>(tw);
     for (int k = 0; k < n; ++k) rot[k] = unit_root(k, 4LL * n);  // e^{-2 pi i k / 4N} = e^{-i pi k / 2N}
-    cp_dst_plan* p = new (std::nothrow) cp_dst_plan();
+    cp::PlanPtr<cp_dst_plan> p(new (std::nothrow) cp_dst_plan());
     if (!p) return cp::fail(CP_ENOMEM, "cp_dst_plan_create: host allocation failed");
-    p->n = n; p->device = device; p->d_tw = nullptr; p->d_rot = nullptr; p->d_kx = nullptr; p->d_ln_kx = nullptr;
+    p->n = n; p->device = device;
     cp::DeviceScope scope(device);
-    int status = scope.ok() ? CP_OK : cp::fail(CP_EDEVICE, "cp_dst_plan_create: cannot select device %d", device);
-    if (status == CP_OK && (hipMalloc(&p->d_tw, tw.size() * sizeof(cplx)) != hipSuccess || hipMalloc(&p->d_rot, n * sizeof(cplx)) != hipSuccess ||
-                            (kx && (hipMalloc(&p->d_kx, n * sizeof(double)) != hipSuccess || hipMalloc(&p->d_ln_kx, 8 * (size_t)n * sizeof(double)) != hipSuccess))))
-        status = cp::fail(CP_ENOMEM, "cp_dst_plan_create: device allocation failed");
-    if (status == CP_OK && (hipMemcpy(p->d_tw, tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice) != hipSuccess ||
-                            hipMemcpy(p->d_rot, rot.data(), n * sizeof(cplx), hipMemcpyHostToDevice) != hipSuccess ||
-                            (kx && hipMemcpy(p->d_kx, kx, n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)))
-        status = cp::fail(CP_EDEVICE, "cp_dst_plan_create: upload failed");
-    if (status == CP_OK && kx) {      // log of the abscissa with the kernels' own logarithm (default stream, then waited for: plan creation is synchronous)
-        hipLaunchKernelGGL(dst_log_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, p->d_kx, p->d_ln_kx, n);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) status = cp::fail(CP_EDEVICE, "cp_dst_plan_create: cannot tabulate log k");
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_dst_plan_create: cannot select device %d", device);
+    hipError_t e = p->d_tw.upload(tw.data(), tw.size());
+    if (e == hipSuccess) e = p->d_rot.upload(rot.data(), n);
+    if (e == hipSuccess && kx) e = p->d_kx.upload(kx, n);
+    if (e == hipSuccess && kx) e = p->d_ln_kx.alloc(8 * (size_t)n);
+    if (e != hipSuccess) return cp::place_status("cp_dst_plan_create", device, e);
+    if (kx) {      // log of the abscissa with the kernels' own logarithm (default stream, then waited for: plan creation is synchronous)
+        hipLaunchKernelGGL(dst_log_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, p->d_kx.get(), p->d_ln_kx.get(), n);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return cp::fail(CP_EDEVICE, "cp_dst_plan_create: cannot tabulate log k");
     }
-    if (status != CP_OK) {
-        cp_dst_plan_destroy(p);
-        return status;
-    }
-    *out = p;
+    *out = p.release();
     return CP_OK;
 }
 

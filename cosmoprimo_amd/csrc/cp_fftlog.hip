@@ -32,22 +32,12 @@ struct cp_fftlog_plan {
     int in_left, out_left;
     Launcher l;
     int max_grid[VAR_COUNT];  // resident workgroups on the device (CUs x occupancy) per kernel variant
-    double* d_pre;
-    double* d_post;
-    cplx* d_u;
-    cplx* d_tw;
-    unsigned* d_ticket;      // CP_CU_SLOTS arrival counters, zeroed once here and never again (cp_fftlog_kernel.h: balances_cu)
+    cp::DeviceArray<double> d_pre, d_post;
+    cp::DeviceArray<cplx> d_u, d_tw;
+    cp::DeviceArray<unsigned> d_ticket;      // CP_CU_SLOTS arrival counters, zeroed once here and never again (cp_fftlog_kernel.h: balances_cu)
     cp_fftlog_large* large;  // Np > CP_FFTLOG_MAX_NP: the general-size path (cp_fftlog_large.hip), everything above unused
+    ~cp_fftlog_plan() { cp_fftlog_large_destroy(large); }
 };
-
-#define CP_HIP(call)                                                                               \
-    do {                                                                                           \
-        hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            status = cp::fail(e_ == hipErrorOutOfMemory ? CP_ENOMEM : CP_EDEVICE, "%s: %s", #call, hipGetErrorString(e_)); \
-            goto done;                                                                             \
-        }                                                                                          \
-    } while (0)
 
 bool cp_fftlog_plan_view(const cp_fftlog_plan* p, cp_fftlog_tables_view* out) {
     if (!p || p->large || !out) return false;
@@ -78,102 +68,55 @@ extern "C" int cp_fftlog_plan_create(cp_fftlog_plan** out, int n, int npad, int 
     // (the plan stages nker x npad entries of three tables on the host: a request beyond 2^28 entries -- 8 GB -- is refused, not attempted)
     if ((long long)nker * npad > (1LL << 28))
         return cp::fail(CP_EUNSUPPORTED, "cp_fftlog_plan_create: %d transforms of padded size %d: tables of more than 2^28 entries", nker, npad);
-    if (npad > CP_FFTLOG_MAX_NP) {  // one packed pair no longer fits the LDS: elementwise kernels around a library FFT
-        cp_fftlog_plan* p = new (std::nothrow) cp_fftlog_plan();
-        if (!p) return cp::fail(CP_ENOMEM, "cp_fftlog_plan_create: host allocation failed");
-        p->n = n; p->npad = npad; p->nker = nker; p->device = device;
-        p->in_left = (npad - n) / 2;
-        p->out_left = (npad - n) - (npad - n) / 2;
-        p->d_pre = p->d_post = nullptr;
-        p->d_u = p->d_tw = nullptr;
-        p->d_ticket = nullptr;
-        p->large = nullptr;
-        cp::DeviceScope scope(device);
-        int st = scope.ok() ? cp_fftlog_large_create(&p->large, n, npad, nker, pre, post, u_re_im, device)
-                          : cp::fail(CP_EDEVICE, "cp_fftlog_plan_create: cannot select device %d", device);
-        if (st != CP_OK) {
-            delete p;
-            return st;
-        }
-        *out = p;
-        return CP_OK;
-    }
-    if (!find_launcher(npad, &l))
+    const bool large = npad > CP_FFTLOG_MAX_NP;  // one packed pair no longer fits the LDS: elementwise kernels around a library FFT
+    if (!large && !find_launcher(npad, &l))
         return cp::fail(CP_EUNSUPPORTED, "cp_fftlog_plan_create: padded size %d outside the LDS-resident kernel range [4, %d]", npad,
                         CP_FFTLOG_MAX_NP);
-    int status = CP_OK;
-    cp_fftlog_plan* p = new (std::nothrow) cp_fftlog_plan();
+    cp::PlanPtr<cp_fftlog_plan> p(new (std::nothrow) cp_fftlog_plan());
     if (!p) return cp::fail(CP_ENOMEM, "cp_fftlog_plan_create: host allocation failed");
-    p->large = nullptr;
     p->n = n;
     p->npad = npad;
     p->nker = nker;
     p->device = device;
     p->in_left = (npad - n) / 2;              // fftlog.py:152
     p->out_left = (npad - n) - (npad - n) / 2;  // fftlog.py:153
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_fftlog_plan_create: cannot select device %d", device);
+    if (large) {
+        const int st = cp_fftlog_large_create(&p->large, n, npad, nker, pre, post, u_re_im, device);
+        if (st != CP_OK) return st;
+        *out = p.release();
+        return CP_OK;
+    }
     p->l = l;
-    p->d_pre = p->d_post = nullptr;
-    p->d_u = p->d_tw = nullptr;
-    p->d_ticket = nullptr;
-    {
-        cp::DeviceScope scope(device);
-        std::vector<cplx> tw, u((size_t)nker * npad);
-        if (!scope.ok()) {
-            status = cp::fail(CP_EDEVICE, "cp_fftlog_plan_create: cannot select device %d", device);
-            goto done;
-        }
-        l.build_tw(tw);
-        for (int k = 0; k < nker; ++k) l.build_u(u_re_im + (size_t)k * 2 * (npad / 2 + 1), u.data() + (size_t)k * npad);
-        const size_t tbytes = (size_t)nker * npad * sizeof(double);
-        CP_HIP(hipMalloc(&p->d_pre, tbytes));
-        CP_HIP(hipMalloc(&p->d_post, tbytes));
-        CP_HIP(hipMalloc(&p->d_u, u.size() * sizeof(cplx)));
-        CP_HIP(hipMalloc(&p->d_tw, tw.size() * sizeof(cplx)));
-        CP_HIP(hipMemcpy(p->d_pre, pre, tbytes, hipMemcpyHostToDevice));
-        CP_HIP(hipMemcpy(p->d_post, post, tbytes, hipMemcpyHostToDevice));
-        CP_HIP(hipMemcpy(p->d_u, u.data(), u.size() * sizeof(cplx), hipMemcpyHostToDevice));
-        CP_HIP(hipMemcpy(p->d_tw, tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice));
-        CP_HIP(hipMalloc(&p->d_ticket, CP_CU_SLOTS * sizeof(unsigned)));
-        CP_HIP(hipMemset(p->d_ticket, 0, CP_CU_SLOTS * sizeof(unsigned)));  // before the plan exists for any caller: nothing to race with
-        int ncu = 0;
-        CP_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-        for (int v = 0; v < VAR_COUNT; ++v) {
-            p->max_grid[v] = 0;
-            if (!l.func[v]) continue;
-            const int lds_v = l.lds_bytes + l.lds_extra[v];
-            if (lds_v > 64 * 1024) CP_HIP(hipFuncSetAttribute(l.func[v], hipFuncAttributeMaxDynamicSharedMemorySize, lds_v));
-            int nblk = 0;
-            CP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, l.func[v], l.block, lds_v));
-            if (nblk < 1) {
-                status = cp::fail(CP_EDEVICE, "cp_fftlog_plan_create: kernel variant %d for npad=%d does not fit on a CU", v, npad);
-                goto done;
-            }
-            p->max_grid[v] = nblk * ncu;
-        }
+    std::vector<cplx> tw, u((size_t)nker * npad);
+    l.build_tw(tw);
+    for (int k = 0; k < nker; ++k) l.build_u(u_re_im + (size_t)k * 2 * (npad / 2 + 1), u.data() + (size_t)k * npad);
+    const size_t nt = (size_t)nker * npad;
+    int ncu = 0;
+    hipError_t e = p->d_pre.upload(pre, nt);
+    if (e == hipSuccess) e = p->d_post.upload(post, nt);
+    if (e == hipSuccess) e = p->d_u.upload(u.data(), u.size());
+    if (e == hipSuccess) e = p->d_tw.upload(tw.data(), tw.size());
+    if (e == hipSuccess) e = p->d_ticket.zeros(CP_CU_SLOTS);      // before the plan exists for any caller: nothing to race with
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
+    for (int v = 0; v < VAR_COUNT && e == hipSuccess; ++v) {
+        p->max_grid[v] = 0;
+        if (!l.func[v]) continue;
+        const int lds_v = l.lds_bytes + l.lds_extra[v];
+        int nblk = 0;
+        if (lds_v > 64 * 1024) e = hipFuncSetAttribute(l.func[v], hipFuncAttributeMaxDynamicSharedMemorySize, lds_v);
+        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, l.func[v], l.block, lds_v);
+        if (e != hipSuccess) break;
+        if (nblk < 1) return cp::fail(CP_EDEVICE, "cp_fftlog_plan_create: kernel variant %d for npad=%d does not fit on a CU", v, npad);
+        p->max_grid[v] = nblk * ncu;
     }
-done:
-    if (status != CP_OK) {
-        cp_fftlog_plan_destroy(p);
-        return status;
-    }
-    *out = p;
+    if (e != hipSuccess) return cp::place_status("cp_fftlog_plan_create", device, e);
+    *out = p.release();
     return CP_OK;
 }
 
-extern "C" int cp_fftlog_plan_destroy(cp_fftlog_plan* p) {
-    if (!p) return CP_OK;
-    {
-        cp::DeviceScope scope(p->device);
-        if (p->d_pre) (void)hipFree(p->d_pre);
-        if (p->d_post) (void)hipFree(p->d_post);
-        if (p->d_u) (void)hipFree(p->d_u);
-        if (p->d_tw) (void)hipFree(p->d_tw);
-        if (p->d_ticket) (void)hipFree(p->d_ticket);
-        cp_fftlog_large_destroy(p->large);
-    }
-    delete p;
-    return CP_OK;
-}
+extern "C" int cp_fftlog_plan_destroy(cp_fftlog_plan* p) { return cp::destroy_plan(p); }
 
 static int grid_for(const cp_fftlog_plan* p, int variant, long long nbatch) {
     const long long npairs = ((nbatch + 1) / 2) * p->nker;

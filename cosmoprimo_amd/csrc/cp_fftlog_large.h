@@ -7,4 +7,4 @@ struct cp_fftlog_large;
 int cp_fftlog_large_create(cp_fftlog_large** out, int n, int npad, int nker, const double* pre, const double* post, const double* u_re_im, int device);
 int cp_fftlog_large_execute(cp_fftlog_large* p, const double* d_in, double* d_out, long long nbatch, int ext_l, double val_l, int ext_r, double val_r,
                             int keep_padding, hipStream_t stream);
-void cp_fftlog_large_destroy(cp_fftlog_large* p);
+void cp_fftlog_large_destroy(cp_fftlog_large* p);      // with the plan's device current (cp_fftlog.hip: the owning plan's destructor)

@@ -415,29 +415,26 @@ struct cp_fftlog_large {
     int n1, log2c;
     Radices rd;
     long long chunk;       // pairs per pass through the scratch
-    double* d_pre;
-    double* d_post;
-    cplx* d_u;             // (nker, n1, 4096)
-    cplx* d_tw;            // w_4096^i | w_Np^i (i < 256 n1) | w_(16 n1)^i (i < 16 n1) | w_4096^(t q) at [q][t]
+    cp::DeviceArray<double> d_pre, d_post;
+    cp::DeviceArray<cplx> d_u;       // (nker, n1, 4096)
+    cp::DeviceArray<cplx> d_tw;      // w_4096^i | w_Np^i (i < 256 n1) | w_(16 n1)^i (i < 16 n1) | w_4096^(t q) at [q][t]
     int row_grid;          // workgroups of the persistent row kernel: two per CU (68 KB of LDS each)
-    cplx* d_work;          // (chunk, npad)
-    unsigned* d_mag;       // (2 chunk)
+    cp::DeviceArray<cplx> d_work;        // (chunk, npad)
+    cp::DeviceArray<unsigned> d_mag;     // (2 chunk)
     std::mutex lock;       // the scratch is shared: one execute is ENQUEUED at a time ...
     hipEvent_t done;       // ... and an execute waits, on its own stream, for the event the previous execute recorded behind its last kernel,
     bool has_done;         // so that executes of one plan on different streams cannot overlap on the device
+    ~cp_fftlog_large() {
+        if (done) (void)hipEventDestroy(done);
+    }
 };
 
 int cp_fftlog_large_create(cp_fftlog_large** out, int n, int npad, int nker, const double* pre, const double* post, const double* u_re_im, int device) {
     *out = nullptr;
     if (npad > (1 << 24) || npad < 4 * ROW) return cp::fail(CP_EUNSUPPORTED, "padded size %d is outside the range of the large-size path (2^14 .. 2^24)", npad);
-    cp_fftlog_large* p = new (std::nothrow) cp_fftlog_large();
+    std::unique_ptr<cp_fftlog_large> p(new (std::nothrow) cp_fftlog_large());      // (the caller holds the device scope)
     if (!p) return cp::fail(CP_ENOMEM, "cp_fftlog_plan_create: host allocation failed");
     p->n = n; p->npad = npad; p->nker = nker; p->device = device;
-    p->d_pre = p->d_post = nullptr;
-    p->d_u = p->d_tw = p->d_work = nullptr;
-    p->d_mag = nullptr;
-    p->done = nullptr;
-    p->has_done = false;
     const int n1 = npad / ROW;
     p->n1 = n1;
     int log2c = 0;
@@ -462,7 +459,6 @@ int cp_fftlog_large_create(cp_fftlog_large** out, int n, int npad, int nker, con
         for (long long i = 0; i < 16LL * n1; ++i) tw[ROW + 256 * (size_t)n1 + i] = cpfft::unit_root(i, 16LL * n1);
         u.resize((size_t)nker * npad);
     } catch (const std::bad_alloc&) {
-        delete p;
         return cp::fail(CP_ENOMEM, "cp_fftlog_plan_create: host allocation failed");
     }
     const int nh = npad / 2 + 1;
@@ -483,40 +479,25 @@ int cp_fftlog_large_create(cp_fftlog_large** out, int n, int npad, int nker, con
                 u[((size_t)ker * n1 + k1) * ROW + (pos & 15) * 256 + (pos >> 4)] = v;      // position 16 t + q at [q][t]: a wave reads 1 KB segments
             }
     }
-    const size_t tb = (size_t)nker * npad * sizeof(double);
-    bool ok = hipMalloc(&p->d_pre, tb) == hipSuccess && hipMalloc(&p->d_post, tb) == hipSuccess &&
-              hipMalloc(&p->d_u, u.size() * sizeof(cplx)) == hipSuccess && hipMalloc(&p->d_tw, tw.size() * sizeof(cplx)) == hipSuccess &&
-              hipMalloc(&p->d_work, (size_t)chunk * npad * sizeof(cplx)) == hipSuccess &&
-              hipMalloc(&p->d_mag, (size_t)chunk * 2 * sizeof(unsigned)) == hipSuccess;
-    ok = ok && hipMemcpy(p->d_pre, pre, tb, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(p->d_post, post, tb, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(p->d_u, u.data(), u.size() * sizeof(cplx), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(p->d_tw, tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-        cp_fftlog_large_destroy(p);
-        return cp::fail(CP_ENOMEM, "cp_fftlog_plan_create: cannot allocate the tables / scratch of the large-size path on device %d", device);
-    }
+    const size_t nt = (size_t)nker * npad;
+    hipError_t e = p->d_pre.upload(pre, nt);
+    if (e == hipSuccess) e = p->d_post.upload(post, nt);
+    if (e == hipSuccess) e = p->d_u.upload(u.data(), u.size());
+    if (e == hipSuccess) e = p->d_tw.upload(tw.data(), tw.size());
+    if (e == hipSuccess) e = p->d_work.alloc((size_t)chunk * npad);
+    if (e == hipSuccess) e = p->d_mag.alloc((size_t)chunk * 2);
+    if (e != hipSuccess) return cp::place_status("cp_fftlog_plan_create", device, e);
     if (hipEventCreateWithFlags(&p->done, hipEventDisableTiming) != hipSuccess) {
         p->done = nullptr;
-        cp_fftlog_large_destroy(p);
         return cp::fail(CP_EDEVICE, "cp_fftlog_plan_create: cannot create the stream-ordering event of the large-size path");
     }
     hipDeviceProp_t prop;
     p->row_grid = hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0 ? 2 * prop.multiProcessorCount : 512;
-    *out = p;
+    *out = p.release();
     return CP_OK;
 }
 
-void cp_fftlog_large_destroy(cp_fftlog_large* p) {
-    if (!p) return;
-    if (p->d_pre) (void)hipFree(p->d_pre);
-    if (p->d_post) (void)hipFree(p->d_post);
-    if (p->d_u) (void)hipFree(p->d_u);
-    if (p->d_tw) (void)hipFree(p->d_tw);
-    if (p->d_work) (void)hipFree(p->d_work);
-    if (p->d_mag) (void)hipFree(p->d_mag);
-    if (p->done) (void)hipEventDestroy(p->done);
-    delete p;
-}
+void cp_fftlog_large_destroy(cp_fftlog_large* p) { delete p; }
 
 int cp_fftlog_large_execute(cp_fftlog_large* p, const double* d_in, double* d_out, long long nbatch, int ext_l, double val_l, int ext_r, double val_r,
                             int keep_padding, hipStream_t st) {

@@ -3,8 +3,10 @@
 #pragma once
 #include <atomic>
 #include <hip/hip_runtime.h>
+#include <memory>
 
 #include "../../include/cosmoprimo_amd.h"
+#include "cp_device_array.h"
 #include "cp_error.h"
 
 namespace cpfft {
@@ -82,6 +84,24 @@ public:
     DeviceScope& operator=(const DeviceScope&) = delete;
     bool ok() const { return ok_; }
 };
+
+// What every cp_*_destroy does: the plan's DeviceArray members (cp_device_array.h) are freed with the plan's device current.
+template <class Plan>
+int destroy_plan(Plan* p) {
+    if (!p) return CP_OK;
+    DeviceScope scope(p->device);
+    delete p;
+    return CP_OK;
+}
+// a plan under construction: destroyed that way on every way out of its constructor but release()
+struct PlanDelete {
+    template <class Plan>
+    void operator()(Plan* p) const {
+        (void)destroy_plan(p);
+    }
+};
+template <class Plan>
+using PlanPtr = std::unique_ptr<Plan, PlanDelete>;
 
 // The workspace of the entries that evaluate spectra themselves: the cosmologies' constants, 64-byte aligned, and -- for the kernels that evaluate on a
 // shared grid of nk wavenumbers -- the (3, nk) table cp_power_coefficients writes, 64-byte aligned behind them.

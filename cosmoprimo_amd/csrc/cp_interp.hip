@@ -97,10 +97,10 @@ extern "C" int cp_interp_linear(const double* d_xp, const double* d_fp, long lon
 struct cp_interp_table {
     int device;
     long long n;
-    double* d_xf;         // (n, 2): (x_i, f_i)
-    double* d_x;          // (n): the knots alone (bisection of the irregular case)
-    double* d_f;
-    int* d_flag;          // raised by samples outside [x_0, x_{n-1}] / NaN
+    cp::DeviceArray<double> d_xf;      // (n, 2): (x_i, f_i)
+    cp::DeviceArray<double> d_x;       // (n): the knots alone (bisection of the irregular case)
+    cp::DeviceArray<double> d_f;
+    cp::DeviceArray<int> d_flag;       // raised by samples outside [x_0, x_{n-1}] / NaN
     int law;              // 0 none (bisection), 1 uniform in x, 2 uniform in log2 x
     long long first;      // the law holds from this knot on (the knots before it: bisection among them)
     double a, b;          // index = first + (T(x) - a) * b
@@ -142,25 +142,21 @@ extern "C" int cp_interp_table_create(cp_interp_table** table, long long n, cons
     if (n > (1LL << 27)) return cp::fail(CP_EUNSUPPORTED, "cp_interp_table_create: %lld rows (at most 2^27: the table is staged as pairs on the host)", n);
     for (long long i = 1; i < n; ++i)
         if (!(x[i] >= x[i - 1])) return cp::fail(CP_EINVAL, "cp_interp_table_create: x must be ascending (row %lld)", i);
-    cp_interp_table* t = new (std::nothrow) cp_interp_table();
+    cp::PlanPtr<cp_interp_table> t(new (std::nothrow) cp_interp_table());
     if (!t) return cp::fail(CP_ENOMEM, "cp_interp_table_create: out of host memory");
-    t->device = device; t->n = n; t->law = 0; t->first = 0; t->a = 0.; t->b = 0.; t->x0 = x[0]; t->xn = x[n - 1];
-    t->d_xf = t->d_x = t->d_f = nullptr; t->d_flag = nullptr;
+    t->device = device; t->n = n; t->x0 = x[0]; t->xn = x[n - 1];
     const cpit::Law law = cpit::find_law(x, n);      // uniform in x, uniform in log x behind a few leading knots, or neither (cp_interp_table.h)
     t->law = law.law; t->first = law.first; t->a = law.a; t->b = law.b;
     cp::DeviceScope scope(device);
-    if (!scope.ok()) { delete t; return cp::fail(CP_EDEVICE, "cp_interp_table_create: cannot select device %d", device); }
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_interp_table_create: cannot select device %d", device);
     std::vector<double> pairs(2 * (size_t)n);
     for (long long i = 0; i < n; ++i) { pairs[2 * i] = x[i]; pairs[2 * i + 1] = f[i]; }
-    const int zero = 0;
-    bool ok = hipMalloc(&t->d_xf, 2 * n * sizeof(double)) == hipSuccess && hipMalloc(&t->d_x, n * sizeof(double)) == hipSuccess &&
-              hipMalloc(&t->d_f, n * sizeof(double)) == hipSuccess && hipMalloc(&t->d_flag, sizeof(int)) == hipSuccess;
-    ok = ok && hipMemcpy(t->d_xf, pairs.data(), 2 * n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(t->d_x, x, n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(t->d_f, f, n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(t->d_flag, &zero, sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { (void)cp_interp_table_destroy(t); return cp::fail(CP_ENOMEM, "cp_interp_table_create: device allocation or upload failed"); }
-    *table = t;
+    hipError_t e = t->d_xf.upload(pairs.data(), pairs.size());
+    if (e == hipSuccess) e = t->d_x.upload(x, n);
+    if (e == hipSuccess) e = t->d_f.upload(f, n);
+    if (e == hipSuccess) e = t->d_flag.zeros(1);
+    if (e != hipSuccess) return cp::place_status("cp_interp_table_create", device, e);
+    *table = t.release();
     return CP_OK;
 }
 
@@ -197,7 +193,7 @@ int interp_table_apply(const cp_interp_table* t, const real* d_x, real* d_out, l
     } else {
         const long long blocks = (nx + 255) / 256;
         const unsigned grid = (unsigned)(blocks < 256 * 16 ? blocks : 256 * 16);
-        const cpit::Pair* xf = reinterpret_cast<const cpit::Pair*>(t->d_xf);
+        const cpit::Pair* xf = reinterpret_cast<const cpit::Pair*>(t->d_xf.get());
         if (t->law == 1) hipLaunchKernelGGL((interp_table_kernel<1, real>), dim3(grid), dim3(256), 0, hs, xf, t->n, t->first, t->a, t->b, d_x, d_out, nx, flag);
         else hipLaunchKernelGGL((interp_table_kernel<2, real>), dim3(grid), dim3(256), 0, hs, xf, t->n, t->first, t->a, t->b, d_x, d_out, nx, flag);
         st = cp::launch_status(who);
@@ -226,16 +222,7 @@ extern "C" int cp_interp_table_apply_f32(const cp_interp_table* t, const float* 
     return interp_table_apply<float>(t, d_x, d_out, nx, outside, stream, "cp_interp_table_apply_f32");
 }
 
-extern "C" int cp_interp_table_destroy(cp_interp_table* t) {
-    if (!t) return CP_OK;
-    cp::DeviceScope scope(t->device);
-    if (t->d_xf) (void)hipFree(t->d_xf);
-    if (t->d_x) (void)hipFree(t->d_x);
-    if (t->d_f) (void)hipFree(t->d_f);
-    if (t->d_flag) (void)hipFree(t->d_flag);
-    delete t;
-    return CP_OK;
-}
+extern "C" int cp_interp_table_destroy(cp_interp_table* t) { return cp::destroy_plan(t); }
 
 // ---- cubic splines at many points: one lane per query ------------------------------------------------------------------------------------
 // The operator form of cp_spline_apply (a band of weights per query, shared by all rows) suits thousands of rows on a fixed set of queries.

@@ -183,18 +183,10 @@ void rlaunch(bool backward, const RArgs& A, int grid, hipStream_t stream) {
 
 struct cp_rfft_plan {
     int size, device;
-    cplx* d_tw;
-    cplx* d_rot;
+    cp::DeviceArray<cplx> d_tw, d_rot;
 };
 
-extern "C" int cp_rfft_plan_destroy(cp_rfft_plan* p) {
-    if (!p) return CP_OK;
-    cp::DeviceScope scope(p->device);
-    if (p->d_tw) (void)hipFree(p->d_tw);
-    if (p->d_rot) (void)hipFree(p->d_rot);
-    delete p;
-    return CP_OK;
-}
+extern "C" int cp_rfft_plan_destroy(cp_rfft_plan* p) { return cp::destroy_plan(p); }
 
 extern "C" int cp_rfft_plan_create(cp_rfft_plan** out, int size, int device) {
     if (!out) return cp::fail(CP_EINVAL, "cp_rfft_plan_create: null plan pointer");
@@ -208,21 +200,15 @@ extern "C" int cp_rfft_plan_create(cp_rfft_plan** out, int size, int device) {
     CP_RFFT_SIZES(X)
 #undef X
     for (int k = 0; k < m; ++k) rot[k] = unit_root(k, size);
-    cp_rfft_plan* p = new (std::nothrow) cp_rfft_plan();
+    cp::PlanPtr<cp_rfft_plan> p(new (std::nothrow) cp_rfft_plan());
     if (!p) return cp::fail(CP_ENOMEM, "cp_rfft_plan_create: host allocation failed");
-    p->size = size; p->device = device; p->d_tw = nullptr; p->d_rot = nullptr;
+    p->size = size; p->device = device;
     cp::DeviceScope scope(device);
-    int status = scope.ok() ? CP_OK : cp::fail(CP_EDEVICE, "cp_rfft_plan_create: cannot select device %d", device);
-    if (status == CP_OK && (hipMalloc(&p->d_tw, tw.size() * sizeof(cplx)) != hipSuccess || hipMalloc(&p->d_rot, m * sizeof(cplx)) != hipSuccess))
-        status = cp::fail(CP_ENOMEM, "cp_rfft_plan_create: device allocation failed");
-    if (status == CP_OK && (hipMemcpy(p->d_tw, tw.data(), tw.size() * sizeof(cplx), hipMemcpyHostToDevice) != hipSuccess ||
-                            hipMemcpy(p->d_rot, rot.data(), m * sizeof(cplx), hipMemcpyHostToDevice) != hipSuccess))
-        status = cp::fail(CP_EDEVICE, "cp_rfft_plan_create: upload failed");
-    if (status != CP_OK) {
-        cp_rfft_plan_destroy(p);
-        return status;
-    }
-    *out = p;
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_rfft_plan_create: cannot select device %d", device);
+    hipError_t e = p->d_tw.upload(tw.data(), tw.size());
+    if (e == hipSuccess) e = p->d_rot.upload(rot.data(), m);
+    if (e != hipSuccess) return cp::place_status("cp_rfft_plan_create", device, e);
+    *out = p.release();
     return CP_OK;
 }
 

@@ -1197,22 +1197,14 @@ extern "C" int cp_fftlog_spline_execute(const cp_fftlog_plan* fftlog, const cp_s
 // ---- natural spline on a geometric grid, solved inside the FFTLog kernel (fftlog_geospline_kernel above) -----------------------------------------
 struct cp_geospline_plan {
     int n, nq, ws, ne, S, device;
-    int* d_qe;
-    double* d_qa;
-    GeoConsts* d_consts;
+    cp::DeviceArray<int> d_qe;
+    cp::DeviceArray<double> d_qa;
+    cp::DeviceArray<GeoConsts> d_consts;
     cp_fftlog_plan* prefiltered;      // plans of cp_geospline_plan_create_prefiltered: the transform whose output is the B-spline coefficients
+    ~cp_geospline_plan() { (void)cp_fftlog_plan_destroy(prefiltered); }
 };
 
-extern "C" int cp_geospline_plan_destroy(cp_geospline_plan* p) {
-    if (!p) return CP_OK;
-    cp::DeviceScope scope(p->device);
-    if (p->d_qe) (void)hipFree(p->d_qe);
-    if (p->d_qa) (void)hipFree(p->d_qa);
-    if (p->d_consts) (void)hipFree(p->d_consts);
-    if (p->prefiltered) (void)cp_fftlog_plan_destroy(p->prefiltered);
-    delete p;
-    return CP_OK;
-}
+extern "C" int cp_geospline_plan_destroy(cp_geospline_plan* p) { return cp::destroy_plan(p); }
 
 namespace {
 
@@ -1280,15 +1272,11 @@ void geometric_bspline_pieces(long double rho, long double basis[4][4]) {
 int upload_geospline(cp_geospline_plan* p, const std::vector<int>& qj, const std::vector<double>& qa, const GeoConsts& consts) {
     const int nq = p->nq, device = p->device;
     cp::DeviceScope scope(device);
-    int status = scope.ok() ? CP_OK : cp::fail(CP_EDEVICE, "cp_geospline_plan_create: cannot select device %d", device);
-    if (status == CP_OK && (hipMalloc(&p->d_qe, nq * sizeof(int)) != hipSuccess || hipMalloc(&p->d_qa, nq * sizeof(double)) != hipSuccess ||
-                            hipMalloc(&p->d_consts, sizeof(GeoConsts)) != hipSuccess))
-        status = cp::fail(CP_ENOMEM, "cp_geospline_plan_create: device allocation failed");
-    if (status == CP_OK && (hipMemcpy(p->d_qe, qj.data(), nq * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-                            hipMemcpy(p->d_qa, qa.data(), nq * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-                            hipMemcpy(p->d_consts, &consts, sizeof(GeoConsts), hipMemcpyHostToDevice) != hipSuccess))
-        status = cp::fail(CP_EDEVICE, "cp_geospline_plan_create: upload failed");
-    return status;
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_geospline_plan_create: cannot select device %d", device);
+    hipError_t e = p->d_qe.upload(qj.data(), nq);
+    if (e == hipSuccess) e = p->d_qa.upload(qa.data(), nq);
+    if (e == hipSuccess) e = p->d_consts.upload(&consts, 1);
+    return e == hipSuccess ? CP_OK : cp::place_status("cp_geospline_plan_create", device, e);
 }
 
 }  // namespace
@@ -1315,10 +1303,9 @@ extern "C" int cp_geospline_plan_create(cp_geospline_plan** out, const double* k
     if (ws + ne > n - 2) ws = n - 2 - ne;
     if (ws < 2 || jmin - ws < GEO_HALO || ws + ne - 1 - jmax < GEO_HALO)
         return cp::fail(CP_EUNSUPPORTED, "cp_geospline_plan_create: the queries come within %d knots of the ends of the grid", GEO_HALO);
-    cp_geospline_plan* p = new (std::nothrow) cp_geospline_plan();
+    cp::PlanPtr<cp_geospline_plan> p(new (std::nothrow) cp_geospline_plan());
     if (!p) return cp::fail(CP_ENOMEM, "cp_geospline_plan_create: host allocation failed");
-    p->n = n; p->nq = nq; p->ws = ws; p->ne = ne; p->S = S; p->device = device; p->d_qe = nullptr; p->d_qa = nullptr; p->d_consts = nullptr;
-    p->prefiltered = nullptr;
+    p->n = n; p->nq = nq; p->ws = ws; p->ne = ne; p->S = S; p->device = device;
     GeoConsts consts{};
     {
         // a N_{i-1} + b N_i + c N_{i+1} = d_i on the infinite grid: N_i = kappa (sum_{j <= i} pL^(i-j) d_j + sum_{j > i} pR^(j-i) d_j), pL the root of
@@ -1340,12 +1327,9 @@ extern "C" int cp_geospline_plan_create(cp_geospline_plan** out, const double* k
     }
     for (int q = 0; q < nq; ++q)
         if (qj[q] >= 0) qj[q] -= ws;
-    const int status = upload_geospline(p, qj, qa, consts);
-    if (status != CP_OK) {
-        cp_geospline_plan_destroy(p);
-        return status;
-    }
-    *out = p;
+    const int status = upload_geospline(p.get(), qj, qa, consts);
+    if (status != CP_OK) return status;
+    *out = p.release();
     return CP_OK;
 }
 
@@ -1404,27 +1388,22 @@ extern "C" int cp_geospline_plan_create_prefiltered(cp_geospline_plan** out, int
             u[2 * m + 1] = (double)((ui * dr - ur * di) * inv);
         }
     }
-    cp_geospline_plan* p = new (std::nothrow) cp_geospline_plan();
+    cp::PlanPtr<cp_geospline_plan> p(new (std::nothrow) cp_geospline_plan());
     if (!p) return cp::fail(CP_ENOMEM, "%s: host allocation failed", who);
-    p->n = n; p->nq = nq; p->ws = ws; p->ne = ne; p->S = 0; p->device = device; p->d_qe = nullptr; p->d_qa = nullptr; p->d_consts = nullptr;
-    p->prefiltered = nullptr;
+    p->n = n; p->nq = nq; p->ws = ws; p->ne = ne; p->S = 0; p->device = device;
     int status = cp_fftlog_plan_create(&p->prefiltered, n, npad, 1, pre, post, u.data(), device);
-    if (status == CP_OK) {
-        GeoConsts consts{};
-        for (int i = 0; i < 4; ++i)
-            for (int e = 0; e < 4; ++e) consts.basis.k[i][e] = (double)basis[i][e];
-        for (int q = 0; q < nq; ++q)
-            if (qj[q] >= 0) {
-                qj[q] -= ws;
-                qa[q] = 1. - qa[q];
-            }
-        status = upload_geospline(p, qj, qa, consts);
-    }
-    if (status != CP_OK) {
-        cp_geospline_plan_destroy(p);
-        return status;
-    }
-    *out = p;
+    if (status != CP_OK) return status;
+    GeoConsts consts{};
+    for (int i = 0; i < 4; ++i)
+        for (int e = 0; e < 4; ++e) consts.basis.k[i][e] = (double)basis[i][e];
+    for (int q = 0; q < nq; ++q)
+        if (qj[q] >= 0) {
+            qj[q] -= ws;
+            qa[q] = 1. - qa[q];
+        }
+    status = upload_geospline(p.get(), qj, qa, consts);
+    if (status != CP_OK) return status;
+    *out = p.release();
     return CP_OK;
 }
 
@@ -1444,7 +1423,7 @@ extern "C" int cp_sigma_rz_analytic_prefiltered(int engine, long long ncosmo, co
     if (spline->device != device) return cp::fail(CP_EINVAL, "cp_sigma_rz_analytic_prefiltered: the spline plan lives on device %d", spline->device);
     cp_fftlog_tables_view f;
     if (!cp_fftlog_plan_view(spline->prefiltered, &f)) return cp::fail(CP_EINVAL, "cp_sigma_rz_analytic_prefiltered: plan without device tables");
-    const GeoTail geo{spline->nq, spline->ws, spline->d_qe, spline->d_qa, &spline->d_consts->basis};
+    const GeoTail geo{spline->nq, spline->ws, spline->d_qe, spline->d_qa, &spline->d_consts.get()->basis};
     return sigma_rz_fused_launch("cp_sigma_rz_analytic_prefiltered", engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, pk_params, d_k, f, nullptr, &geo, d_growth_sq, nz,
                                  d_out, d_pk_out, d_work, device, stream);
 }

@@ -587,12 +587,11 @@ int build_system(int n, const double* x, int bc, std::vector<double>& lo, std::v
 
 struct cp_spline_plan {
     int n, nq, bw, device;
-    double* d_wb;
-    int* d_j0;
-    int* d_tile;
+    cp::DeviceArray<double> d_wb;
+    cp::DeviceArray<int> d_j0, d_tile;
     int ntiles, span_max;
-    double* d_wdense;    // operators that are dense (band wider than half the knots): (nq_pad, n_pad) row-major, zero padded, for the MFMA kernel
-    int* d_kwin;         // windows of knots per tile of 64 queries, for the matrix-core kernel
+    cp::DeviceArray<double> d_wdense;    // operators that are dense (band wider than half the knots): (nq_pad, n_pad) row-major, zero padded, for the MFMA kernel
+    cp::DeviceArray<int> d_kwin;         // windows of knots per tile of 64 queries, for the matrix-core kernel
     int n_pad, nq_pad;
     bool prefer_dense;
     bool sub_windows;          // linop_mfma_kernel<true>: the tiles of 16 queries need at most two thirds of the chunks of their tiles of 64
@@ -605,17 +604,7 @@ bool cp_spline_plan_view(const cp_spline_plan* p, cp_spline_band_view* out) {
     return true;
 }
 
-extern "C" int cp_spline_plan_destroy(cp_spline_plan* p) {
-    if (!p) return CP_OK;
-    cp::DeviceScope scope(p->device);
-    if (p->d_wb) (void)hipFree(p->d_wb);
-    if (p->d_j0) (void)hipFree(p->d_j0);
-    if (p->d_tile) (void)hipFree(p->d_tile);
-    if (p->d_wdense) (void)hipFree(p->d_wdense);
-    if (p->d_kwin) (void)hipFree(p->d_kwin);
-    delete p;
-    return CP_OK;
-}
+extern "C" int cp_spline_plan_destroy(cp_spline_plan* p) { return cp::destroy_plan(p); }
 
 // Dense operator on the host (row-major nq x n); exposed so that tests can pin it against scipy without a GPU.
 extern "C" int cp_spline_operator(int n, const double* x, int nq, const double* xq, int bc, int nu, int extrapolate, double* w_out, int* inside_out) {
@@ -756,12 +745,10 @@ static int plan_from_dense(cp_spline_plan** out, int n, int nq, const double* w,
         q0 = q;
     }
     const int ntiles = (int)(tile.size() / 4);
-    cp_spline_plan* p = new (std::nothrow) cp_spline_plan();
+    cp::PlanPtr<cp_spline_plan> p(new (std::nothrow) cp_spline_plan());
     if (!p) return cp::fail(CP_ENOMEM, "cp_spline_plan_create: host allocation failed");
-    p->n = n; p->nq = nq; p->bw = bw; p->device = device; p->d_wb = nullptr; p->d_j0 = nullptr; p->d_tile = nullptr;
+    p->n = n; p->nq = nq; p->bw = bw; p->device = device;
     p->ntiles = ntiles; p->span_max = span_max;
-    p->d_wdense = nullptr;
-    p->d_kwin = nullptr;
     p->n_pad = (n + 15) / 16 * 16;
     p->nq_pad = (nq + 63) / 64 * 64;
     // A dense copy (zero outside the bands) serves the matrix-core kernel, which treats the operator as a block-banded GEMM: a tile of 64
@@ -842,25 +829,14 @@ static int plan_from_dense(cp_spline_plan** out, int n, int nq, const double* w,
     p->col_last = std::min(p->col_last, n);
     p->col_first = std::min(p->col_first, p->col_last);
     cp::DeviceScope scope(device);
-    int status = scope.ok() ? CP_OK : cp::fail(CP_EDEVICE, "cp_spline_plan_create: cannot select device %d", device);
-    if (status == CP_OK && (hipMalloc(&p->d_wb, wb.size() * sizeof(double)) != hipSuccess || hipMalloc(&p->d_j0, nq * sizeof(int)) != hipSuccess ||
-                            hipMalloc(&p->d_tile, tile.size() * sizeof(int)) != hipSuccess))
-        status = cp::fail(CP_ENOMEM, "cp_spline_plan_create: device allocation failed");
-    if (status == CP_OK && (hipMemcpy(p->d_wb, wb.data(), wb.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-                            hipMemcpy(p->d_j0, j0.data(), nq * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-                            hipMemcpy(p->d_tile, tile.data(), tile.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess))
-        status = cp::fail(CP_EDEVICE, "cp_spline_plan_create: upload failed");
-    if (status == CP_OK && dense &&
-        (hipMalloc(&p->d_wdense, wd.size() * sizeof(double)) != hipSuccess ||
-         hipMemcpy(p->d_wdense, wd.data(), wd.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-         hipMalloc(&p->d_kwin, kwin.size() * sizeof(int)) != hipSuccess ||
-         hipMemcpy(p->d_kwin, kwin.data(), kwin.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess))
-        status = cp::fail(CP_ENOMEM, "cp_spline_plan_create: cannot upload the dense operator");
-    if (status != CP_OK) {
-        cp_spline_plan_destroy(p);
-        return status;
-    }
-    *out = p;
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_spline_plan_create: cannot select device %d", device);
+    hipError_t e = p->d_wb.upload(wb.data(), wb.size());
+    if (e == hipSuccess) e = p->d_j0.upload(j0.data(), nq);
+    if (e == hipSuccess) e = p->d_tile.upload(tile.data(), tile.size());
+    if (e == hipSuccess && dense) e = p->d_wdense.upload(wd.data(), wd.size());
+    if (e == hipSuccess && dense) e = p->d_kwin.upload(kwin.data(), kwin.size());
+    if (e != hipSuccess) return cp::place_status("cp_spline_plan_create", device, e);
+    *out = p.release();
     return CP_OK;
 }
 

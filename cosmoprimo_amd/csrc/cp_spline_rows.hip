@@ -191,21 +191,13 @@ __global__ __launch_bounds__(256) void spline_rows_kernel(const RowsArgs A) {
 struct cp_spline_rows_plan {
     RowsTables T;
     int device;
-    double* d_tab;
-    int* d_qj;
-    double* d_qw;
+    cp::DeviceArray<double> d_tab;
+    cp::DeviceArray<int> d_qj;
+    cp::DeviceArray<double> d_qw;
     size_t lds_bytes;
 };
 
-extern "C" int cp_spline_rows_plan_destroy(cp_spline_rows_plan* p) {
-    if (!p) return CP_OK;
-    cp::DeviceScope scope(p->device);
-    if (p->d_tab) (void)hipFree(p->d_tab);
-    if (p->d_qj) (void)hipFree(p->d_qj);
-    if (p->d_qw) (void)hipFree(p->d_qw);
-    delete p;
-    return CP_OK;
-}
+extern "C" int cp_spline_rows_plan_destroy(cp_spline_rows_plan* p) { return cp::destroy_plan(p); }
 
 extern "C" int cp_spline_rows_plan_create(cp_spline_rows_plan** out, int n, const double* x, int bc, int extrapolate, int nq, const double* xq, int device) {
     if (!out) return cp::fail(CP_EINVAL, "cp_spline_rows_plan_create: null plan pointer");
@@ -310,27 +302,22 @@ extern "C" int cp_spline_rows_plan_create(cp_spline_rows_plan** out, int n, cons
         qw[4 * k + 3] = (b * b * b - b) * (h[j] * h[j]) / 6.;
         qj[k] = j - w0;
     }
-    cp_spline_rows_plan* p = new (std::nothrow) cp_spline_rows_plan();
+    cp::PlanPtr<cp_spline_rows_plan> p(new (std::nothrow) cp_spline_rows_plan());
     if (!p) return cp::fail(CP_ENOMEM, "cp_spline_rows_plan_create: host allocation failed");
     p->device = device;
-    p->d_tab = nullptr; p->d_qj = nullptr; p->d_qw = nullptr;
     p->lds_bytes = lds;
     p->T.fix_first = bc == CP_SPLINE_NOT_A_KNOT && w0 == 0;
     p->T.fix_last = bc == CP_SPLINE_NOT_A_KNOT && w1 == n;
     for (int i = 0; i < 4; ++i) p->T.fix[i] = fix[i];
     p->T.n_src = n; p->T.w0 = w0; p->T.nw = nw; p->T.nq = nq; p->T.S = S; p->T.halo = halo; p->T.R = R; p->T.nslots = nslots;
     cp::DeviceScope scope(device);
-    const bool ok = scope.ok() && hipMalloc(&p->d_tab, tab.size() * sizeof(double)) == hipSuccess && hipMalloc(&p->d_qj, qj.size() * sizeof(int)) == hipSuccess &&
-                    hipMalloc(&p->d_qw, qw.size() * sizeof(double)) == hipSuccess &&
-                    hipMemcpy(p->d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
-                    hipMemcpy(p->d_qj, qj.data(), qj.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-                    hipMemcpy(p->d_qw, qw.data(), qw.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-        cp_spline_rows_plan_destroy(p);
-        return cp::fail(CP_ENOMEM, "cp_spline_rows_plan_create: cannot place the tables on device %d", device);
-    }
-    p->T.tab = p->d_tab; p->T.qj = p->d_qj; p->T.qw = p->d_qw;
-    *out = p;
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_spline_rows_plan_create: cannot select device %d", device);
+    hipError_t e = p->d_tab.upload(tab.data(), tab.size());
+    if (e == hipSuccess) e = p->d_qj.upload(qj.data(), qj.size());
+    if (e == hipSuccess) e = p->d_qw.upload(qw.data(), qw.size());
+    if (e != hipSuccess) return cp::place_status("cp_spline_rows_plan_create", device, e);
+    p->T.tab = p->d_tab.get(); p->T.qj = p->d_qj.get(); p->T.qw = p->d_qw.get();
+    *out = p.release();
     return CP_OK;
 }
 
@@ -344,8 +331,7 @@ extern "C" int cp_spline_rows_plan_info(const cp_spline_rows_plan* p, int* first
 }
 
 static int launch_rows(const char* who, const cp_spline_rows_plan* p, const RowsArgs& A, long long nrows, void* stream) {
-    int ncu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device) != hipSuccess || ncu <= 0) ncu = 256;
+    const int ncu = cp::cu_count(p->device);
     const long long blocks = ((nrows + p->T.R - 1) / p->T.R + 3) / 4;
     long long per_cu = (160 * 1024) / (long long)p->lds_bytes;
     per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);

@@ -8,9 +8,11 @@ from . import _lib
 from . import _device as dv
 
 
-class DST(object):
+class DST(dv.PlanOwner):
 
     """Plan for rows of length ``n`` (256, 1024 or 4096); ``kx``: optional abscissa for the fused log(kx x) / exp(y)/kx maps."""
+
+    _destroy = 'cp_dst_plan_destroy'
 
     def __init__(self, n, kx=None, device=None):
         self.device = dv.resolve_device(device)
@@ -63,11 +65,3 @@ class DST(object):
         _lib.check(lib.cp_dst_forward_analytic(self._handle, _lib.ENGINES[engine], *args, out.data_ptr(), work.data_ptr(), 2 if split else 0,
                                                dv.stream_of(self.device)))
         return out
-
-    def __del__(self):
-        try:
-            if self._handle:
-                _lib.load().cp_dst_plan_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass

@@ -144,9 +144,11 @@ def _extrap_code(e):
     return _lib.EXTRAP_CONSTANT, float(e)
 
 
-class _Plan(object):
+class _Plan(dv.PlanOwner):
 
     """Owner of a ``cp_fftlog_plan`` (device tables); freed with the object."""
+
+    _destroy = 'cp_fftlog_plan_destroy'
 
     def __init__(self, n, npad, pre, post, u, device):
         import ctypes
@@ -162,14 +164,6 @@ class _Plan(object):
     @property
     def handle(self):
         return self._handle
-
-    def __del__(self):
-        try:
-            if self._handle:
-                _lib.load().cp_fftlog_plan_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
 
 
 def _torch():
@@ -547,10 +541,13 @@ class BaseFFTEngine(object):
         self.nthreads = nthreads
 
 
-class MI355XFFTEngine(BaseFFTEngine):
+class MI355XFFTEngine(BaseFFTEngine, dv.PlanOwner):
 
     """The fused HIP FFTLog kernel (pad, prefactor, FFT, u, inverse FFT, postfactor, crop in one launch) when given to :class:`FFTlog`;
     ``forward`` / ``backward`` are the two real FFTs of the reference's protocol on the device, for code that calls them itself."""
+
+    _destroy = 'cp_rfft_plan_destroy'
+    _handle_attr = '_rfft_plans'
     name = 'mi355x'
 
     def __init__(self, size, nparallel=1, nthreads=None, device=None, **kwargs):
@@ -665,14 +662,6 @@ class MI355XFFTEngine(BaseFFTEngine):
     def backward(self, fun):
         """``irfft(conj(fun), n=size, axis=-1)`` (reference fftlog.py:541-544): (..., size // 2 + 1) complex -> (..., size) real."""
         return self._run(fun, backward=True)
-
-    def __del__(self):
-        try:
-            for handle in self.__dict__.get('_rfft_plans', {}).values():
-                _lib.load().cp_rfft_plan_destroy(handle)
-            self._rfft_plans = {}
-        except Exception:
-            pass
 
 
 class NumpyFFTEngine(MI355XFFTEngine):

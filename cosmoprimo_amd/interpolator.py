@@ -219,13 +219,16 @@ def _fftlog_then_spline(fft, op, rows, device, sqrt=False):
     return out
 
 
-class _GeoSpline(object):
+class _GeoSpline(dv.PlanOwner):
 
     """Owner of a ``cp_geospline_plan``: the natural spline from a geometric grid (the output grid of an FFTLog) to fixed queries, evaluated inside the
     FFTLog kernel.  With ``fft`` (and :data:`_GEOSPLINE_PREFILTERED`) the plan owns a copy of that transform with the B-spline prefilter folded into
     its ``u`` (``prefiltered`` True: execute takes no FFTLog plan); otherwise, or where the library refuses that (a postfactor that is no power law),
     the spline is solved on the CU from the transform's ordinary output.  ``handle`` is None where the library refuses both (queries near the ends
     of the grid, too wide a span)."""
+
+    _destroy = 'cp_geospline_plan_destroy'
+    _handle_attr = 'handle'
 
     def __init__(self, knots, queries, device, fft=None, keep=None):
         import ctypes
@@ -249,14 +252,6 @@ class _GeoSpline(object):
             return
         _lib.check(status)
         self.handle = handle
-
-    def __del__(self):
-        try:
-            if self.handle:
-                _lib.load().cp_geospline_plan_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
 _GEOSPLINE_MIN_ROWS = 8193      # below: the band-operator kernel of _fftlog_then_spline (launch- / latency-bound regime) ...

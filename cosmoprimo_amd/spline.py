@@ -10,9 +10,11 @@ from . import _lib
 from . import _device as dv
 
 
-class LinearOperator(object):
+class LinearOperator(dv.PlanOwner):
 
     """out[..., q] = post(scale * sum_j W[q, j] y[..., j]) with W banded; owns a ``cp_spline_plan``."""
+
+    _destroy = 'cp_spline_plan_destroy'
 
     def __init__(self, handle, n, nq, device):
         self._handle, self.n, self.nq, self.device = handle, n, nq, device
@@ -112,14 +114,6 @@ class LinearOperator(object):
                                                          dv.stream_of(self.device)))
         return out
 
-    def __del__(self):
-        try:
-            if self._handle:
-                _lib.load().cp_spline_plan_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
-
 
 def dense_operator(x, xq, bc='natural', nu=0, extrapolate=False):
     """The dense (nq, n) spline operator on the host (numpy); rows of out-of-range queries are NaN unless ``extrapolate``."""
@@ -133,7 +127,7 @@ def dense_operator(x, xq, bc='natural', nu=0, extrapolate=False):
     return w
 
 
-class SplicedClampedSpline(object):
+class SplicedClampedSpline(dv.PlanOwner):
 
     """Clamped cubic spline through knots whose values are contiguous pieces of the rows of two arrays, evaluated at fixed queries: the
     tridiagonal system of ``scipy.interpolate.CubicSpline(knots, values, bc_type='clamped')`` solved for every row in LDS (``cp_splice_*``),
@@ -141,6 +135,8 @@ class SplicedClampedSpline(object):
 
     pieces : up to three (source, start, count): knots take the columns [start, start + count) of the rows of array ``source`` (0 or 1).
     Raises NotImplementedError when the knots do not fit the kernel's scheme (the caller applies the spline as operators then)."""
+
+    _destroy = 'cp_splice_plan_destroy'
 
     def __init__(self, knots, pieces, xq, device=None):
         self.device = dv.resolve_device(device)
@@ -176,20 +172,14 @@ class SplicedClampedSpline(object):
                                                out.data_ptr(), dv.stream_of(self.device)))
         return out
 
-    def __del__(self):
-        try:
-            if self._handle:
-                _lib.load().cp_splice_plan_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
 
-
-class SplineRows(object):
+class SplineRows(dv.PlanOwner):
 
     """Natural, clamped or not-a-knot cubic spline through fixed knots ``x`` for very many rows, evaluated at fixed queries ``xq``, by elimination in LDS
     (``cp_spline_rows_*``): the function ``LinearOperator.spline(x, xq, bc=...)`` applies as a banded operator, at a tenth of the arithmetic and
     reading only the knots the queries can see.  Raises NotImplementedError where the scheme does not fit (very long windows): use the operator then."""
+
+    _destroy = 'cp_spline_rows_plan_destroy'
 
     def __init__(self, x, xq, bc='natural', extrapolate=False, device=None):
         self.device = dv.resolve_device(device)
@@ -242,11 +232,3 @@ class SplineRows(object):
             fun = _lib.load().cp_spline_rows_pairs if pairs else _lib.load().cp_spline_rows_second_derivatives
             _lib.check(fun(self._handle, y.data_ptr(), nrows, out.data_ptr(), dv.stream_of(self.device)))
         return out
-
-    def __del__(self):
-        try:
-            if self._handle:
-                _lib.load().cp_spline_rows_plan_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass

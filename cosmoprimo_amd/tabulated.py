@@ -40,10 +40,13 @@ class TabulatedEngine(BaseEngine):
             self._tables[name] = _InterpTable(self.z, array, self.device)
 
 
-class _InterpTable(object):
+class _InterpTable(dv.PlanOwner):
 
     """Owner of a ``cp_interp_table``: one column of the table with its redshifts on the device, and the law of the redshift grid (uniform, uniform in
     the logarithm behind a few leading knots as data/desi.dat, neither) from which the kernel guesses a sample's interval instead of bisecting."""
+
+    _destroy = 'cp_interp_table_destroy'
+    _handle_attr = 'handle'
 
     def __init__(self, x, f, device):
         import ctypes
@@ -71,14 +74,6 @@ class _InterpTable(object):
         apply = _lib.load().cp_interp_table_apply if tz.dtype == dv.torch().float64 else _lib.load().cp_interp_table_apply_f32
         _lib.check(apply(self.handle, tz.data_ptr(), out.data_ptr(), tz.numel(), ctypes.byref(outside), stream))
         return bool(outside.value)
-
-    def __del__(self):
-        try:
-            if self.handle:
-                _lib.load().cp_interp_table_destroy(self.handle)
-                self.handle = None
-        except Exception:
-            pass
 
 
 class Background(BaseSection):
