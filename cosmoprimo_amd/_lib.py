@@ -201,6 +201,11 @@ SIGNATURES['cp_taylor_predict_columns'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE +
 SIGNATURES['cp_taylor_jacobian'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + _WHERE)
 SIGNATURES['cp_taylor_vjp'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong] + _WHERE)      # d_cot, ldc; d_grad, d_work, work_doubles
 SIGNATURES['cp_taylor_jvp'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + _ARRAY + _WHERE)      # d_tan, K; d_out, ldo
+_GN_TAIL = _ARRAY + _ARRAY + _ARRAY + [ctypes.c_void_p] * 4 + [ctypes.c_longlong]      # d_weights, ldw; d_data, ldd; d_value, ldv; d_fisher, d_grad, d_chi2, d_work, work_doubles
+SIGNATURES['cp_taylor_gauss_newton'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _GN_TAIL + _WHERE)
+SIGNATURES['cp_taylor_gauss_newton_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong])
+SIGNATURES['cp_mlp_gauss_newton'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _GN_TAIL + _WHERE)
+SIGNATURES['cp_mlp_gauss_newton_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int, ctypes.c_longlong])
 SIGNATURES['cp_mlp_predict'] = (ctypes.c_int, _MLP_HEAD + [ctypes.c_void_p] + _WHERE)
 SIGNATURES['cp_mlp_predict_columns'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _WHERE)
 SIGNATURES['cp_mlp_jacobian'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _ARRAY + _WHERE)      # d_value, ldv; d_jac, ldj

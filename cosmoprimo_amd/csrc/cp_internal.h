@@ -62,6 +62,26 @@ struct Tables;
 }
 bool cp_splice_plan_uniform_view(const cp_splice_plan* plan, cpsu::Tables* out, int* device);
 
+// What the Gauss-Newton entry points (cp_mlp_gauss_newton.hip, cp_taylor_gauss_newton.hip: kernels in files of their own, so that every kernel of
+// cp_mlp.hip and cp_taylor.hip stays what it is) take from the engines' files: the checks of mlp_front / taylor_front under the caller's name, the
+// network's layout, and the launch of the kernel that cp_*_predict_columns launches, inside the caller's device scope (they open none of their own).
+namespace cp {
+struct MlpLayout {
+    int ndim, L, M, nr;      // nr: rows of an LDS buffer (the widest layer rounded up to 8)
+    int d[10];               // ndim, the widths, M
+    int act[8];
+    long long off[9];        // start of layer l in the packed buffer
+};
+int mlp_front_layout(const char* who, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, int yfunction, long long col0,
+                     long long ncols, MlpLayout* layout);
+int mlp_predict_launch(const char* who, const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M,
+                       const double* d_params, const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction,
+                       long long col0, long long ncols, double* d_out, long long ldo, void* stream);
+int taylor_front_checks(const char* who, long long B, int ndim, int T, int max_power, int M, long long col0, long long ncols, long long ld, const char* what);
+int taylor_predict_launch(const char* who, const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, const double* d_derivatives,
+                          int M, long long col0, long long ncols, double* d_out, long long ldo, void* stream);
+}  // namespace cp
+
 // Dynamic LDS above 64 KB is an opt-in per kernel AND per device (hipFuncAttributeMaxDynamicSharedMemorySize).  Raises the limit of KERNEL to the
 // whole 160 KB of a CU the first time it is launched on the device that is current (once per (kernel, device): a multi-GPU process configures every
 // device it launches on, and a later launch with more LDS than the first finds the limit already at the maximum).

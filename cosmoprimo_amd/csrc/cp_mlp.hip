@@ -1076,6 +1076,31 @@ void mlp_dh_launch(const double* r, long long ldr, const double* W, long long ld
 
 }  // namespace
 
+// For cp_mlp_gauss_newton (cp_mlp_gauss_newton.hip; declared in cp_internal.h): the checks of mlp_front under its name with the network's layout, and the
+// forward kernel on a range of columns inside its device scope -- what cp_mlp_predict_columns launches, so the value it writes has those bits.
+int cp::mlp_front_layout(const char* who, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, int yfunction, long long col0,
+                         long long ncols, MlpLayout* layout) {
+    MlpFwdArgs F{};
+    const int status = mlp_front(who, nullptr, B, ndim, nlayers, widths, activations, M, nullptr, nullptr, nullptr, nullptr, nullptr, yfunction, col0, ncols, &F);
+    if (status != CP_OK) return status;
+    const MlpNet& N = F.net;
+    layout->ndim = N.ndim, layout->L = N.L, layout->M = N.M, layout->nr = N.nr;
+    for (int l = 0; l < ML_MAX_LAYERS + 2; ++l) layout->d[l] = l <= N.L + 1 ? N.d[l] : 0;
+    for (int l = 0; l < ML_MAX_LAYERS; ++l) layout->act[l] = l < N.L ? N.act[l] : 0;
+    for (int l = 0; l <= ML_MAX_LAYERS; ++l) layout->off[l] = l <= N.L ? N.off[l] : 0;
+    return CP_OK;
+}
+
+int cp::mlp_predict_launch(const char* who, const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M,
+                           const double* d_params, const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction,
+                           long long col0, long long ncols, double* d_out, long long ldo, void* stream) {
+    MlpFwdArgs A{};
+    const int status = mlp_front(who, d_x, B, ndim, nlayers, widths, activations, M, d_params, d_xoffset, d_xscale, d_yoffset, d_yscale, yfunction, col0, ncols, &A);
+    if (status != CP_OK) return status;
+    A.out = d_out, A.ldo = ldo;
+    return mlp_yfunction(yfunction, [&](auto y) { return mlp_forward_launch<decltype(y)::value>(who, A, stream); });
+}
+
 extern "C" long long cp_mlp_param_count(int ndim, int nlayers, const int* widths, int M) {
     MlpNet net;
     const int status = mlp_net("cp_mlp_param_count", ndim, nlayers, widths, nullptr, M, &net);

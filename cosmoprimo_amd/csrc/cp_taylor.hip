@@ -464,6 +464,18 @@ int taylor_front(const char* who, long long B, int ndim, int T, int max_power, i
 
 }  // namespace
 
+// For cp_taylor_gauss_newton (cp_taylor_gauss_newton.hip; declared in cp_internal.h): the checks of taylor_front under its name, and the GEMM of
+// cp_taylor_predict_columns on a range inside its device scope.
+int cp::taylor_front_checks(const char* who, long long B, int ndim, int T, int max_power, int M, long long col0, long long ncols, long long ld, const char* what) {
+    return taylor_front(who, B, ndim, T, max_power, M, col0, ncols, ld, what);
+}
+
+int cp::taylor_predict_launch(const char* who, const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T,
+                              const double* d_derivatives, int M, long long col0, long long ncols, double* d_out, long long ldo, void* stream) {
+    const TaylorArgs A{d_x, d_center, d_powers, d_derivatives, d_out, B, ldo, T, M, ndim, (int)col0, (int)(col0 + ncols), 0};
+    return taylor_launch<TY_PREDICT>(who, A, stream);
+}
+
 // cp_taylor_predict is the range [0, M) with row stride M of the same call
 static int taylor_predict(const char* who, const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                           const double* d_derivatives, int M, long long col0, long long ncols, double* d_out, long long ldo, int device, void* stream) {

@@ -8,7 +8,7 @@ One front, four back ends.  The four methods share one plan (``Emulator._plan``:
 ``{key: view}``); each is then one call of the engine per run and nothing else.  What ``Emulator`` uses of an engine: ``name``, ``device``, ``_dev``
 (for its device), and ``predict`` / ``jacobian`` / ``vjp`` / ``jvp`` with ``columns=`` / ``return_value=``.
 
-The helpers that both engines' ``predict`` / ``jacobian`` / ``vjp`` open with (``_columns``, ``_cotangent``, ``_tangent``, ``_empty``) live here as well; the engines
+The helpers that both engines' ``predict`` / ``jacobian`` / ``vjp`` open with (``_columns``, ``_cotangent``, ``_tangent``, ``_operand``, ``_gauss_newton``, ``_empty``) live here as well; the engines
 import this module, which imports them only where it builds one.  Nothing on the path of a call imports anything: at B = 1 a call is its Python.
 """
 import numpy as np
@@ -38,6 +38,40 @@ def _cotangent(cotangent, B, ncols, device):
     if cotangent.dtype != torch.float64 or (ncols > 1 and cotangent.stride(1) != 1) or (B > 1 and cotangent.stride(0) < ncols):
         cotangent = cotangent.to(torch.float64).contiguous()
     return cotangent, int(cotangent.stride(0)) if B > 1 else ncols
+
+
+def _operand(operand, B, ncols, device, what):
+    """``(operand, ld)``: weights or data on ``device`` as ``cp_*_gauss_newton`` reads them -- one row (ncols,) shared by all points, ``ld = 0``, or
+    (B, ncols) as :func:`_cotangent` gives it (rows of any stride at least ncols)."""
+    torch = dv.torch()
+    operand = dv.to_device(operand, device, cache=False)
+    if operand.ndim == 1:
+        if int(operand.shape[0]) != ncols:
+            raise ValueError('{} must be of shape ({:d},) or ({:d}, {:d}), got {}'.format(what, ncols, B, ncols, tuple(operand.shape)))
+        return operand.to(torch.float64).contiguous(), 0
+    if tuple(operand.shape) != (B, ncols):
+        raise ValueError('{} must be of shape ({:d},) or ({:d}, {:d}), got {}'.format(what, ncols, B, ncols, tuple(operand.shape)))
+    return _cotangent(operand, B, ncols, device)
+
+
+def _gauss_newton(d, check, entry, need, head, where, B, ndim, start, ncols, weights, data, return_value):
+    """What both engines' ``gauss_newton`` do behind their ``_enter``: the operands, the workspace (``need`` doubles, minus a status on an error: raised by ``check``), the
+    results, one call of ``entry``.  Returns ``fisher``, or ``(fisher, grad, chi2)`` with data, the value (B, ncols) prepended if asked for."""
+    if need < 0:
+        check(-need)
+    width = max(ncols, 0)
+    weights, ldw = _operand(weights, B, width, d['device'], 'weights')
+    if data is not None:
+        data, ldd = _operand(data, B, width, d['device'], 'data')
+    work, fisher = _empty(d, need), _empty(d, B, ndim, ndim)
+    grad, chi2 = (_empty(d, B, ndim), _empty(d, B)) if data is not None else (None, None)
+    value = _empty(d, B, width) if return_value else None
+    check(entry(*head, start, ncols, weights.data_ptr(), ldw, data.data_ptr() if data is not None else None, ldd if data is not None else 0,
+                     value.data_ptr() if return_value else None, width, fisher.data_ptr(), grad.data_ptr() if data is not None else None,
+                     chi2.data_ptr() if data is not None else None, work.data_ptr(), need, *where))
+    toret = (fisher, grad, chi2) if data is not None else (fisher,)
+    toret = ((value,) if return_value else ()) + toret
+    return toret[0] if len(toret) == 1 else toret
 
 
 def _tangent(tangents, B, ndim, device):
@@ -322,6 +356,68 @@ class Emulator(object):
             return toret
         values.update(fixed)
         return values, toret
+
+    def gauss_newton(self, params, weights, data=None, device=False, return_value=False):
+        """Fisher matrices and Gauss-Newton normal equations of a weighted least-squares fit of ``data`` to the emulated outputs, for every point of a batch,
+        with ``J`` the Jacobian of :meth:`jacobian` and ``y`` the prediction: ``fisher[b, i, j] = sum w J_i J_j``,
+        ``gradient[b, i] = sum w (data - y) J_i``, ``chi2[b] = sum w (data - y)^2``, the sums over the entries of the outputs that ``weights`` names.
+        A Levenberg-Marquardt step solves ``(F + lambda diag F) delta = g``: ``g = -1/2 d chi2 / d theta`` and ``F`` is the Gauss-Newton half Hessian.
+        ``params`` as in :meth:`predict`.  ``weights`` (inverse variances) and ``data``: ``{varied key: array or tensor}``, each broadcastable to
+        ``(B,) + shape`` of that output (``shape`` alone with scalar parameters), as :meth:`vjp` takes its cotangents.  A weight of exactly 0 drops its entry,
+        whatever the data or the emulator hold there (NaN included): a mask.  The keys of ``weights`` select the outputs: a fixed key is accepted and
+        contributes nothing, an unknown key raises ``KeyError``, an empty dictionary gives zeros; a key of ``data`` that is not in ``weights`` raises
+        ``KeyError``, a varied key of ``weights`` missing from a given ``data`` ``ValueError``.
+
+        Returns ``fisher`` (B, ndim, ndim) in the order of ``Emulator.params`` (no leading axis if every parameter is a scalar), or with ``data``
+        ``(fisher, gradient, chi2)``, ``gradient`` ``{parameter name: (B,)}`` as :meth:`vjp` returns its gradients and ``chi2`` (B,).  Computed on the
+        device without forming the Jacobian (:meth:`MLPEmulatorEngine.gauss_newton`, :meth:`TaylorEmulatorEngine.gauss_newton`): the columns are planned
+        by :func:`column_runs` over the varied keys of ``weights``, one call of the engine per maximal contiguous run, the runs' results added in run
+        order.  Host arrays by default; ``device=True``: torch tensors, and no synchronisation with the device.  ``return_value=True``: the values are
+        prepended, what ``predict(params, device=device, keys=list(weights))`` returns."""
+        X, B, scalar = self._points(params)
+        torch = dv.torch()
+        runs, fixed = self._plan(list(weights), exact=True)
+        if data is not None:
+            unknown = [key for key in data if key not in weights]
+            if unknown:
+                raise KeyError('data for {}, which hold no weights'.format(unknown))
+            missing = [key for key in weights if key in self.varied_keys and key not in data]
+            if missing:
+                raise ValueError('no data for {}'.format(missing))
+        dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, *weights.values())
+        ndim = len(self.params)
+
+        def block(operands, entries):
+            blocks = [torch.broadcast_to(dv.to_device(operands[key], dev, cache=False).to(torch.float64), (B,) + shape).reshape(B, hi - lo)
+                      for key, shape, lo, hi in entries if hi > lo]
+            return blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1)
+
+        totals, values = None, {}
+        for start, stop, entries in runs:
+            out = self.engine.gauss_newton(X, block(weights, entries), data=block(data, entries) if data is not None else None, columns=(start, stop),
+                                           return_value=return_value)
+            out = out if isinstance(out, tuple) else (out,)
+            if return_value:
+                values.update(_split(out[0] if device else dv.to_host(out[0]), (B,), entries, start, scalar))
+                out = out[1:]
+            totals = out if totals is None else tuple(a + b for a, b in zip(totals, out))
+        if totals is None:
+            totals = (torch.zeros((B, ndim, ndim), dtype=torch.float64, device=dev),)
+            if data is not None:
+                totals += (torch.zeros((B, ndim), dtype=torch.float64, device=dev), torch.zeros((B,), dtype=torch.float64, device=dev))
+        if not device:
+            totals = tuple(dv.to_host(total) for total in totals)
+        toret = totals[0][0] if scalar else totals[0]
+        if data is not None:
+            toret = (toret, {name: (totals[1][0, i] if scalar else totals[1][:, i]) for i, name in enumerate(self.params)}, totals[2][0] if scalar else totals[2])
+        if not return_value:
+            return toret
+        for key in self.varied_keys:      # empty outputs hold no column and join no run
+            if key in weights and key not in values:
+                values[key] = self.predict(params, device=device, keys=[key])[key]
+        values = {key: values[key] for key in self.varied_keys if key in values}      # predict's order: the calculator's, then the fixed outputs
+        values.update(fixed)
+        return (values,) + (toret if isinstance(toret, tuple) else (toret,))
 
     def to_calculator(self, device=False):
         """Callable ``**params -> dict`` with the contract of ``get_calculator``'s."""

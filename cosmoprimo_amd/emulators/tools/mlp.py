@@ -27,7 +27,7 @@ import ctypes
 import numpy as np
 
 from ... import _device as dv, _lib
-from .base import _columns, _cotangent, _empty, _tangent
+from .base import _columns, _cotangent, _empty, _gauss_newton, _tangent
 
 ACTIVATIONS = ('silu', 'relu', 'tanh', 'identity-silu')
 ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-8      # optax.adam's defaults
@@ -419,6 +419,22 @@ class MLPEmulatorEngine(object):
         _lib.check(_lib.load().cp_mlp_jvp(*head, start, ncols, tangents.data_ptr(), K, value.data_ptr(), width, out.data_ptr(), width, *where))
         out = out[:, 0] if single else out
         return (value, out) if return_value else out
+
+    def gauss_newton(self, X, weights, data=None, columns=None, return_value=False):
+        """Fisher matrices and Gauss-Newton normal equations of :meth:`predict` at the points ``X`` (B, ndim), with ``J`` the Jacobian of :meth:`jacobian`:
+        device tensors ``fisher`` (B, ndim, ndim), ``fisher[b, i, j] = sum_c weights[b, c] J[b, i, c] J[b, j, c]`` (symmetric bit for bit), and with
+        ``data`` ``(fisher, grad, chi2)``, ``grad[b, i] = sum_c weights[b, c] (data[b, c] - predict(X)[b, c]) J[b, i, c]`` (B, ndim) and
+        ``chi2[b] = sum_c weights[b, c] (data[b, c] - predict(X)[b, c])^2`` (B,) (``cp_mlp_gauss_newton``: the tangent kernel's tile of ``J`` is contracted
+        over its columns in registers and LDS; no (B, ndim, M) array anywhere).  ``weights``, ``data``: (M,) shared by all points or (B, M), device tensors
+        or host arrays (uploaded), rows of any stride.  A weight of exactly 0 drops its column, whatever it holds.  ``columns = (start, stop)``: the sums
+        over those output columns only, ``weights`` and ``data`` (stop - start,) or (B, stop - start).  ``return_value=True``:
+        ``predict(X, columns=columns)`` is prepended, bit for bit.  Nothing is read back and the call does not wait for the device."""
+        d, X, B, head, where = self._enter(X)
+        net = d['net']
+        start, ncols = _columns(columns, net['M'])
+        lib = _lib.load()
+        need = int(lib.cp_mlp_gauss_newton_workspace_doubles(B, net['ndim'], net['L'], net['widths'], net['M'], ncols))
+        return _gauss_newton(d, _lib.check, lib.cp_mlp_gauss_newton, need, head, where, B, net['ndim'], start, ncols, weights, data, return_value)
 
     def __getstate__(self):
         state = {'name': self.name, 'nhidden': tuple(self.nhidden), 'activation': tuple(self.activation), 'params': self.params,

@@ -672,7 +672,12 @@ int cp_spline_tables_apply_f32(const double* d_xk, const double* d_coef, const i
  *   in a parameter, or in its tangent component, that only ever has power 0 leaves the result finite.  No atomics: two calls give the same bits, a range
  *   gives the bits of the same columns of the full call, and K = ndim identity tangents give the bits of jacobian on finite inputs.  The argument checks
  *   are those of jacobian (ldo in the place of ldj), then K < 1: CP_EINVAL, before any device call; more than 2^37 rows B K or K > 2^31 - 1:
- *   CP_EUNSUPPORTED; B = 0: CP_OK. */
+ *   CP_EUNSUPPORTED; B = 0: CP_OK.
+ * gauss_newton : Fisher matrices and Gauss-Newton normal equations of predict_columns on a range, with the arguments, the results and the contract of
+ *   cp_mlp_gauss_newton below (J the Jacobian of jacobian, bit for bit; the zero-weight select; exact symmetry; no atomics; no (B, ndim, .) array), in
+ *   csrc/cp_taylor_gauss_newton.hip.  d_value, where given, receives what predict_columns writes on the range.  d_work: work_doubles >=
+ *   cp_taylor_gauss_newton_workspace_doubles(B, ndim, T, M, ncols).  The argument checks are those of jacobian (ldv, where d_value is given, in the place
+ *   of ldj), then the strides, the caps, B = 0, the null pointers and the workspace as there, before any device call. */
 int cp_taylor_predict(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                       const double* d_derivatives, int M, double* d_out, int device, void* stream);
 int cp_taylor_predict_columns(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
@@ -687,6 +692,11 @@ int cp_taylor_vjp(const double* d_x, long long B, const double* d_center, const 
 int cp_taylor_jvp(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                   const double* d_derivatives, int M, long long col0, long long ncols, const double* d_tan, long long K, double* d_out, long long ldo,
                   int device, void* stream);
+long long cp_taylor_gauss_newton_workspace_doubles(long long B, int ndim, int T, int M, long long ncols);
+int cp_taylor_gauss_newton(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
+                           const double* d_derivatives, int M, long long col0, long long ncols, const double* d_weights, long long ldw, const double* d_data,
+                           long long ldd, double* d_value, long long ldv, double* d_fisher, double* d_grad, double* d_chi2, double* d_work,
+                           long long work_doubles, int device, void* stream);
 
 /* ---- Multi-layer perceptron emulator of a calculator (reference emulators/tools/mlp.py; csrc/cp_mlp.hip): batched prediction, loss and gradient of
  *      a training batch, Adam step, all float64.  Everything is on the device; no call reads anything back, allocates or waits for the stream. ----
@@ -726,6 +736,19 @@ int cp_taylor_jvp(const double* d_x, long long B, const double* d_center, const 
  *   inputs.  A NaN in row b of d_x makes the K rows of point b NaN, a NaN in d_tan[b][k] row b K + k, and touches no other row.  The argument checks
  *   are those of jacobian (ldo in the place of ldj), then K < 1: CP_EINVAL, before any device call; more than 2^37 rows B K or K > 2^31 - 1:
  *   CP_EUNSUPPORTED; B = 0: CP_OK.
+ * gauss_newton : Fisher matrices and Gauss-Newton normal equations of predict_columns on a range, per point b over its columns c, J the Jacobian of
+ *   jacobian: d_fisher (B, ndim, ndim) contiguous = sum_c w[b][c] J[b][i][c] J[b][j][c]; d_grad (B, ndim) = sum_c w[b][c] (data[b][c] - value[b][c]) J[b][i][c];
+ *   d_chi2 (B) = sum_c w[b][c] (data[b][c] - value[b][c])^2, without any (B, ndim, .) array, workspace included (csrc/cp_mlp_gauss_newton.hip,
+ *   csrc/cp_gauss_newton.h).  d_weights, d_data: (B, ncols) with row strides ldw, ldd >= ncols, or ONE row shared by all points (stride 0).  d_data NULL:
+ *   d_grad and d_chi2 are NULL too and nothing of the residual is computed.  d_value: NULL, or (B, ncols) with row stride ldv >= ncols, which receives
+ *   predict_columns on that range bit for bit.  A weight of exactly 0 drops its column: it contributes exactly 0 to all three results whatever the data,
+ *   the value or the derivative hold there (NaN, Inf: a select, not a product); every other non-finite input reaches its own point's results only.
+ *   d_fisher[b] is symmetric bit for bit (one triangle is computed and mirrored); no atomics: two calls give the same bits, and a call without data gives
+ *   the d_fisher bits of one with.  d_work: work_doubles >= cp_mlp_gauss_newton_workspace_doubles(B, ..., ncols) doubles of device workspace (minus the
+ *   status on an error): the value (B, ncols) and the column tiles' partial sums.  At most three launches.  The argument checks are those of jacobian up
+ *   to the range of columns, then the strides, the caps (CP_EUNSUPPORTED: more than 2^31 - 1 row tiles of floor(64 / ndim) points, or more than 2^39 sums
+ *   B (ndim^2 + ndim + 1)), B = 0: CP_OK, the null pointers (d_grad or d_chi2 without d_data, or d_data without both: CP_EINVAL) and the workspace, all
+ *   before any device call.
  * loss_grad : d_X (b, ndim), d_Y (b, M) already scaled; d_loss (one device double) = mean((Y - prediction)^2); d_grad (packed layout; NULL: loss
  *   only, with the same bits) its gradient.  d_work: work_doubles >= cp_mlp_workspace_doubles(b, ...) doubles of device workspace.  Reductions run in a
  *   fixed order: two calls give bit-identical results.
@@ -751,6 +774,11 @@ int cp_mlp_vjp(const double* d_x, long long B, int ndim, int nlayers, const int*
 int cp_mlp_jvp(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
                const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
                long long ncols, const double* d_tan, long long K, double* d_value, long long ldv, double* d_out, long long ldo, int device, void* stream);
+long long cp_mlp_gauss_newton_workspace_doubles(long long B, int ndim, int nlayers, const int* widths, int M, long long ncols);
+int cp_mlp_gauss_newton(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
+                        const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
+                        long long ncols, const double* d_weights, long long ldw, const double* d_data, long long ldd, double* d_value, long long ldv,
+                        double* d_fisher, double* d_grad, double* d_chi2, double* d_work, long long work_doubles, int device, void* stream);
 int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long b, int ndim, int nlayers, const int* widths, const int* activations, int M,
                      const double* d_params, double* d_work, long long work_doubles, double* d_loss, double* d_grad, int device, void* stream);
 int cp_mlp_adam(double* d_params, double* d_m, double* d_v, const double* d_grad, long long n, double lr, double b1, double b2, double eps, double c1,
