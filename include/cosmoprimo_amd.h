@@ -796,7 +796,8 @@ int cp_rows_screen(const double* d_x, long long nrows, long long n, int require_
  * ceil(nrows / rows_per_cosmology) of them); knots8, weights8 : host, the 8 knots (positive, ascending) and weights of the fit's window.  Per row,
  * rho its ratio: precision = interp(s / rho, knots, weights) on the fit samples, center = interp(s / rho, knots[2:6], 1 - weights[2:6]) (np.interp,
  * 0 outside), the weighted least-squares fit of s^1 .. s^-3 on the fit samples, xinow = (1 - center) xi + center fit.  A NaN among the fit samples
- * makes the row NaN, as in the reference.  Arguments are checked before any device call (CP_EINVAL). */
+ * makes the row NaN, as in the reference.  A ratio that leaves no fit sample any weight makes the row NaN throughout (0 / 0 in the first pivot), where
+ * the reference raises LinAlgError.  Arguments are checked before any device call (CP_EINVAL). */
 int cp_kirkby2013_rows(const double* d_xi, double* d_xinow, long long nrows, int ns, const double* d_s, int fit_begin, int fit_end, const double* d_rescale,
                        long long rows_per_cosmology, const double* knots8, const double* weights8, int device, void* stream);
 
