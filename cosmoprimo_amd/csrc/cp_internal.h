@@ -62,15 +62,17 @@ struct Tables;
 }
 bool cp_splice_plan_uniform_view(const cp_splice_plan* plan, cpsu::Tables* out, int* device);
 
-// What the Gauss-Newton entry points (cp_mlp_gauss_newton.hip, cp_taylor_gauss_newton.hip: kernels in files of their own, so that every kernel of
-// cp_mlp.hip and cp_taylor.hip stays what it is) take from the engines' files: the checks of mlp_front / taylor_front under the caller's name, the
-// network's layout, and the launch of the kernel that cp_*_predict_columns launches, inside the caller's device scope (they open none of their own).
+// What the Gauss-Newton entry points (cp_mlp_gauss_newton.hip, cp_taylor_gauss_newton.hip: entry points only; their kernels are variants of the one
+// __global__ template of cp_mlp_tangent.h and of cp_taylor_gemm.h, which is how kernels share source here and still keep their instructions) take
+// from the engines' files: the checks of mlp_front / taylor_front under the caller's name, the network's layout, and the launch of the kernel that
+// cp_*_predict_columns launches, inside the caller's device scope (they open none of their own).
 namespace cp {
+// the layout of a network, the one list of its fields (cp_mlp_tangent.h: MlpNet is this and the count of parameters); at most 8 hidden layers
 struct MlpLayout {
     int ndim, L, M, nr;      // nr: rows of an LDS buffer (the widest layer rounded up to 8)
     int d[10];               // ndim, the widths, M
     int act[8];
-    long long off[9];        // start of layer l in the packed buffer
+    long long off[9];        // start of layer l in the packed buffer (l = L: the output layer)
 };
 int mlp_front_layout(const char* who, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, int yfunction, long long col0,
                      long long ncols, MlpLayout* layout);

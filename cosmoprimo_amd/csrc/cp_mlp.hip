@@ -20,7 +20,7 @@
 // limit), 80 KB at widths up to 64 (two workgroups fill the 160 KB of a CU exactly).
 // Jacobian (cp_mlp_jacobian: mlp_forward_kernel, then mlp_tangent_kernel).  Forward mode with a row per (point, parameter) pair in the same tile scheme; primal
 // and tangent of the hidden layers in LDS, updated in place, NR x (80 + 64) x 8 bytes: 36 KB at widths <= 32, 72 KB at widths up to 64 -- two workgroups
-// per CU at every width, the registers' limit (profiles/jacobian.txt).  Details above the kernel.
+// per CU at every width, the registers' limit (profiles/jacobian.txt).  The kernel and its details: cp_mlp_tangent.h.
 // Gradient.  gW_out = h^T . r (mlp_gw_out_kernel) and dh = r . W_out^T (mlp_dh_kernel) on the matrix cores, both operands straight from memory: in the
 // first both are contiguous along the 16 lanes of a k (and the column sums of r, the bias gradient, are taken from the fragments already loaded);
 // in the second both are contiguous along k, a wave takes one slice of the M inner indices of a row tile and stores a partial result, summed in
@@ -32,34 +32,22 @@
 // group of modes stores the pre-activations as the training pass does and, in its epilogue, the weighted cotangent w = cot yscale f'(v) beside (or
 // instead of) the prediction; mlp_dh_kernel multiplies w by the transposed columns of the output kernel; mlp_input_grad_kernel sums its slices and
 // walks the hidden layers back in LDS.  No (B, ndim, .) array exists anywhere.  Details above the kernels.
-// Jacobian-vector product (cp_mlp_jvp: out (B K, .) = tan . d predict / d x along K directions per point; mlp_forward_kernel, then mlp_jvp_kernel).  The
-// tangent kernel with a row per (point, direction) pair and the input tangent tan[b][k][i] / xscale[i]: the same LDS, registers and occupancy, and with
-// K = ndim identity tangents the same bits.  No (B, ndim, .) array exists anywhere.
+// Jacobian-vector product (cp_mlp_jvp: out (B K, .) = tan . d predict / d x along K directions per point; mlp_forward_kernel, then mlp_tangent_kernel in its
+// jvp variant).  The tangent kernel with a row per (point, direction) pair and the input tangent tan[b][k][i] / xscale[i]: the same LDS, registers and
+// occupancy, and with K = ndim identity tangents the same bits.  No (B, ndim, .) array exists anywhere.
 // Host side.  cp_mlp_predict(_columns), cp_mlp_jacobian, cp_mlp_vjp and cp_mlp_jvp are back ends of one front: mlp_front holds their common checks and fills the
 // forward kernel's arguments, mlp_yfunction turns the y function into a template argument, mlp_dh_launch picks mlp_dh_kernel<NJ> (vjp and training step);
-// an entry point adds its strides, grid cap, null pointers, workspace and ONE device scope, in that order.  No device function is shared between kernels
-// beyond those above: every kernel is held to its instructions.
-#include "cp_internal.h"
-#include "cp_math.h"
-#include <type_traits>
+// an entry point adds its strides, grid cap, null pointers, workspace and ONE device scope, in that order.
+// Every kernel is held to its instructions (tools/compare_device_code.py).  Where kernels share source -- the jacobian, jvp and Gauss-Newton variants of
+// mlp_tangent_kernel -- they are ONE __global__ template whose variants are chosen at compile time (cp_mlp_tangent.h): a device function for the shared
+// body changed its callers' instructions, and copies of the body had to be kept equal by hand.  The small device functions named above are the only others.
+#include "cp_mlp_tangent.h"      // the tile's constants, MlpNet, mlp_load and mlp_mask, the tangent kernel and its launch
 
 namespace {
 
-typedef double ml_v4d __attribute__((ext_vector_type(4)));
-
-constexpr int ML_ROWS = 64, ML_COLS = 256, ML_RS = 80, ML_MAX_NDIM = 32, ML_MAX_LAYERS = 8, ML_MAX_WIDTH = 64;
 constexpr int ML_TRAIN = 3;      // mode of the forward kernel: 0 .. 2 predict with the y function CP_MLP_Y_*, 3 the training forward pass,
 constexpr int ML_VJP = 4;        // 4 .. 6 the forward pass of the vector-Jacobian product with the y function CP_MLP_Y_* (mode - 4)
 constexpr int ML_GS = 64;        // row stride of the LDS buffers of mlp_input_grad_kernel (the vector ALUs read them, a row per lane)
-enum { ACT_SILU = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_IDENTITY_SILU = 3 };
-
-struct MlpNet {
-    int ndim, L, M, nr;                 // nr: rows of an LDS buffer
-    int d[ML_MAX_LAYERS + 2];           // ndim, the widths, M
-    int act[ML_MAX_LAYERS];
-    long long off[ML_MAX_LAYERS + 1];   // start of layer l in the packed buffer (l = L: the output layer)
-    long long total;
-};
 
 // workspace of cp_mlp_loss_grad, in doubles
 struct MlpWork {
@@ -97,30 +85,6 @@ __device__ __forceinline__ double activate(int act, double v, double alpha, doub
         case ACT_TANH: return tanh(v);
         default: return ((1. - beta) + beta / (1. + cpmath::exp_mid(-alpha * v))) * v;
     }
-}
-
-// The operands of the eight inner indices 8 p .. 8 p + 7 for one wave: two MFMA steps.  A row of the right operand past K is never read: its place in
-// the left operand is 0, and 0 x NaN would not be (row 0 is fetched in its place and masked by mlp_mask).
-__device__ __forceinline__ void mlp_load(const double* B, const int K, const int M, const double* buf, const int p, const int l15, const int g, const int (&colj)[4],
-                                         double (&a)[2][4], double (&b)[2][4], bool (&keep)[2]) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int k = 8 * p + 4 * h + g;
-        const bool inside = k < K;
-        const double* br = B + (long long)(inside ? k : 0) * M;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b[h][j] = br[colj[j]];
-        keep[h] = inside;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) a[h][i] = buf[k * ML_RS + 16 * i + l15];
-    }
-}
-
-__device__ __forceinline__ void mlp_mask(double (&b)[2][4], const bool (&keep)[2]) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b[h][j] = keep[h] ? b[h][j] : 0.;
 }
 
 template <int MODE>
@@ -278,19 +242,6 @@ __global__ __launch_bounds__(256, 2) void mlp_forward_kernel(const MlpFwdArgs A)
     }
 }
 
-struct MlpJacArgs {
-    const double* x;          // (B, ndim) raw parameters
-    const double* params;
-    const double* xoff;
-    const double* xscale;
-    const double* yscale;
-    const double* value;      // (B, ncols) with row stride ldv: the prediction on [c0, cend), written by the forward kernel before this one
-    double* jac;              // (R, ncols) with row stride ldj, R = B ndim: row b ndim + i is point b, parameter i
-    long long R, ldv, ldj;
-    int c0, cend;
-    MlpNet net;
-};
-
 // act'(z) of one pre-activation, the formulas of mlp_dz_kernel and of activate_tangent (relu: 0 at z <= 0, and a NaN stays one as in activate_tangent;
 // the training step's kernel keeps its own copy with the terms its alpha and beta gradients share, and its bits)
 __device__ __forceinline__ double activate_derivative(int act, double v, double alpha, double beta) {
@@ -308,341 +259,6 @@ __device__ __forceinline__ double activate_derivative(int act, double v, double 
             const double s = sigmoid(alpha * v);
             return (1. - beta) + beta * (s + alpha * v * (s * (1. - s)));
         }
-    }
-}
-
-// act(z) and act'(z) of one pre-activation: the value as activate() forms it, the derivative as activate_derivative() does, with the exponential or
-// tanh that they share taken once (written out: through the two functions the compiler took it twice, and the tangent kernel grew by half)
-__device__ __forceinline__ void activate_tangent(int act, double v, double alpha, double beta, double& h, double& d) {
-    switch (act) {
-        case ACT_SILU: {
-            const double e = 1. + cpmath::exp_mid(-v), s = 1. / e;
-            h = v / e;
-            d = s * (1. + v * (1. - s));
-            break;
-        }
-        case ACT_RELU:
-            h = v > 0. ? v : (v != v ? v : 0.);
-            d = v > 0. ? 1. : (v != v ? v : 0.);
-            break;
-        case ACT_TANH: {
-            const double t = tanh(v);
-            h = t;
-            d = 1. - t * t;
-            break;
-        }
-        default: {
-            const double e = 1. + cpmath::exp_mid(-alpha * v), s = 1. / e;
-            h = ((1. - beta) + beta / e) * v;
-            d = (1. - beta) + beta * (s + alpha * v * (s * (1. - s)));
-        }
-    }
-}
-
-// Tangent kernel (cp_mlp_jacobian): forward mode through the network, a ROW being a (point, parameter) pair r = b ndim + i, in the tile scheme of
-// mlp_forward_kernel (64 rows x 256 columns per workgroup; 64 is no multiple of most ndim, so a point's rows may lie in two workgroups: every lane finds
-// its own b and i).  A lane carries the primal activation h and the tangent dh of its row through the hidden layers on the vector ALUs: z = h W + b,
-// dz = dh W, h = act(z), dh = act'(z) dz, from h_0 = (x - xoffset) / xscale and dh_0 = e_i / xscale[i] (one FMA each per weight and LDS read).  The last
-// tangent is multiplied by the output kernel on the matrix cores (no bias; operand fetch, masking and prefetch of the forward kernel), and the epilogue
-// multiplies by yscale[c] f'(v), f' from the prediction that the forward kernel stored before this launch: ln 10 y for 10^v, sqrt(1 + y^2) for sinh.
-// LDS.  ONE buffer of tangents, k-major with the row stride of 80 doubles (after the last layer it is the MFMA's left operand), and one of primal
-// activations, which only the vector ALUs read (64 consecutive doubles per k), with a row stride of 64: a layer is updated IN PLACE -- a wave keeps its at
-// most 16 neurons (h, dh) in registers (64, free until the MFMA accumulators are needed) until every wave has read the layer's inputs, one more barrier
-// per layer.  nr x (80 + 64) x 8 bytes = 36 KB at widths <= 32 and 72 KB at widths up to 64: two workgroups per CU at every width, the registers' limit.
-// (With two buffers each, 144 KB at widths up to 64, a CU held one workgroup and a row cost 1.8 x the forward kernel's: profiles/jacobian.txt.)
-template <int MODE>
-__global__ __launch_bounds__(256, 2) void mlp_tangent_kernel(const MlpJacArgs A) {
-    extern __shared__ double ml_lds[];
-    constexpr int PS = 64;      // row stride of the primal buffers
-    const MlpNet& N = A.net;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int l15 = lane & 15, g = lane >> 4;
-    const long long row0 = (long long)blockIdx.x * ML_ROWS;
-    const long long b0 = row0 / N.ndim;      // the tile's first point and the parameter its first row stands for: row0 + t is point b0 + (i0 + t) / ndim
-    const int i0 = (int)(row0 - b0 * N.ndim);
-    const int c0 = A.c0, cend = A.cend;
-    const int col0 = c0 + (int)blockIdx.y * ML_COLS + wave * 64;
-    double* const curt = ml_lds;                    // tangents, nr x ML_RS
-    double* const curp = ml_lds + N.nr * ML_RS;     // primal activations, nr x PS
-    {      // the inputs of the tile's rows and their tangents, k-major; rows past the end: finite, never stored
-        const bool inside = row0 + lane < A.R;
-        const long long b = b0 + (i0 + lane) / N.ndim;
-        const int mine = (i0 + lane) % N.ndim;
-        for (int i = wave; i < N.ndim; i += 4) {
-            double v = 0., t = 0.;
-            if (inside) {
-                const double xs = A.xscale[i];
-                v = (A.x[b * N.ndim + i] - A.xoff[i]) / xs;
-                t = i == mine ? 1. / xs : 0.;
-            }
-            curp[i * PS + lane] = v;
-            curt[i * ML_RS + lane] = t;
-        }
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int l = 0; l < N.L; ++l) {
-        const int nin = N.d[l], nout = N.d[l + 1], act = N.act[l];
-        const double* W = A.params + N.off[l];
-        const double* bias = W + nin * nout;
-        const double alpha = bias[nout], beta = bias[nout + 1];
-        // the layer in place: a wave's neurons j = wave + 4 q (at most 16: four groups of four) stay in registers until every wave has read the inputs
-        double hn[4][4], tn[4][4];
-#pragma unroll
-        for (int grp = 0; grp < 4; ++grp) {
-            const int j0 = wave + 16 * grp;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) hn[grp][q] = tn[grp][q] = 0.;
-            if (j0 >= nout) continue;      // (wave-uniform)
-            int jq[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) jq[q] = j0 + 4 * q < nout ? j0 + 4 * q : j0;
-            double accz[4] = {0., 0., 0., 0.}, acct[4] = {0., 0., 0., 0.};
-#pragma unroll 2
-            for (int k = 0; k < nin; ++k) {
-                const double hv = curp[k * PS + lane], tv = curt[k * ML_RS + lane];
-                const double* wr = W + k * nout;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const double w = wr[jq[q]];
-                    accz[q] = fma(hv, w, accz[q]);
-                    acct[q] = fma(tv, w, acct[q]);
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                double dval;
-                activate_tangent(act, accz[q] + bias[jq[q]], alpha, beta, hn[grp][q], dval);
-                tn[grp][q] = dval * acct[q];
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int grp = 0; grp < 4; ++grp)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int j = wave + 16 * grp + 4 * q;
-                if (j < nout) {
-                    curp[j * PS + lane] = hn[grp][q];
-                    curt[j * ML_RS + lane] = tn[grp][q];
-                }
-            }
-        for (int j = nout + wave; j < ((nout + 7) & ~7); j += 4) curt[j * ML_RS + lane] = 0.;      // the left operand's rows up to the next pair of MFMA steps
-        __syncthreads();
-    }
-    // the output layer on the matrix cores: acc = dh_L . W_out[:, columns]
-    const int K = N.d[N.L], M = N.M;
-    const double* Wo = A.params + N.off[N.L];
-    const bool active = col0 < cend;      // (wave-uniform; an idle wave multiplies the last column: no branch round the MFMAs)
-    ml_v4d acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = ml_v4d{0., 0., 0., 0.};
-    int colj[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int col = col0 + 16 * j + l15;
-        colj[j] = col < cend ? col : cend - 1;      // columns past the end of the range repeat its last one (never stored)
-    }
-    {
-        const int npairs = (K + 7) / 8;
-        double a0[2][4], b0[2][4];
-        bool keep[2];
-        mlp_load(Wo, K, M, curt, 0, l15, g, colj, a0, b0, keep);
-        mlp_mask(b0, keep);
-#pragma unroll 1
-        for (int p = 0; p < npairs; ++p) {
-            double a1[2][4], b1[2][4];
-            mlp_load(Wo, K, M, curt, p + 1 < npairs ? p + 1 : p, l15, g, colj, a1, b1, keep);
-            __builtin_amdgcn_sched_barrier(0);      // the loads are issued here, not moved below the MFMAs
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[h][i], b0[h][j], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) a0[h][i] = a1[h][i], b0[h][i] = b1[h][i];
-            __builtin_amdgcn_sched_barrier(0);
-            mlp_mask(b0, keep);
-        }
-    }
-    if (!active) return;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int col = col0 + 16 * j + l15;
-        if (col >= cend) continue;
-        const double ys = A.yscale[col];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int t = 16 * i + g + 4 * r;
-                if (row0 + t >= A.R) continue;
-                double d = ys;
-                if (MODE != CP_MLP_Y_NONE) {
-                    const double y = A.value[(b0 + (i0 + t) / N.ndim) * A.ldv + (col - c0)];
-                    d *= MODE == CP_MLP_Y_EXP10 ? 2.302585092994045684 * y : sqrt(fma(y, y, 1.));
-                }
-                A.jac[(row0 + t) * A.ldj + (col - c0)] = acc[i][j][r] * d;
-            }
-    }
-}
-
-// Directional derivatives (cp_mlp_jvp): mlp_tangent_kernel with a row per (point, direction) pair r = b K + k and dh_0[i] = tan[b][k][i] / xscale[i] in the
-// place of e_i / xscale[i] -- the same tile, LDS buffers, in-place layer update, MFMA sequence and epilogue, operation for operation, so that K = ndim
-// identity tangents give the bits of cp_mlp_jacobian.  J.R = B K rows, J.jac the (B K, ncols) result.  (Written out, not shared with the tangent kernel
-// through a device function: that changed the tangent kernel's instructions.)
-struct MlpJvpArgs {
-    MlpJacArgs J;
-    const double* tan;        // (B, K, ndim), raw-parameter units
-    int K;
-};
-
-template <int MODE>
-__global__ __launch_bounds__(256, 2) void mlp_jvp_kernel(const MlpJvpArgs P) {
-    const MlpJacArgs& A = P.J;
-    const int nd = P.K;
-    extern __shared__ double ml_lds[];
-    constexpr int PS = 64;      // row stride of the primal buffers
-    const MlpNet& N = A.net;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    const int l15 = lane & 15, g = lane >> 4;
-    const long long row0 = (long long)blockIdx.x * ML_ROWS;
-    const long long b0 = row0 / nd;      // the tile's first point and the direction its first row stands for: row0 + t is point b0 + (k0 + t) / K
-    const int i0 = (int)(row0 - b0 * nd);
-    const int c0 = A.c0, cend = A.cend;
-    const int col0 = c0 + (int)blockIdx.y * ML_COLS + wave * 64;
-    double* const curt = ml_lds;                    // tangents, nr x ML_RS
-    double* const curp = ml_lds + N.nr * ML_RS;     // primal activations, nr x PS
-    {      // the inputs of the tile's rows and their tangents, k-major; rows past the end: finite, never stored
-        const bool inside = row0 + lane < A.R;
-        const long long b = b0 + (i0 + lane) / nd;
-        const double* tan = P.tan + (row0 + lane) * N.ndim;      // row r = b K + k: tan[b][k] is row r of the (B K, ndim) array
-        for (int i = wave; i < N.ndim; i += 4) {
-            double v = 0., t = 0.;
-            if (inside) {
-                const double xs = A.xscale[i];
-                v = (A.x[b * N.ndim + i] - A.xoff[i]) / xs;
-                t = tan[i] / xs;
-            }
-            curp[i * PS + lane] = v;
-            curt[i * ML_RS + lane] = t;
-        }
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int l = 0; l < N.L; ++l) {
-        const int nin = N.d[l], nout = N.d[l + 1], act = N.act[l];
-        const double* W = A.params + N.off[l];
-        const double* bias = W + nin * nout;
-        const double alpha = bias[nout], beta = bias[nout + 1];
-        // the layer in place: a wave's neurons j = wave + 4 q (at most 16: four groups of four) stay in registers until every wave has read the inputs
-        double hn[4][4], tn[4][4];
-#pragma unroll
-        for (int grp = 0; grp < 4; ++grp) {
-            const int j0 = wave + 16 * grp;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) hn[grp][q] = tn[grp][q] = 0.;
-            if (j0 >= nout) continue;      // (wave-uniform)
-            int jq[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) jq[q] = j0 + 4 * q < nout ? j0 + 4 * q : j0;
-            double accz[4] = {0., 0., 0., 0.}, acct[4] = {0., 0., 0., 0.};
-#pragma unroll 2
-            for (int k = 0; k < nin; ++k) {
-                const double hv = curp[k * PS + lane], tv = curt[k * ML_RS + lane];
-                const double* wr = W + k * nout;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const double w = wr[jq[q]];
-                    accz[q] = fma(hv, w, accz[q]);
-                    acct[q] = fma(tv, w, acct[q]);
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                double dval;
-                activate_tangent(act, accz[q] + bias[jq[q]], alpha, beta, hn[grp][q], dval);
-                tn[grp][q] = dval * acct[q];
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int grp = 0; grp < 4; ++grp)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int j = wave + 16 * grp + 4 * q;
-                if (j < nout) {
-                    curp[j * PS + lane] = hn[grp][q];
-                    curt[j * ML_RS + lane] = tn[grp][q];
-                }
-            }
-        for (int j = nout + wave; j < ((nout + 7) & ~7); j += 4) curt[j * ML_RS + lane] = 0.;      // the left operand's rows up to the next pair of MFMA steps
-        __syncthreads();
-    }
-    // the output layer on the matrix cores: acc = dh_L . W_out[:, columns]
-    const int K = N.d[N.L], M = N.M;
-    const double* Wo = A.params + N.off[N.L];
-    const bool active = col0 < cend;      // (wave-uniform; an idle wave multiplies the last column: no branch round the MFMAs)
-    ml_v4d acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = ml_v4d{0., 0., 0., 0.};
-    int colj[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int col = col0 + 16 * j + l15;
-        colj[j] = col < cend ? col : cend - 1;      // columns past the end of the range repeat its last one (never stored)
-    }
-    {
-        const int npairs = (K + 7) / 8;
-        double a0[2][4], b0[2][4];
-        bool keep[2];
-        mlp_load(Wo, K, M, curt, 0, l15, g, colj, a0, b0, keep);
-        mlp_mask(b0, keep);
-#pragma unroll 1
-        for (int p = 0; p < npairs; ++p) {
-            double a1[2][4], b1[2][4];
-            mlp_load(Wo, K, M, curt, p + 1 < npairs ? p + 1 : p, l15, g, colj, a1, b1, keep);
-            __builtin_amdgcn_sched_barrier(0);      // the loads are issued here, not moved below the MFMAs
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[h][i], b0[h][j], acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) a0[h][i] = a1[h][i], b0[h][i] = b1[h][i];
-            __builtin_amdgcn_sched_barrier(0);
-            mlp_mask(b0, keep);
-        }
-    }
-    if (!active) return;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int col = col0 + 16 * j + l15;
-        if (col >= cend) continue;
-        const double ys = A.yscale[col];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int t = 16 * i + g + 4 * r;
-                if (row0 + t >= A.R) continue;
-                double d = ys;
-                if (MODE != CP_MLP_Y_NONE) {
-                    const double y = A.value[(b0 + (i0 + t) / nd) * A.ldv + (col - c0)];
-                    d *= MODE == CP_MLP_Y_EXP10 ? 2.302585092994045684 * y : sqrt(fma(y, y, 1.));
-                }
-                A.jac[(row0 + t) * A.ldj + (col - c0)] = acc[i][j][r] * d;
-            }
     }
 }
 
@@ -1014,30 +630,6 @@ int mlp_forward_launch(const char* who, const MlpFwdArgs& A, void* stream) {
     return CP_OK;
 }
 
-template <int MODE>
-int mlp_tangent_launch(const char* who, const MlpJacArgs& A, void* stream) {
-    const long long nrt = (A.R + ML_ROWS - 1) / ML_ROWS, nct = (A.cend - A.c0 + ML_COLS - 1) / ML_COLS;      // (checked by the caller)
-    const size_t lds = (size_t)A.net.nr * (ML_RS + 64) * sizeof(double);      // 36 KB at widths <= 32, at most 72 KB
-    if (lds > 64 * 1024) {
-        const hipError_t e = cp::allow_full_lds<mlp_tangent_kernel<MODE>>();
-        if (e != hipSuccess) return cp::launch_status(who, e);
-    }
-    hipLaunchKernelGGL(mlp_tangent_kernel<MODE>, dim3((unsigned)nrt, (unsigned)nct), dim3(256), lds, static_cast<hipStream_t>(stream), A);
-    return CP_OK;
-}
-
-template <int MODE>
-int mlp_jvp_launch(const char* who, const MlpJvpArgs& A, void* stream) {
-    const long long nrt = (A.J.R + ML_ROWS - 1) / ML_ROWS, nct = (A.J.cend - A.J.c0 + ML_COLS - 1) / ML_COLS;      // (checked by the caller)
-    const size_t lds = (size_t)A.J.net.nr * (ML_RS + 64) * sizeof(double);      // 36 KB at widths <= 32, at most 72 KB
-    if (lds > 64 * 1024) {
-        const hipError_t e = cp::allow_full_lds<mlp_jvp_kernel<MODE>>();
-        if (e != hipSuccess) return cp::launch_status(who, e);
-    }
-    hipLaunchKernelGGL(mlp_jvp_kernel<MODE>, dim3((unsigned)nrt, (unsigned)nct), dim3(256), lds, static_cast<hipStream_t>(stream), A);
-    return CP_OK;
-}
-
 // What cp_mlp_predict, cp_mlp_predict_columns, cp_mlp_jacobian, cp_mlp_vjp and cp_mlp_jvp share: their checks up to the range of columns, in that order, then the
 // network, the inputs and the range in F.  What follows is the entry point's own: its strides, its grid cap, the empty batch, its null pointers, its
 // workspace, the device, and the outputs in F.
@@ -1083,11 +675,7 @@ int cp::mlp_front_layout(const char* who, long long B, int ndim, int nlayers, co
     MlpFwdArgs F{};
     const int status = mlp_front(who, nullptr, B, ndim, nlayers, widths, activations, M, nullptr, nullptr, nullptr, nullptr, nullptr, yfunction, col0, ncols, &F);
     if (status != CP_OK) return status;
-    const MlpNet& N = F.net;
-    layout->ndim = N.ndim, layout->L = N.L, layout->M = N.M, layout->nr = N.nr;
-    for (int l = 0; l < ML_MAX_LAYERS + 2; ++l) layout->d[l] = l <= N.L + 1 ? N.d[l] : 0;
-    for (int l = 0; l < ML_MAX_LAYERS; ++l) layout->act[l] = l < N.L ? N.act[l] : 0;
-    for (int l = 0; l <= ML_MAX_LAYERS; ++l) layout->off[l] = l <= N.L ? N.off[l] : 0;
+    *layout = F.net;      // (MlpNet is the layout and its total; the entries past the last layer are the zeros of F{})
     return CP_OK;
 }
 
@@ -1167,15 +755,16 @@ extern "C" int cp_mlp_jacobian(const double* d_x, long long B, int ndim, int nla
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
     F.out = d_value, F.ldo = ldv;
     const MlpJacArgs J{d_x, d_params, d_xoffset, d_xscale, d_yscale, d_value, d_jac, B * ndim, ldv, ldj, F.c0, F.cend, F.net};
+    const dim3 grid((unsigned)((J.R + ML_ROWS - 1) / ML_ROWS), (unsigned)((ncols + ML_COLS - 1) / ML_COLS));      // (checked above)
     const int launched = mlp_yfunction(yfunction, [&](auto y) {
         const int forward = mlp_forward_launch<decltype(y)::value>(who, F, stream);
-        return forward != CP_OK ? forward : mlp_tangent_launch<decltype(y)::value>(who, J, stream);
+        return forward != CP_OK ? forward : mlp_tangent_launch<decltype(y)::value>(who, J, grid, 0, stream);
     });
     if (launched != CP_OK) return launched;
     return cp::launch_status(who);
 }
 
-// Two launches on the stream as in cp_mlp_jacobian: the forward kernel writes the prediction on the range, mlp_jvp_kernel reads it
+// Two launches on the stream as in cp_mlp_jacobian: the forward kernel writes the prediction on the range, the tangent kernel's jvp variant reads it
 extern "C" int cp_mlp_jvp(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
                           const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
                           long long ncols, const double* d_tan, long long K, double* d_value, long long ldv, double* d_out, long long ldo, int device,
@@ -1195,9 +784,10 @@ extern "C" int cp_mlp_jvp(const double* d_x, long long B, int ndim, int nlayers,
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
     F.out = d_value, F.ldo = ldv;
     const MlpJvpArgs J{{d_x, d_params, d_xoffset, d_xscale, d_yscale, d_value, d_out, B * K, ldv, ldo, F.c0, F.cend, F.net}, d_tan, (int)K};
+    const dim3 grid((unsigned)((J.R + ML_ROWS - 1) / ML_ROWS), (unsigned)((ncols + ML_COLS - 1) / ML_COLS));      // (checked above)
     const int launched = mlp_yfunction(yfunction, [&](auto y) {
         const int forward = mlp_forward_launch<decltype(y)::value>(who, F, stream);
-        return forward != CP_OK ? forward : mlp_jvp_launch<decltype(y)::value>(who, J, stream);
+        return forward != CP_OK ? forward : mlp_tangent_launch<decltype(y)::value>(who, J, grid, 0, stream);
     });
     if (launched != CP_OK) return launched;
     return cp::launch_status(who);

@@ -5,7 +5,12 @@
 Each directory holds NAME.s per source, written by ``hipcc <the Makefile's flags> -S --cuda-device-only -o DIR/NAME.s NAME.hip`` (as
 tools/kernel_resources_json.py compiles).  Per kernel symbol (mangled names, so the argument structs' names count) the instruction text between the
 symbol's label and its ``.Lfunc_end`` (local labels without the function's position in the file), the kernel descriptor and the metadata entry (registers, spills, scratch, static LDS, kernarg size, arguments) must be equal.  Prints
-the number of kernels compared and every line outside the kernels' bodies and metadata that differs; exit status 1 if any kernel differs."""
+the number of kernels compared and every line outside the kernels' bodies and metadata that differs; exit status 1 if any kernel differs.
+
+A change that merges or renames kernels gives its map from parent symbols to result symbols as repeated ``--rename OLD=NEW``, OLD and NEW substrings of
+the mangled names (``--rename 14mlp_jvp_kernelILi0EEEvNS_10MlpJvpArgsE=18mlp_tangent_kernelILi0ENS_10MlpJvpArgsEEEvT0_``): every OLD in the parent's assembly
+is read as NEW before the kernels are paired.  A symbol that no OLD names is paired exactly as before."""
+import argparse
 import collections
 import glob
 import os
@@ -40,12 +45,24 @@ def split(text):
     return bodies, meta, rest
 
 
+def renamed(text, renames):
+    """The parent's assembly with every OLD replaced by NEW: the symbol's label, descriptor, metadata entry and any reference to it alike."""
+    for old, new in renames:
+        text = text.replace(old, new)
+    return text
+
+
 def main():
-    parent, result = sys.argv[1:3]
+    parser = argparse.ArgumentParser()
+    parser.add_argument('parent')
+    parser.add_argument('result')
+    parser.add_argument('--rename', action='append', default=[], metavar='OLD=NEW')
+    args = parser.parse_args()
+    parent, result, renames = args.parent, args.result, [tuple(pair.split('=', 1)) for pair in args.rename]
     compared, differ = 0, []
     for path in sorted(glob.glob(os.path.join(parent, '*.s'))):
         name = os.path.basename(path)
-        (b0, m0, r0), (b1, m1, r1) = split(open(path).read()), split(open(os.path.join(result, name)).read())
+        (b0, m0, r0), (b1, m1, r1) = split(renamed(open(path).read(), renames)), split(open(os.path.join(result, name)).read())
         if sorted(b0) != sorted(b1) or sorted(m0) != sorted(m1):
             differ.append('%s: kernels %s' % (name, sorted(set(b0) ^ set(b1)) + sorted(set(m0) ^ set(m1))))
         for symbol in sorted(set(b0) & set(b1)):
