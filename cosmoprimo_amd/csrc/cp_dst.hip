@@ -8,8 +8,9 @@
 // C'_k = Re(e^{-i pi k / 2N} V_k).  Two real rows are packed as v_a + i v_b and separated after the FFT through
 // V_a[k] = (V[k] + conj V[N-k]) / 2, V_b[k] = (V[k] - conj V[N-k]) / 2i.  The inverse runs the same network backwards:
 // Hermitian-symmetrised spectra H = H_a + i H_b, v = conj(FFT(conj H)).
-// The FFT reuses the pass machinery of the FFTLog kernel (cp_fft_core.h): radix-16 butterflies in registers, swizzled
-// LDS exchanges, middle-pass twiddles resident in LDS.  Optional fused elementwise maps for the filter:
+// The FFT is the workgroup transform of cp_fft_workgroup.h (the passes of the FFTLog kernel, cp_fft_core.h; cp_rfft.hip runs it too).  What the
+// kernels of this file and of cp_wallish_tail.h do to a PAIR around it -- the split layout's index, the separation of the forward spectrum, the Hermitian
+// packing of the inverse, a generated pair into the transform -- is written once, ahead of the kernels.  Optional fused elementwise maps for the filter:
 // forward input log(k_n x_n), inverse output exp(y_n) / k_n.  HBM traffic: 16 N bytes per row (read + write), HBM-bound.
 #include <hip/hip_runtime.h>
 
@@ -20,7 +21,7 @@
 #include "../../include/cosmoprimo_amd.h"
 #include "cp_error.h"
 #include "cp_internal.h"
-#include "cp_fft_core.h"
+#include "cp_fft_workgroup.h"
 #include "cp_fftlog_tables.h"
 #include "cp_math.h"
 #include "cp_power_eval.h"
@@ -43,20 +44,6 @@ struct Args {
     int split;          // coefficients stored de-interleaved: Y_0, Y_2, ... in the first half of the row, Y_1, Y_3, ... in the second
 };
 
-// LDS position of frequency k after the full DIF network (digit reversal of the mixed-radix plan)
-template <int N, int P>
-__device__ __forceinline__ int pos_of_freq(int k) {
-    using PL = Plan<N, P>;
-    int pos = 0;
-#pragma unroll
-    for (int i = 0; i < PL::NPASS; ++i) {
-        const int R = PL::radix(i), M = PL::len(i) / R;
-        pos += (k % R) * M;
-        k /= R;
-    }
-    return pos;
-}
-
 // Powers of two that bring a row whose largest sample has the high dword `top` (hi_abs) to the order of 1, and back: exact factors, so that the two
 // rows of a pair meet in the complex FFT at the same magnitude whatever theirs are (2^-1022 .. 2^1022: subnormal and the very largest rows end within 2)
 __device__ __forceinline__ void row_scale(unsigned top, double& to_unit, double& back) {
@@ -78,36 +65,47 @@ __device__ __forceinline__ void norm_scale(unsigned long long sq, double& to_uni
     up = __builtin_bit_cast(double, (unsigned long long)(1023 + k) << 52);
 }
 
-template <int N, int P>
-__device__ __forceinline__ cplx lds_at(const cplx* lds, int pos) {
-    return lds[swz<N>(pos)];
+// ---- two real rows through one complex transform: the pieces the kernels below (and cp_wallish_tail.h) share ----
+// position of coefficient j in its row: the wallish2018 filter treats even- and odd-indexed coefficients as two sequences (bao_filter.py:373), so they can
+// be written / read as two half rows (split) instead of being gathered by separate copy kernels
+template <int N>
+__device__ __forceinline__ int split_at(int split, int j) {
+    return split ? ((j & 1) * (N / 2) + (j >> 1)) : j;
 }
 
-// all DIF passes; pass 0 takes x from registers, the result is left in LDS in digit-reversed order
-template <int N, int P, int I>
-__device__ __forceinline__ void dif_rest(int t, const Args& A, cplx* lds, const cplx* ltw) {
-    using PL = Plan<N, P>;
-    if constexpr (I < PL::NPASS) {
-        cplx x[P];
-        __syncthreads();
-        asm volatile("" : "+v"(t));  // no address sharing across passes (register pressure, see cp_fftlog_body.h)
-        Pass<N, P, I>::load_lds(t, lds, x);
-        Pass<N, P, I>::butterflies(x);
-        Pass<N, P, I>::twiddle_apply_lds(t, ltw + (PL::tw_offset(I) - N), x);
-        Pass<N, P, I>::store_lds(t, lds, x);
-        dif_rest<N, P, I + 1>(t, A, lds, ltw);
+// forward: frequencies k (v) and N - k (u) of the packed transform and rot = e^{-i pi k / 2N} = (cos, -sin) give coefficient N - 1 - k of either row, but for its
+// norm f:  V_a = ((p + r)/2, (q - s)/2), V_b = ((q + s)/2, (r - p)/2);  C' = cos * re + sin * im
+__device__ __forceinline__ double separated_a(cplx v, cplx u, cplx rot) { return 0.5 * (rot.re * (v.re + u.re) - rot.im * (v.im - u.im)); }
+__device__ __forceinline__ double separated_b(cplx v, cplx u, cplx rot) { return 0.5 * (rot.re * (v.im + u.im) - rot.im * (u.re - v.re)); }
+
+// inverse: the scaled coefficients N - 1 - k (A) and k - 1 (B) of a row and rot give frequency k >= 1 of its Hermitian-symmetrised spectrum (k = 0: A alone,
+// real); the pair goes into the transform as conj(H_a + i H_b) (the transform runs forward)
+__device__ __forceinline__ cplx hermitian_bin(double A, double B, cplx rot) {
+    const double cs = rot.re, sn = -rot.im;
+    return cplx{0.5 * (A * cs + B * sn), 0.5 * (A * sn - B * cs)};
+}
+__device__ __forceinline__ cplx conj_packed(cplx Ha, cplx Hb) { return cplx{Ha.re - Hb.im, -(Ha.im + Hb.re)}; }
+
+// A pair that generate_row (below) has left in the thread's own slots (row a at 2 m, row b at 2 m + 1, m = t + T r in Makhoul order) into the
+// transform's registers, the (-1)^n sign folded in.  A row with a sample that is not finite raises its flag; the barrier publishes the flags and lets every
+// thread read its slots before the first pass overwrites the region.  The caller zeroes a flagged row in x (written there: behind a return of this function
+// the join of that branch changed the order of the butterflies' operands).
+template <int N, int P>
+__device__ __forceinline__ void pack_generated_pair(int t, bool has_b, const double* slots, int* bad_row, cplx* x) {
+    constexpr int T = N / P;
+    bool bad_a = false, bad_b = false;
+#pragma unroll
+    for (int r = 0; r < P; ++r) {      // the thread's own slots: no barrier
+        const int m = t + T * r;
+        const bool lower = m < N / 2;
+        const double a = slots[2 * m], b = has_b ? slots[2 * m + 1] : 0.;
+        bad_a |= not_finite(a);
+        bad_b |= not_finite(b);
+        x[r].re = lower ? a : -a;
+        x[r].im = lower ? b : -b;
     }
-}
-
-template <int N, int P>
-__device__ __forceinline__ void dif_all(int t, const Args& A, cplx* x, cplx* lds, const cplx* ltw) {
-    using PL = Plan<N, P>;
-    Pass<N, P, 0>::butterflies(x);
-    cplx w[P];
-    Pass<N, P, 0>::twiddle_load(t, A.tw + PL::tw_offset(0), w);
-    Pass<N, P, 0>::twiddle_apply(w, x);
-    Pass<N, P, 0>::store_lds(t, lds, x);
-    dif_rest<N, P, 1>(t, A, lds, ltw);
+    if (bad_a) bad_row[0] = 1;
+    if (bad_b) bad_row[1] = 1;
     __syncthreads();
 }
 
@@ -120,13 +118,13 @@ __device__ __forceinline__ void dif_all(int t, const Args& A, cplx* x, cplx* lds
 
 template <int N, int P, bool INVERSE>
 __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
-    using PL = Plan<N, P>;
-    constexpr int T = PL::T;
+    using WG = WorkgroupFft<N, P>;
+    constexpr int T = WG::T;
     extern __shared__ __attribute__((aligned(4096))) char smem[];  // 4096: see LdsView (cp_fft_core.h)
     cplx* lds = reinterpret_cast<cplx*>(smem);
-    cplx* ltw = lds + lds_data_slots(N, P);  // data slots of one packed pair (padded layout for N = 4096), then the tables
+    cplx* ltw = WG::twiddles(lds);  // data slots of one packed pair, then the tables
     const int t = threadIdx.x;
-    for (int i = t; i < PL::TW_TOTAL - N; i += T) ltw[i] = A.tw[N + i];
+    for (int i = t; i < WG::TW_SLOTS; i += T) ltw[i] = A.tw[N + i];
     const long long npairs = (A.nrows + 1) / 2;
     const double fn = sqrt(2. / N), fl = sqrt(1. / N);
     // Rows stay independent although two of them share one complex FFT (scipy transforms row by row): a row holding a sample that is
@@ -158,14 +156,14 @@ __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
         }
     };
     // inverse transform: half of a pair's samples (the coefficients N - 1 - k of both rows) the same way; the other half (k - 1) are read in place
-    auto at_ = [&](int j) { return A.split ? ((j & 1) * (N / 2) + (j >> 1)) : j; };
+    auto at = [&](int j) { return split_at<N>(A.split, j); };      // position of coefficient j in its row
     auto fetch_inverse = [&](long long p) {
         const double* ra = A.in + 2 * p * N;
         const double* rb = 2 * p + 1 < A.nrows ? ra + N : ra;
 #pragma unroll
         for (int r = 0; r < P; ++r) {
             // CP_DST_INVERSE_VIA_LDS: the rows as they lie in memory (every coefficient read ONCE; the threads pick what they need out of LDS)
-            const int ia = CP_DST_INVERSE_VIA_LDS ? t + T * r : at_(N - 1 - (t + T * r));
+            const int ia = CP_DST_INVERSE_VIA_LDS ? t + T * r : at(N - 1 - (t + T * r));
             na[r] = ra[ia];
             nb[r] = rb[ia];
         }
@@ -181,9 +179,6 @@ __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
         double* oa = A.out + 2 * p * N;
         double* ob = has_b ? oa + N : oa;
         cplx x[P];
-        // position of coefficient j in its row: the wallish2018 filter treats even- and odd-indexed coefficients as two sequences
-        // (bao_filter.py:373), so they can be written / read as two half rows instead of being gathered by separate copy kernels
-        auto at = [&](int j) { return A.split ? ((j & 1) * (N / 2) + (j >> 1)) : j; };
         if (t == 0) bad_row[0] = bad_row[1] = pair_flag = 0, row_top[0] = row_top[1] = 0u, row_sq[0] = row_sq[1] = 0ull;
         __syncthreads();  // LDS reuse across pairs (and the table fill on the first one)
         int tt = t;
@@ -239,19 +234,17 @@ __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
                 x[r].re *= sa;
                 x[r].im *= sb;
             }
-            dif_all<N, P>(tt, A, x, lds, ltw);
+            WG::forward(tt, A.tw, x, lds, ltw);
             asm volatile("" : "+v"(tt));
             // separate the two rows, rotate, scale; frequency k -> output index N - 1 - k
 #pragma unroll 4
             for (int s = 0; s < P; ++s) {
                 const int k = tt + T * s;
-                const cplx v = lds_at<N, P>(lds, pos_of_freq<N, P>(k));
-                const cplx u = lds_at<N, P>(lds, pos_of_freq<N, P>((N - k) % N));
+                const cplx v = WG::at(lds, WG::pos_of_freq(k));
+                const cplx u = WG::at(lds, WG::pos_of_freq((N - k) % N));
                 const cplx rot = A.rot[k];  // (cos, -sin)
                 const double f = k == 0 ? fl : fn;
-                // V_a = ((p + r)/2, (q - s)/2), V_b = ((q + s)/2, (r - p)/2);  C' = cos * re + sin * im
-                const double ya = 0.5 * (rot.re * (v.re + u.re) - rot.im * (v.im - u.im));
-                const double yb = 0.5 * (rot.re * (v.im + u.im) - rot.im * (u.re - v.re));
+                const double ya = separated_a(v, u, rot), yb = separated_b(v, u, rot);
                 oa[at(N - 1 - k)] = skip_a ? nan : f * ya * up_a * back_a;
                 if (has_b) ob[at(N - 1 - k)] = skip_b ? nan : f * yb * up_b * back_b;
             }
@@ -303,20 +296,17 @@ __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
                         Ba = (k == 0 ? fa : fb) * (((CP_DST_ABLATE & 2) ? na[r] : ra[at(ib)]) * sa); Bb = (k == 0 ? fa : fb) * (((CP_DST_ABLATE & 2) ? nb[r] : rb[at(ib)]) * sb);
                     }
                     const cplx rot = A.rot[k];
-                    const double cs = rot.re, sn = -rot.im;
                     cplx Ha, Hb;
                     if (k == 0) {
                         Ha = cplx{Aa, 0.};
                         Hb = cplx{Ab, 0.};
                     } else {
-                        Ha = cplx{0.5 * (Aa * cs + Ba * sn), 0.5 * (Aa * sn - Ba * cs)};
-                        Hb = cplx{0.5 * (Ab * cs + Bb * sn), 0.5 * (Ab * sn - Bb * cs)};
+                        Ha = hermitian_bin(Aa, Ba, rot);
+                        Hb = hermitian_bin(Ab, Bb, rot);
                     }
                     if (!keep_a) Ha = cplx{0., 0.};
                     if (!keep_b) Hb = cplx{0., 0.};
-                    // conj(H_a + i H_b)
-                    x[r].re = Ha.re - Hb.im;
-                    x[r].im = -(Ha.im + Hb.re);
+                    x[r] = conj_packed(Ha, Hb);
                 }
             };
             spectrum(true, has_b, true);
@@ -347,7 +337,7 @@ __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
                 // finite rows whose sum overflowed in the packing stay as they are (skip_a = skip_b = false): nothing to separate
                 if (skip_a | skip_b) spectrum(!skip_a, has_b && !skip_b, false);
             }
-            if (!(CP_DST_ABLATE & 8)) dif_all<N, P>(tt, A, x, lds, ltw);
+            if (!(CP_DST_ABLATE & 8)) WG::forward(tt, A.tw, x, lds, ltw);
             else {
                 Pass<N, P, 0>::store_lds(tt, lds, x);
                 __syncthreads();
@@ -359,7 +349,7 @@ __global__ __launch_bounds__(N / P, 2) void dst_kernel(const Args A) {
                 const int n = tt + T * s;
                 const bool even = (n & 1) == 0;
                 const int m = even ? n / 2 : N - 1 - (n - 1) / 2;
-                const cplx g = lds_at<N, P>(lds, pos_of_freq<N, P>(m));
+                const cplx g = WG::at(lds, WG::pos_of_freq(m));
                 double ya = (even ? g.re : -g.re) * up_a * back_a;
                 double yb = (even ? -g.im : g.im) * up_b * back_b;
                 if (A.fused && !(CP_DST_ABLATE & 1)) {
@@ -477,15 +467,15 @@ __device__ __forceinline__ void generate_row(GP G, long long ic, int t, double* 
 
 template <int N, int P, int ENGINE>
 __global__ __launch_bounds__(N / P, 2) void dst_generate_kernel(const GenArgs G) {
-    using PL = Plan<N, P>;
-    constexpr int T = PL::T;
+    using WG = WorkgroupFft<N, P>;
+    constexpr int T = WG::T;
     const Args& A = G.dst;
     extern __shared__ __attribute__((aligned(4096))) char smem[];
     cplx* lds = reinterpret_cast<cplx*>(smem);
-    cplx* ltw = lds + lds_data_slots(N, P);
+    cplx* ltw = WG::twiddles(lds);
     const int t = threadIdx.x;
-    for (int i = t; i < PL::TW_TOTAL - N; i += T) ltw[i] = A.tw[N + i];
-    double* dd_tabs = reinterpret_cast<double*>(ltw + (PL::TW_TOTAL - N));      // 2 x DD_NTAB elimination factors of the box step (G.box only)
+    for (int i = t; i < WG::TW_SLOTS; i += T) ltw[i] = A.tw[N + i];
+    double* dd_tabs = reinterpret_cast<double*>(ltw + WG::TW_SLOTS);      // 2 x DD_NTAB elimination factors of the box step (G.box only)
     if (G.box) cpdd::fill_tables(dd_tabs);
     const long long npairs = (G.ncosmo + 1) / 2;
     const double fn = sqrt(2. / N), fl = sqrt(1. / N);
@@ -498,7 +488,6 @@ __global__ __launch_bounds__(N / P, 2) void dst_generate_kernel(const GenArgs G)
         const bool has_b = 2 * p + 1 < G.ncosmo;
         double* oa = A.out + 2 * p * N;
         double* ob = has_b ? oa + N : oa;
-        auto at = [&](int j) { return A.split ? ((j & 1) * (N / 2) + (j >> 1)) : j; };
         if (t == 0) bad_row[0] = bad_row[1] = 0;
         __syncthreads();  // LDS reuse across pairs (and the table fill on the first one)
         double* slots = reinterpret_cast<double*>(lds);
@@ -508,20 +497,7 @@ __global__ __launch_bounds__(N / P, 2) void dst_generate_kernel(const GenArgs G)
         generate_row<N, P, ENGINE>(&G, 2 * p, tt, slots, cpmath::tables_present(&mt));
         if (has_b) generate_row<N, P, ENGINE>(&G, 2 * p + 1, tt, slots + 1, cpmath::tables_present(&mt));
         cplx x[P];
-        bool bad_a = false, bad_b = false;
-#pragma unroll
-        for (int r = 0; r < P; ++r) {      // the thread's own slots: no barrier
-            const int m = tt + T * r;
-            const bool lower = m < N / 2;
-            const double a = slots[2 * m], b = has_b ? slots[2 * m + 1] : 0.;
-            bad_a |= not_finite(a);
-            bad_b |= not_finite(b);
-            x[r].re = lower ? a : -a;
-            x[r].im = lower ? b : -b;
-        }
-        if (bad_a) bad_row[0] = 1;
-        if (bad_b) bad_row[1] = 1;
-        __syncthreads();      // flags published; every thread has read its slots before the first pass overwrites the region
+        pack_generated_pair<N, P>(tt, has_b, slots, bad_row, x);
         const bool skip_a = bad_row[0] != 0, skip_b = bad_row[1] != 0;
         if (skip_a | skip_b) {
 #pragma unroll
@@ -531,20 +507,19 @@ __global__ __launch_bounds__(N / P, 2) void dst_generate_kernel(const GenArgs G)
             }
         }
         asm volatile("" : "+v"(tt));
-        dif_all<N, P>(tt, A, x, lds, ltw);
+        WG::forward(tt, A.tw, x, lds, ltw);
         asm volatile("" : "+v"(tt));
         if (!G.box) {
 #pragma unroll 4
             for (int s = 0; s < P; ++s) {
                 const int k = tt + T * s;
-                const cplx v = lds_at<N, P>(lds, pos_of_freq<N, P>(k));
-                const cplx u = lds_at<N, P>(lds, pos_of_freq<N, P>((N - k) % N));
+                const cplx v = WG::at(lds, WG::pos_of_freq(k));
+                const cplx u = WG::at(lds, WG::pos_of_freq((N - k) % N));
                 const cplx rot = A.rot[k];
                 const double f = k == 0 ? fl : fn;
-                const double ya = 0.5 * (rot.re * (v.re + u.re) - rot.im * (v.im - u.im));
-                const double yb = 0.5 * (rot.re * (v.im + u.im) - rot.im * (u.re - v.re));
-                oa[at(N - 1 - k)] = skip_a ? nan : f * ya;
-                if (has_b) ob[at(N - 1 - k)] = skip_b ? nan : f * yb;
+                const double ya = separated_a(v, u, rot), yb = separated_b(v, u, rot);
+                oa[split_at<N>(A.split, N - 1 - k)] = skip_a ? nan : f * ya;
+                if (has_b) ob[split_at<N>(A.split, N - 1 - k)] = skip_b ? nan : f * yb;
             }
             continue;
         }
@@ -557,12 +532,12 @@ __global__ __launch_bounds__(N / P, 2) void dst_generate_kernel(const GenArgs G)
 #pragma unroll
             for (int s = 0; s < P; ++s) {
                 const int k = tt + T * s;
-                const cplx v = lds_at<N, P>(lds, pos_of_freq<N, P>(k));
-                const cplx u = lds_at<N, P>(lds, pos_of_freq<N, P>((N - k) % N));
+                const cplx v = WG::at(lds, WG::pos_of_freq(k));
+                const cplx u = WG::at(lds, WG::pos_of_freq((N - k) % N));
                 const cplx rot = A.rot[k];
                 const double f = k == 0 ? fl : fn;
-                va[s] = skip_a ? nan : f * (0.5 * (rot.re * (v.re + u.re) - rot.im * (v.im - u.im)));
-                vb[s] = skip_b ? nan : f * (0.5 * (rot.re * (v.im + u.im) - rot.im * (u.re - v.re)));
+                va[s] = skip_a ? nan : f * separated_a(v, u, rot);
+                vb[s] = skip_b ? nan : f * separated_b(v, u, rot);
             }
             __syncthreads();      // every thread has its coefficients: the data region is free
             double* seqs = reinterpret_cast<double*>(lds);
@@ -624,8 +599,7 @@ __global__ __launch_bounds__(N / P, 2) void dst_generate_kernel(const GenArgs G)
 
 template <int N>
 void launch(bool inverse, const Args& A, int grid, hipStream_t stream) {
-    constexpr int P = 16, T = N / P;
-    constexpr int lds = (lds_data_slots(N, P) + Plan<N, P>::TW_TOTAL - N) * (int)sizeof(cplx);
+    constexpr int P = 16, T = N / P, lds = WorkgroupFft<N, P>::lds_bytes();
     if (lds > 64 * 1024) {  // opt in to more than 64 KiB of dynamic LDS (once per process would do; the call is cheap)
         (void)cp::allow_full_lds<&dst_kernel<N, P, true>>();
         (void)cp::allow_full_lds<&dst_kernel<N, P, false>>();
@@ -695,12 +669,14 @@ extern "C" int cp_dst_execute(const cp_dst_plan* p, const double* d_in, double* 
 
 namespace {
 
+// dst_generate_kernel, wallish_tail_kernel, wallish_full_kernel: the transform's LDS and the 2 x DD_NTAB elimination factors of the box step behind it
+constexpr int WALLISH_LDS = WorkgroupFft<4096, 16>::lds_bytes(2 * cpdd::DD_NTAB * (int)sizeof(double));
+
 template <int ENGINE>
 void launch_generate(const GenArgs& G, int grid, hipStream_t stream) {
     constexpr int N = 4096, P = 16, T = N / P;
-    constexpr int lds = (lds_data_slots(N, P) + Plan<N, P>::TW_TOTAL - N) * (int)sizeof(cplx) + 2 * cpdd::DD_NTAB * (int)sizeof(double);
     (void)cp::allow_full_lds<&dst_generate_kernel<N, P, ENGINE>>();
-    hipLaunchKernelGGL((dst_generate_kernel<N, P, ENGINE>), dim3(grid), dim3(T), lds, stream, G);
+    hipLaunchKernelGGL((dst_generate_kernel<N, P, ENGINE>), dim3(grid), dim3(T), WALLISH_LDS, stream, G);
 }
 
 }  // namespace
@@ -708,8 +684,6 @@ void launch_generate(const GenArgs& G, int grid, hipStream_t stream) {
 extern "C" long long cp_dst_forward_analytic_workspace_bytes(long long ncosmo) { return ncosmo < 0 ? -1 : cp::coef_workspace_bytes(ncosmo, 0); }
 
 namespace {
-
-constexpr int WALLISH_LDS = (4096 + Plan<4096, 16>::TW_TOTAL - 4096) * (int)sizeof(cplx) + 2 * cpdd::DD_NTAB * (int)sizeof(double);
 
 bool bad_margins(int margin_first, int margin_second) { return margin_first < 0 || 2 * margin_first >= 2048 || margin_second < 0 || margin_second >= 2048; }
 

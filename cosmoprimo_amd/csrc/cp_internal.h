@@ -63,7 +63,8 @@ struct Tables;
 bool cp_splice_plan_uniform_view(const cp_splice_plan* plan, cpsu::Tables* out, int* device);
 
 // What the Gauss-Newton entry points (cp_mlp_gauss_newton.hip, cp_taylor_gauss_newton.hip: entry points only; their kernels are variants of the one
-// __global__ template of cp_mlp_tangent.h and of cp_taylor_gemm.h, which is how kernels share source here and still keep their instructions) take
+// __global__ template of cp_mlp_tangent.h and of cp_taylor_gemm.h, which is how kernels share source here and still keep their instructions; the row
+// transforms share inlined functions that keep them, cp_fft_workgroup.h) take
 // from the engines' files: the checks of mlp_front / taylor_front under the caller's name, the network's layout, and the launch of the kernel that
 // cp_*_predict_columns launches, inside the caller's device scope (they open none of their own).
 namespace cp {

@@ -9,8 +9,8 @@
 // and back  Z_k = E_k + i O_k  with  E_k = (X_k + conj X_{M-k}) / 2,  O_k = (X_k - conj X_{M-k}) / 2 e^{+2 pi i k / N},  z = IFFT_M(Z) =
 // conj(FFT_M(conj Z)) / M.  A workgroup takes a row at a time: rows never share a transform, so a NaN or a huge row cannot reach another
 // (numpy transforms row by row); a row that holds a NaN or an infinity is stored as NaN, every number of it, as the paired transforms of the
-// library store such a row (cp_dst.hip, cp_fftlog_body.h).  The complex FFT is the pass machinery of the FFTLog kernel (cp_fft_core.h): radix-16 butterflies in
-// registers, swizzled LDS exchanges, the twiddles of the passes behind the first resident in LDS.  The imaginary parts of the DC and Nyquist
+// library store such a row (cp_dst.hip, cp_fftlog_body.h).  The complex FFT is the workgroup transform of cp_fft_workgroup.h, which cp_dst.hip runs too: the
+// passes of the FFTLog kernel (cp_fft_core.h), the twiddles of the passes behind the first resident in LDS.  The imaginary parts of the DC and Nyquist
 // bins are ignored on the way back, as numpy's c2r does.  HBM: 8 N + 16 (M + 1) bytes per row either way.
 #include <hip/hip_runtime.h>
 
@@ -20,7 +20,7 @@
 
 #include "../../include/cosmoprimo_amd.h"
 #include "cp_error.h"
-#include "cp_fft_core.h"
+#include "cp_fft_workgroup.h"
 #include "cp_fftlog_tables.h"
 #include "cp_internal.h"
 
@@ -37,56 +37,15 @@ struct RArgs {
     int conj_input;      // backward: transform conj(in) (the reference's engine convention)
 };
 
-template <int M, int P>
-__device__ __forceinline__ int rpos_of_freq(int k) {
-    using PL = Plan<M, P>;
-    int pos = 0;
-#pragma unroll
-    for (int i = 0; i < PL::NPASS; ++i) {
-        const int R = PL::radix(i), MM = PL::len(i) / R;
-        pos += (k % R) * MM;
-        k /= R;
-    }
-    return pos;
-}
-
-template <int M, int P, int I>
-__device__ __forceinline__ void rdif_rest(int t, cplx* lds, const cplx* ltw) {
-    using PL = Plan<M, P>;
-    if constexpr (I < PL::NPASS) {
-        cplx x[P];
-        __syncthreads();
-        asm volatile("" : "+v"(t));
-        Pass<M, P, I>::load_lds(t, lds, x);
-        Pass<M, P, I>::butterflies(x);
-        Pass<M, P, I>::twiddle_apply_lds(t, ltw + (PL::tw_offset(I) - M), x);
-        Pass<M, P, I>::store_lds(t, lds, x);
-        rdif_rest<M, P, I + 1>(t, lds, ltw);
-    }
-}
-
-// forward complex FFT of the M points held as x[r] = z[t + T r]; result in LDS, frequency k at swz(rpos_of_freq(k))
-template <int M, int P>
-__device__ __forceinline__ void rdif_all(int t, const RArgs& A, cplx* x, cplx* lds, const cplx* ltw) {
-    using PL = Plan<M, P>;
-    Pass<M, P, 0>::butterflies(x);
-    cplx w[P];
-    Pass<M, P, 0>::twiddle_load(t, A.tw + PL::tw_offset(0), w);
-    Pass<M, P, 0>::twiddle_apply(w, x);
-    Pass<M, P, 0>::store_lds(t, lds, x);
-    rdif_rest<M, P, 1>(t, lds, ltw);
-    __syncthreads();
-}
-
 template <int M, int P, bool BACKWARD>
 __global__ __launch_bounds__(M / P) void rfft_kernel(const RArgs A) {
-    using PL = Plan<M, P>;
-    constexpr int T = PL::T, N = 2 * M;
+    using WG = WorkgroupFft<M, P>;
+    constexpr int T = WG::T, N = 2 * M;
     extern __shared__ __attribute__((aligned(4096))) char rsmem[];
     cplx* lds = reinterpret_cast<cplx*>(rsmem);
-    cplx* ltw = lds + lds_data_slots(M, P);
+    cplx* ltw = WG::twiddles(lds);
     const int t = threadIdx.x;
-    for (int i = t; i < PL::TW_TOTAL - M; i += T) ltw[i] = A.tw[M + i];
+    for (int i = t; i < WG::TW_SLOTS; i += T) ltw[i] = A.tw[M + i];
     // A row with a sample that is not finite: left to the arithmetic, a NaN reaches every bin, but an infinity ends as +-Inf in a few (DC or
     // Nyquist of the forward transform, the samples that only additions reach on the way back).  The thread that meets such a sample raises the
     // row's flag before its first LDS store, the barriers of the transform publish it, and the row is stored as NaN.  Two flags taken in turn:
@@ -111,14 +70,14 @@ __global__ __launch_bounds__(M / P) void rfft_kernel(const RArgs A) {
                 bad |= not_finite(x[r].re) || not_finite(x[r].im);
             }
             if (bad) bad_row[turn] = 1;
-            rdif_all<M, P>(tt, A, x, lds, ltw);
+            WG::forward(tt, A.tw, x, lds, ltw);
             asm volatile("" : "+v"(tt));
             const bool skip = bad_row[turn] != 0;
 #pragma unroll 4
             for (int s = 0; s < P; ++s) {
                 const int k = tt + T * s;
-                const cplx v = lds[swz<M, P>(rpos_of_freq<M, P>(k))];
-                const cplx u = lds[swz<M, P>(rpos_of_freq<M, P>((M - k) % M))];
+                const cplx v = lds[swz<M, P>(WG::pos_of_freq(k))];
+                const cplx u = lds[swz<M, P>(WG::pos_of_freq((M - k) % M))];
                 const cplx w = A.rot[k];
                 const cplx e = cplx{0.5 * (v.re + u.re), 0.5 * (v.im - u.im)};
                 const cplx o = cplx{0.5 * (v.im + u.im), 0.5 * (u.re - v.re)};
@@ -150,14 +109,14 @@ __global__ __launch_bounds__(M / P) void rfft_kernel(const RArgs A) {
                 x[r].im = -(e.im + o.re);
             }
             if (bad) bad_row[turn] = 1;
-            rdif_all<M, P>(tt, A, x, lds, ltw);
+            WG::forward(tt, A.tw, x, lds, ltw);
             asm volatile("" : "+v"(tt));
             const bool skip = bad_row[turn] != 0;
             const double scale = 1. / M;
 #pragma unroll 4
             for (int s = 0; s < P; ++s) {
                 const int m = tt + T * s;
-                const cplx g = lds[swz<M, P>(rpos_of_freq<M, P>(m))];
+                const cplx g = lds[swz<M, P>(WG::pos_of_freq(m))];
                 dst[m] = skip ? cplx{nan, nan} : cplx{g.re * scale, -g.im * scale};
             }
         }
@@ -166,8 +125,7 @@ __global__ __launch_bounds__(M / P) void rfft_kernel(const RArgs A) {
 
 template <int M, int P>
 void rlaunch(bool backward, const RArgs& A, int grid, hipStream_t stream) {
-    constexpr int T = M / P;
-    constexpr int lds = (lds_data_slots(M, P) + Plan<M, P>::TW_TOTAL - M) * (int)sizeof(cplx);
+    constexpr int T = M / P, lds = WorkgroupFft<M, P>::lds_bytes();
     if (lds > 64 * 1024) {
         (void)cp::allow_full_lds<&rfft_kernel<M, P, true>>();
         (void)cp::allow_full_lds<&rfft_kernel<M, P, false>>();

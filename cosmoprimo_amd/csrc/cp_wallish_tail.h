@@ -1,5 +1,6 @@
 // cp_wallish_tail.h -- wallish2018 behind its forward transform as ONE kernel (reference bao_filter.py:373-431).  Part of cp_dst.hip (included inside its
-// anonymous namespace, behind the transform kernels whose pass machinery it uses); the C entry point cp_wallish_tail is at the end of that file.
+// anonymous namespace, behind the transform kernels: it runs the same workgroup transform, cp_fft_workgroup.h, and takes the handling of a pair --
+// separated_a / _b, hermitian_bin, conj_packed, pack_generated_pair -- from the head of that file); the C entry point cp_wallish_tail is at the end of that file.
 //
 // The three steps that follow the forward sine transform -- second derivatives of the two coefficient sequences, the box between their maxima and its
 // removal (:373-405: wallish_dd_box_kernel), the inverse transform with exp(.) / k_lin (:407-413: dst_kernel<..., true>) and the clamped spline through
@@ -204,8 +205,8 @@ __device__ __forceinline__ void tail_splice_row(double* row, double* outrow, int
 template <int SU>
 __device__ __forceinline__ void tail_stages(long long p, bool has_b, int t, cplx* lds, cplx* ltw, double* dd_tabs, const cpmath::MathTables& mt, int* bad_row) {
     constexpr int N = 4096, P = 16, NS = N / 2, S = 32;
-    using PL = Plan<N, P>;
-    constexpr int T = PL::T;
+    using WG = WorkgroupFft<N, P>;
+    constexpr int T = WG::T;
     using namespace cpdd;
     const double fn = sqrt(2. / N), fl = sqrt(1. / N);
     const double nan = __builtin_nan("");
@@ -271,28 +272,23 @@ __device__ __forceinline__ void tail_stages(long long p, bool has_b, int t, cplx
 #else
                 const cplx rot = rots[tt + T * r];
 #endif
-                const double cs = rot.re, sn = -rot.im;
-                cplx Ha = cplx{0.5 * (Aa * cs + Ba * sn), 0.5 * (Aa * sn - Ba * cs)};
-                cplx Hb = cplx{0.5 * (Ab * cs + Bb * sn), 0.5 * (Ab * sn - Bb * cs)};
+                cplx Ha = hermitian_bin(Aa, Ba, rot), Hb = hermitian_bin(Ab, Bb, rot);
                 if (r == 0 && k0) {
                     Ha = cplx{Aa, 0.};
                     Hb = cplx{Ab, 0.};
                 }
                 if (skip_a) Ha = cplx{0., 0.};
                 if (skip_b || !has_b) Hb = cplx{0., 0.};
-                x[r].re = Ha.re - Hb.im;
-                x[r].im = -(Ha.im + Hb.re);
+                x[r] = conj_packed(Ha, Hb);
             }
         }
         __syncthreads();      // every read of the sequences is done: the transform takes the region
-        {
-            Args A{};      // (the pass machinery of dst_kernel takes its twiddles from here)
-            A.tw = tail_args()->tw;
-            if (!(CP_TAIL_ABLATE & 2)) dif_all<N, P>(tt, A, x, lds, ltw);
-            else {
-                Pass<N, P, 0>::store_lds(tt, lds, x);
-                __syncthreads();
-            }
+        if (!(CP_TAIL_ABLATE & 2)) {
+            const cplx* tw = tail_args()->tw;
+            WG::forward(tt, tw, x, lds, ltw);
+        } else {
+            Pass<N, P, 0>::store_lds(tt, lds, x);
+            __syncthreads();
         }
         asm volatile("" : "+v"(tt));
         // ---- 4. exp(.) / k_lin on the stretch; the pair as two real rows in natural order ----
@@ -362,20 +358,20 @@ __device__ __forceinline__ void tail_stages(long long p, bool has_b, int t, cplx
 template <int SU>
 __global__ __launch_bounds__(256, 2) void wallish_tail_kernel(const TailArgs G_by_value) {
     constexpr int N = 4096, P = 16, NS = N / 2;
-    using PL = Plan<N, P>;
-    constexpr int T = PL::T;
+    using WG = WorkgroupFft<N, P>;
+    constexpr int T = WG::T;
     using namespace cpdd;
-    static_assert(!padded_lds(N, P) && lds_data_slots(N, P) == N, "four sequences of 2048 doubles / two real rows of 4096 fill the data region");
+    static_assert(!padded_lds(N, P) && WG::DATA_SLOTS == N, "four sequences of 2048 doubles / two real rows of 4096 fill the data region");
     extern __shared__ __attribute__((aligned(4096))) char smem[];
     cplx* lds = reinterpret_cast<cplx*>(smem);
-    cplx* ltw = lds + N;
-    double* dd_tabs = reinterpret_cast<double*>(ltw + (PL::TW_TOTAL - N));
+    cplx* ltw = WG::twiddles(lds);
+    double* dd_tabs = reinterpret_cast<double*>(ltw + WG::TW_SLOTS);
     const int t = threadIdx.x;
     long long npairs;
     {
         TailArgsK g = tail_args();
         const cplx* tw = g->tw;
-        for (int i = t; i < PL::TW_TOTAL - N; i += T) ltw[i] = tw[N + i];
+        for (int i = t; i < WG::TW_SLOTS; i += T) ltw[i] = tw[N + i];
         npairs = (g->nrows + 1) / 2;
     }
     fill_tables(dd_tabs);
@@ -449,10 +445,10 @@ __device__ __forceinline__ GenArgsK gen_args() {
 template <int SU, int ENGINE>
 __global__ __launch_bounds__(256, 2) void wallish_full_kernel(const FullArgs F) {
     constexpr int N = 4096, P = 16, NS = N / 2;
-    using PL = Plan<N, P>;
-    constexpr int T = PL::T;
+    using WG = WorkgroupFft<N, P>;
+    constexpr int T = WG::T;
     using namespace cpdd;
-    static_assert(!padded_lds(N, P) && lds_data_slots(N, P) == N, "the generated samples go through natural-order slots of the data region");
+    static_assert(!padded_lds(N, P) && WG::DATA_SLOTS == N, "the generated samples go through natural-order slots of the data region");
 #if CP_FULL_KERNARG_RELOAD
 #define CP_GEN() gen_args()
 #else
@@ -460,12 +456,12 @@ __global__ __launch_bounds__(256, 2) void wallish_full_kernel(const FullArgs F) 
 #endif
     extern __shared__ __attribute__((aligned(4096))) char smem[];
     cplx* lds = reinterpret_cast<cplx*>(smem);
-    cplx* ltw = lds + N;
-    double* dd_tabs = reinterpret_cast<double*>(ltw + (PL::TW_TOTAL - N));
+    cplx* ltw = WG::twiddles(lds);
+    double* dd_tabs = reinterpret_cast<double*>(ltw + WG::TW_SLOTS);
     const int t = threadIdx.x;
     {
         const cplx* tw = CP_GEN()->dst.tw;
-        for (int i = t; i < PL::TW_TOTAL - N; i += T) ltw[i] = tw[N + i];
+        for (int i = t; i < WG::TW_SLOTS; i += T) ltw[i] = tw[N + i];
     }
     fill_tables(dd_tabs);
     __shared__ int bad_row[2];
@@ -490,20 +486,7 @@ __global__ __launch_bounds__(256, 2) void wallish_full_kernel(const FullArgs F) 
         if (has_b) generate_row<N, P, ENGINE>(CP_GEN(), 2 * p + 1, tt, seqs + 1, cpmath::tables_present(&mt));
         {
             cplx x[P];
-            bool bad_a = false, bad_b = false;
-#pragma unroll
-            for (int r = 0; r < P; ++r) {      // the thread's own slots: no barrier
-                const int m = tt + T * r;
-                const bool lower = m < N / 2;
-                const double a = seqs[2 * m], b = has_b ? seqs[2 * m + 1] : 0.;
-                bad_a |= !(fabs(a) <= 1.7976931348623157e308);
-                bad_b |= !(fabs(b) <= 1.7976931348623157e308);
-                x[r].re = lower ? a : -a;
-                x[r].im = lower ? b : -b;
-            }
-            if (bad_a) bad_row[0] = 1;
-            if (bad_b) bad_row[1] = 1;
-            __syncthreads();      // flags published; every thread has read its slots before the first pass overwrites the region
+            pack_generated_pair<N, P>(tt, has_b, seqs, bad_row, x);
             const bool skip_a = bad_row[0] != 0, skip_b = bad_row[1] != 0;
             if (skip_a | skip_b) {
 #pragma unroll
@@ -512,9 +495,8 @@ __global__ __launch_bounds__(256, 2) void wallish_full_kernel(const FullArgs F) 
                     if (skip_b) x[r].im = 0.;
                 }
             }
-            Args A{};      // (the pass machinery takes its twiddles from here)
-            A.tw = CP_GEN()->dst.tw;
-            dif_all<N, P>(tt, A, x, lds, ltw);
+            const cplx* tw = CP_GEN()->dst.tw;
+            WG::forward(tt, tw, x, lds, ltw);
         }
         asm volatile("" : "+v"(tt));
         // ---- 1. the pair's coefficients (frequency k of the packed transform -> coefficient 4095 - k of either row) into the four sequences, XOR layout ----
@@ -543,8 +525,8 @@ __global__ __launch_bounds__(256, 2) void wallish_full_kernel(const FullArgs F) 
                 const cplx rot = rots[tt + T * s];
 #endif
                 const double f = (s == 0 && first) ? fl : fn;
-                va[s] = skip_a ? nan : f * (0.5 * (rot.re * (v.re + u.re) - rot.im * (v.im - u.im)));
-                vb[s] = skip_b ? nan : f * (0.5 * (rot.re * (v.im + u.im) - rot.im * (u.re - v.re)));
+                va[s] = skip_a ? nan : f * separated_a(v, u, rot);
+                vb[s] = skip_b ? nan : f * separated_b(v, u, rot);
             }
             __syncthreads();      // every thread has its coefficients: the data region is free
             const int wa = 127 - (tt >> 1);
