@@ -1118,6 +1118,23 @@ extern "C" int cp_splice_plan_set_scheme(cp_splice_plan* p, int scheme) {
     return CP_OK;
 }
 
+// what the plan chose: elimination[5] = S, halo, ntab_left, uniform_end, LDS bytes of splice_kernel; uniform[7] = whether the uniform-stretch scheme fits,
+// then its S, nm, wl, wr, gb0, ngb (zeros where it does not)
+extern "C" int cp_splice_plan_info(const cp_splice_plan* p, int* elimination, int* uniform) {
+    if (!p) return cp::fail(CP_EINVAL, "cp_splice_plan_info: null plan");
+    if (elimination) {
+        elimination[0] = p->T.S; elimination[1] = p->T.halo; elimination[2] = p->T.ntab_left; elimination[3] = p->T.uniform_end;
+        elimination[4] = (int)p->lds_bytes;
+    }
+    if (uniform) {
+        const bool fits = p->has_uniform;
+        uniform[0] = fits ? 1 : 0;
+        uniform[1] = fits ? p->U.S : 0; uniform[2] = fits ? p->U.nm : 0; uniform[3] = fits ? p->U.wl : 0; uniform[4] = fits ? p->U.wr : 0;
+        uniform[5] = fits ? p->U.gb0 : 0; uniform[6] = fits ? p->U.ngb : 0;
+    }
+    return CP_OK;
+}
+
 extern "C" int cp_splice_apply(const cp_splice_plan* p, const double* d_src0, int n0, const double* d_src1, int n1, long long nrows, const double* d_tophat,
                                double* d_out, void* stream) {
     if (!p) return cp::fail(CP_EINVAL, "cp_splice_apply: null plan");

@@ -158,6 +158,16 @@ class SplicedClampedSpline(dv.PlanOwner):
     def scheme(self, scheme):
         _lib.check(_lib.load().cp_splice_plan_set_scheme(self._handle, int(scheme)))
 
+    @property
+    def layout(self):
+        """What the plan chose (``cp_splice_plan_info``): S, halo, ntab_left, uniform_end and lds_bytes of the elimination kernel; ``uniform``: None where the
+        uniform-stretch scheme does not fit, else its S, nm, wl, wr, gb0 and ngb."""
+        elimination, uniform = (ctypes.c_int * 5)(), (ctypes.c_int * 7)()
+        _lib.check(_lib.load().cp_splice_plan_info(self._handle, elimination, uniform))
+        layout = dict(zip(('S', 'halo', 'ntab_left', 'uniform_end', 'lds_bytes'), elimination))
+        layout['uniform'] = dict(zip(('S', 'nm', 'wl', 'wr', 'gb0', 'ngb'), uniform[1:])) if uniform[0] else None
+        return layout
+
     def __call__(self, rows0, rows1=None, tophat=None):
         """rows0 (nrows, n0), rows1 (nrows, n1) device tensors -> (nrows, nq); ``tophat`` (nq,): rows0 / ((rows0 / spline - 1) tophat + 1)."""
         torch = dv.torch()

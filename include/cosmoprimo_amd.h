@@ -444,6 +444,11 @@ int cp_splice_plan_destroy(cp_splice_plan* plan);
  * csrc/cp_splice_uniform.h) -- the default where it fits.  cp_splice_plan_set_scheme(plan, 1) returns CP_EUNSUPPORTED where it does not. */
 int cp_splice_plan_scheme(const cp_splice_plan* plan);
 int cp_splice_plan_set_scheme(cp_splice_plan* plan, int scheme);
+/* What the plan chose (either pointer may be null).  elimination[5]: knots per lane S, the run-in `halo` of a sweep, ntab_left and uniform_end (knots
+ * [0, ntab_left) and [uniform_end, nknots) have a table slot of their own, those between share one; both nknots without such a stretch), the LDS bytes of
+ * a workgroup.  uniform[7]: whether the uniform-stretch scheme fits, then its knots per lane, the knots of the stretch, the knots staged in front of and
+ * behind it, the first block of 64 queries that goes through the spline and the number of such blocks (zeros where it does not fit). */
+int cp_splice_plan_info(const cp_splice_plan* plan, int* elimination, int* uniform);
 
 /* ---- natural / clamped cubic spline of very many rows by elimination in LDS (csrc/cp_spline_rows.hip) ----
  * The same function as cp_spline_plan_create(bc, nu = 0) + cp_spline_apply / cp_spline_apply_grouped

@@ -144,8 +144,9 @@ def test_brieden_resampling_in_one_kernel(cp):
 def test_brieden_resample_against_the_oracle():
     """cp_brieden_resample on its own, through the C ABI, against the oracle's restatement of what it replaces (oracle/interp.py: pad_log +
     natural spline of log10 P on log10 k, interpolator.py:42-87, 345-350; bao_filter.py:500-509): smooth and wiggly samples, rs_drag ratios on
-    both sides of 1 and exactly 1 (every query on a knot), 3 to 8 samples per lane, batches that do not fill a workgroup; a k_fid that is not a
-    geometric grid gives NaN over its range, nothing else."""
+    both sides of 1 and exactly 1 (every query on a knot), 3, 4, 6 and 8 samples per lane (5 and 7, and the sizes at which the last lane is full, owns
+    one knot or straddles the last one: tests/test_brieden_edges_gpu.py), batches that do not fill a workgroup; a k_fid that is not a geometric grid
+    gives NaN over its range, nothing else."""
     import torch
     from oracle import interp as ointerp
     from cosmoprimo_amd import _lib, _device as dv

@@ -21,8 +21,11 @@ def pad_knots(x, y, kmin=1e-7, kmax=1e2):
             np.concatenate([[y[0] + sl * (xa - x[0]), y[0] + sl * (xb - x[0])], y, [y[-1] + sr * (xc - x[-1]), y[-1] + sr * (xd - x[-1])]]))
 
 
-def second_derivatives_as_the_kernel(x, y, X):
-    """M at the n + 4 padded knots, in the kernel's steps: S knots per lane, 64 lanes."""
+def second_derivatives_as_the_kernel(x, y, X, mistake=None, scaled=True):
+    """M at the n + 4 padded knots, in the kernel's steps: S knots per lane, 64 lanes.  ``scaled=False``: in the kernel's units of 6 kappa / h^2.
+    ``mistake`` (tests/test_brieden_truth_host.py: what the tolerance rule must notice; never made in the library): 'tlast', the B correction of a lane that
+    straddles the last knot counted from its knot S - 1, which does not exist, instead of from knot n - 1; 'no_A', the A correction left out."""
+    assert mistake in (None, 'tlast', 'no_A')
     n = x.size
     S = (n + 63) // 64
     reach = (32 + S) // S
@@ -57,13 +60,19 @@ def second_derivatives_as_the_kernel(x, y, X):
     A = amplitude(X[1] - X[0], X[2] - X[1], m0[0], m0[1])
     B = amplitude(X[-1] - X[-2], X[-2] - X[-3], m0[-1], m0[-2])
     i = np.arange(n)
+    from_end = n - 1 - i
+    if mistake == 'tlast':
+        own = ((n - 1) // S) * S      # the lane that holds knot n - 1: its knot S - 1 lies dr knots beyond it
+        from_end = from_end + np.where(i >= own, (own + S - 1) - (n - 1), 0)
+    if mistake == 'no_A':
+        A = 0.
     with np.errstate(under='ignore'):
-        m = m0 + np.where(i <= 40 + S, A * P**np.minimum(i, 400), 0.) + np.where(n - 1 - i <= 40 + S, B * P**np.minimum(n - 1 - i, 400), 0.)
+        m = m0 + np.where(i <= 40 + S, A * P**np.minimum(i, 400), 0.) + np.where(n - 1 - i <= 40 + S, B * P**np.minimum(from_end, 400), 0.)
     full = np.zeros(n + 4)
     full[2:-2] = m
     full[1] = -(X[2] - X[1]) * m[0] / (2. * ((X[1] - X[0]) + (X[2] - X[1])))
     full[-2] = -(X[-2] - X[-3]) * m[-1] / (2. * ((X[-1] - X[-2]) + (X[-2] - X[-3])))
-    return full * (6. * KAPPA / h**2)
+    return full * (6. * KAPPA / h**2) if scaled else full
 
 
 @pytest.mark.parametrize('n', [341, 129, 200, 512, 450])

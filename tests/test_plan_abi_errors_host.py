@@ -1,7 +1,7 @@
 """CPU: what the entry points of the plan types answer without touching a device -- every refusal of the ten constructors (cp_fftlog_plan_create on both
 of its paths, cp_rfft_plan_create, cp_dst_plan_create, cp_spline_plan_create, cp_linop_plan_create, cp_spline_rows_plan_create, cp_splice_plan_create,
 cp_interp_table_create, cp_geospline_plan_create and _create_prefiltered), the null-plan answers of their *_info / *_columns / *_law / *_scheme /
-*_set_scheme entries and *_destroy(NULL) -- against tests/golden/plan_abi_errors.json: status AND message of each call as the library answered before
+*_set_scheme entries (cp_splice_plan_info among them) and *_destroy(NULL) -- against tests/golden/plan_abi_errors.json: status AND message of each call as the library answered before
 its plans were given one owner of their device tables (tools/gen_plan_abi_errors.py holds the table of calls and wrote the file).  The calls with two
 faults at once pin the order of the checks.  Every constructor is called with an output pointer that holds garbage, and must leave it null on every
 failure.
@@ -23,7 +23,7 @@ CONSTRUCTORS = ['cp_fftlog_plan_create', 'cp_rfft_plan_create', 'cp_dst_plan_cre
                 'cp_spline_rows_plan_create', 'cp_splice_plan_create', 'cp_interp_table_create', 'cp_geospline_plan_create',
                 'cp_geospline_plan_create_prefiltered']
 OTHERS = ['cp_fftlog_plan_info', 'cp_spline_plan_info', 'cp_spline_plan_columns', 'cp_spline_rows_plan_info', 'cp_geospline_plan_info', 'cp_interp_table_law',
-          'cp_splice_plan_scheme', 'cp_splice_plan_set_scheme', 'cp_fftlog_plan_destroy', 'cp_rfft_plan_destroy', 'cp_dst_plan_destroy', 'cp_spline_plan_destroy',
+          'cp_splice_plan_scheme', 'cp_splice_plan_set_scheme', 'cp_splice_plan_info', 'cp_fftlog_plan_destroy', 'cp_rfft_plan_destroy', 'cp_dst_plan_destroy', 'cp_spline_plan_destroy',
           'cp_spline_rows_plan_destroy', 'cp_splice_plan_destroy', 'cp_interp_table_destroy', 'cp_geospline_plan_destroy']
 GARBAGE = 0x5a5a5a50      # what the plan pointer holds before a constructor is called
 

@@ -58,8 +58,12 @@ def build(knots, pieces, xq):
     return T
 
 
-def run(T, rows):
-    """cp_splice_uniform.h restated: rows = (array 0, array 1) of ONE vector -> the spline at the queries (the others return their own column)."""
+def run(T, rows, mistake=None):
+    """cp_splice_uniform.h restated: rows = (array 0, array 1) of ONE vector -> the spline at the queries (the others return their own column).
+    ``mistake`` (tests/test_splice_truth_host.py: what the tolerance rule must notice; never made in the library): 'mb_exchanged', mb0 and mb1 in each
+    other's lane; 'carry_from_1', the causal carry of the previous segment applied from the lane's knot 1 instead of 0; 'end_value', the slot behind
+    the stretch left holding the repeated end value instead of the second derivative of the knot there."""
+    assert mistake in (None, 'mb_exchanged', 'carry_from_1', 'end_value')
     S, nm, wl, wr = T['S'], T['nm'], T['wl'], T['wr']
     yu = rows[T['src_u']][T['col_u']:T['col_u'] + nm]
     gl = rows[T['src_l']][T['col_l']:T['col_l'] + wl] if wl else np.zeros(0)
@@ -87,13 +91,15 @@ def run(T, rows):
     sums = [np.sum(w[0] * (vl - yu[0]) + w[1] * (ul - yu[0])), np.sum(w[2] * (vl - gl_last) + w[3] * (ul - gl_last)),
             np.sum(w[4] * (ur - yu[-1]) + w[5] * (vr - yu[-1])), np.sum(w[6] * (ur - gr_first) + w[7] * (vr - gr_first))]
     gin = np.concatenate([g[1:, 0], [0.]])
-    gin[T['lane_b']] += T['mb0'] * sums[2]
-    gin[T['lane_b'] - 1] += T['mb1'] * sums[2]
+    mb0, mb1 = (T['mb1'], T['mb0']) if mistake == 'mb_exchanged' else (T['mb0'], T['mb1'])
+    gin[T['lane_b']] += mb0 * sums[2]
+    gin[T['lane_b'] - 1] += mb1 * sums[2]
     fin = np.concatenate([[0.], f[:-1]])
     fin[0] += sums[0]
     t = np.arange(S)
-    m = (e + P**(S - t)[None, :] * gin[:, None] + P**(t + 1)[None, :] * fin[:, None]).ravel()
-    buf = np.concatenate([[sums[1]], m[:nm], [sums[3]]])      # second derivatives (unscaled) at knots -1 .. nm of the stretch
+    causal = np.where(t >= 1, P**(t + 1), 0.) if mistake == 'carry_from_1' else P**(t + 1)
+    m = (e + P**(S - t)[None, :] * gin[:, None] + causal[None, :] * fin[:, None]).ravel()
+    buf = np.concatenate([[sums[1]], m[:nm], [yu[-1] if mistake == 'end_value' else sums[3]]])      # second derivatives (unscaled) at knots -1 .. nm of the stretch
     yy = np.concatenate([[gl_last], yu, [gr_first]])
     out = rows[0].copy()
     for i in range(64 * T['ngb']):

@@ -107,7 +107,7 @@ NULL_PLAN = [('cp_fftlog_plan_info', 'null plan', [None, 4, None, None, None]), 
              ('cp_spline_plan_columns', 'null plan', [None, None, None]), ('cp_spline_rows_plan_info', 'null plan', [None, None, None, None, None]),
              ('cp_geospline_plan_info', 'null plan', [None, None, None, None]), ('cp_interp_table_law', 'null table', [None, None, None]),
              ('cp_splice_plan_scheme', 'null plan (scheme 0)', [None]), ('cp_splice_plan_set_scheme', 'null plan', [None, 0]),
-             ('cp_splice_plan_set_scheme', 'null plan and scheme 5', [None, 5])] + [(entry, 'destroy(NULL)', [None]) for entry in OTHERS if entry.endswith('_destroy')]
+             ('cp_splice_plan_set_scheme', 'null plan and scheme 5', [None, 5]), ('cp_splice_plan_info', 'null plan', [None, None, None])] + [(entry, 'destroy(NULL)', [None]) for entry in OTHERS if entry.endswith('_destroy')]
 
 
 def table():
