@@ -207,7 +207,11 @@ SIGNATURES['cp_taylor_gauss_newton'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _G
 SIGNATURES['cp_taylor_gauss_newton_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong])
 SIGNATURES['cp_mlp_gauss_newton'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _GN_TAIL + _WHERE)
 SIGNATURES['cp_mlp_gauss_newton_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int, ctypes.c_longlong])
-SIGNATURES['cp_mlp_predict'] = (ctypes.c_int, _MLP_HEAD + [ctypes.c_void_p] + _WHERE)
+SIGNATURES['cp_lm_layout'] = (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)])
+# B, ndim; the state x, fisher, grad, chi2, lambda, status, naccepted; the trial xt, fisher_t, grad_t, chi2_t; lo, hi; up, down, lmin, lmax, ftol; next
+SIGNATURES['cp_lm_step'] = (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int] + [ctypes.c_void_p] * 13 + [ctypes.c_double] * 5 + [ctypes.c_void_p] + _WHERE)
+SIGNATURES['cp_spd_inverse'] = (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int] + [ctypes.c_void_p] * 3 + _WHERE)
+SIGNATURES['cp_mlp_predict'] =(ctypes.c_int, _MLP_HEAD + [ctypes.c_void_p] + _WHERE)
 SIGNATURES['cp_mlp_predict_columns'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _WHERE)
 SIGNATURES['cp_mlp_jacobian'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _ARRAY + _WHERE)      # d_value, ldv; d_jac, ldj
 SIGNATURES['cp_mlp_vjp'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _ARRAY + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong] + _WHERE)      # d_cot, ldc; d_value, ldv; d_grad, d_work, work_doubles

@@ -1,0 +1,269 @@
+// cp_lm.hip -- what stands between two calls of cp_*_gauss_newton in a batch of Levenberg-Marquardt fits (cp_lm_step), and the covariance behind the
+// last one (cp_spd_inverse): B independent fits of 1 <= ndim <= 32 parameters, one launch each, nothing read back.
+// Mapping.  A fit is a group of G lanes, G the smallest power of two >= ndim: 64 / G fits per wave, four waves per workgroup (two at G = 32: the static
+// LDS stays under 64 KB).  Lane i of a group owns parameter i and row i of the fit's lower triangle, in the wave's own LDS with the row stride G + 1
+// (64 (G + 1) doubles per wave: 17 KB at G = 32; nothing of a row in registers, no scratch).  A value goes from one lane of a group to all of them by
+// __shfl; the column steps of the factorisation are separated by cp::wave_lds_phase().  No workgroup barrier, no atomics: two calls give the same bits,
+// and a fit reads and writes nothing of another.
+// Arithmetic.  Every operation is a float64 operation rounded once, in a stated order (no contraction into FMAs: tests/lm_reference.py restates them in
+// numpy); divisions and square roots are the correctly rounded ones.
+//   factor: for columns j in order, t_i = A[i][j] - sum_{k < j, in order} L[i][k] L[j][k] for i >= j; the pivot d = t_j must be > 0 and finite;
+//           L[j][j] = sqrt(d), L[i][j] = t_i / L[j][j].
+//   solve:  L y = r with r_i -= L[i][j] y_j for j ascending, y_j = r_j / L[j][j]; then L^T z = y with r_i -= L[j][i] z_j for j DEscending.
+//   A held parameter h of cp_lm_step is taken out of the system by A[h][h] = 1, A[h][.] = A[.][h] = 0, r_h = 0: the free parameters see exact zeros.
+#include <cfloat>
+
+#include "cp_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int lm_threads(int G) { return G == 32 ? 128 : 256; }
+
+struct LmArgs {
+    long long B;
+    int ndim;
+    double *x, *fisher, *grad, *chi2, *lambda;
+    int *status, *naccepted;
+    const double *xt, *fisher_t, *grad_t, *chi2_t, *lo, *hi;
+    double up, down, lmin, lmax, ftol;
+    double* next;
+};
+
+__device__ __forceinline__ bool lm_finite(double v) { return fabs(v) <= DBL_MAX; }
+
+// the value lane j of this lane's group holds
+template <int G>
+__device__ __forceinline__ double group_value(double v, int j) {
+    return G == 1 ? v : __shfl(v, j, G);
+}
+
+// In place: the group's raw matrix in L (row i, column j at L[i (G + 1) + j]; the triangle j <= i is read) becomes its Cholesky factor.  diag: this
+// lane's diagonal entry as the system takes it; held: the group's held parameters, a bit each.  lii: L[i][i].  Returns 0, or the 1-based column of the
+// first pivot that is not > 0 or not finite (what follows it is then meaningless, and harmless).
+template <int G>
+__device__ __forceinline__ int lm_factor(double* L, const int i, const int n, const unsigned held, const double diag, double& lii) {
+    constexpr int S = G + 1;
+    const bool hi = (held >> i) & 1u;
+    int bad = 0;
+    lii = 1.;
+    for (int j = 0; j < n; ++j) {
+        double t = i == j ? diag : L[i * S + j];
+        if (hi || ((held >> j) & 1u)) t = i == j ? 1. : 0.;
+        for (int k = 0; k < j; ++k) t -= L[i * S + k] * L[j * S + k];
+        const double d = group_value<G>(t, j);
+        if (!bad && !(d > 0. && lm_finite(d))) bad = j + 1;
+        const double r = sqrt(d);
+        if (i == j) lii = r;
+        if (i >= j) L[i * S + j] = i == j ? r : t / r;
+        cp::wave_lds_phase();
+    }
+    return bad;
+}
+
+// z_i of L L^T z = r, r_i this lane's right-hand side with r_k = 0 for k < first; z is valid for i >= first (all of it with first = 0)
+template <int G>
+__device__ __forceinline__ double lm_solve(const double* L, const int i, const int n, const double lii, double r, const int first) {
+    constexpr int S = G + 1;
+    for (int j = first; j < n; ++j) {
+        double q = 0.;
+        if (i == j) q = r / lii;
+        const double y = group_value<G>(q, j);
+        if (i > j) r -= L[i * S + j] * y;
+        else if (i == j) r = y;
+    }
+    for (int j = n - 1; j >= first; --j) {
+        double q = 0.;
+        if (i == j) q = r / lii;
+        const double z = group_value<G>(q, j);
+        if (i < j) r -= L[j * S + i] * z;
+        else if (i == j) r = z;
+    }
+    return r;
+}
+
+template <int G>
+__global__ __launch_bounds__(lm_threads(G)) void lm_step_kernel(const LmArgs a) {
+    constexpr int S = G + 1, FPW = 64 / G, WAVES = lm_threads(G) / 64;
+    __shared__ double lds[WAVES * 64 * S];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = lane & (G - 1), f = lane / G, n = a.ndim;
+    const long long b = ((long long)blockIdx.x * WAVES + wave) * FPW + f;
+    double* const L = lds + (wave * FPW + f) * (G * S);
+    const bool fit = b < a.B, live = fit && i < n;
+    const double inf = __builtin_huge_val();
+
+    // the decision, every lane of the group alike
+    int status = 1, nacc = 0;
+    double chi = 0., chit = 0., lam = 1.;
+    if (fit) status = a.status[b], nacc = a.naccepted[b], chi = a.chi2[b], chit = a.chi2_t[b], lam = a.lambda[b];
+    const bool frozen = status != 0;
+    const bool accept = !frozen && lm_finite(chit) && chit <= chi;
+    if (accept) {
+        if (lm_finite(chi) && chi - chit <= a.ftol * chi) status = 1;
+        if (nacc > 0) {
+            lam = lam * a.down;
+            lam = lam < a.lmin ? a.lmin : lam;
+        }
+        ++nacc;
+        chi = chit;
+    } else if (!frozen) {
+        if (chi == inf) {
+            status = 3;
+        } else {
+            lam = lam * a.up;
+            if (lam > a.lmax) lam = a.lmax, status = 2;
+        }
+    }
+
+    // the trial into the state where it is accepted; the point the next step leaves from
+    double xv = 0., gv = 0., lo = 0., hi = 0.;
+    if (live) {
+        xv = accept ? a.xt[b * n + i] : a.x[b * n + i];
+        gv = accept ? a.grad_t[b * n + i] : a.grad[b * n + i];
+        lo = a.lo[i], hi = a.hi[i];
+        if (accept) a.x[b * n + i] = xv, a.grad[b * n + i] = gv;
+    }
+    if (fit) {
+        const double* const from = (accept ? a.fisher_t : a.fisher) + b * n * n;
+        for (int e = i; e < n * n; e += G) {
+            const double v = from[e];
+            if (accept) a.fisher[b * n * n + e] = v;
+            L[(e / n) * S + e % n] = v;
+        }
+    }
+    cp::wave_lds_phase();
+
+    const bool hold = live && status == 0 && ((xv >= hi && gv > 0.) || (xv <= lo && gv < 0.));
+    const unsigned long long all = __ballot(hold);
+    const unsigned held = (unsigned)((all >> (lane - i)) & (G == 32 ? 0xffffffffull : (1ull << G) - 1ull));
+    const double fii = live ? L[i * S + i] : 1.;
+    double lii;
+    const int bad = lm_factor<G>(L, i, n, held, fii + lam * fii, lii);
+    if (status == 0 && bad) status = 3;
+    const double delta = lm_solve<G>(L, i, n, lii, hold ? 0. : gv, 0);
+
+    if (live) {
+        double v = xv;
+        if (status == 0 && !hold) {
+            v = xv + delta;
+            v = v < lo ? lo : v;
+            v = v > hi ? hi : v;
+        }
+        a.next[b * n + i] = v;
+    }
+    if (fit && !frozen && i == 0) a.chi2[b] = chi, a.lambda[b] = lam, a.status[b] = status, a.naccepted[b] = nacc;
+}
+
+template <int G>
+__global__ __launch_bounds__(lm_threads(G)) void spd_inverse_kernel(const long long B, const int n, const double* a, double* inv, int* info) {
+    constexpr int S = G + 1, FPW = 64 / G, WAVES = lm_threads(G) / 64;
+    __shared__ double lds[WAVES * 64 * S];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = lane & (G - 1), f = lane / G;
+    const long long b = ((long long)blockIdx.x * WAVES + wave) * FPW + f;
+    double* const L = lds + (wave * FPW + f) * (G * S);
+    const bool fit = b < B, live = fit && i < n;
+    if (fit)
+        for (int e = i; e < n * n; e += G) L[(e / n) * S + e % n] = a[b * n * n + e];
+    cp::wave_lds_phase();
+    double lii;
+    const int bad = lm_factor<G>(L, i, n, 0u, live ? L[i * S + i] : 1., lii);
+    const double nan = __builtin_nan("");
+    for (int c = 0; c < n; ++c) {      // column c of the inverse, its rows i >= c; mirrored
+        const double z = lm_solve<G>(L, i, n, lii, i == c ? 1. : 0., c);
+        if (live && i >= c) {
+            const double v = bad ? nan : z;
+            inv[b * n * n + (long long)i * n + c] = v;
+            inv[b * n * n + (long long)c * n + i] = v;
+        }
+    }
+    if (fit && i == 0) info[b] = bad;
+}
+
+int lanes_of(int ndim) {
+    int G = 1;
+    while (G < ndim) G *= 2;
+    return G;
+}
+
+// what the three entry points check first, in this order; *per_workgroup: fits of a workgroup
+int lm_front(const char* who, long long B, int ndim, int* G, int* per_workgroup) {
+    if (B < 0 || ndim < 1) return cp::fail(CP_EINVAL, "%s: %lld fits of %d parameters", who, B, ndim);
+    if (ndim > 32) return cp::fail(CP_EUNSUPPORTED, "%s: %d parameters (at most 32)", who, ndim);
+    *G = lanes_of(ndim);
+    *per_workgroup = lm_threads(*G) / *G;
+    if (B > 0x7fffffffLL * *per_workgroup)
+        return cp::fail(CP_EUNSUPPORTED, "%s: %lld fits of %d parameters (at most 2^31 - 1 workgroups of %d fits)", who, B, ndim, *per_workgroup);
+    return CP_OK;
+}
+
+template <int G>
+void step_launch(const LmArgs& a, unsigned grid, hipStream_t stream) {
+    hipLaunchKernelGGL(lm_step_kernel<G>, dim3(grid), dim3(lm_threads(G)), 0, stream, a);
+}
+
+template <int G>
+void inverse_launch(long long B, int ndim, const double* d_a, double* d_inv, int* d_info, unsigned grid, hipStream_t stream) {
+    hipLaunchKernelGGL(spd_inverse_kernel<G>, dim3(grid), dim3(lm_threads(G)), 0, stream, B, ndim, d_a, d_inv, d_info);
+}
+
+}  // namespace
+
+extern "C" int cp_lm_layout(int ndim, int* lanes_per_fit, int* fits_per_workgroup) {
+    int G, per;
+    const int status = lm_front("cp_lm_layout", 0, ndim, &G, &per);
+    if (status != CP_OK) return status;
+    if (!lanes_per_fit || !fits_per_workgroup) return cp::fail(CP_EINVAL, "cp_lm_layout: null pointer");
+    *lanes_per_fit = G, *fits_per_workgroup = per;
+    return CP_OK;
+}
+
+extern "C" int cp_lm_step(long long B, int ndim, double* d_x, double* d_fisher, double* d_grad, double* d_chi2, double* d_lambda, int* d_status, int* d_naccepted,
+                          const double* d_xt, const double* d_fisher_t, const double* d_grad_t, const double* d_chi2_t, const double* d_lo, const double* d_hi, double up,
+                          double down, double lmin, double lmax, double ftol, double* d_next, int device, void* stream) {
+    int G, per;
+    const int status = lm_front("cp_lm_step", B, ndim, &G, &per);
+    if (status != CP_OK) return status;
+    if (B == 0) return CP_OK;
+    if (!d_x || !d_fisher || !d_grad || !d_chi2 || !d_lambda || !d_status || !d_naccepted || !d_xt || !d_fisher_t || !d_grad_t || !d_chi2_t || !d_lo || !d_hi || !d_next)
+        return cp::fail(CP_EINVAL, "cp_lm_step: null pointer");
+    if (!(up > 1.) || !(down > 0. && down <= 1.) || !(lmin > 0. && lmin <= lmax) || !(ftol >= 0.))
+        return cp::fail(CP_EINVAL, "cp_lm_step: up = %g (> 1), down = %g (in (0, 1]), lmin = %g, lmax = %g (0 < lmin <= lmax), ftol = %g (>= 0)", up, down, lmin, lmax, ftol);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_lm_step: cannot select device %d", device);
+    const LmArgs a{B, ndim, d_x, d_fisher, d_grad, d_chi2, d_lambda, d_status, d_naccepted, d_xt, d_fisher_t, d_grad_t, d_chi2_t, d_lo, d_hi, up, down, lmin, lmax, ftol, d_next};
+    const unsigned grid = (unsigned)((B + per - 1) / per);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (G) {
+        case 1: step_launch<1>(a, grid, s); break;
+        case 2: step_launch<2>(a, grid, s); break;
+        case 4: step_launch<4>(a, grid, s); break;
+        case 8: step_launch<8>(a, grid, s); break;
+        case 16: step_launch<16>(a, grid, s); break;
+        default: step_launch<32>(a, grid, s); break;
+    }
+    return cp::launch_status("cp_lm_step");
+}
+
+extern "C" int cp_spd_inverse(long long B, int ndim, const double* d_a, double* d_inv, int* d_info, int device, void* stream) {
+    int G, per;
+    const int status = lm_front("cp_spd_inverse", B, ndim, &G, &per);
+    if (status != CP_OK) return status;
+    if (B == 0) return CP_OK;
+    if (!d_a || !d_inv || !d_info) return cp::fail(CP_EINVAL, "cp_spd_inverse: null pointer");
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_spd_inverse: cannot select device %d", device);
+    const unsigned grid = (unsigned)((B + per - 1) / per);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (G) {
+        case 1: inverse_launch<1>(B, ndim, d_a, d_inv, d_info, grid, s); break;
+        case 2: inverse_launch<2>(B, ndim, d_a, d_inv, d_info, grid, s); break;
+        case 4: inverse_launch<4>(B, ndim, d_a, d_inv, d_info, grid, s); break;
+        case 8: inverse_launch<8>(B, ndim, d_a, d_inv, d_info, grid, s); break;
+        case 16: inverse_launch<16>(B, ndim, d_a, d_inv, d_info, grid, s); break;
+        default: inverse_launch<32>(B, ndim, d_a, d_inv, d_info, grid, s); break;
+    }
+    return cp::launch_status("cp_spd_inverse");
+}

@@ -10,10 +10,14 @@ One front, four back ends.  The four methods share one plan (``Emulator._plan``:
 
 The helpers that both engines' ``predict`` / ``jacobian`` / ``vjp`` open with (``_columns``, ``_cotangent``, ``_tangent``, ``_operand``, ``_gauss_newton``, ``_empty``) live here as well; the engines
 import this module, which imports them only where it builds one.  Nothing on the path of a call imports anything: at B = 1 a call is its Python.
+
+``Emulator.least_squares`` runs batched Levenberg-Marquardt fits on ``gauss_newton``; what stands between two of its calls is one launch, :func:`lm_step` (with
+:func:`lm_state` and :func:`spd_inverse`: module-level, over device tensors, for normal equations of any origin).
 """
 import numpy as np
 
 from ... import _device as dv
+from ... import _lib
 
 
 def _columns(columns, M):
@@ -72,6 +76,72 @@ def _gauss_newton(d, check, entry, need, head, where, B, ndim, start, ncols, wei
     toret = (fisher, grad, chi2) if data is not None else (fisher,)
     toret = ((value,) if return_value else ()) + toret
     return toret[0] if len(toret) == 1 else toret
+
+
+LM_STATE = ('x', 'fisher', 'gradient', 'chi2', 'lambda', 'status', 'naccepted')
+LM_TRIAL = ('x', 'fisher', 'gradient', 'chi2')
+
+
+def lm_state(x, lambda0=1e-3):
+    """The state of B Levenberg-Marquardt fits that start at ``x`` (B, ndim), a float64 device tensor, as :func:`lm_step` takes it: nothing accepted yet
+    (``chi2 = +inf``: the first trial is the start itself), ``lambda = lambda0``, ``status = 0``."""
+    torch = dv.torch()
+    B, ndim = (int(s) for s in x.shape)
+    new = lambda *shape, **kwargs: torch.zeros(shape, dtype=kwargs.get('dtype', torch.float64), device=x.device)      # noqa: E731
+    return {'x': x.clone(), 'fisher': new(B, ndim, ndim), 'gradient': new(B, ndim), 'chi2': torch.full((B,), float('inf'), dtype=torch.float64, device=x.device),
+            'lambda': torch.full((B,), float(lambda0), dtype=torch.float64, device=x.device), 'status': new(B, dtype=torch.int32), 'naccepted': new(B, dtype=torch.int32)}
+
+
+def lm_step(state, trial, lo, hi, lambda_up=10., lambda_down=0.1, lambda_min=1e-12, lambda_max=1e12, ftol=1e-8):
+    """Everything between two ``gauss_newton`` calls of B Levenberg-Marquardt fits at once, in one launch (``cp_lm_step``, csrc/cp_lm.hip), whatever
+    produced the normal equations.  ``state``: contiguous device tensors ``x`` (B, ndim), ``fisher`` (B, ndim, ndim), ``gradient`` (B, ndim), ``chi2``,
+    ``lambda`` (B,) float64, ``status``, ``naccepted`` (B,) int32 (:func:`lm_state`), updated in place.  ``trial``: ``x``, ``fisher``, ``gradient``,
+    ``chi2``, what ``gauss_newton`` returned at ``trial['x']``.  ``lo``, ``hi``: (ndim,) device tensors, the box (infinite where open).
+
+    Per fit: a fit whose ``status`` is not 0 is left alone.  The trial is accepted if its ``chi2`` is finite and not above the state's; it is then copied
+    into the state, ``lambda`` is multiplied by ``lambda_down`` (not below ``lambda_min``; not on the first acceptance), and the fit has converged
+    (``status = 1``) if ``chi2`` went down by no more than ``ftol`` times itself.  A rejected trial multiplies ``lambda`` by ``lambda_up``; beyond
+    ``lambda_max`` the fit has stalled (``status = 2``); a start that is not finite fails (``status = 3``).  A running fit then holds the parameters that
+    sit on a bound with the gradient pointing out of the box, solves ``(F + lambda diag F) delta = g`` on the others by Cholesky (a pivot that is not
+    positive: ``status = 3``) and moves them by ``delta``, clipped to the box.  Returns ``next`` (B, ndim), the next trial point: ``x`` for a fit that is
+    not running.  Nothing is read back and the call does not wait for the device."""
+    torch = dv.torch()
+    x = state['x']
+    if x.ndim != 2:
+        raise ValueError('the state holds x of shape (B, ndim), got {}'.format(tuple(x.shape)))
+    B, ndim = (int(s) for s in x.shape)
+    shapes = {'x': (B, ndim), 'fisher': (B, ndim, ndim), 'gradient': (B, ndim), 'chi2': (B,), 'lambda': (B,), 'status': (B,), 'naccepted': (B,)}
+    for name in LM_STATE:      # written in place: taken as they are or not at all
+        tensor = state[name]
+        if tuple(tensor.shape) != shapes[name] or tensor.dtype != (torch.int32 if name in ('status', 'naccepted') else torch.float64) or not tensor.is_contiguous() \
+                or tensor.device != x.device:
+            raise ValueError('state[{!r}] must be a contiguous {} tensor of shape {} on {}'.format(name, 'int32' if name in ('status', 'naccepted') else 'float64', shapes[name], x.device))
+    read = []
+    for name in LM_TRIAL:
+        tensor = dv.to_device(trial[name], x.device, cache=False)
+        if tuple(tensor.shape) != shapes[name]:
+            raise ValueError('trial[{!r}] must be of shape {}, got {}'.format(name, shapes[name], tuple(tensor.shape)))
+        read.append(tensor)
+    lo, hi = (dv.to_device(bound, x.device).reshape(-1) for bound in (lo, hi))
+    if int(lo.shape[0]) != ndim or int(hi.shape[0]) != ndim:
+        raise ValueError('lo and hi must be of shape ({:d},)'.format(ndim))
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().cp_lm_step(B, ndim, *[state[name].data_ptr() for name in LM_STATE], *[tensor.data_ptr() for tensor in read], lo.data_ptr(), hi.data_ptr(),
+                                      float(lambda_up), float(lambda_down), float(lambda_min), float(lambda_max), float(ftol), out.data_ptr(), x.device.index,
+                                      dv.stream_of(x.device)))
+    return out
+
+
+def spd_inverse(a):
+    """``(inverse, info)`` of the symmetric positive-definite matrices ``a`` (B, ndim, ndim), a device tensor, by Cholesky in one launch
+    (``cp_spd_inverse``): symmetric bit for bit; ``info`` (B,) int32 is 0, or the 1-based index of the failing pivot of a matrix whose inverse is then NaN."""
+    torch = dv.torch()
+    a = a.to(torch.float64).contiguous()
+    if a.ndim != 3 or a.shape[1] != a.shape[2]:
+        raise ValueError('matrices of shape (B, ndim, ndim), got {}'.format(tuple(a.shape)))
+    inv, info = torch.empty_like(a), torch.empty((int(a.shape[0]),), dtype=torch.int32, device=a.device)
+    _lib.check(_lib.load().cp_spd_inverse(int(a.shape[0]), int(a.shape[1]), a.data_ptr(), inv.data_ptr(), info.data_ptr(), a.device.index, dv.stream_of(a.device)))
+    return inv, info
 
 
 def _tangent(tangents, B, ndim, device):
@@ -357,11 +427,33 @@ class Emulator(object):
         values.update(fixed)
         return values, toret
 
+    def _staged(self, weights, data, B, dev):
+        """What :meth:`gauss_newton` and :meth:`least_squares` read of ``weights`` and ``data`` (the latter or None), checked, on the device ``dev``:
+        ``([(start, stop, entries, weights block, data block or None), ...], fixed)``, a maximal contiguous run of columns of :meth:`_plan` over the keys of
+        ``weights`` each, its operands broadcast to (B, stop - start)."""
+        torch = dv.torch()
+        runs, fixed = self._plan(list(weights), exact=True)
+        if data is not None:
+            unknown = [key for key in data if key not in weights]
+            if unknown:
+                raise KeyError('data for {}, which hold no weights'.format(unknown))
+            missing = [key for key in weights if key in self.varied_keys and key not in data]
+            if missing:
+                raise ValueError('no data for {}'.format(missing))
+
+        def block(operands, entries):
+            blocks = [torch.broadcast_to(dv.to_device(operands[key], dev, cache=False).to(torch.float64), (B,) + shape).reshape(B, hi - lo)
+                      for key, shape, lo, hi in entries if hi > lo]
+            return blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1)
+
+        return [(start, stop, entries, block(weights, entries), block(data, entries) if data is not None else None) for start, stop, entries in runs], fixed
+
     def gauss_newton(self, params, weights, data=None, device=False, return_value=False):
         """Fisher matrices and Gauss-Newton normal equations of a weighted least-squares fit of ``data`` to the emulated outputs, for every point of a batch,
         with ``J`` the Jacobian of :meth:`jacobian` and ``y`` the prediction: ``fisher[b, i, j] = sum w J_i J_j``,
         ``gradient[b, i] = sum w (data - y) J_i``, ``chi2[b] = sum w (data - y)^2``, the sums over the entries of the outputs that ``weights`` names.
-        A Levenberg-Marquardt step solves ``(F + lambda diag F) delta = g``: ``g = -1/2 d chi2 / d theta`` and ``F`` is the Gauss-Newton half Hessian.
+        A Levenberg-Marquardt step solves ``(F + lambda diag F) delta = g``: ``g = -1/2 d chi2 / d theta`` and ``F`` is the Gauss-Newton half Hessian
+        (:meth:`least_squares` runs such fits on the device).
         ``params`` as in :meth:`predict`.  ``weights`` (inverse variances) and ``data``: ``{varied key: array or tensor}``, each broadcastable to
         ``(B,) + shape`` of that output (``shape`` alone with scalar parameters), as :meth:`vjp` takes its cotangents.  A weight of exactly 0 drops its entry,
         whatever the data or the emulator hold there (NaN included): a mask.  The keys of ``weights`` select the outputs: a fixed key is accepted and
@@ -376,26 +468,12 @@ class Emulator(object):
         prepended, what ``predict(params, device=device, keys=list(weights))`` returns."""
         X, B, scalar = self._points(params)
         torch = dv.torch()
-        runs, fixed = self._plan(list(weights), exact=True)
-        if data is not None:
-            unknown = [key for key in data if key not in weights]
-            if unknown:
-                raise KeyError('data for {}, which hold no weights'.format(unknown))
-            missing = [key for key in weights if key in self.varied_keys and key not in data]
-            if missing:
-                raise ValueError('no data for {}'.format(missing))
         dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, *weights.values())
+        staged, fixed = self._staged(weights, data, B, dev)
         ndim = len(self.params)
-
-        def block(operands, entries):
-            blocks = [torch.broadcast_to(dv.to_device(operands[key], dev, cache=False).to(torch.float64), (B,) + shape).reshape(B, hi - lo)
-                      for key, shape, lo, hi in entries if hi > lo]
-            return blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1)
-
         totals, values = None, {}
-        for start, stop, entries in runs:
-            out = self.engine.gauss_newton(X, block(weights, entries), data=block(data, entries) if data is not None else None, columns=(start, stop),
-                                           return_value=return_value)
+        for start, stop, entries, wblock, dblock in staged:
+            out = self.engine.gauss_newton(X, wblock, data=dblock, columns=(start, stop), return_value=return_value)
             out = out if isinstance(out, tuple) else (out,)
             if return_value:
                 values.update(_split(out[0] if device else dv.to_host(out[0]), (B,), entries, start, scalar))
@@ -418,6 +496,59 @@ class Emulator(object):
         values = {key: values[key] for key in self.varied_keys if key in values}      # predict's order: the calculator's, then the fixed outputs
         values.update(fixed)
         return (values,) + (toret if isinstance(toret, tuple) else (toret,))
+
+    def least_squares(self, params, weights, data, bounds=None, niterations=20, lambda0=1e-3, lambda_up=10., lambda_down=0.1, lambda_min=1e-12, lambda_max=1e12,
+                      ftol=1e-8, device=False):
+        """B weighted least-squares fits of ``data`` to the emulated outputs at once, by Levenberg-Marquardt on the device: ``niterations`` times
+        :meth:`gauss_newton` at the trial points, then :func:`lm_step` (one launch: acceptance, the damping of each fit, the active set of the box, the
+        damped Cholesky solve, the stopping rule).  ``params``: the start, as :meth:`predict` takes it (scalars or arrays of B values); ``weights``,
+        ``data``: as :meth:`gauss_newton` takes them, with the same ``KeyError`` / ``ValueError`` rules (their broadcast blocks are staged once, not per
+        iteration).  ``bounds``: ``{name: (lo, hi)}``, by default the limits of ``Emulator.params`` -- the box the emulator was trained on --, infinite
+        where open; the start is clipped to them.  ``lambda0``: the first damping of ``(F + lambda diag F) delta = g``; the other controls are those of
+        :func:`lm_step`.  The count of iterations is fixed and a fit that is over (``status``: 1 converged by ``ftol``, 2 stalled at ``lambda_max``, 3 no
+        finite start or no positive-definite system) is left alone by the later steps: nothing is tested on the host.
+
+        Returns ``(best, chi2, info)``: ``best`` ``{parameter name: (B,)}`` the best point met, ``chi2`` (B,) there, ``info`` a dictionary of ``fisher``
+        (B, ndim, ndim) and ``gradient`` ``{name: (B,)}`` there (the bits :meth:`gauss_newton` returns at ``best``), ``covariance`` (the inverse of the
+        undamped ``fisher`` by :func:`spd_inverse`, NaN where it is not positive definite), ``status``, ``naccepted`` and ``lambda`` (B,); no leading
+        axis if every parameter is a scalar.  Host arrays by default; ``device=True``: torch tensors, and no synchronisation with the device anywhere."""
+        X, B, scalar = self._points(params)
+        torch = dv.torch()
+        dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, *weights.values())
+        if data is None:
+            raise ValueError('least_squares needs data')
+        staged, fixed = self._staged(weights, data, B, dev)
+        names = list(self.params)
+        ndim = len(names)
+        limits = dict(self.params)
+        if bounds is not None:
+            unknown = [name for name in bounds if name not in limits]
+            if unknown:
+                raise KeyError('no parameter {}'.format(unknown))
+            limits.update({name: tuple(limit) for name, limit in bounds.items()})
+        lo, hi = (dv.to_device(np.array([limits[name][side] for name in names], dtype='f8'), dev) for side in (0, 1))
+        x = torch.clamp(dv.to_device(X, dev, cache=False), min=lo, max=hi)
+        state = lm_state(x, lambda0=lambda0)
+        for iteration in range(int(niterations)):
+            totals = None
+            for start, stop, entries, wblock, dblock in staged:
+                out = self.engine.gauss_newton(x, wblock, data=dblock, columns=(start, stop))
+                totals = out if totals is None else tuple(a + b for a, b in zip(totals, out))
+            if totals is None:
+                totals = (torch.zeros((B, ndim, ndim), dtype=torch.float64, device=dev), torch.zeros((B, ndim), dtype=torch.float64, device=dev),
+                          torch.zeros((B,), dtype=torch.float64, device=dev))
+            x = lm_step(state, dict(zip(LM_TRIAL, (x,) + tuple(totals))), lo, hi, lambda_up=lambda_up, lambda_down=lambda_down, lambda_min=lambda_min,
+                        lambda_max=lambda_max, ftol=ftol)
+        covariance = spd_inverse(state['fisher'])[0]
+        out = dict(state, covariance=covariance)
+        if not device:
+            out = {name: dv.to_host(value) for name, value in out.items()}
+        if scalar:
+            out = {name: value[0] for name, value in out.items()}
+        best = {name: out['x'][..., i] for i, name in enumerate(names)}
+        info = {name: out[name] for name in ('fisher', 'covariance', 'status', 'naccepted', 'lambda')}
+        info['gradient'] = {name: out['gradient'][..., i] for i, name in enumerate(names)}
+        return best, out['chi2'], info
 
     def to_calculator(self, device=False):
         """Callable ``**params -> dict`` with the contract of ``get_calculator``'s."""

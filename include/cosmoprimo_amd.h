@@ -789,6 +789,34 @@ int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long b, int ndim
 int cp_mlp_adam(double* d_params, double* d_m, double* d_v, const double* d_grad, long long n, double lr, double b1, double b2, double eps, double c1,
                 double c2, int device, void* stream);
 
+/* ---- batched Levenberg-Marquardt fits on the normal equations of cp_*_gauss_newton (csrc/cp_lm.hip) ----
+ * B independent fits of 1 <= ndim <= 32 parameters; everything on the device, one launch per call, nothing read back, no atomics (two calls give the
+ * same bits; a NaN in fit b reaches fit b only).
+ * cp_lm_step : everything between two calls of gauss_newton.  State per fit, read and written: d_x (B, ndim), d_fisher (B, ndim, ndim), d_grad (B, ndim),
+ *   d_chi2 (B), d_lambda (B), d_status (B) and d_naccepted (B) int32.  Read only: the trial d_xt, d_fisher_t, d_grad_t, d_chi2_t of the same shapes (what
+ *   gauss_newton returned at d_xt) and the box d_lo, d_hi (ndim; +-inf allowed).  Written: d_next (B, ndim), the next trial point.  Per fit, in this order:
+ *   1. status != 0: nothing of the state changes, next = x.
+ *   2. the trial is accepted if and only if chi2_t is finite and chi2_t <= chi2 (chi2 = +inf: nothing accepted yet, the first trial is the start).
+ *   3. accepted: converged = chi2 finite and chi2 - chi2_t <= ftol chi2; lambda = max(lambda down, lmin) unless naccepted was 0; the trial is copied
+ *      into the state, naccepted += 1; status = 1 if converged.
+ *   4. rejected: chi2 = +inf (the start itself is not finite): status = 3; else lambda = lambda up, and beyond lmax: lambda = lmax, status = 2 (stalled).
+ *   5. status still 0: parameter i is held if (x_i >= hi_i and g_i > 0) or (x_i <= lo_i and g_i < 0); on the free ones (F + lambda diag F) delta = g by
+ *      Cholesky (columns in order; forward substitution ascending, back substitution descending), the diagonal as F_ii + lambda F_ii; a pivot that is not
+ *      > 0 or not finite: status = 3; else next_i = min(max(x_i + delta_i, lo_i), hi_i) on the free parameters (a NaN stays one), x_i exactly on the held.
+ *   6. a terminal status reached in this call: next = x.
+ *   Every operation is a float64 operation rounded once (no FMA contraction), divisions and square roots correctly rounded.
+ * cp_spd_inverse : d_inv[b] (ndim, ndim) = d_a[b]^-1 by the same Cholesky, the triangle computed once and mirrored (symmetric bit for bit); d_info[b]
+ *   (int32) = 0, or the 1-based index of the first failing pivot: d_inv[b] is then NaN throughout.
+ * cp_lm_layout : what the two launches use -- lanes per fit (the smallest power of two >= ndim: 64 / lanes fits per wave) and fits per workgroup.
+ * Checks, in this order, before any device call: B < 0 or ndim < 1: CP_EINVAL; ndim > 32: CP_EUNSUPPORTED; more than 2^31 - 1 workgroups of fits:
+ *   CP_EUNSUPPORTED; B = 0: CP_OK; a null pointer: CP_EINVAL; up > 1, 0 < down <= 1, 0 < lmin <= lmax, ftol >= 0, none a NaN: else CP_EINVAL. */
+enum cp_lm_status { CP_LM_RUNNING = 0, CP_LM_CONVERGED = 1, CP_LM_STALLED = 2, CP_LM_FAILED = 3 };
+int cp_lm_layout(int ndim, int* lanes_per_fit, int* fits_per_workgroup);
+int cp_lm_step(long long B, int ndim, double* d_x, double* d_fisher, double* d_grad, double* d_chi2, double* d_lambda, int* d_status, int* d_naccepted,
+               const double* d_xt, const double* d_fisher_t, const double* d_grad_t, const double* d_chi2_t, const double* d_lo, const double* d_hi, double up,
+               double down, double lmin, double lmax, double ftol, double* d_next, int device, void* stream);
+int cp_spd_inverse(long long B, int ndim, const double* d_a, double* d_inv, int* d_info, int device, void* stream);
+
 /* ---- row screening utility (cp_fftlog_execute and cp_dst_execute screen their rows themselves; this pass is for callers that want
  *      the flags, e.g. to count or report the rows a batch loses) ----
  * d_x : (nrows, n) device.  d_ok[row] = 1 if every entry of the row is finite (and > 0 if require_positive: the fused log map of
