@@ -721,8 +721,9 @@ extern "C" int cp_growth_ode_tables(long long ncosmo, const cp_param* params, in
     st = cpcosmo::ncdm_knots(nsp, device, "cp_growth_ode_tables", &A.ncdm_knots);
     if (st != CP_OK) return st;
     A.tab = d_tab;
-    hipLaunchKernelGGL(growth_ode_kernel, dim3((unsigned)((ncosmo + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), A);
-    return cp::launch_status("cp_growth_ode_tables");
+    cp::Launches on("cp_growth_ode_tables", stream);
+    on.run<growth_ode_kernel>((unsigned)((ncosmo + 63) / 64), 64, 0, A);
+    return on.status();
 }
 
 extern "C" int cp_ncdm_knots(double* zc_out, int n) {
@@ -740,7 +741,6 @@ extern "C" int cp_ncdm_tables(long long ncosmo, int nspecies, cp_param h, cp_par
     if (!m_ncdm || !T_ncdm_over_cmb || !nodes || !weights || !d_tab) return cp::fail(CP_EINVAL, "cp_ncdm_tables: null pointer");
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_ncdm_tables: cannot select device %d", device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
     NcdmArgs A;
     A.ncosmo = ncosmo;
     A.nsp = nspecies;
@@ -756,9 +756,10 @@ extern "C" int cp_ncdm_tables(long long ncosmo, int nspecies, cp_param h, cp_par
     for (int q = 0; q < nq; ++q) R.v[q] = nodes[q], R.v[nq + q] = weights[q];
     for (int q = 2 * nq; q < 2 * NCDM_MAX_NQ; ++q) R.v[q] = 0.;
     const long long n1 = ncosmo * nspecies * CP_NCDM_NKNOTS, n2 = ncosmo * nspecies * 2;
-    hipLaunchKernelGGL(ncdm_momenta_kernel, dim3((unsigned)((n1 + 127) / 128)), dim3(128), 0, st, A, R);
-    hipLaunchKernelGGL(ncdm_spline_kernel, dim3((unsigned)((n2 + 63) / 64)), dim3(64), 0, st, A);
-    return cp::launch_status("cp_ncdm_tables");
+    cp::Launches on("cp_ncdm_tables", stream);
+    on.run<ncdm_momenta_kernel>((unsigned)((n1 + 127) / 128), 128, 0, A, R);
+    on.run<ncdm_spline_kernel>((unsigned)((n2 + 63) / 64), 64, 0, A);
+    return on.status();
 }
 
 extern "C" int cp_background_knots(double* zc_out, int n) {
@@ -801,9 +802,9 @@ extern "C" int cp_distance_from_radial(const double* d_chi, const double* d_z, l
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_distance_from_radial: cannot select device %d", device);
     const long long blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(distance_from_radial_kernel, dim3((unsigned)(blocks < 256 * 16 ? blocks : 256 * 16)), dim3(256), 0, static_cast<hipStream_t>(stream), d_chi, d_z,
-                       n, K, kind, d_out);
-    return cp::launch_status("cp_distance_from_radial");
+    cp::Launches on("cp_distance_from_radial", stream);
+    on.run<distance_from_radial_kernel>((unsigned)(blocks < 256 * 16 ? blocks : 256 * 16), 256, 0, d_chi, d_z, n, K, kind, d_out);
+    return on.status();
 }
 
 extern "C" int cp_background_distance(long long ncosmo, long long nz, const cp_param* params, int second_is_omega_m, const double* d_z,
@@ -848,12 +849,13 @@ extern "C" int cp_background_eval(long long ncosmo, long long nz, const cp_param
     const long long nsamp = ncosmo * nz;
     const int block = 256;
     const long long grid = (nsamp + block - 1) / block;
-    if (kind == CP_BG_RS || kind == CP_BG_RS_COSMOMC) hipLaunchKernelGGL(rs_kernel, dim3((unsigned)nsamp), dim3(64), 0, static_cast<hipStream_t>(stream), A);
-    else if (is_time && A.nsp) hipLaunchKernelGGL((bg_kernel<NK_TIME, true, true>), dim3((unsigned)grid), dim3(block), 0, static_cast<hipStream_t>(stream), A);
-    else if (is_time) hipLaunchKernelGGL((bg_kernel<NK_TIME, true, false>), dim3((unsigned)grid), dim3(block), 0, static_cast<hipStream_t>(stream), A);
-    else if (A.nsp) hipLaunchKernelGGL((bg_kernel<NK_DIST, false, true>), dim3((unsigned)grid), dim3(block), 0, static_cast<hipStream_t>(stream), A);
-    else hipLaunchKernelGGL((bg_kernel<NK_DIST, false, false>), dim3((unsigned)grid), dim3(block), 0, static_cast<hipStream_t>(stream), A);
-    return cp::launch_status("cp_background_distance");
+    cp::Launches on("cp_background_distance", stream);
+    if (kind == CP_BG_RS || kind == CP_BG_RS_COSMOMC) on.run<rs_kernel>((unsigned)nsamp, 64, 0, A);
+    else if (is_time && A.nsp) on.run<bg_kernel<NK_TIME, true, true>>((unsigned)grid, block, 0, A);
+    else if (is_time) on.run<bg_kernel<NK_TIME, true, false>>((unsigned)grid, block, 0, A);
+    else if (A.nsp) on.run<bg_kernel<NK_DIST, false, true>>((unsigned)grid, block, 0, A);
+    else on.run<bg_kernel<NK_DIST, false, false>>((unsigned)grid, block, 0, A);
+    return on.status();
 }
 
 // ---- derived parameters of a batch of cosmologies (BaseCosmoParams.__getitem__ -> _get_derived, cosmology.py:331-415), one launch -------------------
@@ -916,6 +918,7 @@ extern "C" int cp_derived_parameters(long long ncosmo, const cp_param* params, d
     A.ncosmo = ncosmo;
     cpcosmo::copy_params(A.p, params, CP_BG_NPARAMS);
     A.out = d_out;
-    hipLaunchKernelGGL(derived_parameters_kernel, dim3((unsigned)((ncosmo + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), A);
-    return cp::launch_status("cp_derived_parameters");
+    cp::Launches on("cp_derived_parameters", stream);
+    on.run<derived_parameters_kernel>((unsigned)((ncosmo + 255) / 256), 256, 0, A);
+    return on.status();
 }

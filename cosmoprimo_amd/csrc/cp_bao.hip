@@ -266,9 +266,9 @@ extern "C" int cp_wallish_finish(const double* d_pk, const double* d_a, const do
     if (!d_pk || !d_a || !d_tophat || !d_out) return cp::fail(CP_EINVAL, "cp_wallish_finish: null pointer");
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_wallish_finish: cannot select device %d", device);
-    hipLaunchKernelGGL(wallish_finish_kernel, dim3(grid_for(nrows * n)), dim3(256), 0, static_cast<hipStream_t>(stream), d_pk, d_a, d_b, d_tophat, d_out,
-                       nrows * n, n);
-    return cp::launch_status("cp_wallish_finish");
+    cp::Launches on("cp_wallish_finish", stream);
+    on.run<wallish_finish_kernel>(grid_for(nrows * n), 256, 0, d_pk, d_a, d_b, d_tophat, d_out, nrows * n, n);
+    return on.status();
 }
 
 extern "C" int cp_brieden_ratio(const double* d_rows, const double* d_now, const double* d_g0, const double* d_correction, const double* d_ratio_fid,
@@ -278,9 +278,9 @@ extern "C" int cp_brieden_ratio(const double* d_rows, const double* d_now, const
     if (!d_rows || !d_now || !d_g0 || !d_correction || !d_ratio_fid || !d_pknow || !d_ratio) return cp::fail(CP_EINVAL, "cp_brieden_ratio: null pointer");
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_brieden_ratio: cannot select device %d", device);
-    hipLaunchKernelGGL(brieden_ratio_kernel, dim3(grid_for(nb * n)), dim3(256), 0, static_cast<hipStream_t>(stream), d_rows, d_now, d_g0, d_correction,
-                       d_ratio_fid, d_pknow, d_ratio, nb, n);
-    return cp::launch_status("cp_brieden_ratio");
+    cp::Launches on("cp_brieden_ratio", stream);
+    on.run<brieden_ratio_kernel>(grid_for(nb * n), 256, 0, d_rows, d_now, d_g0, d_correction, d_ratio_fid, d_pknow, d_ratio, nb, n);
+    return on.status();
 }
 
 extern "C" int cp_brieden_knots(const double* d_envelope, const double* d_pknow, const double* d_ratio_now_fid, const double* d_k_fid,
@@ -291,9 +291,9 @@ extern "C" int cp_brieden_knots(const double* d_envelope, const double* d_pknow,
     if (!d_envelope || !d_pknow || !d_ratio_now_fid || !d_k_fid || !d_rescale || !d_xk || !d_yk) return cp::fail(CP_EINVAL, "cp_brieden_knots: null pointer");
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_brieden_knots: cannot select device %d", device);
-    hipLaunchKernelGGL(brieden_knots_kernel, dim3(grid_tiles(nb, n)), dim3(256), 0, static_cast<hipStream_t>(stream), d_envelope, d_pknow,
-                       d_ratio_now_fid, d_k_fid, d_rescale, extrap_kmin, extrap_kmax, d_xk, d_yk, nb, n);
-    return cp::launch_status("cp_brieden_knots");
+    cp::Launches on("cp_brieden_knots", stream);
+    on.run<brieden_knots_kernel>(grid_tiles(nb, n), 256, 0, d_envelope, d_pknow, d_ratio_now_fid, d_k_fid, d_rescale, extrap_kmin, extrap_kmax, d_xk, d_yk, nb, n);
+    return on.status();
 }
 
 // ---- brieden2022: the re-sampling of the smooth spectrum (bao_filter.py:500-509) as ONE kernel, a wave per cosmology --------------------------
@@ -618,13 +618,10 @@ __global__ __launch_bounds__(OPLDS ? 768 : 256, OPLDS ? 1 : CP_RS_WAVES) void br
 namespace {
 
 template <int S, bool PEAKS, bool OPLDS>
-int launch_resample_as(const ResampleArgs& A, size_t lds, int ncu, void* stream) {
+void launch_resample_as(cp::Launches& on, const ResampleArgs& A, size_t lds, int ncu) {
     constexpr int W = OPLDS ? 12 : 4;
-    if (lds > 64 * 1024 && cp::allow_full_lds<brieden_resample_kernel<S, PEAKS, OPLDS>>() != hipSuccess) return CP_EDEVICE;
     const long long blocks = (A.nb + W - 1) / W, resident = (long long)ncu * (OPLDS ? 1 : CP_RS_WAVES);
-    hipLaunchKernelGGL((brieden_resample_kernel<S, PEAKS, OPLDS>), dim3((unsigned)(blocks < resident ? blocks : resident)), dim3(64 * W), lds,
-                       static_cast<hipStream_t>(stream), A);
-    return CP_OK;
+    on.run<brieden_resample_kernel<S, PEAKS, OPLDS>>((unsigned)(blocks < resident ? blocks : resident), 64 * W, lds, A);
 }
 
 template <bool PEAKS>
@@ -636,11 +633,12 @@ int launch_resample(ResampleArgs& A, const char* who, int device, void* stream) 
     const size_t shared = 3 * (size_t)n * sizeof(double), per_wave = 2 * ((size_t)n + 8) * sizeof(double), op = PEAKS ? (size_t)A.np * n * sizeof(double) : 0;
     const bool oplds = PEAKS && 12 * per_wave + shared + op + 2048 <= 160 * 1024;
     const size_t lds = oplds ? 12 * per_wave + shared + op : 4 * per_wave + shared;
-    int st = CP_OK;
+    cp::Launches on(who, stream);
     auto go = [&](auto sc) {
         constexpr int S = decltype(sc)::value;
-        if constexpr (PEAKS) st = oplds ? launch_resample_as<S, true, true>(A, lds, ncu, stream) : launch_resample_as<S, true, false>(A, lds, ncu, stream);
-        else st = launch_resample_as<S, false, false>(A, lds, ncu, stream);
+        if constexpr (!PEAKS) launch_resample_as<S, false, false>(on, A, lds, ncu);
+        else if (oplds) launch_resample_as<S, true, true>(on, A, lds, ncu);
+        else launch_resample_as<S, true, false>(on, A, lds, ncu);
     };
     switch ((n + 63) / 64) {      // samples per lane
         case 3: go(std::integral_constant<int, 3>{}); break;
@@ -650,8 +648,7 @@ int launch_resample(ResampleArgs& A, const char* who, int device, void* stream) 
         case 7: go(std::integral_constant<int, 7>{}); break;
         default: go(std::integral_constant<int, 8>{}); break;
     }
-    if (st != CP_OK) return cp::fail(st, "%s: cannot configure the kernel's LDS", who);
-    return cp::launch_status(who);
+    return on.status();
 }
 
 bool resample_sizes_ok(int n) { return (n + 63) / 64 >= RS_SMIN && (n + 63) / 64 <= RS_SMAX; }
@@ -700,9 +697,9 @@ extern "C" int cp_brieden_finish(const double* d_pk, const double* d_resampled, 
     if (!d_pk || !d_resampled || !d_out) return cp::fail(CP_EINVAL, "cp_brieden_finish: null pointer");
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_brieden_finish: cannot select device %d", device);
-    hipLaunchKernelGGL(brieden_finish_kernel, dim3(grid_tiles(nb, n > 0 ? n : 1)), dim3(256), 0, static_cast<hipStream_t>(stream), d_pk, d_resampled, d_out, nb, nk,
-                       first, n);
-    return cp::launch_status("cp_brieden_finish");
+    cp::Launches on("cp_brieden_finish", stream);
+    on.run<brieden_finish_kernel>(grid_tiles(nb, n > 0 ? n : 1), 256, 0, d_pk, d_resampled, d_out, nb, nk, first, n);
+    return on.status();
 }
 
 extern "C" int cp_wallish_dd_box(const double* d_y, long long nrows, int n, int margin_first, int margin_second, int offset_first, int offset_second,
@@ -719,17 +716,10 @@ extern "C" int cp_wallish_dd_box(const double* d_y, long long nrows, int n, int 
     const size_t lds = ((size_t)4 * (n + 64) + 2 * DD_NTAB) * sizeof(double);
     const long long resident = (long long)ncu * (long long)((160 * 1024) / lds < 1 ? 1 : (160 * 1024) / lds);
     const unsigned grid = (unsigned)((nrows + 3) / 4 < resident ? (nrows + 3) / 4 : resident);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-#define CP_DD_LAUNCH(S_)                                                                                                                             \
-    do {                                                                                                                                             \
-        (void)cp::allow_full_lds<&wallish_dd_box_kernel<S_>>();                                                                                      \
-        hipLaunchKernelGGL(wallish_dd_box_kernel<S_>, dim3(grid), dim3(256), lds, hs, d_y, nrows, margin_first, margin_second, offset_first,          \
-                           offset_second, d_box, d_dd, d_gap);                                                                                       \
-    } while (0)
-    if (n == 1024) CP_DD_LAUNCH(16);
-    else CP_DD_LAUNCH(32);
-#undef CP_DD_LAUNCH
-    return cp::launch_status("cp_wallish_dd_box");
+    cp::Launches on("cp_wallish_dd_box", stream);
+    if (n == 1024) on.run<wallish_dd_box_kernel<16>>(grid, 256, lds, d_y, nrows, margin_first, margin_second, offset_first, offset_second, d_box, d_dd, d_gap);
+    else on.run<wallish_dd_box_kernel<32>>(grid, 256, lds, d_y, nrows, margin_first, margin_second, offset_first, offset_second, d_box, d_dd, d_gap);
+    return on.status();
 }
 
 // ---- wallish2018: the clamped spline through the spliced knots, evaluated on the filter's wavenumbers, and the wiggle damping -- one kernel ----
@@ -1153,19 +1143,19 @@ extern "C" int cp_splice_apply(const cp_splice_plan* p, const double* d_src0, in
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_splice_apply: cannot select device %d", p->device);
     const int ncu = cp::cu_count(p->device);
     const long long blocks = (nrows + 3) / 4;
+    cp::Launches on("cp_splice_apply", stream);
     if (p->use_uniform) {
         cpsu::Args U;
         U.T = p->U;
         U.src0 = d_src0; U.src1 = d_src1 ? d_src1 : d_src0; U.n0 = n0; U.n1 = d_src1 ? n1 : n0; U.nrows = nrows; U.tophat = d_tophat; U.out = d_out;
-        return cp::launch_status("cp_splice_apply",
-                                 cpsu::launch(U, (unsigned)(blocks < ncu ? blocks : ncu), p->uniform_lds_bytes, static_cast<hipStream_t>(stream)));
+        if (!cpsu::launch(on, U, (unsigned)(blocks < ncu ? blocks : ncu), p->uniform_lds_bytes)) return cp::launch_status("cp_splice_apply", hipErrorInvalidValue);
+        return on.status();
     }
     SpliceArgs A;
     A.T = p->T;
     A.src0 = d_src0; A.src1 = d_src1 ? d_src1 : d_src0; A.n0 = n0; A.n1 = d_src1 ? n1 : n0; A.nrows = nrows; A.tophat = d_tophat; A.out = d_out;
-    (void)cp::allow_full_lds<&splice_kernel>();
     const long long per_cu = p->lds_bytes ? (160 * 1024) / (long long)p->lds_bytes : 1;
     const long long resident = (long long)ncu * (per_cu < 1 ? 1 : per_cu);
-    hipLaunchKernelGGL(splice_kernel, dim3((unsigned)(blocks < resident ? blocks : resident)), dim3(256), p->lds_bytes, static_cast<hipStream_t>(stream), A);
-    return cp::launch_status("cp_splice_apply");
+    on.run<splice_kernel>((unsigned)(blocks < resident ? blocks : resident), 256, p->lds_bytes, A);
+    return on.status();
 }

@@ -231,8 +231,8 @@ const double* ncdm_knots_device(int device);
 // ---- the host side that the entry points taking a batch of cosmologies share -------------------------------------------------------------------------
 // An entry point of that family runs its checks in this order -- sizes and codes, the engine (engine_known), the empty batch, null pointers, the
 // massive-neutrino argument (ncdm_species): all without a device --, then opens ONE cp::DeviceScope, fetches the neutrino knots if its kernel reads them
-// (ncdm_knots), fills the cosmology block of its kernel's arguments (fill_cosmology), launches -- the coefficients first (cp_power_coefficients,
-// cp_internal.h) where its kernel reads them -- and returns ONE cp::launch_status under its public name.
+// (ncdm_knots), fills the cosmology block of its kernel's arguments (fill_cosmology), launches through ONE cp::Launches under its public name -- the coefficients first
+// (cp_power_coefficients, cp_internal.h) where its kernel reads them -- and returns its status.
 
 inline bool engine_known(int engine) { return engine >= CP_ENGINE_EH && engine <= CP_ENGINE_BBKS; }
 

@@ -598,14 +598,10 @@ __global__ __launch_bounds__(N / P, 2) void dst_generate_kernel(const GenArgs G)
 #include CP_TAIL_HEADER      // wallish_tail_kernel: everything of the filter behind its forward transform (cp_wallish_tail below)
 
 template <int N>
-void launch(bool inverse, const Args& A, int grid, hipStream_t stream) {
+void launch(cp::Launches& on, bool inverse, const Args& A, int grid) {
     constexpr int P = 16, T = N / P, lds = WorkgroupFft<N, P>::lds_bytes();
-    if (lds > 64 * 1024) {  // opt in to more than 64 KiB of dynamic LDS (once per process would do; the call is cheap)
-        (void)cp::allow_full_lds<&dst_kernel<N, P, true>>();
-        (void)cp::allow_full_lds<&dst_kernel<N, P, false>>();
-    }
-    if (inverse) hipLaunchKernelGGL((dst_kernel<N, P, true>), dim3(grid), dim3(T), lds, stream, A);
-    else hipLaunchKernelGGL((dst_kernel<N, P, false>), dim3(grid), dim3(T), lds, stream, A);
+    if (inverse) on.run<dst_kernel<N, P, true>>(grid, T, lds, A);
+    else on.run<dst_kernel<N, P, false>>(grid, T, lds, A);
 }
 
 }  // namespace
@@ -639,8 +635,9 @@ extern "C" int cp_dst_plan_create(cp_dst_plan** out, int n, const double* kx, in
     if (e == hipSuccess && kx) e = p->d_ln_kx.alloc(8 * (size_t)n);
     if (e != hipSuccess) return cp::place_status("cp_dst_plan_create", device, e);
     if (kx) {      // log of the abscissa with the kernels' own logarithm (default stream, then waited for: plan creation is synchronous)
-        hipLaunchKernelGGL(dst_log_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, p->d_kx.get(), p->d_ln_kx.get(), n);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return cp::fail(CP_EDEVICE, "cp_dst_plan_create: cannot tabulate log k");
+        cp::Launches on("cp_dst_plan_create", nullptr);
+        on.run<dst_log_kernel>((n + 255) / 256, 256, 0, p->d_kx.get(), p->d_ln_kx.get(), n);
+        if (on.status() != CP_OK || hipDeviceSynchronize() != hipSuccess) return cp::fail(CP_EDEVICE, "cp_dst_plan_create: cannot tabulate log k");
     }
     *out = p.release();
     return CP_OK;
@@ -660,24 +657,17 @@ extern "C" int cp_dst_execute(const cp_dst_plan* p, const double* d_in, double* 
     A.in = d_in; A.out = d_out; A.nrows = nrows; A.tw = p->d_tw; A.rot = p->d_rot; A.kx = p->d_kx; A.ikx = p->d_ln_kx ? p->d_ln_kx + 3 * (size_t)p->n : nullptr; A.fused = fused; A.split = (flags & CP_DST_SPLIT) != 0;
     const long long npairs = (nrows + 1) / 2;
     const int grid = (int)(npairs < 512 ? npairs : 512);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (p->n == 256) launch<256>(inverse != 0, A, grid, s);
-    else if (p->n == 1024) launch<1024>(inverse != 0, A, grid, s);
-    else launch<4096>(inverse != 0, A, grid, s);
-    return cp::launch_status("cp_dst_execute");
+    cp::Launches on("cp_dst_execute", stream);
+    if (p->n == 256) launch<256>(on, inverse != 0, A, grid);
+    else if (p->n == 1024) launch<1024>(on, inverse != 0, A, grid);
+    else launch<4096>(on, inverse != 0, A, grid);
+    return on.status();
 }
 
 namespace {
 
 // dst_generate_kernel, wallish_tail_kernel, wallish_full_kernel: the transform's LDS and the 2 x DD_NTAB elimination factors of the box step behind it
 constexpr int WALLISH_LDS = WorkgroupFft<4096, 16>::lds_bytes(2 * cpdd::DD_NTAB * (int)sizeof(double));
-
-template <int ENGINE>
-void launch_generate(const GenArgs& G, int grid, hipStream_t stream) {
-    constexpr int N = 4096, P = 16, T = N / P;
-    (void)cp::allow_full_lds<&dst_generate_kernel<N, P, ENGINE>>();
-    hipLaunchKernelGGL((dst_generate_kernel<N, P, ENGINE>), dim3(grid), dim3(T), WALLISH_LDS, stream, G);
-}
 
 }  // namespace
 
@@ -746,13 +736,14 @@ int dst_forward_analytic(const cp_dst_plan* p, int engine, long long ncosmo, con
     st = cpcosmo::ncdm_knots(nsp, p->device, who, &knots);
     if (st != CP_OK) return st;
     char* coef = cp::coef_workspace(d_work, ncosmo).coef;
-    cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, knots, pk_params, coef, stream);
+    cp::Launches on(who, stream);
+    cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, knots, pk_params, coef, on);
     GenArgs G{};
     fill_generate(G, p, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, pk_params, d_out, (flags & CP_DST_SPLIT) != 0, coef);
     G.box = d_box; G.margin_first = margin_first; G.margin_second = margin_second; G.off0 = offset_first; G.off1 = offset_second;
     const int grid = wallish_grid(ncosmo, p->device);
-    cpcosmo::dispatch_engine(engine, [&](auto e) { launch_generate<decltype(e)::value>(G, grid, static_cast<hipStream_t>(stream)); });
-    return cp::launch_status(who);
+    cpcosmo::dispatch_engine(engine, [&](auto e) { on.run<dst_generate_kernel<4096, 16, decltype(e)::value>>(grid, 4096 / 16, WALLISH_LDS, G); });
+    return on.status();
 }
 
 }  // namespace
@@ -786,20 +777,12 @@ extern "C" int cp_wallish_tail(const cp_dst_plan* p, const cp_splice_plan* splic
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_wallish_tail: cannot select device %d", p->device);
     TailArgs G{};
     fill_tail(G, p, U, nrows, d_coef, d_pk, margin_first, margin_second, offset_first, offset_second, d_tophat, d_box, d_out);
-    (void)cp::allow_full_lds<&wallish_tail_kernel<49>>();
-    hipLaunchKernelGGL(wallish_tail_kernel<49>, dim3(wallish_grid(nrows, p->device)), dim3(256), WALLISH_LDS, static_cast<hipStream_t>(stream), G);
-    return cp::launch_status("cp_wallish_tail");
+    cp::Launches on("cp_wallish_tail", stream);
+    on.run<wallish_tail_kernel<49>>(wallish_grid(nrows, p->device), 256, WALLISH_LDS, G);
+    return on.status();
 }
 
 // ---- cp_wallish_full: wallish2018 of a batch of analytic cosmologies, one kernel (wallish_full_kernel, cp_wallish_tail.h) ----
-namespace {
-template <int ENGINE>
-void launch_full(const FullArgs& F, int grid, int lds, hipStream_t stream) {
-    (void)cp::allow_full_lds<&wallish_full_kernel<49, ENGINE>>();
-    hipLaunchKernelGGL((wallish_full_kernel<49, ENGINE>), dim3(grid), dim3(256), lds, stream, F);
-}
-}  // namespace
-
 extern "C" int cp_wallish_full(const cp_dst_plan* p, const cp_splice_plan* splice, int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m,
                                const cp_ncdm* ncdm, const cp_param* pk_params, const double* d_pk, int npk, int margin_first, int margin_second, int offset_first,
                                int offset_second, const double* d_tophat, int* d_box, double* d_coef, double* d_out, void* d_work, void* stream) {
@@ -822,11 +805,12 @@ extern "C" int cp_wallish_full(const cp_dst_plan* p, const cp_splice_plan* splic
     st = cpcosmo::ncdm_knots(nsp, p->device, who, &knots);
     if (st != CP_OK) return st;
     char* coef = cp::coef_workspace(d_work, ncosmo).coef;
-    cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, knots, pk_params, coef, stream);
+    cp::Launches on(who, stream);
+    cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, knots, pk_params, coef, on);
     FullArgs F{};
     fill_tail(F.tail, p, U, ncosmo, d_coef, d_pk, margin_first, margin_second, offset_first, offset_second, d_tophat, d_box, d_out);
     fill_generate(F.gen, p, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, pk_params, nullptr, true, coef);
     const int grid = wallish_grid(ncosmo, p->device);
-    cpcosmo::dispatch_engine(engine, [&](auto e) { launch_full<decltype(e)::value>(F, grid, WALLISH_LDS, static_cast<hipStream_t>(stream)); });
-    return cp::launch_status(who);
+    cpcosmo::dispatch_engine(engine, [&](auto e) { on.run<wallish_full_kernel<49, decltype(e)::value>>(grid, 256, WALLISH_LDS, F); });
+    return on.status();
 }

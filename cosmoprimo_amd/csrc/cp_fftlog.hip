@@ -105,7 +105,7 @@ extern "C" int cp_fftlog_plan_create(cp_fftlog_plan** out, int n, int npad, int 
         if (!l.func[v]) continue;
         const int lds_v = l.lds_bytes + l.lds_extra[v];
         int nblk = 0;
-        if (lds_v > 64 * 1024) e = hipFuncSetAttribute(l.func[v], hipFuncAttributeMaxDynamicSharedMemorySize, lds_v);
+        if (lds_v > 64 * 1024) e = cp::allow_full_lds(l.func[v]);      // (the occupancy query below needs the limit raised; a launch finds it so: cp::Launches)
         if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, l.func[v], l.block, lds_v);
         if (e != hipSuccess) break;
         if (nblk < 1) return cp::fail(CP_EDEVICE, "cp_fftlog_plan_create: kernel variant %d for npad=%d does not fit on a CU", v, npad);
@@ -189,8 +189,9 @@ static int execute_impl(const cp_fftlog_plan* p, const double* d_in, double* d_o
     // the padded length must stay below 2^31 elements (Np <= 8192: nker < 262144)
     if ((long long)p->nker * p->npad >= (1LL << 31) || 2LL * grid * p->npad >= (1LL << 31))
         return cp::fail(CP_EUNSUPPORTED, "cp_fftlog_execute: nker = %d kernels of padded size %d exceed the row-walk range", p->nker, p->npad);
-    p->l.launch(variant, A, grid, static_cast<hipStream_t>(stream));
-    return cp::launch_status("cp_fftlog_execute");
+    cp::Launches on("cp_fftlog_execute", stream);
+    p->l.launch(on, variant, A, grid);
+    return on.status();
 }
 
 extern "C" int cp_fftlog_execute(const cp_fftlog_plan* p, const double* d_in, double* d_out, long long nbatch, int extrap_left,

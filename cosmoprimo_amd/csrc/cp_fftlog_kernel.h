@@ -8,13 +8,14 @@
 #include "cp_fftlog_body.h"
 #include "cp_fftlog_dispatch.h"
 #include "cp_fftlog_tables.h"
+#include "cp_internal.h"
 
 namespace cpfft {
 
 struct Launcher {
     // [variant]: kernel entry (nullptr when the variant does not exist for this size)
     const void* func[VAR_COUNT];
-    void (*launch)(int variant, const FftlogArgs&, int grid, hipStream_t stream);
+    void (*launch)(cp::Launches& on, int variant, const FftlogArgs&, int grid);
     int np, p, block, lds_bytes;
     int lds_extra[VAR_COUNT];  // dynamic LDS a variant asks for beyond lds_bytes (the ticket word of a variant that balances its CU)
     void (*build_tw)(std::vector<cplx>&);
@@ -286,28 +287,28 @@ constexpr bool has_half() {
 }
 
 template <int NP, int P>
-void launch_impl(int variant, const FftlogArgs& A, int grid, hipStream_t stream) {
+void launch_impl(cp::Launches& on, int variant, const FftlogArgs& A, int grid) {
     constexpr int T = Plan<NP, P>::T;
     constexpr int lds = Fftlog<NP, P>::LDS_BYTES;
     if constexpr (has_half<NP, P>()) {
         if (variant == VAR_HALF_ZERO) {
             constexpr int extra = balances_cu<NP, P, IN_HALF_ZERO, OUT_HALF>() ? CP_BALANCE_LDS : 0;
-            hipLaunchKernelGGL((fftlog_kernel<NP, P, IN_HALF_ZERO, OUT_HALF>), dim3(grid), dim3(T), lds + extra, stream, A);
+            on.run<fftlog_kernel<NP, P, IN_HALF_ZERO, OUT_HALF>>(grid, T, lds + extra, A);
             return;
         }
         if (variant == VAR_HALF) {
-            hipLaunchKernelGGL((fftlog_kernel<NP, P, IN_HALF, OUT_HALF>), dim3(grid), dim3(T), lds, stream, A);
+            on.run<fftlog_kernel<NP, P, IN_HALF, OUT_HALF>>(grid, T, lds, A);
             return;
         }
         if (variant == VAR_HALF_ZERO_WINDOW) {
-            hipLaunchKernelGGL((fftlog_kernel<NP, P, IN_HALF_ZERO, OUT_HALF_WINDOW>), dim3(grid), dim3(T), lds, stream, A);
+            on.run<fftlog_kernel<NP, P, IN_HALF_ZERO, OUT_HALF_WINDOW>>(grid, T, lds, A);
             return;
         }
     }
     if (variant == VAR_LOG)
-        hipLaunchKernelGGL((fftlog_kernel<NP, P, IN_LOG, OUT_GENERIC>), dim3(grid), dim3(T), lds, stream, A);
+        on.run<fftlog_kernel<NP, P, IN_LOG, OUT_GENERIC>>(grid, T, lds, A);
     else
-        hipLaunchKernelGGL((fftlog_kernel<NP, P, IN_GENERIC, OUT_GENERIC>), dim3(grid), dim3(T), lds, stream, A);
+        on.run<fftlog_kernel<NP, P, IN_GENERIC, OUT_GENERIC>>(grid, T, lds, A);
 }
 
 template <int NP, int P>

@@ -316,12 +316,12 @@ __global__ __launch_bounds__(256) void column_direct_kernel(const ColumnArgs A) 
 }
 
 template <bool FIRST>
-void launch_columns(const ColumnArgs& C, long long np, hipStream_t st) {
+void launch_columns(cp::Launches& on, const ColumnArgs& C, long long np) {
     const unsigned direct = (unsigned)(np * (ROW / 256));
-    if (C.n1 == 4) hipLaunchKernelGGL((column_direct_kernel<FIRST, 4>), dim3(direct), dim3(256), 0, st, C);
-    else if (C.n1 == 8) hipLaunchKernelGGL((column_direct_kernel<FIRST, 8>), dim3(direct), dim3(256), 0, st, C);
-    else if (C.n1 == 16) hipLaunchKernelGGL((column_direct_kernel<FIRST, 16>), dim3(direct), dim3(256), 0, st, C);
-    else hipLaunchKernelGGL(column_kernel<FIRST>, dim3((unsigned)(np * (ROW >> C.log2c))), dim3(256), 0, st, C);
+    if (C.n1 == 4) on.run<column_direct_kernel<FIRST, 4>>(direct, 256, 0, C);
+    else if (C.n1 == 8) on.run<column_direct_kernel<FIRST, 8>>(direct, 256, 0, C);
+    else if (C.n1 == 16) on.run<column_direct_kernel<FIRST, 16>>(direct, 256, 0, C);
+    else on.run<column_kernel<FIRST>>((unsigned)(np * (ROW >> C.log2c)), 256, 0, C);
 }
 
 struct RowArgs {
@@ -510,27 +510,28 @@ int cp_fftlog_large_execute(cp_fftlog_large* p, const double* d_in, double* d_ou
     if (p->has_done && hipStreamWaitEvent(st, p->done, 0) != hipSuccess)   // the previous execute (any stream) is done with the scratch
         return cp::fail(CP_EDEVICE, "cp_fftlog_execute: hipStreamWaitEvent failed");
     const int segs = p->npad / 4096;           // 16 independent samples per thread, one atomic per workgroup
+    cp::Launches on("cp_fftlog_execute", st);
     for (long long p0 = 0; p0 < npairs; p0 += p->chunk) {
         const long long np = npairs - p0 < p->chunk ? npairs - p0 : p->chunk;
         if (hipMemsetAsync(p->d_mag, 0, (size_t)np * 2 * sizeof(unsigned), st) != hipSuccess)
             return cp::fail(CP_EDEVICE, "cp_fftlog_execute: hipMemsetAsync failed");
         ScreenArgs SA;
         SA.in = d_in; SA.pre = p->d_pre; SA.mag = p->d_mag; SA.pair0 = p0; SA.nbatch = nbatch; SA.S = S; SA.segs = segs;
-        hipLaunchKernelGGL(screen_kernel, dim3((unsigned)(2 * np * segs)), dim3(256), 0, st, SA);
+        on.run<screen_kernel>((unsigned)(2 * np * segs), 256, 0, SA);
         ColumnArgs C;
         C.in = d_in; C.out = d_out; C.pre = p->d_pre; C.post = p->d_post; C.work = p->d_work; C.mag = p->d_mag; C.tw = p->d_tw;
         C.pair0 = p0; C.nbatch = nbatch; C.S = S; C.n1 = p->n1; C.log2c = p->log2c; C.rd = p->rd;
         C.out_off = keep_padding ? 0 : out_left;
         C.n_out = keep_padding ? p->npad : p->n;
-        launch_columns<true>(C, np, st);
+        launch_columns<true>(on, C, np);
         RowArgs R;
         R.work = p->d_work; R.u = p->d_u; R.tw = p->d_tw; R.tw_a = p->d_tw + ROW; R.tw_b = p->d_tw + ROW + 256 * (size_t)p->n1;
         R.tw0 = R.tw_b + 16 * (size_t)p->n1;
         R.pair0 = p0; R.nrows = np * p->n1; R.n1 = p->n1; R.nker = p->nker;
-        hipLaunchKernelGGL(row_kernel, dim3((unsigned)(R.nrows < p->row_grid ? R.nrows : p->row_grid)), dim3(256), 0, st, R);
-        launch_columns<false>(C, np, st);
+        on.run<row_kernel>((unsigned)(R.nrows < p->row_grid ? R.nrows : p->row_grid), 256, 0, R);
+        launch_columns<false>(on, C, np);
     }
-    if (const int status = cp::launch_status("cp_fftlog_execute"); status != CP_OK) return status;
+    if (const int status = on.status(); status != CP_OK) return status;
     if (hipEventRecord(p->done, st) != hipSuccess) return cp::fail(CP_EDEVICE, "cp_fftlog_execute: hipEventRecord failed");
     p->has_done = true;
     return CP_OK;

@@ -55,7 +55,7 @@ int plan(const char* who, long long B, int ndim, long long ncols, Plan* plan);
 int check_operands(const char* who, long long ncols, long long ldw, const double* d_data, long long ldd, const double* d_value, long long ldv);
 int check_pointers(const char* who, const double* d_weights, const double* d_data, const double* d_fisher, const double* d_grad, const double* d_chi2,
                    const double* d_work, long long work_doubles, const Plan& plan, const char* sizer);
-void sum_launch(const Plan& plan, const Tail& tail, double* d_fisher, double* d_grad, double* d_chi2, void* stream);
+void sum_launch(cp::Launches& on, const Plan& plan, const Tail& tail, double* d_fisher, double* d_grad, double* d_chi2);
 
 #ifdef __HIPCC__
 // the epilogue of one wave on its 64 x 64 accumulators: this lane's row of sums over the wave's columns colw .. colw + 63 into the wave's F[k][lane]

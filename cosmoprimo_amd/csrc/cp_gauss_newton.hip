@@ -59,10 +59,9 @@ int check_pointers(const char* who, const double* d_weights, const double* d_dat
     return CP_OK;
 }
 
-void sum_launch(const Plan& plan, const Tail& tail, double* d_fisher, double* d_grad, double* d_chi2, void* stream) {
+void sum_launch(cp::Launches& on, const Plan& plan, const Tail& tail, double* d_fisher, double* d_grad, double* d_chi2) {
     const long long entries = tail.B * plan.S;
-    hipLaunchKernelGGL(gn_sum_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), tail.part, tail.B, tail.ndim, (int)plan.nct,
-                       d_fisher, d_grad, d_chi2);
+    on.run<gn_sum_kernel>((unsigned)((entries + 255) / 256), 256, 0, tail.part, tail.B, tail.ndim, (int)plan.nct, d_fisher, d_grad, d_chi2);
 }
 
 }  // namespace cpgn

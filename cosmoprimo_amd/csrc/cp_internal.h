@@ -12,6 +12,9 @@
 namespace cpfft {
 struct cplx;
 }
+namespace cp {
+class Launches;      // the launches of one entry point (below)
+}
 
 // device tables of a fused-kernel FFTLog plan (npad <= 8192); false for plans of the general-size path
 struct cp_fftlog_tables_view {
@@ -34,12 +37,12 @@ bool cp_spline_plan_view(const cp_spline_plan* plan, cp_spline_band_view* out);
 
 // The constants of a batch of cosmologies for the evaluation of engine `engine` (cppower::CosmoConsts: fit coefficients of EH98 / no-wiggle, Gamma of
 // BBKS, the primordial constants of pk_params -- NULL: transfer functions only) into d_work (cp_power_workspace_bytes(ncosmo) bytes): the first of
-// the two kernels cp_power_eval launches.  A launch and nothing else: its caller (a public entry point) has validated the arguments (nsp from
-// cpcosmo::ncdm_species), holds the cp::DeviceScope, has fetched the knots (cpcosmo::ncdm_knots) and reads the launch status once, behind its own kernel.
+// the two kernels cp_power_eval launches.  A launch among its caller's (`on`) and nothing else: the caller (a public entry point) has validated the arguments
+// (nsp from cpcosmo::ncdm_species), holds the cp::DeviceScope, has fetched the knots (cpcosmo::ncdm_knots) and reads the launch status once, behind its own kernel.
 // d_k / d_ln_k (n wavenumbers; optional): extra workgroups of the same launch write the (3, n) table log k, k^1.08, k^1.4 of the kernels that evaluate on
 // a shared grid (cp_power_eval.h: powers_of_wavenumber) -- a launch of their own for 1024 values was 3 % of the fused sigma(r, z) call
 void cp_power_coefficients(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, int nsp, const double* knots,
-                           const cp_param* pk_params, void* d_work, void* stream, const double* d_k = nullptr, double* d_ln_k = nullptr, int n = 0);
+                           const cp_param* pk_params, void* d_work, cp::Launches& on, const double* d_k = nullptr, double* d_ln_k = nullptr, int n = 0);
 
 // the one-kernel route of cp_sigma_rz_analytic (cp_sigma.hip), called by it with its arguments checked (nsp from cpcosmo::ncdm_species): opens the scope and reads the launch status under its name
 int cp_sigma_rz_fused(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, int nsp, const cp_param* pk_params,
@@ -66,7 +69,7 @@ bool cp_splice_plan_uniform_view(const cp_splice_plan* plan, cpsu::Tables* out, 
 // __global__ template of cp_mlp_tangent.h and of cp_taylor_gemm.h, which is how kernels share source here and still keep their instructions; the row
 // transforms share inlined functions that keep them, cp_fft_workgroup.h) take
 // from the engines' files: the checks of mlp_front / taylor_front under the caller's name, the network's layout, and the launch of the kernel that
-// cp_*_predict_columns launches, inside the caller's device scope (they open none of their own).
+// cp_*_predict_columns launches, among the caller's launches (cp::Launches, below): inside its device scope, under its name, its status the caller's to read.
 namespace cp {
 // the layout of a network, the one list of its fields (cp_mlp_tangent.h: MlpNet is this and the count of parameters); at most 8 hidden layers
 struct MlpLayout {
@@ -77,18 +80,13 @@ struct MlpLayout {
 };
 int mlp_front_layout(const char* who, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, int yfunction, long long col0,
                      long long ncols, MlpLayout* layout);
-int mlp_predict_launch(const char* who, const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M,
+int mlp_predict_launch(Launches& on, const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M,
                        const double* d_params, const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction,
-                       long long col0, long long ncols, double* d_out, long long ldo, void* stream);
+                       long long col0, long long ncols, double* d_out, long long ldo);
 int taylor_front_checks(const char* who, long long B, int ndim, int T, int max_power, int M, long long col0, long long ncols, long long ld, const char* what);
-int taylor_predict_launch(const char* who, const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, const double* d_derivatives,
-                          int M, long long col0, long long ncols, double* d_out, long long ldo, void* stream);
-}  // namespace cp
+int taylor_predict_launch(Launches& on, const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, const double* d_derivatives,
+                          int M, long long col0, long long ncols, double* d_out, long long ldo);
 
-// Dynamic LDS above 64 KB is an opt-in per kernel AND per device (hipFuncAttributeMaxDynamicSharedMemorySize).  Raises the limit of KERNEL to the
-// whole 160 KB of a CU the first time it is launched on the device that is current (once per (kernel, device): a multi-GPU process configures every
-// device it launches on, and a later launch with more LDS than the first finds the limit already at the maximum).
-namespace cp {
 // The calling thread on `device` for the lifetime of the scope, and back on the device it came from on every way out.  A call on the device that
 // is already current costs one hipGetDevice and nothing else; ok() is false only when a switch was needed and failed.
 class DeviceScope {
@@ -159,12 +157,21 @@ inline int balanced_grid(long long npairs, long long resident, long long* rounds
     return (int)((npairs + r - 1) / r);
 }
 
-// the status of entry point `who` after its launches: reads (and clears) the runtime's last error once
+// the status of entry point `who` whose launches ended with `e`
 inline int launch_status(const char* who, hipError_t e) {
     return e == hipSuccess ? CP_OK : fail(CP_EDEVICE, "%s: launch failed: %s", who, hipGetErrorString(e));
 }
-inline int launch_status(const char* who) { return launch_status(who, hipGetLastError()); }
 
+// Dynamic LDS above 64 KB is an opt-in per kernel AND per device (hipFuncAttributeMaxDynamicSharedMemorySize).  Raises the limit of `kernel` on the
+// device that is current to the whole 160 KB of a CU less the kernel's static LDS (the limit covers both: a kernel with __shared__ variables of its
+// own gets what they leave).
+inline hipError_t allow_full_lds(const void* kernel) {
+    hipFuncAttributes attr;
+    const hipError_t e = hipFuncGetAttributes(&attr, kernel);
+    return e != hipSuccess ? e : hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)attr.sharedSizeBytes);
+}
+// ... the first time KERNEL is launched on the device that is current (once per (kernel, device): a multi-GPU process configures every device it
+// launches on, and a later launch with more LDS than the first finds the limit already at the maximum)
 template <auto KERNEL>
 inline hipError_t allow_full_lds() {
     static std::atomic<bool> configured[64];      // (zero-initialised; two threads may both set the same attribute to the same value: harmless, and no data race)
@@ -172,13 +179,36 @@ inline hipError_t allow_full_lds() {
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev >= 0 && dev < 64 && configured[dev].load(std::memory_order_acquire)) return hipSuccess;
-    hipFuncAttributes attr;      // the limit covers static + dynamic LDS: a kernel with __shared__ variables of its own gets what they leave
-    e = hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(KERNEL));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - (int)attr.sharedSizeBytes);
+    e = allow_full_lds(reinterpret_cast<const void*>(KERNEL));
     if (e == hipSuccess && dev >= 0 && dev < 64) configured[dev].store(true, std::memory_order_release);
     return e;
 }
+
+// The launches of entry point `who` on `stream` (the void* of the ABI), inside its DeviceScope.  run<KERNEL> opts in to the full LDS of the
+// instantiation it launches when the launch asks for more than 64 KB, so no site names a kernel twice or reasons about its LDS; at most 64 KB it
+// is the launch and nothing else.  A failed opt-in stops the entry point: neither that kernel nor any later one of this object is launched, and
+// status() reports it as it does a failed launch, with the opt-in's error.  status() reads (and clears) the runtime's last error: once per entry
+// point, behind its last launch.
+class Launches {
+    const char* who_;
+    hipStream_t stream_;
+    hipError_t refused_ = hipSuccess;
+
+public:
+    Launches(const char* who, void* stream) : who_(who), stream_(static_cast<hipStream_t>(stream)) {}
+    Launches(const Launches&) = delete;
+    Launches& operator=(const Launches&) = delete;
+    const char* who() const { return who_; }
+    template <auto KERNEL, class... Args>
+    void run(dim3 grid, dim3 block, size_t lds, const Args&... args) {
+        if (refused_ != hipSuccess || (lds > 64 * 1024 && (refused_ = allow_full_lds<KERNEL>()) != hipSuccess)) return;
+        KERNEL<<<grid, block, lds, stream_>>>(args...);
+    }
+    int status() {
+        const hipError_t last = hipGetLastError();
+        return launch_status(who_, refused_ != hipSuccess ? refused_ : last);
+    }
+};
 
 // Kernels that hand data from lane to lane of ONE wave through LDS without a workgroup barrier (the tridiagonal eliminations of cp_bao.hip and
 // cp_spline_rows.hip): the hardware executes a wave's LDS instructions in order; this pins the compiler to the same order between the phases

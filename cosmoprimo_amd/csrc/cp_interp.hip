@@ -81,9 +81,9 @@ extern "C" int cp_interp_linear(const double* d_xp, const double* d_fp, long lon
     const int ncoarse = (int)((n + stride - 1) / stride);
     const long long blocks = (nx + 255) / 256;
     const unsigned grid = (unsigned)(blocks < 256 * 8 ? blocks : 256 * 8);
-    hipLaunchKernelGGL(interp_linear_kernel, dim3(grid), dim3(256), ncoarse * sizeof(double), static_cast<hipStream_t>(stream), d_xp, d_fp, n, stride,
-                       ncoarse, d_x, d_out, nx);
-    return cp::launch_status("cp_interp_linear");
+    cp::Launches on("cp_interp_linear", stream);
+    on.run<interp_linear_kernel>(grid, 256, ncoarse * sizeof(double), d_xp, d_fp, n, stride, ncoarse, d_x, d_out, nx);
+    return on.status();
 }
 
 // ---- the same interpolation on a table kept as a plan: (x, f) pairs, the interval GUESSED from the sample -----------------------------------
@@ -181,6 +181,7 @@ int interp_table_apply(const cp_interp_table* t, const real* d_x, real* d_out, l
     cp::DeviceScope scope(t->device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, t->device);
     hipStream_t hs = static_cast<hipStream_t>(stream);
+    cp::Launches on(who, stream);
     int st = CP_OK;
     // The plan has ONE flag word.  A call that does not ask (outside == NULL) hands the kernels no flag at all, so it leaves nothing behind for a
     // later call to trip over; a call that asks clears the word on its own stream in front of its kernels and reads it back behind them: calls
@@ -194,14 +195,14 @@ int interp_table_apply(const cp_interp_table* t, const real* d_x, real* d_out, l
         const long long blocks = (nx + 255) / 256;
         const unsigned grid = (unsigned)(blocks < 256 * 16 ? blocks : 256 * 16);
         const cpit::Pair* xf = reinterpret_cast<const cpit::Pair*>(t->d_xf.get());
-        if (t->law == 1) hipLaunchKernelGGL((interp_table_kernel<1, real>), dim3(grid), dim3(256), 0, hs, xf, t->n, t->first, t->a, t->b, d_x, d_out, nx, flag);
-        else hipLaunchKernelGGL((interp_table_kernel<2, real>), dim3(grid), dim3(256), 0, hs, xf, t->n, t->first, t->a, t->b, d_x, d_out, nx, flag);
-        st = cp::launch_status(who);
+        if (t->law == 1) on.run<interp_table_kernel<1, real>>(grid, 256, 0, xf, t->n, t->first, t->a, t->b, d_x, d_out, nx, flag);
+        else on.run<interp_table_kernel<2, real>>(grid, 256, 0, xf, t->n, t->first, t->a, t->b, d_x, d_out, nx, flag);
+        st = on.status();
     }
     if (st == CP_OK && outside) {
         if (t->law == 0) {
-            hipLaunchKernelGGL(flag_outside_kernel, dim3(1024), dim3(256), 0, hs, reinterpret_cast<const double*>(d_x), nx, t->x0, t->xn, t->d_flag);
-            st = cp::launch_status(who);
+            on.run<flag_outside_kernel>(1024, 256, 0, reinterpret_cast<const double*>(d_x), nx, t->x0, t->xn, t->d_flag);
+            st = on.status();
         }
         // the flag comes back with the stream drained: the caller of the reference gets its exception from the call itself (tabulated.py:33-34)
         int host = 0;
@@ -339,17 +340,15 @@ extern "C" int cp_spline_points(const double* d_xk, const double* d_y, const dou
     const int ncoarse = (int)((n + stride - 1) / stride);
     const long long blocks = (nq + 255) / 256;
     const unsigned grid = (unsigned)(blocks < 256 * 8 ? blocks : 256 * 8);
+    cp::Launches on("cp_spline_points", stream);
     if (ncol == 1 && n <= SPLINE_LDS_KNOTS && nq >= 65536) {      // a catalogue through one spline: the spline in LDS (a few samples: not worth filling it per workgroup)
         const size_t lds = (size_t)(n + 4 * (n - 1)) * sizeof(double);
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&spline_points_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         const unsigned lgrid = (unsigned)(blocks < 256 * 4 ? blocks : 256 * 4);
-        hipLaunchKernelGGL(spline_points_lds_kernel, dim3(lgrid), dim3(256), lds, static_cast<hipStream_t>(stream), d_xk, d_y, d_s, (int)n, d_xq, d_out, nq, nu,
-                           extrapolate);
-        return cp::launch_status("cp_spline_points");
+        on.run<spline_points_lds_kernel>(lgrid, 256, lds, d_xk, d_y, d_s, (int)n, d_xq, d_out, nq, nu, extrapolate);
+        return on.status();
     }
-    hipLaunchKernelGGL(spline_points_kernel, dim3(grid), dim3(256), ncoarse * sizeof(double), static_cast<hipStream_t>(stream), d_xk, d_y, d_s, n, ncol, stride,
-                       ncoarse, d_xq, d_out, nq, nu, extrapolate);
-    return cp::launch_status("cp_spline_points");
+    on.run<spline_points_kernel>(grid, 256, ncoarse * sizeof(double), d_xk, d_y, d_s, n, ncol, stride, ncoarse, d_xq, d_out, nq, nu, extrapolate);
+    return on.status();
 }
 
 // ---- cubic splines of many rows, each at ITS OWN queries: one lane per (row, query) --------------------------------------------------------
@@ -400,7 +399,7 @@ extern "C" int cp_spline_rows_at_queries(const double* d_xk, const double* d_y, 
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_spline_rows_at_queries: cannot select device %d", device);
     const long long blocks = (nrows * nq + 255) / 256;
     const unsigned grid = (unsigned)(blocks < 256 * 16 ? blocks : 256 * 16);
-    hipLaunchKernelGGL(spline_rows_at_queries_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), d_xk, d_y, d_m, nrows, n, d_xq, nq, d_out,
-                       transposed);
-    return cp::launch_status("cp_spline_rows_at_queries");
+    cp::Launches on("cp_spline_rows_at_queries", stream);
+    on.run<spline_rows_at_queries_kernel>(grid, 256, 0, d_xk, d_y, d_m, nrows, n, d_xq, nq, d_out, transposed);
+    return on.status();
 }

@@ -199,16 +199,6 @@ int lm_front(const char* who, long long B, int ndim, int* G, int* per_workgroup)
     return CP_OK;
 }
 
-template <int G>
-void step_launch(const LmArgs& a, unsigned grid, hipStream_t stream) {
-    hipLaunchKernelGGL(lm_step_kernel<G>, dim3(grid), dim3(lm_threads(G)), 0, stream, a);
-}
-
-template <int G>
-void inverse_launch(long long B, int ndim, const double* d_a, double* d_inv, int* d_info, unsigned grid, hipStream_t stream) {
-    hipLaunchKernelGGL(spd_inverse_kernel<G>, dim3(grid), dim3(lm_threads(G)), 0, stream, B, ndim, d_a, d_inv, d_info);
-}
-
 }  // namespace
 
 extern "C" int cp_lm_layout(int ndim, int* lanes_per_fit, int* fits_per_workgroup) {
@@ -235,16 +225,16 @@ extern "C" int cp_lm_step(long long B, int ndim, double* d_x, double* d_fisher, 
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_lm_step: cannot select device %d", device);
     const LmArgs a{B, ndim, d_x, d_fisher, d_grad, d_chi2, d_lambda, d_status, d_naccepted, d_xt, d_fisher_t, d_grad_t, d_chi2_t, d_lo, d_hi, up, down, lmin, lmax, ftol, d_next};
     const unsigned grid = (unsigned)((B + per - 1) / per);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    cp::Launches on("cp_lm_step", stream);
     switch (G) {
-        case 1: step_launch<1>(a, grid, s); break;
-        case 2: step_launch<2>(a, grid, s); break;
-        case 4: step_launch<4>(a, grid, s); break;
-        case 8: step_launch<8>(a, grid, s); break;
-        case 16: step_launch<16>(a, grid, s); break;
-        default: step_launch<32>(a, grid, s); break;
+        case 1: on.run<lm_step_kernel<1>>(grid, lm_threads(1), 0, a); break;
+        case 2: on.run<lm_step_kernel<2>>(grid, lm_threads(2), 0, a); break;
+        case 4: on.run<lm_step_kernel<4>>(grid, lm_threads(4), 0, a); break;
+        case 8: on.run<lm_step_kernel<8>>(grid, lm_threads(8), 0, a); break;
+        case 16: on.run<lm_step_kernel<16>>(grid, lm_threads(16), 0, a); break;
+        default: on.run<lm_step_kernel<32>>(grid, lm_threads(32), 0, a); break;
     }
-    return cp::launch_status("cp_lm_step");
+    return on.status();
 }
 
 extern "C" int cp_spd_inverse(long long B, int ndim, const double* d_a, double* d_inv, int* d_info, int device, void* stream) {
@@ -256,14 +246,14 @@ extern "C" int cp_spd_inverse(long long B, int ndim, const double* d_a, double* 
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_spd_inverse: cannot select device %d", device);
     const unsigned grid = (unsigned)((B + per - 1) / per);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    cp::Launches on("cp_spd_inverse", stream);
     switch (G) {
-        case 1: inverse_launch<1>(B, ndim, d_a, d_inv, d_info, grid, s); break;
-        case 2: inverse_launch<2>(B, ndim, d_a, d_inv, d_info, grid, s); break;
-        case 4: inverse_launch<4>(B, ndim, d_a, d_inv, d_info, grid, s); break;
-        case 8: inverse_launch<8>(B, ndim, d_a, d_inv, d_info, grid, s); break;
-        case 16: inverse_launch<16>(B, ndim, d_a, d_inv, d_info, grid, s); break;
-        default: inverse_launch<32>(B, ndim, d_a, d_inv, d_info, grid, s); break;
+        case 1: on.run<spd_inverse_kernel<1>>(grid, lm_threads(1), 0, B, ndim, d_a, d_inv, d_info); break;
+        case 2: on.run<spd_inverse_kernel<2>>(grid, lm_threads(2), 0, B, ndim, d_a, d_inv, d_info); break;
+        case 4: on.run<spd_inverse_kernel<4>>(grid, lm_threads(4), 0, B, ndim, d_a, d_inv, d_info); break;
+        case 8: on.run<spd_inverse_kernel<8>>(grid, lm_threads(8), 0, B, ndim, d_a, d_inv, d_info); break;
+        case 16: on.run<spd_inverse_kernel<16>>(grid, lm_threads(16), 0, B, ndim, d_a, d_inv, d_info); break;
+        default: on.run<spd_inverse_kernel<32>>(grid, lm_threads(32), 0, B, ndim, d_a, d_inv, d_info); break;
     }
-    return cp::launch_status("cp_spd_inverse");
+    return on.status();
 }

@@ -41,6 +41,7 @@ extern "C" int cp_math_eval(int kind, const double* d_x, double* d_y, long long 
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_math_eval: cannot select device %d", device);
     const long long blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(math_eval_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, static_cast<hipStream_t>(stream), kind, d_x, d_y, n);
-    return cp::launch_status("cp_math_eval");
+    cp::Launches on("cp_math_eval", stream);
+    on.run<math_eval_kernel>((unsigned)(blocks < 4096 ? blocks : 4096), 256, 0, kind, d_x, d_y, n);
+    return on.status();
 }

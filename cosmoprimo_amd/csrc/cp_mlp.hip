@@ -618,15 +618,10 @@ void mlp_vjp_work(const MlpNet& net, long long B, long long ncols, MlpWork* ws) 
 }
 
 template <int MODE>
-int mlp_forward_launch(const char* who, const MlpFwdArgs& A, void* stream) {
+int mlp_forward_launch(cp::Launches& on, const MlpFwdArgs& A) {
     const long long nrt = (A.R + ML_ROWS - 1) / ML_ROWS, nct = (A.cend - A.c0 + ML_COLS - 1) / ML_COLS;
-    if (nrt > 0x7fffffffLL || nct > 65535) return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d results (at most 2^37 rows, 2^24 - 256 columns)", who, A.R, A.net.M);
-    const size_t lds = (size_t)2 * A.net.nr * ML_RS * sizeof(double);      // 40 KB at widths <= 32, at most 80 KB
-    if (lds > 64 * 1024) {
-        const hipError_t e = cp::allow_full_lds<mlp_forward_kernel<MODE>>();
-        if (e != hipSuccess) return cp::launch_status(who, e);
-    }
-    hipLaunchKernelGGL(mlp_forward_kernel<MODE>, dim3((unsigned)nrt, (unsigned)nct), dim3(256), lds, static_cast<hipStream_t>(stream), A);
+    if (nrt > 0x7fffffffLL || nct > 65535) return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d results (at most 2^37 rows, 2^24 - 256 columns)", on.who(), A.R, A.net.M);
+    on.run<mlp_forward_kernel<MODE>>(dim3((unsigned)nrt, (unsigned)nct), 256, (size_t)2 * A.net.nr * ML_RS * sizeof(double), A);      // 40 KB at widths <= 32, at most 80 KB
     return CP_OK;
 }
 
@@ -656,20 +651,20 @@ int mlp_yfunction(int yfunction, F&& f) {
 }
 
 // mlp_dh_kernel for a last hidden layer of width H: r (b, M) with row stride ldr times the transposed W (H, M) with row stride ldw, in the slices of ws
-void mlp_dh_launch(const double* r, long long ldr, const double* W, long long ldw, long long b, int H, int M, const MlpWork& ws, double* part, hipStream_t st) {
+void mlp_dh_launch(cp::Launches& on, const double* r, long long ldr, const double* W, long long ldw, long long b, int H, int M, const MlpWork& ws, double* part) {
     const dim3 grid((unsigned)ws.nrt, (unsigned)((ws.nsl + 3) / 4));
     switch ((H + 15) / 16) {
-        case 1: hipLaunchKernelGGL(mlp_dh_kernel<1>, grid, dim3(256), 0, st, r, ldr, W, ldw, b, H, M, ws.nsl, ws.ks, part); break;
-        case 2: hipLaunchKernelGGL(mlp_dh_kernel<2>, grid, dim3(256), 0, st, r, ldr, W, ldw, b, H, M, ws.nsl, ws.ks, part); break;
-        case 3: hipLaunchKernelGGL(mlp_dh_kernel<3>, grid, dim3(256), 0, st, r, ldr, W, ldw, b, H, M, ws.nsl, ws.ks, part); break;
-        default: hipLaunchKernelGGL(mlp_dh_kernel<4>, grid, dim3(256), 0, st, r, ldr, W, ldw, b, H, M, ws.nsl, ws.ks, part);
+        case 1: on.run<mlp_dh_kernel<1>>(grid, 256, 0, r, ldr, W, ldw, b, H, M, ws.nsl, ws.ks, part); break;
+        case 2: on.run<mlp_dh_kernel<2>>(grid, 256, 0, r, ldr, W, ldw, b, H, M, ws.nsl, ws.ks, part); break;
+        case 3: on.run<mlp_dh_kernel<3>>(grid, 256, 0, r, ldr, W, ldw, b, H, M, ws.nsl, ws.ks, part); break;
+        default: on.run<mlp_dh_kernel<4>>(grid, 256, 0, r, ldr, W, ldw, b, H, M, ws.nsl, ws.ks, part);
     }
 }
 
 }  // namespace
 
 // For cp_mlp_gauss_newton (cp_mlp_gauss_newton.hip; declared in cp_internal.h): the checks of mlp_front under its name with the network's layout, and the
-// forward kernel on a range of columns inside its device scope -- what cp_mlp_predict_columns launches, so the value it writes has those bits.
+// forward kernel on a range of columns among its launches -- what cp_mlp_predict_columns launches, so the value it writes has those bits.
 int cp::mlp_front_layout(const char* who, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, int yfunction, long long col0,
                          long long ncols, MlpLayout* layout) {
     MlpFwdArgs F{};
@@ -679,14 +674,14 @@ int cp::mlp_front_layout(const char* who, long long B, int ndim, int nlayers, co
     return CP_OK;
 }
 
-int cp::mlp_predict_launch(const char* who, const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M,
+int cp::mlp_predict_launch(Launches& on, const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M,
                            const double* d_params, const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction,
-                           long long col0, long long ncols, double* d_out, long long ldo, void* stream) {
+                           long long col0, long long ncols, double* d_out, long long ldo) {
     MlpFwdArgs A{};
-    const int status = mlp_front(who, d_x, B, ndim, nlayers, widths, activations, M, d_params, d_xoffset, d_xscale, d_yoffset, d_yscale, yfunction, col0, ncols, &A);
+    const int status = mlp_front(on.who(), d_x, B, ndim, nlayers, widths, activations, M, d_params, d_xoffset, d_xscale, d_yoffset, d_yscale, yfunction, col0, ncols, &A);
     if (status != CP_OK) return status;
     A.out = d_out, A.ldo = ldo;
-    return mlp_yfunction(yfunction, [&](auto y) { return mlp_forward_launch<decltype(y)::value>(who, A, stream); });
+    return mlp_yfunction(yfunction, [&](auto y) { return mlp_forward_launch<decltype(y)::value>(on, A); });
 }
 
 extern "C" long long cp_mlp_param_count(int ndim, int nlayers, const int* widths, int M) {
@@ -718,9 +713,9 @@ static int mlp_predict(const char* who, const double* d_x, long long B, int ndim
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
     A.out = d_out, A.ldo = ldo;
-    const int launched = mlp_yfunction(yfunction, [&](auto y) { return mlp_forward_launch<decltype(y)::value>(who, A, stream); });
-    if (launched != CP_OK) return launched;
-    return cp::launch_status(who);
+    cp::Launches on(who, stream);
+    const int launched = mlp_yfunction(yfunction, [&](auto y) { return mlp_forward_launch<decltype(y)::value>(on, A); });
+    return launched != CP_OK ? launched : on.status();
 }
 
 extern "C" int cp_mlp_predict(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
@@ -756,12 +751,13 @@ extern "C" int cp_mlp_jacobian(const double* d_x, long long B, int ndim, int nla
     F.out = d_value, F.ldo = ldv;
     const MlpJacArgs J{d_x, d_params, d_xoffset, d_xscale, d_yscale, d_value, d_jac, B * ndim, ldv, ldj, F.c0, F.cend, F.net};
     const dim3 grid((unsigned)((J.R + ML_ROWS - 1) / ML_ROWS), (unsigned)((ncols + ML_COLS - 1) / ML_COLS));      // (checked above)
+    cp::Launches on(who, stream);
     const int launched = mlp_yfunction(yfunction, [&](auto y) {
-        const int forward = mlp_forward_launch<decltype(y)::value>(who, F, stream);
-        return forward != CP_OK ? forward : mlp_tangent_launch<decltype(y)::value>(who, J, grid, 0, stream);
+        const int forward = mlp_forward_launch<decltype(y)::value>(on, F);
+        if (forward == CP_OK) mlp_tangent_launch<decltype(y)::value>(on, J, grid, 0);
+        return forward;
     });
-    if (launched != CP_OK) return launched;
-    return cp::launch_status(who);
+    return launched != CP_OK ? launched : on.status();
 }
 
 // Two launches on the stream as in cp_mlp_jacobian: the forward kernel writes the prediction on the range, the tangent kernel's jvp variant reads it
@@ -785,12 +781,13 @@ extern "C" int cp_mlp_jvp(const double* d_x, long long B, int ndim, int nlayers,
     F.out = d_value, F.ldo = ldv;
     const MlpJvpArgs J{{d_x, d_params, d_xoffset, d_xscale, d_yscale, d_value, d_out, B * K, ldv, ldo, F.c0, F.cend, F.net}, d_tan, (int)K};
     const dim3 grid((unsigned)((J.R + ML_ROWS - 1) / ML_ROWS), (unsigned)((ncols + ML_COLS - 1) / ML_COLS));      // (checked above)
+    cp::Launches on(who, stream);
     const int launched = mlp_yfunction(yfunction, [&](auto y) {
-        const int forward = mlp_forward_launch<decltype(y)::value>(who, F, stream);
-        return forward != CP_OK ? forward : mlp_tangent_launch<decltype(y)::value>(who, J, grid, 0, stream);
+        const int forward = mlp_forward_launch<decltype(y)::value>(on, F);
+        if (forward == CP_OK) mlp_tangent_launch<decltype(y)::value>(on, J, grid, 0);
+        return forward;
     });
-    if (launched != CP_OK) return launched;
-    return cp::launch_status(who);
+    return launched != CP_OK ? launched : on.status();
 }
 
 extern "C" long long cp_mlp_vjp_workspace_doubles(long long B, int ndim, int nlayers, const int* widths, int M, long long ncols) {
@@ -828,15 +825,15 @@ extern "C" int cp_mlp_vjp(const double* d_x, long long B, int ndim, int nlayers,
     if (work_doubles < ws.total) return cp::fail(CP_EINVAL, "%s: workspace of %lld doubles, %lld needed (cp_mlp_vjp_workspace_doubles)", who, work_doubles, ws.total);
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    cp::Launches on(who, stream);
     F.cot = d_cot, F.out = d_value, F.work = d_work, F.ldo = ldv, F.ldc = ldc;
-    const int launched = mlp_yfunction(yfunction, [&](auto y) { return mlp_forward_launch<ML_VJP + decltype(y)::value>(who, F, stream); });
+    const int launched = mlp_yfunction(yfunction, [&](auto y) { return mlp_forward_launch<ML_VJP + decltype(y)::value>(on, F); });
     if (launched != CP_OK) return launched;
     // dh of the last hidden layer, in slices of the columns: the weighted cotangent times the columns [col0, col0 + ncols) of the output kernel
-    mlp_dh_launch(d_work + ws.resid, ncols, d_params + N.off[N.L] + col0, M, B, N.d[N.L], (int)ncols, ws, d_work + ws.part, st);
+    mlp_dh_launch(on, d_work + ws.resid, ncols, d_params + N.off[N.L] + col0, M, B, N.d[N.L], (int)ncols, ws, d_work + ws.part);
     const MlpGradArgs G{d_params, d_xscale, d_work, d_grad, B, N, ws};
-    hipLaunchKernelGGL(mlp_input_grad_kernel, dim3((unsigned)ws.nrt), dim3(256), (size_t)2 * N.nr * ML_GS * sizeof(double), st, G);      // at most 64 KB of LDS
-    return cp::launch_status(who);
+    on.run<mlp_input_grad_kernel>((unsigned)ws.nrt, 256, (size_t)2 * N.nr * ML_GS * sizeof(double), G);
+    return on.status();
 }
 
 extern "C" int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long b, int ndim, int nlayers, const int* widths, const int* activations, int M,
@@ -856,14 +853,14 @@ extern "C" int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long 
     if ((long long)ws.nrt * 64 > 0x7fffffffLL || (b * ML_MAX_WIDTH + 255) / 256 > 0x7fffffffLL) return cp::fail(CP_EUNSUPPORTED, "cp_mlp_loss_grad: batch of %lld rows", b);
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_mlp_loss_grad: cannot select device %d", device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    cp::Launches on(who, stream);
     A.x = d_X, A.params = d_params, A.ytrue = d_Y, A.out = d_work + ws.resid, A.work = d_work, A.R = b;
     A.ldo = M, A.c0 = 0, A.cend = M;
     A.rscale = 2. / ((double)b * (double)M);
-    const int launched = mlp_forward_launch<ML_TRAIN>(who, A, stream);
+    const int launched = mlp_forward_launch<ML_TRAIN>(on, A);
     if (launched != CP_OK) return launched;
-    hipLaunchKernelGGL(mlp_sum_kernel, dim3(1), dim3(1024), 0, st, d_work + ws.losspart, (long long)ws.nrt * ws.nct, 1. / ((double)b * (double)M), d_loss);
-    if (!d_grad) return cp::launch_status(who);
+    on.run<mlp_sum_kernel>(1, 1024, 0, d_work + ws.losspart, (long long)ws.nrt * ws.nct, 1. / ((double)b * (double)M), d_loss);
+    if (!d_grad) return on.status();
     const int L = N.L, H = N.d[L];
     const double* resid = d_work + ws.resid;
     {      // the output layer's gradient
@@ -871,13 +868,13 @@ extern "C" int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long 
         double* gW = d_grad + N.off[L];
         const dim3 grid((unsigned)ws.nct);
         switch ((H + 15) / 16) {
-            case 1: hipLaunchKernelGGL(mlp_gw_out_kernel<1>, grid, dim3(256), 0, st, hL, resid, b, H, M, gW); break;
-            case 2: hipLaunchKernelGGL(mlp_gw_out_kernel<2>, grid, dim3(256), 0, st, hL, resid, b, H, M, gW); break;
-            case 3: hipLaunchKernelGGL(mlp_gw_out_kernel<3>, grid, dim3(256), 0, st, hL, resid, b, H, M, gW); break;
-            default: hipLaunchKernelGGL(mlp_gw_out_kernel<4>, grid, dim3(256), 0, st, hL, resid, b, H, M, gW);
+            case 1: on.run<mlp_gw_out_kernel<1>>(grid, 256, 0, hL, resid, b, H, M, gW); break;
+            case 2: on.run<mlp_gw_out_kernel<2>>(grid, 256, 0, hL, resid, b, H, M, gW); break;
+            case 3: on.run<mlp_gw_out_kernel<3>>(grid, 256, 0, hL, resid, b, H, M, gW); break;
+            default: on.run<mlp_gw_out_kernel<4>>(grid, 256, 0, hL, resid, b, H, M, gW);
         }
     }
-    mlp_dh_launch(resid, M, d_params + N.off[L], M, b, H, M, ws, d_work + ws.part, st);      // dh of the last hidden layer, in slices of the outputs
+    mlp_dh_launch(on, resid, M, d_params + N.off[L], M, b, H, M, ws, d_work + ws.part);      // dh of the last hidden layer, in slices of the outputs
     for (int l = L - 1; l >= 0; --l) {      // hidden layer l: d[l] -> d[l + 1]
         const int nin = N.d[l], nout = N.d[l + 1];
         double* dz = d_work + ws.dz[l & 1];
@@ -885,21 +882,20 @@ extern "C" int cp_mlp_loss_grad(const double* d_X, const double* d_Y, long long 
         double* gl = d_grad + N.off[l];
         const unsigned nblocks = (unsigned)((b * nout + 255) / 256);
         if (l == L - 1)
-            hipLaunchKernelGGL(mlp_dz_kernel, dim3(nblocks), dim3(256), 0, st, d_work + ws.part, ws.nsl, nullptr, nullptr, 0, d_work + ws.z[l], b, nout, N.act[l], ab,
-                               dz, d_work + ws.ca, d_work + ws.cb);
+            on.run<mlp_dz_kernel>(nblocks, 256, 0, d_work + ws.part, ws.nsl, nullptr, nullptr, 0, d_work + ws.z[l], b, nout, N.act[l], ab, dz, d_work + ws.ca,
+                                  d_work + ws.cb);
         else
-            hipLaunchKernelGGL(mlp_dz_kernel, dim3(nblocks), dim3(256), 0, st, nullptr, 0, d_work + ws.dz[(l + 1) & 1], d_params + N.off[l + 1], N.d[l + 2],
-                               d_work + ws.z[l], b, nout, N.act[l], ab, dz, d_work + ws.ca, d_work + ws.cb);
+            on.run<mlp_dz_kernel>(nblocks, 256, 0, nullptr, 0, d_work + ws.dz[(l + 1) & 1], d_params + N.off[l + 1], N.d[l + 2], d_work + ws.z[l], b, nout, N.act[l],
+                                  ab, dz, d_work + ws.ca, d_work + ws.cb);
         const double* hprev = l == 0 ? d_X : d_work + ws.h[l - 1];
-        hipLaunchKernelGGL(mlp_gw_hidden_kernel, dim3((unsigned)(((nin + 1) * nout + 63) / 64)), dim3(1024), 0, st, hprev, dz, b, nin, nout, gl,
-                           N.act[l] != ACT_IDENTITY_SILU);
+        on.run<mlp_gw_hidden_kernel>((unsigned)(((nin + 1) * nout + 63) / 64), 1024, 0, hprev, dz, b, nin, nout, gl, N.act[l] != ACT_IDENTITY_SILU);
         double* gab = gl + (long long)(nin + 1) * nout;
         if (N.act[l] == ACT_IDENTITY_SILU) {
-            hipLaunchKernelGGL(mlp_sum_kernel, dim3(1), dim3(1024), 0, st, d_work + ws.ca, b * nout, 1., gab);
-            hipLaunchKernelGGL(mlp_sum_kernel, dim3(1), dim3(1024), 0, st, d_work + ws.cb, b * nout, 1., gab + 1);
+            on.run<mlp_sum_kernel>(1, 1024, 0, d_work + ws.ca, b * nout, 1., gab);
+            on.run<mlp_sum_kernel>(1, 1024, 0, d_work + ws.cb, b * nout, 1., gab + 1);
         }
     }
-    return cp::launch_status(who);
+    return on.status();
 }
 
 extern "C" int cp_mlp_adam(double* d_params, double* d_m, double* d_v, const double* d_grad, long long n, double lr, double b1, double b2, double eps, double c1,
@@ -911,7 +907,7 @@ extern "C" int cp_mlp_adam(double* d_params, double* d_m, double* d_v, const dou
     if ((n + 255) / 256 > 0x7fffffffLL) return cp::fail(CP_EUNSUPPORTED, "cp_mlp_adam: %lld parameters", n);
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_mlp_adam: cannot select device %d", device);
-    hipLaunchKernelGGL(mlp_adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), d_params, d_m, d_v, d_grad, n, lr, b1,
-                       b2, eps, c1, c2);
-    return cp::launch_status("cp_mlp_adam");
+    cp::Launches on("cp_mlp_adam", stream);
+    on.run<mlp_adam_kernel>((unsigned)((n + 255) / 256), 256, 0, d_params, d_m, d_v, d_grad, n, lr, b1, b2, eps, c1, c2);
+    return on.status();
 }

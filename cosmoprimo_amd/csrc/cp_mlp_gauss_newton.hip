@@ -43,19 +43,19 @@ extern "C" int cp_mlp_gauss_newton(const double* d_x, long long B, int ndim, int
     // the value on the range: to the caller's buffer, else to the workspace, if anything reads it
     double* value = d_value ? d_value : d_work + plan.value;
     const long long ldvalue = d_value ? ldv : ncols;
+    cp::Launches on(who, stream);
     if (d_value || d_data || yfunction != CP_MLP_Y_NONE) {
-        status = cp::mlp_predict_launch(who, d_x, B, ndim, nlayers, widths, activations, M, d_params, d_xoffset, d_xscale, d_yoffset, d_yscale, yfunction, col0, ncols,
-                                        value, ldvalue, stream);
+        status = cp::mlp_predict_launch(on, d_x, B, ndim, nlayers, widths, activations, M, d_params, d_xoffset, d_xscale, d_yoffset, d_yscale, yfunction, col0, ncols,
+                                        value, ldvalue);
         if (status != CP_OK) return status;
     }
     A.x = d_x, A.params = d_params, A.xoff = d_xoffset, A.xscale = d_xscale, A.yscale = d_yscale;
     A.tail = cpgn::Tail{d_weights, d_data, value, d_work + plan.part, ldw, ldd, ldvalue, B, ndim, plan.P, (int)col0, (int)(col0 + ncols)};
     const dim3 grid((unsigned)plan.nrt, (unsigned)plan.nct);
     const size_t epilogue = cpgn::epilogue_lds_doubles(plan.P, ndim);
-    if (yfunction == CP_MLP_Y_NONE) status = mlp_tangent_launch<cpgn::GN_Y_NONE>(who, A, grid, epilogue, stream);
-    else if (yfunction == CP_MLP_Y_EXP10) status = mlp_tangent_launch<cpgn::GN_Y_EXP10>(who, A, grid, epilogue, stream);
-    else status = mlp_tangent_launch<cpgn::GN_Y_SINH>(who, A, grid, epilogue, stream);
-    if (status != CP_OK) return status;
-    cpgn::sum_launch(plan, A.tail, d_fisher, d_grad, d_chi2, stream);
-    return cp::launch_status(who);
+    if (yfunction == CP_MLP_Y_NONE) mlp_tangent_launch<cpgn::GN_Y_NONE>(on, A, grid, epilogue);
+    else if (yfunction == CP_MLP_Y_EXP10) mlp_tangent_launch<cpgn::GN_Y_EXP10>(on, A, grid, epilogue);
+    else mlp_tangent_launch<cpgn::GN_Y_SINH>(on, A, grid, epilogue);
+    cpgn::sum_launch(on, plan, A.tail, d_fisher, d_grad, d_chi2);
+    return on.status();
 }

@@ -296,17 +296,11 @@ __global__ __launch_bounds__(256, 2) void mlp_tangent_kernel(const Args A) {
 }
 
 // The kernel on the stream for the variant of A, inside the caller's device scope.  LDS: the hidden layers' buffers (36 KB at widths <= 32, at most 72 KB),
-// or the Gauss-Newton epilogue's `epilogue` doubles where those are more; above 64 KB the instantiation that is launched is allowed the whole LDS.
+// or the Gauss-Newton epilogue's `epilogue` doubles where those are more.
 template <int YF, class Args>
-int mlp_tangent_launch(const char* who, const Args& A, const dim3 grid, const size_t epilogue, void* stream) {
+void mlp_tangent_launch(cp::Launches& on, const Args& A, const dim3 grid, const size_t epilogue) {
     const size_t hidden = (size_t)A.net.nr * (ML_RS + ML_PS);
-    const size_t lds = (hidden > epilogue ? hidden : epilogue) * sizeof(double);
-    if (lds > 64 * 1024) {
-        const hipError_t e = cp::allow_full_lds<mlp_tangent_kernel<YF, Args>>();
-        if (e != hipSuccess) return cp::launch_status(who, e);
-    }
-    hipLaunchKernelGGL((mlp_tangent_kernel<YF, Args>), grid, dim3(256), lds, static_cast<hipStream_t>(stream), A);
-    return CP_OK;
+    on.run<mlp_tangent_kernel<YF, Args>>(grid, 256, (hidden > epilogue ? hidden : epilogue) * sizeof(double), A);
 }
 
 }  // namespace

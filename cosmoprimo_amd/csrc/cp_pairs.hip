@@ -46,6 +46,7 @@ extern "C" int cp_bilinear_pairs(const double* d_wx, const double* d_wy, const d
     if (blocks > 2147483647LL) return cp::fail(CP_EUNSUPPORTED, "cp_bilinear_pairs: %lld x %d pairs exceed one launch", nbatch, nq);
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_bilinear_pairs: cannot select device %d", device);
-    hipLaunchKernelGGL(bilinear_pairs_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), d_wx, d_wy, d_f, d_out, nbatch, nq, nx, ny);
-    return cp::launch_status("cp_bilinear_pairs");
+    cp::Launches on("cp_bilinear_pairs", stream);
+    on.run<bilinear_pairs_kernel>((unsigned)blocks, 256, 0, d_wx, d_wy, d_f, d_out, nbatch, nq, nx, ny);
+    return on.status();
 }

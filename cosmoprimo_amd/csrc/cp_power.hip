@@ -339,13 +339,12 @@ __global__ __launch_bounds__(256) void variants_kernel(const VarArgs A) {
 extern "C" long long cp_power_workspace_bytes(long long ncosmo) { return ncosmo < 0 ? -1 : (long long)sizeof(CosmoConsts) * ncosmo; }
 
 void cp_power_coefficients(int engine, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, int nsp, const double* knots,
-                           const cp_param* pk_params, void* d_work, void* stream, const double* d_k, double* d_ln_k, int n) {
+                           const cp_param* pk_params, void* d_work, cp::Launches& on, const double* d_k, double* d_ln_k, int n) {
     Args A{};
     cpcosmo::fill_cosmology(A, ncosmo, bg_params, pk_params, second_is_omega_m, ncdm, nsp, knots);
     A.engine = engine;
     const int n_grid = d_k && d_ln_k ? n : 0;
-    hipLaunchKernelGGL(coefficients_kernel, dim3((unsigned)((ncosmo + 63) / 64 + (n_grid + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), A,
-                       static_cast<CosmoConsts*>(d_work), pk_params ? 1 : 0, d_k, d_ln_k, n_grid);
+    on.run<coefficients_kernel>((unsigned)((ncosmo + 63) / 64 + (n_grid + 63) / 64), 64, 0, A, static_cast<CosmoConsts*>(d_work), pk_params ? 1 : 0, d_k, d_ln_k, n_grid);
 }
 
 namespace {
@@ -388,7 +387,8 @@ extern "C" int cp_power_eval(int engine, int what, long long ncosmo, const cp_pa
     const double* knots;
     st = cpcosmo::ncdm_knots(nsp, device, who, &knots);
     if (st != CP_OK) return st;
-    cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, knots, pk_params, d_work, stream);
+    cp::Launches on(who, stream);
+    cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, knots, pk_params, d_work, on);
     cpcosmo::fill_cosmology(A, ncosmo, bg_params, pk_params, second_is_omega_m, ncdm, nsp, knots, d_work);
     A.engine = engine;
     A.what = what;
@@ -399,8 +399,8 @@ extern "C" int cp_power_eval(int engine, int what, long long ncosmo, const cp_pa
     A.z = d_z;
     A.out = d_out;
     const dim3 grid((unsigned)(ncosmo * A.kchunks)), threads((unsigned)block);
-    cpcosmo::dispatch_engine(engine, [&](auto e) { hipLaunchKernelGGL((power_kernel<decltype(e)::value>), grid, threads, 0, static_cast<hipStream_t>(stream), A); });
-    return cp::launch_status(who);
+    cpcosmo::dispatch_engine(engine, [&](auto e) { on.run<power_kernel<decltype(e)::value>>(grid, threads, 0, A); });
+    return on.status();
 }
 
 extern "C" int cp_power_eval_variants(int what, int of, long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm,
@@ -431,8 +431,9 @@ extern "C" int cp_power_eval_variants(int what, int of, long long ncosmo, const 
     A.out = d_out;
     const long long block = 256;
     if (!split_wavenumbers(A, ncosmo, nk, block)) return cp::fail(CP_EUNSUPPORTED, "cp_power_eval_variants: %lld cosmologies x %lld wavenumbers exceed one launch; split the batch", ncosmo, nk);
-    hipLaunchKernelGGL(variants_kernel, dim3((unsigned)(ncosmo * A.kchunks)), dim3((unsigned)block), 0, static_cast<hipStream_t>(stream), A);
-    return cp::launch_status(who);
+    cp::Launches on(who, stream);
+    on.run<variants_kernel>((unsigned)(ncosmo * A.kchunks), (unsigned)block, 0, A);
+    return on.status();
 }
 
 extern "C" int cp_variants_scalars(long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, double* d_out, int device,
@@ -452,8 +453,9 @@ extern "C" int cp_variants_scalars(long long ncosmo, const cp_param* bg_params, 
     VarScalArgs A;
     cpcosmo::fill_cosmology(A, ncosmo, bg_params, nullptr, second_is_omega_m, ncdm, nsp, knots);
     A.out = d_out;
-    hipLaunchKernelGGL(variants_scalars_kernel, dim3((unsigned)((ncosmo + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), A);
-    return cp::launch_status(who);
+    cp::Launches on(who, stream);
+    on.run<variants_scalars_kernel>((unsigned)((ncosmo + 255) / 256), 256, 0, A);
+    return on.status();
 }
 
 extern "C" int cp_eh_scalars(long long ncosmo, const cp_param* bg_params, int second_is_omega_m, const cp_ncdm* ncdm, double* d_out, int device,
@@ -470,6 +472,7 @@ extern "C" int cp_eh_scalars(long long ncosmo, const cp_param* bg_params, int se
     ScalArgs A;
     cpcosmo::fill_cosmology(A, ncosmo, bg_params, nullptr, second_is_omega_m, ncdm, nsp);      // (the kernel reads today's densities only: no knots)
     A.out = d_out;
-    hipLaunchKernelGGL(eh_scalars_kernel, dim3((unsigned)((ncosmo + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), A);
-    return cp::launch_status(who);
+    cp::Launches on(who, stream);
+    on.run<eh_scalars_kernel>((unsigned)((ncosmo + 255) / 256), 256, 0, A);
+    return on.status();
 }

@@ -124,14 +124,10 @@ __global__ __launch_bounds__(M / P) void rfft_kernel(const RArgs A) {
 }
 
 template <int M, int P>
-void rlaunch(bool backward, const RArgs& A, int grid, hipStream_t stream) {
+void rlaunch(cp::Launches& on, bool backward, const RArgs& A, int grid) {
     constexpr int T = M / P, lds = WorkgroupFft<M, P>::lds_bytes();
-    if (lds > 64 * 1024) {
-        (void)cp::allow_full_lds<&rfft_kernel<M, P, true>>();
-        (void)cp::allow_full_lds<&rfft_kernel<M, P, false>>();
-    }
-    if (backward) hipLaunchKernelGGL((rfft_kernel<M, P, true>), dim3(grid), dim3(T), lds, stream, A);
-    else hipLaunchKernelGGL((rfft_kernel<M, P, false>), dim3(grid), dim3(T), lds, stream, A);
+    if (backward) on.run<rfft_kernel<M, P, true>>(grid, T, lds, A);
+    else on.run<rfft_kernel<M, P, false>>(grid, T, lds, A);
 }
 
 // X(M, P): half sizes and points per thread
@@ -182,12 +178,12 @@ static int rfft_run(const cp_rfft_plan* p, const double* d_in, double* d_out, lo
     A.in = d_in; A.out = d_out; A.nrows = nrows; A.tw = p->d_tw; A.rot = p->d_rot; A.conj_input = conj_input;
     const int m = p->size / 2;
     const int grid = (int)(nrows < 2048 ? nrows : 2048);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    cp::Launches on(what, stream);
 #define X(M_, P_) \
-    if (m == M_) rlaunch<M_, P_>(backward, A, grid, s);
+    if (m == M_) rlaunch<M_, P_>(on, backward, A, grid);
     CP_RFFT_SIZES(X)
 #undef X
-    return cp::launch_status(what);
+    return on.status();
 }
 
 extern "C" int cp_rfft_forward(const cp_rfft_plan* p, const double* d_in, double* d_out, long long nrows, void* stream) {

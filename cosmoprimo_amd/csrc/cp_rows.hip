@@ -52,6 +52,7 @@ extern "C" int cp_rows_screen(const double* d_x, long long nrows, long long n, i
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_rows_screen: cannot select device %d", device);
     const unsigned grid = (unsigned)(nrows < 65536 ? nrows : 65536);
-    hipLaunchKernelGGL(rows_screen_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), d_x, nrows, n, require_positive, d_ok, d_scale);
-    return cp::launch_status("cp_rows_screen");
+    cp::Launches on("cp_rows_screen", stream);
+    on.run<rows_screen_kernel>(grid, 256, 0, d_x, nrows, n, require_positive, d_ok, d_scale);
+    return on.status();
 }

@@ -878,15 +878,9 @@ __global__ __launch_bounds__(NP / P, 2) void fftlog_geospline_kernel(const GeoAr
 }
 
 template <int ENGINE>
-hipError_t launch(const SigmaArgs& S, int grid, size_t lds, hipStream_t stream) {
-    if (S.qe) {      // the radii come from B-spline coefficients
-        if (lds > 64 * 1024) (void)cp::allow_full_lds<&sigma_rz_kernel<ENGINE, true>>();
-        hipLaunchKernelGGL((sigma_rz_kernel<ENGINE, true>), dim3(grid), dim3(NP / P), lds, stream, S);
-        return hipGetLastError();
-    }
-    if (lds > 64 * 1024) (void)cp::allow_full_lds<&sigma_rz_kernel<ENGINE, false>>();
-    hipLaunchKernelGGL((sigma_rz_kernel<ENGINE, false>), dim3(grid), dim3(NP / P), lds, stream, S);
-    return hipGetLastError();
+void launch(cp::Launches& on, const SigmaArgs& S, int grid, size_t lds) {
+    if (S.qe) on.run<sigma_rz_kernel<ENGINE, true>>(grid, NP / P, lds, S);      // the radii come from B-spline coefficients
+    else on.run<sigma_rz_kernel<ENGINE, false>>(grid, NP / P, lds, S);
 }
 
 // what the fused kernel needs of a prefiltered spline plan (cp_geospline_plan, below)
@@ -930,7 +924,8 @@ int sigma_rz_fused_launch(const char* who, int engine, long long ncosmo, const c
     const int st = cpcosmo::ncdm_knots(nsp, device, who, &knots);
     if (st != CP_OK) return st;
     const cp::CoefWorkspace w = cp::coef_workspace(d_work, ncosmo);
-    cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, knots, pk_params, w.coef, stream, d_k, w.ln_k, f.n);      // (and the table of the wavenumbers)
+    cp::Launches on(who, stream);
+    cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, knots, pk_params, w.coef, on, d_k, w.ln_k, f.n);      // (and the table of the wavenumbers)
     SigmaArgs S{};
     S.fft = fused_fftlog_args(f, nullptr, ncosmo);
     cpcosmo::fill_cosmology(S, ncosmo, bg_params, pk_params, second_is_omega_m, ncdm, nsp, nullptr, w.coef);
@@ -956,9 +951,8 @@ int sigma_rz_fused_launch(const char* who, int engine, long long ncosmo, const c
         int d = 1, m = 1, sl = 0;
         if (std::sscanf(env, "%d,%d,%d", &d, &m, &sl) == 3 && d >= 1 && m >= 1 && sl >= 0 && sl <= 4096) { S.stagger_div = d; S.stagger_mod = m; S.stagger_sleeps = sl; }
     }
-    hipError_t e = hipSuccess;
-    cpcosmo::dispatch_engine(engine, [&](auto en) { e = launch<decltype(en)::value>(S, grid, lds, static_cast<hipStream_t>(stream)); });
-    return cp::launch_status(who, e);
+    cpcosmo::dispatch_engine(engine, [&](auto en) { launch<decltype(en)::value>(on, S, grid, lds); });
+    return on.status();
 }
 
 }  // namespace
@@ -1115,7 +1109,8 @@ int functional_launch(const char* who, bool normalise, FunctionalArgs& S, int en
     st = cpcosmo::ncdm_knots(nsp, device, who, &knots);
     if (st != CP_OK) return st;
     const cp::CoefWorkspace w = cp::coef_workspace(d_work, ncosmo);
-    cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, knots, pk_params, w.coef, stream, d_k, w.ln_k, nk);      // (and the table of the wavenumbers)
+    cp::Launches on(who, stream);
+    cp_power_coefficients(engine, ncosmo, bg_params, second_is_omega_m, ncdm, nsp, knots, pk_params, w.coef, on, d_k, w.ln_k, nk);      // (and the table of the wavenumbers)
     cpcosmo::fill_cosmology(S, ncosmo, bg_params, pk_params, second_is_omega_m, ncdm, nsp, knots, w.coef);
     S.nk = nk;
     S.k = d_k;
@@ -1123,13 +1118,12 @@ int functional_launch(const char* who, bool normalise, FunctionalArgs& S, int en
     S.functional = d_functional;
     S.pk_out = d_pk_out;
     const dim3 grid((unsigned)((ncosmo + 3) / 4));
-    hipStream_t hs = static_cast<hipStream_t>(stream);
     cpcosmo::dispatch_engine(engine, [&](auto e) {
         constexpr int ENGINE = decltype(e)::value;
-        if (normalise) hipLaunchKernelGGL(sigma8_normalise_kernel<ENGINE>, grid, dim3(256), 0, hs, S);
-        else hipLaunchKernelGGL(sigma_functional_kernel<ENGINE>, grid, dim3(256), 0, hs, S);
+        if (normalise) on.run<sigma8_normalise_kernel<ENGINE>>(grid, 256, 0, S);
+        else on.run<sigma_functional_kernel<ENGINE>>(grid, 256, 0, S);
     });
-    return cp::launch_status(who);
+    return on.status();
 }
 
 }  // namespace
@@ -1189,9 +1183,9 @@ extern "C" int cp_fftlog_spline_execute(const cp_fftlog_plan* fftlog, const cp_s
     using F = Fftlog<NP, P, IN_HALF_ZERO, OUT_HALF>;
     const size_t lds = (size_t)F::LDS_BYTES + (size_t)(2 * b.nq) * sizeof(double);
     if (lds > 160 * 1024) return cp::fail(CP_EUNSUPPORTED, "cp_fftlog_spline_execute: %d queries exceed the LDS staging", b.nq);
-    if (lds > 64 * 1024) (void)cp::allow_full_lds<&fftlog_spline_kernel>();
-    hipLaunchKernelGGL(fftlog_spline_kernel, dim3(pairs_grid(nbatch, lds, f.device)), dim3(NP / P), lds, static_cast<hipStream_t>(stream), R);
-    return cp::launch_status("cp_fftlog_spline_execute");
+    cp::Launches on("cp_fftlog_spline_execute", stream);
+    on.run<fftlog_spline_kernel>(pairs_grid(nbatch, lds, f.device), NP / P, lds, R);
+    return on.status();
 }
 
 // ---- natural spline on a geometric grid, solved inside the FFTLog kernel (fftlog_geospline_kernel above) -----------------------------------------
@@ -1466,9 +1460,6 @@ extern "C" int cp_fftlog_geospline_execute(const cp_fftlog_plan* fftlog, const c
     // (prefiltered: the coefficients of the stretch behind the FFT's tables; up to 373 knots keep four workgroups on a CU)
     const size_t lds = (size_t)F::LDS_BYTES + (coef ? (((size_t)2 * (spline->ne + 2) * sizeof(double) + 15) / 16) * 16 : 0);
     const bool few = spline->nq <= 256;
-    if (lds > 64 * 1024)
-        (void)(!coef ? cp::allow_full_lds<&fftlog_geospline_kernel<false>>()
-                     : few ? cp::allow_full_lds<&fftlog_geospline_kernel<true, 4>>() : cp::allow_full_lds<&fftlog_geospline_kernel<true, GEO_QMAX>>());
     const long long resident = (long long)cp::cu_count(f.device) * workgroups_per_cu(lds);
     long long grid;
     if (group > 0) {      // a multiple of 8 (one share per XCD), every workgroup of an XCD the same number of rounds
@@ -1478,8 +1469,9 @@ extern "C" int cp_fftlog_geospline_execute(const cp_fftlog_plan* fftlog, const c
     } else {
         grid = cp::balanced_grid((nbatch + 1) / 2, resident);
     }
-    if (coef && few) hipLaunchKernelGGL((fftlog_geospline_kernel<true, 4>), dim3((unsigned)grid), dim3(NP / P), lds, static_cast<hipStream_t>(stream), R);
-    else if (coef) hipLaunchKernelGGL((fftlog_geospline_kernel<true, GEO_QMAX>), dim3((unsigned)grid), dim3(NP / P), lds, static_cast<hipStream_t>(stream), R);
-    else hipLaunchKernelGGL(fftlog_geospline_kernel<false>, dim3((unsigned)grid), dim3(NP / P), lds, static_cast<hipStream_t>(stream), R);
-    return cp::launch_status("cp_fftlog_geospline_execute");
+    cp::Launches on("cp_fftlog_geospline_execute", stream);
+    if (coef && few) on.run<fftlog_geospline_kernel<true, 4>>((unsigned)grid, NP / P, lds, R);
+    else if (coef) on.run<fftlog_geospline_kernel<true, GEO_QMAX>>((unsigned)grid, NP / P, lds, R);
+    else on.run<fftlog_geospline_kernel<false>>((unsigned)grid, NP / P, lds, R);
+    return on.status();
 }

@@ -235,23 +235,17 @@ __global__ __launch_bounds__(256) void splice_uniform_kernel(const Args A) {
     }
 }
 
-template <int S>
-inline hipError_t launch_s(const Args& A, unsigned grid, size_t lds, hipStream_t stream) {
-    (void)cp::allow_full_lds<&splice_uniform_kernel<S>>();
-    hipLaunchKernelGGL(splice_uniform_kernel<S>, dim3(grid), dim3(256), lds, stream, A);
-    return hipGetLastError();
-}
-
-inline hipError_t launch(const Args& A, unsigned grid, size_t lds, hipStream_t stream) {
+// false: no instantiation for the plan's samples per segment
+inline bool launch(cp::Launches& on, const Args& A, unsigned grid, size_t lds) {
     switch (A.T.S) {
-        case 33: return launch_s<33>(A, grid, lds, stream);
-        case 37: return launch_s<37>(A, grid, lds, stream);
-        case 41: return launch_s<41>(A, grid, lds, stream);
-        case 45: return launch_s<45>(A, grid, lds, stream);
-        case 49: return launch_s<49>(A, grid, lds, stream);
-        case 53: return launch_s<53>(A, grid, lds, stream);
-        case 57: return launch_s<57>(A, grid, lds, stream);
-        default: return hipErrorInvalidValue;
+        case 33: on.run<splice_uniform_kernel<33>>(grid, 256, lds, A); return true;
+        case 37: on.run<splice_uniform_kernel<37>>(grid, 256, lds, A); return true;
+        case 41: on.run<splice_uniform_kernel<41>>(grid, 256, lds, A); return true;
+        case 45: on.run<splice_uniform_kernel<45>>(grid, 256, lds, A); return true;
+        case 49: on.run<splice_uniform_kernel<49>>(grid, 256, lds, A); return true;
+        case 53: on.run<splice_uniform_kernel<53>>(grid, 256, lds, A); return true;
+        case 57: on.run<splice_uniform_kernel<57>>(grid, 256, lds, A); return true;
+        default: return false;
     }
 }
 

@@ -233,13 +233,10 @@ __global__ __launch_bounds__(256) void spline_outer_kernel(const OuterArgs O) {
 }
 
 template <int R>
-hipError_t launch_outer(const OuterArgs& O, size_t lds, hipStream_t stream) {
-    if (lds > 64 * 1024)
-        (void)cp::allow_full_lds<&spline_outer_kernel<R>>();
+void launch_outer(cp::Launches& on, const OuterArgs& O, size_t lds) {
     const long long nitems = ((O.a.nrows + R - 1) / R) * O.a.ntiles;
     const int grid = (int)(nitems < 256 * 8 ? nitems : 256 * 8);
-    hipLaunchKernelGGL(spline_outer_kernel<R>, dim3(grid), dim3(256), lds, stream, O);
-    return hipGetLastError();
+    on.run<spline_outer_kernel<R>>(grid, 256, lds, O);
 }
 
 // ---- dense operators on the matrix cores -------------------------------------------------------------------------------------------
@@ -507,13 +504,10 @@ __global__ __launch_bounds__(256, 4) void linop_mid_mfma_kernel(const MidArgs A)
 }
 
 template <int R>
-hipError_t launch_apply(const Args& A, size_t lds, hipStream_t stream) {
-    if (lds > 64 * 1024)
-        (void)cp::allow_full_lds<&spline_apply_kernel<R>>();
+void launch_apply(cp::Launches& on, const Args& A, size_t lds) {
     const long long nitems = ((A.nrows + R - 1) / R) * A.ntiles;
     const int grid = (int)(nitems < 256 * 8 ? nitems : 256 * 8);
-    hipLaunchKernelGGL(spline_apply_kernel<R>, dim3(grid), dim3(256), lds, stream, A);
-    return hipGetLastError();
+    on.run<spline_apply_kernel<R>>(grid, 256, lds, A);
 }
 
 // scipy.interpolate.CubicSpline: tridiagonal system for the knot first derivatives s (lower, diag, upper) and the
@@ -910,9 +904,10 @@ extern "C" int cp_spline_apply_grouped(const cp_spline_plan* p, const double* d_
         D.kwin = p->d_kwin; D.post_op = post_op; D.scale = scale; D.group = group;
         const long long items = ((nrows + 16 * LINOP_MT - 1) / (16 * LINOP_MT)) * ((p->nq_pad + 255) / 256);
         const int grid = (int)(items < 256 * 2 ? items : 256 * 2);
-        if (p->sub_windows) hipLaunchKernelGGL(linop_mfma_kernel<true>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), D);
-        else hipLaunchKernelGGL(linop_mfma_kernel<false>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), D);
-        return cp::launch_status("cp_spline_apply");
+        cp::Launches on("cp_spline_apply", stream);
+        if (p->sub_windows) on.run<linop_mfma_kernel<true>>(grid, 256, 0, D);
+        else on.run<linop_mfma_kernel<false>>(grid, 256, 0, D);
+        return on.status();
     }
     // rows per work item: as many as keep the staged knots within 64 KB of LDS (two workgroups per CU), and no more than there are rows
     int rows = 16;
@@ -927,8 +922,11 @@ extern "C" int cp_spline_apply_grouped(const cp_spline_plan* p, const double* d_
     A.y = d_y; A.out = d_out; A.nrows = nrows; A.n = p->n; A.nq = p->nq; A.bw = p->bw; A.wb = p->d_wb; A.j0 = p->d_j0;
     A.tile = p->d_tile; A.ntiles = p->ntiles; A.span_max = p->span_max;
     A.post_op = post_op; A.scale = scale; A.group = group;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    return cp::launch_status("cp_spline_apply", rows == 16 ? launch_apply<16>(A, lds, hs) : rows == 8 ? launch_apply<8>(A, lds, hs) : launch_apply<4>(A, lds, hs));
+    cp::Launches on("cp_spline_apply", stream);
+    if (rows == 16) launch_apply<16>(on, A, lds);
+    else if (rows == 8) launch_apply<8>(on, A, lds);
+    else launch_apply<4>(on, A, lds);
+    return on.status();
 }
 
 
@@ -953,8 +951,11 @@ extern "C" int cp_spline_apply_outer(const cp_spline_plan* p, const double* d_y,
     A.tile = p->d_tile; A.ntiles = p->ntiles; A.span_max = p->span_max;
     A.post_op = post_op; A.scale = scale; A.group = 0;
     O.g = d_g; O.nz = nz;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    return cp::launch_status("cp_spline_apply_outer", rows == 8 ? launch_outer<8>(O, lds, hs) : rows == 4 ? launch_outer<4>(O, lds, hs) : launch_outer<2>(O, lds, hs));
+    cp::Launches on("cp_spline_apply_outer", stream);
+    if (rows == 8) launch_outer<8>(on, O, lds);
+    else if (rows == 4) launch_outer<4>(on, O, lds);
+    else launch_outer<2>(on, O, lds);
+    return on.status();
 }
 
 
@@ -974,8 +975,9 @@ extern "C" int cp_linop_apply_mid(const cp_spline_plan* p, const double* d_y, do
     M.w = p->d_wdense; M.j0 = p->d_j0; M.post_op = post_op; M.scale = scale;
     const long long items = nbatch * ((ninner + 64 * MID_NT - 1) / (64 * MID_NT)) * (p->nq_pad / 64);
     const int grid = (int)(items < 256 * 8 ? items : 256 * 8);
-    hipLaunchKernelGGL(linop_mid_mfma_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), M);
-    return cp::launch_status("cp_linop_apply_mid");
+    cp::Launches on("cp_linop_apply_mid", stream);
+    on.run<linop_mid_mfma_kernel>(grid, 256, 0, M);
+    return on.status();
 }
 
 
@@ -1354,11 +1356,11 @@ extern "C" int cp_tables_rows(const cp_spline_plan* kplan, const cp_spline_plan*
     T.post_op = post_op; T.scale = scale;
     const long long items = nbatch * ((kplan->nq_pad + 255) / 256);
     const int grid = (int)(items < 256 * 2 ? items : 256 * 2);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    if (post_op == CP_SPLINE_POST_EXP10) hipLaunchKernelGGL(tables_rows_kernel<CP_SPLINE_POST_EXP10>, dim3(grid), dim3(256), 0, hs, T);
-    else if (post_op == CP_SPLINE_POST_SQRT) hipLaunchKernelGGL(tables_rows_kernel<CP_SPLINE_POST_SQRT>, dim3(grid), dim3(256), 0, hs, T);
-    else hipLaunchKernelGGL(tables_rows_kernel<CP_SPLINE_POST_NONE>, dim3(grid), dim3(256), 0, hs, T);
-    return cp::launch_status("cp_tables_rows");
+    cp::Launches on("cp_tables_rows", stream);
+    if (post_op == CP_SPLINE_POST_EXP10) on.run<tables_rows_kernel<CP_SPLINE_POST_EXP10>>(grid, 256, 0, T);
+    else if (post_op == CP_SPLINE_POST_SQRT) on.run<tables_rows_kernel<CP_SPLINE_POST_SQRT>>(grid, 256, 0, T);
+    else on.run<tables_rows_kernel<CP_SPLINE_POST_NONE>>(grid, 256, 0, T);
+    return on.status();
 }
 
 extern "C" int cp_tables_rows_direct(const cp_spline_rows_plan* kplan, const cp_spline_plan* zplan, const double* d_tables, const double* d_m, double* d_out,
@@ -1384,16 +1386,16 @@ extern "C" int cp_tables_rows_direct(const cp_spline_rows_plan* kplan, const cp_
     const int nqt = (kv.nq + 255) / 256;
     const long long items = nbatch * nqt;
     const int grid = (int)(items < 256 * 8 ? items : (256 * 8 / nqt > 0 ? (256 * 8 / nqt) * nqt : nqt));      // a multiple of the tiles of a row: a workgroup keeps its tile
-    hipStream_t hs = static_cast<hipStream_t>(stream);
+    cp::Launches on("cp_tables_rows_direct", stream);
     auto launch = [&](auto pairs) {
         constexpr bool PAIRS = decltype(pairs)::value;
-        if (post_op == CP_SPLINE_POST_EXP10) hipLaunchKernelGGL((tables_rows_direct_kernel<CP_SPLINE_POST_EXP10, PAIRS>), dim3(grid), dim3(256), 0, hs, T);
-        else if (post_op == CP_SPLINE_POST_SQRT) hipLaunchKernelGGL((tables_rows_direct_kernel<CP_SPLINE_POST_SQRT, PAIRS>), dim3(grid), dim3(256), 0, hs, T);
-        else hipLaunchKernelGGL((tables_rows_direct_kernel<CP_SPLINE_POST_NONE, PAIRS>), dim3(grid), dim3(256), 0, hs, T);
+        if (post_op == CP_SPLINE_POST_EXP10) on.run<tables_rows_direct_kernel<CP_SPLINE_POST_EXP10, PAIRS>>(grid, 256, 0, T);
+        else if (post_op == CP_SPLINE_POST_SQRT) on.run<tables_rows_direct_kernel<CP_SPLINE_POST_SQRT, PAIRS>>(grid, 256, 0, T);
+        else on.run<tables_rows_direct_kernel<CP_SPLINE_POST_NONE, PAIRS>>(grid, 256, 0, T);
     };
     if (d_m) launch(std::false_type{});
     else launch(std::true_type{});
-    return cp::launch_status("cp_tables_rows_direct");
+    return on.status();
 }
 
 // ---- clamped cubic spline through uniformly spaced knots with one run of knots removed -------------------------------------
@@ -1489,8 +1491,9 @@ extern "C" int cp_gap_spline(const double* d_y, const int* d_box, double* d_out,
     if (ncol > 2147483647LL) return cp::fail(CP_EUNSUPPORTED, "cp_gap_spline: too many columns for one launch");
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_gap_spline: cannot select device %d", device);
-    hipLaunchKernelGGL(gap_spline_kernel, dim3((unsigned)ncol), dim3(64), 0, static_cast<hipStream_t>(stream), d_y, d_box, d_out, ncol, n);
-    return cp::launch_status("cp_gap_spline");
+    cp::Launches on("cp_gap_spline", stream);
+    on.run<gap_spline_kernel>((unsigned)ncol, 64, 0, d_y, d_box, d_out, ncol, n);
+    return on.status();
 }
 
 
@@ -1544,9 +1547,9 @@ extern "C" int cp_wallish_box(const double* d_dd, long long ncol, int n, int mar
     if ((ncol + 3) / 4 > 2147483647LL) return cp::fail(CP_EUNSUPPORTED, "cp_wallish_box: too many columns for one launch");
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_wallish_box: cannot select device %d", device);
-    hipLaunchKernelGGL(wallish_box_kernel, dim3((unsigned)((ncol + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), d_dd, ncol, n, margin_first,
-                       margin_second, offset_first, offset_second, d_box);
-    return cp::launch_status("cp_wallish_box");
+    cp::Launches on("cp_wallish_box", stream);
+    on.run<wallish_box_kernel>((unsigned)((ncol + 3) / 4), 256, 0, d_dd, ncol, n, margin_first, margin_second, offset_first, offset_second, d_box);
+    return on.status();
 }
 
 
@@ -1679,7 +1682,7 @@ extern "C" int cp_spline_columns(const double* d_xk, const double* d_yk, long lo
     if (!d_xk || !d_yk || !d_xq || !d_out || !d_scratch) return cp::fail(CP_EINVAL, "cp_spline_columns: null device pointer");
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_spline_columns: cannot select device %d", device);
-    hipLaunchKernelGGL(column_spline_kernel, dim3((unsigned)((ncol + 63) / 64 * column_parts(n))), dim3(64), 0, static_cast<hipStream_t>(stream), d_xk, d_yk,
-                       ncol, n, d_xq, nq, d_out, d_scratch);
-    return cp::launch_status("cp_spline_columns");
+    cp::Launches on("cp_spline_columns", stream);
+    on.run<column_spline_kernel>((unsigned)((ncol + 63) / 64 * column_parts(n)), 64, 0, d_xk, d_yk, ncol, n, d_xq, nq, d_out, d_scratch);
+    return on.status();
 }

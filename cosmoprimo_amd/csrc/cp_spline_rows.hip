@@ -336,14 +336,11 @@ static int launch_rows(const char* who, const cp_spline_rows_plan* p, const Rows
     long long per_cu = (160 * 1024) / (long long)p->lds_bytes;
     per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
     const unsigned grid = (unsigned)std::min(blocks, (long long)ncu * per_cu);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    if (p->T.R == 4) (void)cp::allow_full_lds<&spline_rows_kernel<4>>();
-    else if (p->T.R == 2) (void)cp::allow_full_lds<&spline_rows_kernel<2>>();
-    else (void)cp::allow_full_lds<&spline_rows_kernel<1>>();
-    if (p->T.R == 4) hipLaunchKernelGGL(spline_rows_kernel<4>, dim3(grid), dim3(256), p->lds_bytes, hs, A);
-    else if (p->T.R == 2) hipLaunchKernelGGL(spline_rows_kernel<2>, dim3(grid), dim3(256), p->lds_bytes, hs, A);
-    else hipLaunchKernelGGL(spline_rows_kernel<1>, dim3(grid), dim3(256), p->lds_bytes, hs, A);
-    return cp::launch_status(who);
+    cp::Launches on(who, stream);
+    if (p->T.R == 4) on.run<spline_rows_kernel<4>>(grid, 256, p->lds_bytes, A);
+    else if (p->T.R == 2) on.run<spline_rows_kernel<2>>(grid, 256, p->lds_bytes, A);
+    else on.run<spline_rows_kernel<1>>(grid, 256, p->lds_bytes, A);
+    return on.status();
 }
 
 extern "C" int cp_spline_rows_apply(const cp_spline_rows_plan* p, const double* d_y, long long nrows, int post_op, double scale, int group, double* d_out,

@@ -223,6 +223,7 @@ int spline_tables_apply(const double* d_xk, const double* d_coef, const int* d_o
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
     hipStream_t hs = static_cast<hipStream_t>(stream);
+    cp::Launches on(who, stream);
     int* flag = outside ? d_flag : nullptr;
     if (flag && hipMemsetAsync(flag, 0, sizeof(int), hs) != hipSuccess) return cp::fail(CP_EDEVICE, "%s: clearing the range flag failed", who);
     const ApplyArgs A{d_xk, d_coef, d_ok, nrows, nq, n, per_row ? 1 : 0, flag};
@@ -232,14 +233,13 @@ int spline_tables_apply(const double* d_xk, const double* d_coef, const int* d_o
         nsplit = nsplit < cap ? nsplit : cap;
         nsplit = nsplit < 1 ? 1 : nsplit;
         const size_t lds = (size_t)(n + 4 * (n - 1)) * sizeof(double);
-        if (lds > 64 * 1024) (void)cp::allow_full_lds<&spline_tables_lds_kernel<real>>();
-        hipLaunchKernelGGL(spline_tables_lds_kernel<real>, dim3((unsigned)(nrows * nsplit)), dim3(256), lds, hs, A, d_xq, d_out, (int)nsplit);
+        on.run<spline_tables_lds_kernel<real>>((unsigned)(nrows * nsplit), 256, lds, A, d_xq, d_out, (int)nsplit);
     } else {
         const long long blocks = (nrows * nq + 255) / 256;
         const unsigned grid = (unsigned)(blocks < 256 * 16 ? blocks : 256 * 16);
-        hipLaunchKernelGGL(spline_tables_rows_kernel<real>, dim3(grid), dim3(256), 0, hs, A, d_xq, d_out);
+        on.run<spline_tables_rows_kernel<real>>(grid, 256, 0, A, d_xq, d_out);
     }
-    int st = cp::launch_status(who);
+    int st = on.status();
     if (st == CP_OK && outside) {      // the flag comes back with the stream drained (cp_interp_table_apply)
         int host = 0;
         if (hipMemcpyAsync(&host, d_flag, sizeof(int), hipMemcpyDeviceToHost, hs) != hipSuccess || hipStreamSynchronize(hs) != hipSuccess)
@@ -261,10 +261,10 @@ extern "C" int cp_spline_tables_build(const double* d_xk, const double* d_y, lon
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_spline_tables_build: cannot select device %d", device);
     const size_t lds = (size_t)4 * n * sizeof(double);
-    if (lds > 64 * 1024) (void)cp::allow_full_lds<&spline_tables_build_kernel>();
     const unsigned grid = (unsigned)(nrows < 256 * 32 ? nrows : 256 * 32);
-    hipLaunchKernelGGL(spline_tables_build_kernel, dim3(grid), dim3(64), lds, static_cast<hipStream_t>(stream), d_xk, d_y, nrows, n, order, d_coef, d_ok);
-    return cp::launch_status("cp_spline_tables_build");
+    cp::Launches on("cp_spline_tables_build", stream);
+    on.run<spline_tables_build_kernel>(grid, 64, lds, d_xk, d_y, nrows, n, order, d_coef, d_ok);
+    return on.status();
 }
 
 extern "C" int cp_spline_tables_apply(const double* d_xk, const double* d_coef, const int* d_ok, long long nrows, int n, const double* d_xq, int per_row,

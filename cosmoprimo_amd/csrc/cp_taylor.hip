@@ -100,14 +100,14 @@ __global__ __launch_bounds__(256) void taylor_input_grad_kernel(const double* x,
     if (wave == 0 && r < R) grad[r] = g;
 }
 
-// The GEMM on the stream, inside the device scope of the entry point that calls it
+// The GEMM among the launches of the entry point that calls it: its grid's check; the launch status is the entry point's to read
 template <int FRONT>
-int taylor_launch(const char* who, const TaylorArgs& A, void* stream) {
+int taylor_launch(cp::Launches& on, const TaylorArgs& A) {
     // the row tiles along x: workgroups are dispatched x first, so those in flight share their 256 columns of the right operand in L2
     const long long nrt = (A.R + TY_ROWS - 1) / TY_ROWS, nct = (A.cend - A.c0 + TY_COLS - 1) / TY_COLS;
-    if (nrt > 0x7fffffffLL || nct > 65535) return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d results (at most 2^37 rows, 2^24 - 256 columns)", who, A.R, A.M);
-    const int launched = taylor_gemm_launch<FRONT>(who, A, dim3((unsigned)nrt, (unsigned)nct), A.ndim, 0, stream);      // at most 56 KB of LDS
-    return launched != CP_OK ? launched : cp::launch_status(who);
+    if (nrt > 0x7fffffffLL || nct > 65535) return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d results (at most 2^37 rows, 2^24 - 256 columns)", on.who(), A.R, A.M);
+    taylor_gemm_launch<FRONT>(on, A, dim3((unsigned)nrt, (unsigned)nct), A.ndim, 0);
+    return CP_OK;
 }
 
 // What cp_taylor_predict, cp_taylor_predict_columns, cp_taylor_jacobian, cp_taylor_vjp and cp_taylor_jvp share: their checks, in that order, up to the caps of ndim and
@@ -131,10 +131,10 @@ int cp::taylor_front_checks(const char* who, long long B, int ndim, int T, int m
     return taylor_front(who, B, ndim, T, max_power, M, col0, ncols, ld, what);
 }
 
-int cp::taylor_predict_launch(const char* who, const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T,
-                              const double* d_derivatives, int M, long long col0, long long ncols, double* d_out, long long ldo, void* stream) {
+int cp::taylor_predict_launch(Launches& on, const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T,
+                              const double* d_derivatives, int M, long long col0, long long ncols, double* d_out, long long ldo) {
     const TaylorArgs A{d_x, d_center, d_powers, d_derivatives, d_out, B, ldo, T, M, ndim, (int)col0, (int)(col0 + ncols), 0};
-    return taylor_launch<TY_PREDICT>(who, A, stream);
+    return taylor_launch<TY_PREDICT>(on, A);
 }
 
 // cp_taylor_predict is the range [0, M) with row stride M of the same call
@@ -147,7 +147,9 @@ static int taylor_predict(const char* who, const double* d_x, long long B, const
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
     const TaylorArgs A{d_x, d_center, d_powers, d_derivatives, d_out, B, ldo, T, M, ndim, (int)col0, (int)(col0 + ncols), 0};
-    return taylor_launch<TY_PREDICT>(who, A, stream);
+    cp::Launches on(who, stream);
+    const int launched = taylor_launch<TY_PREDICT>(on, A);
+    return launched != CP_OK ? launched : on.status();
 }
 
 extern "C" int cp_taylor_predict(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
@@ -173,7 +175,9 @@ extern "C" int cp_taylor_jacobian(const double* d_x, long long B, const double* 
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
     const TaylorArgs A{d_x, d_center, d_powers, d_derivatives, d_jac, B * ndim, ldj, T, M, ndim, (int)col0, (int)(col0 + ncols), 0};
-    return taylor_launch<TY_JACOBIAN>(who, A, stream);
+    cp::Launches on(who, stream);
+    const int launched = taylor_launch<TY_JACOBIAN>(on, A);
+    return launched != CP_OK ? launched : on.status();
 }
 
 // One launch: the GEMM with the jvp front end on the B K rows (b, k)
@@ -192,8 +196,9 @@ extern "C" int cp_taylor_jvp(const double* d_x, long long B, const double* d_cen
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
     const TaylorJvpArgs A{{d_x, d_center, d_powers, d_derivatives, d_out, B * K, ldo, T, M, ndim, (int)col0, (int)(col0 + ncols), 0}, d_tan, (int)K};
     const long long nrt = (B * K + TY_ROWS - 1) / TY_ROWS, nct = (ncols + TY_COLS - 1) / TY_COLS;
-    const int launched = taylor_gemm_launch<TY_JVP>(who, A, dim3((unsigned)nrt, (unsigned)nct), ndim, 0, stream);      // at most 72 KB of LDS
-    return launched != CP_OK ? launched : cp::launch_status(who);
+    cp::Launches on(who, stream);
+    taylor_gemm_launch<TY_JVP>(on, A, dim3((unsigned)nrt, (unsigned)nct), ndim, 0);
+    return on.status();
 }
 
 extern "C" long long cp_taylor_vjp_workspace_doubles(long long B, int T) {
@@ -217,12 +222,13 @@ extern "C" int cp_taylor_vjp(const double* d_x, long long B, const double* d_cen
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
     // S (B, T) = cot (B, ncols) . Dt[col0 : col0 + ncols] (ncols, T)
     const TaylorArgs A{d_cot, nullptr, nullptr, d_derivatives_t + col0 * T, d_work, B, T, (int)ncols, T, 0, 0, T, ldc};
-    const int launched = taylor_launch<TY_FIT>(who, A, stream);
+    cp::Launches on(who, stream);
+    const int launched = taylor_launch<TY_FIT>(on, A);
     if (launched != CP_OK) return launched;
     const long long R = B * ndim;
-    hipLaunchKernelGGL(taylor_input_grad_kernel, dim3((unsigned)((R + TY_ROWS - 1) / TY_ROWS)), dim3(256), (size_t)(2 * TY_KC + ndim) * TY_ROWS * sizeof(double) + 2 * 4 * TY_ROWS * sizeof(unsigned), static_cast<hipStream_t>(stream), d_x, d_center,
-                       d_powers, d_work, R, ndim, T, d_grad);
-    return cp::launch_status(who);
+    on.run<taylor_input_grad_kernel>((unsigned)((R + TY_ROWS - 1) / TY_ROWS), 256, (size_t)(2 * TY_KC + ndim) * TY_ROWS * sizeof(double) + 2 * 4 * TY_ROWS * sizeof(unsigned),
+                                     d_x, d_center, d_powers, d_work, R, ndim, T, d_grad);
+    return on.status();
 }
 
 extern "C" int cp_taylor_fit(const double* d_S, int T, int npoints, const double* d_Y, int M, double* d_derivatives, int device, void* stream) {
@@ -231,5 +237,7 @@ extern "C" int cp_taylor_fit(const double* d_S, int T, int npoints, const double
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_taylor_fit: cannot select device %d", device);
     const TaylorArgs A{d_S, nullptr, nullptr, d_Y, d_derivatives, T, M, npoints, M, 0, 0, M, npoints};
-    return taylor_launch<TY_FIT>("cp_taylor_fit", A, stream);
+    cp::Launches on("cp_taylor_fit", stream);
+    const int launched = taylor_launch<TY_FIT>(on, A);
+    return launched != CP_OK ? launched : on.status();
 }

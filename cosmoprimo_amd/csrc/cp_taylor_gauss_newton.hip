@@ -41,14 +41,14 @@ extern "C" int cp_taylor_gauss_newton(const double* d_x, long long B, const doub
     // the value on the range: to the caller's buffer, else to the workspace, if anything reads it
     double* value = d_value ? d_value : d_work + plan.value;
     const long long ldvalue = d_value ? ldv : ncols;
+    cp::Launches on(who, stream);
     if (d_value || d_data) {
-        status = cp::taylor_predict_launch(who, d_x, B, d_center, d_powers, ndim, T, d_derivatives, M, col0, ncols, value, ldvalue, stream);
+        status = cp::taylor_predict_launch(on, d_x, B, d_center, d_powers, ndim, T, d_derivatives, M, col0, ncols, value, ldvalue);
         if (status != CP_OK) return status;
     }
     TaylorGnArgs A{d_x, d_center, d_powers, d_derivatives, T, M,
                    cpgn::Tail{d_weights, d_data, value, d_work + plan.part, ldw, ldd, ldvalue, B, ndim, plan.P, (int)col0, (int)(col0 + ncols)}};
-    status = taylor_gemm_launch<TY_GAUSS_NEWTON>(who, A, dim3((unsigned)plan.nrt, (unsigned)plan.nct), ndim, cpgn::epilogue_lds_doubles(plan.P, ndim), stream);
-    if (status != CP_OK) return status;
-    cpgn::sum_launch(plan, A.tail, d_fisher, d_grad, d_chi2, stream);
-    return cp::launch_status(who);
+    taylor_gemm_launch<TY_GAUSS_NEWTON>(on, A, dim3((unsigned)plan.nrt, (unsigned)plan.nct), ndim, cpgn::epilogue_lds_doubles(plan.P, ndim));
+    cpgn::sum_launch(on, plan, A.tail, d_fisher, d_grad, d_chi2);
+    return on.status();
 }

@@ -324,17 +324,11 @@ __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const Args A) {
 }
 
 // The GEMM on the stream for the front end FRONT, inside the caller's device scope.  LDS: the two operand buffers, x - center, the jvp's tangents (at most
-// 72 KB), or the Gauss-Newton epilogue's `epilogue` doubles where those are more; above 64 KB the instantiation that is launched is allowed the whole LDS.
+// 72 KB), or the Gauss-Newton epilogue's `epilogue` doubles where those are more.
 template <int FRONT, class Args>
-int taylor_gemm_launch(const char* who, const Args& A, const dim3 grid, const int ndim, const size_t epilogue, void* stream) {
+void taylor_gemm_launch(cp::Launches& on, const Args& A, const dim3 grid, const int ndim, const size_t epilogue) {
     const size_t gemm = (size_t)2 * TY_KC * TY_RS + (size_t)(FRONT == TY_FIT ? 0 : FRONT == TY_JVP ? 2 : 1) * ndim * TY_ROWS;
-    const size_t lds = (gemm > epilogue ? gemm : epilogue) * sizeof(double);
-    if (lds > 64 * 1024) {
-        const hipError_t e = cp::allow_full_lds<taylor_gemm_kernel<FRONT, Args>>();
-        if (e != hipSuccess) return cp::launch_status(who, e);
-    }
-    hipLaunchKernelGGL((taylor_gemm_kernel<FRONT, Args>), grid, dim3(256), lds, static_cast<hipStream_t>(stream), A);
-    return CP_OK;
+    on.run<taylor_gemm_kernel<FRONT, Args>>(grid, 256, (gemm > epilogue ? gemm : epilogue) * sizeof(double), A);
 }
 
 }  // namespace

@@ -285,9 +285,10 @@ extern "C" int cp_kirkby2013_rows(const double* d_xi, double* d_xinow, long long
     const long long blocks = (nrows + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     const unsigned grid = (unsigned)(blocks < 2048 ? blocks : 2048);      // a wave per row, 8 workgroups per CU at most; the waves walk the rest
     const bool in_registers = ns % 2 == 0 && ns <= 128 * NV && aligned16(d_xi) && aligned16(d_xinow) && aligned16(d_s);
+    cp::Launches on("cp_kirkby2013_rows", stream);
     if (in_registers)
-        hipLaunchKernelGGL(kirkby_rows_kernel, dim3(grid), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), A);
+        on.run<kirkby_rows_kernel>(grid, BLOCK, 0, A);
     else
-        hipLaunchKernelGGL(kirkby_rows_any_kernel, dim3(grid), dim3(BLOCK), 0, static_cast<hipStream_t>(stream), A);
-    return cp::launch_status("cp_kirkby2013_rows");
+        on.run<kirkby_rows_any_kernel>(grid, BLOCK, 0, A);
+    return on.status();
 }
