@@ -211,6 +211,10 @@ SIGNATURES['cp_lm_layout'] = (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes
 # B, ndim; the state x, fisher, grad, chi2, lambda, status, naccepted; the trial xt, fisher_t, grad_t, chi2_t; lo, hi; up, down, lmin, lmax, ftol; next
 SIGNATURES['cp_lm_step'] = (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int] + [ctypes.c_void_p] * 13 + [ctypes.c_double] * 5 + [ctypes.c_void_p] + _WHERE)
 SIGNATURES['cp_spd_inverse'] = (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int] + [ctypes.c_void_p] * 3 + _WHERE)
+SIGNATURES['cp_gauss_newton_dense_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_longlong])
+# d_jac, ldj; B, ndim, ncols; d_value, ldv; d_data, ldd; d_precision, ldp; d_fisher, d_grad, d_chi2, d_work, work_doubles
+SIGNATURES['cp_gauss_newton_dense'] = (ctypes.c_int, _ARRAY + [ctypes.c_longlong, ctypes.c_int, ctypes.c_longlong] + _ARRAY + _ARRAY + _ARRAY + [ctypes.c_void_p] * 4 +
+                                       [ctypes.c_longlong] + _WHERE)
 SIGNATURES['cp_mlp_predict'] =(ctypes.c_int, _MLP_HEAD + [ctypes.c_void_p] + _WHERE)
 SIGNATURES['cp_mlp_predict_columns'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _WHERE)
 SIGNATURES['cp_mlp_jacobian'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _ARRAY + _WHERE)      # d_value, ldv; d_jac, ldj

@@ -12,7 +12,9 @@ The helpers that both engines' ``predict`` / ``jacobian`` / ``vjp`` open with (`
 import this module, which imports them only where it builds one.  Nothing on the path of a call imports anything: at B = 1 a call is its Python.
 
 ``Emulator.least_squares`` runs batched Levenberg-Marquardt fits on ``gauss_newton``; what stands between two of its calls is one launch, :func:`lm_step` (with
-:func:`lm_state` and :func:`spd_inverse`: module-level, over device tensors, for normal equations of any origin).
+:func:`lm_state` and :func:`spd_inverse`: module-level, over device tensors, for normal equations of any origin).  Under a dense precision matrix
+(``precision=``) the normal equations come from :func:`gauss_newton_dense`, module-level as well: one GEMM on a Jacobian of any origin, which the engines'
+``jacobian`` write run by run into one buffer (``out=``).
 """
 import numpy as np
 
@@ -56,6 +58,27 @@ def _operand(operand, B, ncols, device, what):
     if tuple(operand.shape) != (B, ncols):
         raise ValueError('{} must be of shape ({:d},) or ({:d}, {:d}), got {}'.format(what, ncols, B, ncols, tuple(operand.shape)))
     return _cotangent(operand, B, ncols, device)
+
+
+def _jacobian_out(d, out, B, ndim, width, return_value):
+    """What both engines' ``jacobian`` write: ``(value or None, ldv, jac, ldj)``.  ``out = (value or None, jac)``: the caller's device tensors, written in
+    place -- views (B, width) and (B, ndim, width) of wider buffers (a column slice of the operands of :func:`gauss_newton_dense`), float64 with contiguous
+    columns, the rows of ``jac`` ``ldj >= width`` apart with a point's rows following each other, those of ``value`` ``ldv >= width`` apart --; None: new
+    contiguous tensors (the value only where ``return_value`` asks for it or the engine writes it anyway)."""
+    if out is None:
+        return (_empty(d, B, width) if return_value else None), width, _empty(d, B, ndim, width), width
+    value, jac = out
+    torch = d['torch']
+    for tensor, shape in ((value, (B, width)), (jac, (B, ndim, width))):
+        if tensor is None:
+            continue
+        ld = int(tensor.stride(-2))
+        if tuple(tensor.shape) != shape or tensor.dtype != torch.float64 or tensor.device != d['device'] or (width > 1 and tensor.stride(-1) != 1) or ld < width \
+                or (tensor.ndim == 3 and B > 1 and tensor.stride(0) != ndim * ld):
+            raise ValueError('out must hold float64 tensors of shapes {} and {} on {} with contiguous columns and evenly spaced rows'.format((B, width), (B, ndim, width), d['device']))
+    if return_value and value is None:
+        raise ValueError('out holds no tensor for the value')
+    return value, int(value.stride(0)) if value is not None else width, jac, int(jac.stride(1))
 
 
 def _gauss_newton(d, check, entry, need, head, where, B, ndim, start, ncols, weights, data, return_value):
@@ -142,6 +165,62 @@ def spd_inverse(a):
     inv, info = torch.empty_like(a), torch.empty((int(a.shape[0]),), dtype=torch.int32, device=a.device)
     _lib.check(_lib.load().cp_spd_inverse(int(a.shape[0]), int(a.shape[1]), a.data_ptr(), inv.data_ptr(), info.data_ptr(), a.device.index, dv.stream_of(a.device)))
     return inv, info
+
+
+def _rows(x, shape, device, what):
+    """``(x, ld)``: the operand ``x`` of shape ``shape = (..., nrows, ncols)`` on ``device`` as ``cp_gauss_newton_dense`` reads it -- float64, columns contiguous,
+    rows ``ld >= ncols`` apart, a leading axis continuing the rows: the tensor itself where it is that already (rows of any admissible stride), else a
+    contiguous copy.  A host array is uploaded (through the cache of :func:`_device.upload`: read only)."""
+    torch = dv.torch()
+    x = x.to(device=device) if dv.is_torch(x) else dv.upload(np.asarray(x, dtype='f8'), device)
+    if tuple(x.shape) != shape:
+        raise ValueError('{} must be of shape {}, got {}'.format(what, shape, tuple(x.shape)))
+    ncols, ld = shape[-1], int(x.stride(-2))
+    if x.dtype != torch.float64 or (ncols > 1 and x.stride(-1) != 1) or ld < max(ncols, 1) or (x.ndim == 3 and x.stride(0) != shape[1] * ld):
+        x, ld = x.to(torch.float64).contiguous(), ncols
+    return x, ld
+
+
+def gauss_newton_dense(jacobian, value, precision, data=None):
+    """Fisher matrices and Gauss-Newton normal equations under a dense precision matrix, whatever produced the Jacobian, in one GEMM on the matrix cores
+    (``cp_gauss_newton_dense``, csrc/cp_gauss_newton_dense.hip).  ``jacobian`` (B, ndim, N), ``value`` (B, N) (None is accepted without ``data``),
+    ``precision`` (N, N), symmetric and finite, shared by all points, ``data`` (B, N) or one row (N,): device tensors, with rows of any stride of at
+    least N taken as they are, or host arrays (uploaded).  With ``A_b = [J_b ; data_b - value_b]`` and ``G_b = A_b P A_b^T``: returns ``fisher`` (B, ndim, ndim)
+    ``= G_b[:ndim, :ndim]`` (symmetric bit for bit), or with ``data`` ``(fisher, gradient, chi2)``, ``gradient`` (B, ndim) ``= G_b[:ndim, ndim]`` and ``chi2``
+    (B,) ``= G_b[ndim, ndim]``, device tensors.  A column ``c`` with ``precision[c, c] == 0`` is dropped, whatever the Jacobian, the value or the data hold there
+    (NaN included): a mask.  No atomics: two calls give the same bits.  Nothing is read back and the call does not wait for the device."""
+    torch = dv.torch()
+    device = dv.resolve_device(None, jacobian, value, precision, data)
+    if np.ndim(jacobian) != 3:
+        raise ValueError('jacobian must be of shape (B, ndim, N), got {}'.format(tuple(np.shape(jacobian))))
+    B, ndim, N = (int(s) for s in np.shape(jacobian))
+    jacobian, ldj = _rows(jacobian, (B, ndim, N), device, 'jacobian')
+    precision, ldp = _rows(precision, (N, N), device, 'precision')
+    if data is not None and value is None:
+        raise ValueError('data needs the value')
+    ldv = ldd = 0
+    if value is not None:
+        value, ldv = _rows(value, (B, N), device, 'value')
+    if data is not None:
+        data = data if dv.is_torch(data) else np.asarray(data, dtype='f8')
+        if data.ndim == 1:      # one row shared by all points
+            data = _rows(data[None], (1, N), device, 'data')[0]
+        else:
+            data, ldd = _rows(data, (B, N), device, 'data')
+    new = lambda *shape, **kwargs: (torch.zeros if kwargs.get('zero') else torch.empty)(shape, dtype=torch.float64, device=device)      # noqa: E731
+    empty = B == 0 or N == 0      # nothing to launch: zeros
+    fisher = new(B, ndim, ndim, zero=empty)
+    grad, chi2 = (new(B, ndim, zero=empty), new(B, zero=empty)) if data is not None else (None, None)
+    if not empty:
+        lib = _lib.load()
+        need = int(lib.cp_gauss_newton_dense_workspace_doubles(B, ndim, N))
+        if need < 0:
+            _lib.check(-need)
+        work = new(need)
+        ptr = lambda tensor: tensor.data_ptr() if tensor is not None else None      # noqa: E731
+        _lib.check(lib.cp_gauss_newton_dense(jacobian.data_ptr(), ldj, B, ndim, N, ptr(value), ldv, ptr(data), ldd, precision.data_ptr(), ldp, fisher.data_ptr(), ptr(grad),
+                                             ptr(chi2), work.data_ptr(), need, device.index, dv.stream_of(device)))
+    return fisher if data is None else (fisher, grad, chi2)
 
 
 def _tangent(tangents, B, ndim, device):
@@ -448,7 +527,61 @@ class Emulator(object):
 
         return [(start, stop, entries, block(weights, entries), block(data, entries) if data is not None else None) for start, stop, entries in runs], fixed
 
-    def gauss_newton(self, params, weights, data=None, device=False, return_value=False):
+    def _staged_dense(self, keys, precision, data, B, dev):
+        """What :meth:`gauss_newton` and :meth:`least_squares` read of a dense ``precision`` over the outputs ``keys`` (a sequence of distinct varied keys) and of
+        ``data`` (or None), checked, on the device ``dev``: ``(runs, N, precision, data block (B, N) or None)``.  ``runs``: ``[(start, stop, entries, q0), ...]``,
+        the maximal contiguous runs of :meth:`_plan` over ``keys``, run r filling the columns ``[q0, q0 + stop - start)`` of the N columns of the data
+        vector in the order of the column plan.  ``precision`` is given in the listed order (the outputs flattened in C order and concatenated as
+        listed); it is permuted here, once and on the device, to the order of the column plan."""
+        torch = dv.torch()
+        if isinstance(keys, dict):
+            raise TypeError('with a precision matrix, weights is the sequence of the output keys its rows and columns follow, not a dictionary')
+        keys = [keys] if isinstance(keys, str) else list(keys)
+        if len(set(keys)) != len(keys):
+            raise ValueError('keys listed twice in {}'.format(keys))
+        unknown = [key for key in keys if key not in self.varied_keys]
+        if unknown:
+            raise KeyError('no varied output {}'.format(unknown))
+        if data is not None:
+            unknown = [key for key in data if key not in keys]
+            if unknown:
+                raise KeyError('data for {}, which the precision matrix does not cover'.format(unknown))
+            missing = [key for key in keys if key not in data]
+            if missing:
+                raise ValueError('no data for {}'.format(missing))
+        sizes = {key: int(np.prod(shape, dtype='i8')) for key, shape in zip(self.varied_keys, self.varied_shapes)}
+        listed, N = {}, 0      # where a key starts in the listed order
+        for key in keys:
+            listed[key] = N
+            N += sizes[key]
+        if tuple(np.shape(precision)) != (N, N):
+            raise ValueError('precision must be of shape ({0:d}, {0:d}) for {1}, got {2}'.format(N, keys, tuple(np.shape(precision))))
+        runs, order, q = [], [], 0
+        for start, stop, entries in (self._plan(keys, exact=True)[0] if keys else []):
+            runs.append((start, stop, entries, q))
+            order += [np.arange(listed[key], listed[key] + hi - lo) for key, shape, lo, hi in entries]
+            q += stop - start
+        order = np.concatenate(order) if order else np.zeros(0, dtype='i8')
+        precision = precision.to(device=dev, dtype=torch.float64) if dv.is_torch(precision) else dv.upload(np.asarray(precision, dtype='f8'), dev)
+        if not np.array_equal(order, np.arange(N)):
+            index = dv.upload(order.astype('i8'), dev)
+            precision = precision.index_select(0, index).index_select(1, index)
+        dblock = None
+        if data is not None:
+            blocks = [torch.broadcast_to(dv.to_device(data[key], dev, cache=False).to(torch.float64), (B,) + shape).reshape(B, hi - lo)
+                      for start, stop, entries, q0 in runs for key, shape, lo, hi in entries]
+            dblock = blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1) if blocks else torch.zeros((B, 0), dtype=torch.float64, device=dev)
+        return runs, N, precision.contiguous(), dblock
+
+    def _dense_normal_equations(self, X, runs, precision, dblock, jac, value):
+        """One evaluation under a dense precision matrix: the engine's ``jacobian`` once per run, written straight into its column slice of ``jac``
+        (B, ndim, N) and -- where ``value`` (B, N) is given -- of ``value``, then :func:`gauss_newton_dense`."""
+        for start, stop, entries, q0 in runs:
+            q1 = q0 + stop - start
+            self.engine.jacobian(X, columns=(start, stop), return_value=value is not None, out=(value[:, q0:q1] if value is not None else None, jac[:, :, q0:q1]))
+        return gauss_newton_dense(jac, value, precision, data=dblock)
+
+    def gauss_newton(self, params, weights, data=None, device=False, return_value=False, precision=None):
         """Fisher matrices and Gauss-Newton normal equations of a weighted least-squares fit of ``data`` to the emulated outputs, for every point of a batch,
         with ``J`` the Jacobian of :meth:`jacobian` and ``y`` the prediction: ``fisher[b, i, j] = sum w J_i J_j``,
         ``gradient[b, i] = sum w (data - y) J_i``, ``chi2[b] = sum w (data - y)^2``, the sums over the entries of the outputs that ``weights`` names.
@@ -465,9 +598,42 @@ class Emulator(object):
         device without forming the Jacobian (:meth:`MLPEmulatorEngine.gauss_newton`, :meth:`TaylorEmulatorEngine.gauss_newton`): the columns are planned
         by :func:`column_runs` over the varied keys of ``weights``, one call of the engine per maximal contiguous run, the runs' results added in run
         order.  Host arrays by default; ``device=True``: torch tensors, and no synchronisation with the device.  ``return_value=True``: the values are
-        prepended, what ``predict(params, device=device, keys=list(weights))`` returns."""
+        prepended, what ``predict(params, device=device, keys=list(weights))`` returns.
+
+        ``precision``: a dense precision matrix, ``chi2 = r^T P r`` with ``r = data - y``, ``fisher = J P J^T``, ``gradient = J P r``.  ``weights`` is then
+        the sequence of the distinct varied keys the data vector is made of -- those outputs flattened in C order and concatenated in the listed order, N
+        entries -- (a dictionary raises ``TypeError``, a fixed or unknown key ``KeyError``), ``precision`` (N, N), symmetric, a host array or a device tensor,
+        shared by all points (another shape: ``ValueError``), ``data`` ``{key: ...}`` for exactly those keys.  A column with ``precision[c, c] == 0`` is
+        dropped whatever it holds.  The precision is permuted once, on the device, to the order of the column plan; each maximal contiguous run is one
+        ``jacobian`` call of the engine, which writes straight into its column slice of one (B, ndim, N) Jacobian; :func:`gauss_newton_dense` contracts it
+        in one GEMM on the matrix cores.  Returns, ``device=`` and ``return_value=`` as above."""
         X, B, scalar = self._points(params)
         torch = dv.torch()
+        if precision is not None:
+            dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, precision)
+            runs, N, precision, dblock = self._staged_dense(weights, precision, data, B, dev)
+            ndim = len(self.params)
+            new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)      # noqa: E731
+            jac, value = new(B, ndim, N), new(B, N) if data is not None or return_value else None
+            totals = self._dense_normal_equations(X, runs, precision, dblock, jac, value)
+            totals = totals if isinstance(totals, tuple) else (totals,)
+            if not device:
+                totals = tuple(dv.to_host(total) for total in totals)
+            toret = totals[0][0] if scalar else totals[0]
+            if data is not None:
+                toret = (toret, {name: (totals[1][0, i] if scalar else totals[1][:, i]) for i, name in enumerate(self.params)}, totals[2][0] if scalar else totals[2])
+            if not return_value:
+                return toret
+            values = {}
+            for start, stop, entries, q0 in runs:
+                block = value[:, q0:q0 + stop - start]
+                values.update(_split(block if device else dv.to_host(block.contiguous()), (B,), entries, start, scalar))
+            listed = [weights] if isinstance(weights, str) else list(weights)
+            for key in self.varied_keys:      # empty outputs hold no column and join no run
+                if key in listed and key not in values:
+                    values[key] = self.predict(params, device=device, keys=[key])[key]
+            values = {key: values[key] for key in self.varied_keys if key in values}      # predict's order: the calculator's
+            return (values,) + (toret if isinstance(toret, tuple) else (toret,))
         dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, *weights.values())
         staged, fixed = self._staged(weights, data, B, dev)
         ndim = len(self.params)
@@ -498,7 +664,7 @@ class Emulator(object):
         return (values,) + (toret if isinstance(toret, tuple) else (toret,))
 
     def least_squares(self, params, weights, data, bounds=None, niterations=20, lambda0=1e-3, lambda_up=10., lambda_down=0.1, lambda_min=1e-12, lambda_max=1e12,
-                      ftol=1e-8, device=False):
+                      ftol=1e-8, device=False, precision=None):
         """B weighted least-squares fits of ``data`` to the emulated outputs at once, by Levenberg-Marquardt on the device: ``niterations`` times
         :meth:`gauss_newton` at the trial points, then :func:`lm_step` (one launch: acceptance, the damping of each fit, the active set of the box, the
         damped Cholesky solve, the stopping rule).  ``params``: the start, as :meth:`predict` takes it (scalars or arrays of B values); ``weights``,
@@ -511,13 +677,22 @@ class Emulator(object):
         Returns ``(best, chi2, info)``: ``best`` ``{parameter name: (B,)}`` the best point met, ``chi2`` (B,) there, ``info`` a dictionary of ``fisher``
         (B, ndim, ndim) and ``gradient`` ``{name: (B,)}`` there (the bits :meth:`gauss_newton` returns at ``best``), ``covariance`` (the inverse of the
         undamped ``fisher`` by :func:`spd_inverse`, NaN where it is not positive definite), ``status``, ``naccepted`` and ``lambda`` (B,); no leading
-        axis if every parameter is a scalar.  Host arrays by default; ``device=True``: torch tensors, and no synchronisation with the device anywhere."""
+        axis if every parameter is a scalar.  Host arrays by default; ``device=True``: torch tensors, and no synchronisation with the device anywhere.
+
+        ``precision``: a dense precision matrix (N, N), ``weights`` then the sequence of the keys its rows and columns follow, as :meth:`gauss_newton` takes
+        them.  It is permuted and staged once; an iteration is the engine's ``jacobian`` calls, :func:`gauss_newton_dense` and :func:`lm_step`, and
+        ``info['covariance']`` the inverse of the dense-precision Fisher matrix."""
         X, B, scalar = self._points(params)
         torch = dv.torch()
-        dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, *weights.values())
         if data is None:
             raise ValueError('least_squares needs data')
-        staged, fixed = self._staged(weights, data, B, dev)
+        if precision is not None:
+            dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, precision)
+            runs, N, precision, dblock = self._staged_dense(weights, precision, data, B, dev)
+            jac, value = (torch.empty(shape, dtype=torch.float64, device=dev) for shape in ((B, len(self.params), N), (B, N)))
+        else:
+            dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, *weights.values())
+            staged, fixed = self._staged(weights, data, B, dev)
         names = list(self.params)
         ndim = len(names)
         limits = dict(self.params)
@@ -531,9 +706,12 @@ class Emulator(object):
         state = lm_state(x, lambda0=lambda0)
         for iteration in range(int(niterations)):
             totals = None
-            for start, stop, entries, wblock, dblock in staged:
-                out = self.engine.gauss_newton(x, wblock, data=dblock, columns=(start, stop))
-                totals = out if totals is None else tuple(a + b for a, b in zip(totals, out))
+            if precision is not None:
+                totals = self._dense_normal_equations(x, runs, precision, dblock, jac, value)
+            else:
+                for start, stop, entries, wblock, dblock in staged:
+                    out = self.engine.gauss_newton(x, wblock, data=dblock, columns=(start, stop))
+                    totals = out if totals is None else tuple(a + b for a, b in zip(totals, out))
             if totals is None:
                 totals = (torch.zeros((B, ndim, ndim), dtype=torch.float64, device=dev), torch.zeros((B, ndim), dtype=torch.float64, device=dev),
                           torch.zeros((B,), dtype=torch.float64, device=dev))

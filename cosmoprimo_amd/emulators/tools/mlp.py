@@ -27,7 +27,7 @@ import ctypes
 import numpy as np
 
 from ... import _device as dv, _lib
-from .base import _columns, _cotangent, _empty, _gauss_newton, _tangent
+from .base import _columns, _cotangent, _empty, _gauss_newton, _jacobian_out, _tangent
 
 ACTIVATIONS = ('silu', 'relu', 'tanh', 'identity-silu')
 ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-8      # optax.adam's defaults
@@ -369,17 +369,21 @@ class MLPEmulatorEngine(object):
         _lib.check(_lib.load().cp_mlp_predict_columns(*head, start, ncols, out.data_ptr(), ncols, *where))
         return out
 
-    def jacobian(self, X, columns=None, return_value=False):
+    def jacobian(self, X, columns=None, return_value=False, out=None):
         """Derivative of :meth:`predict` with respect to the raw parameters at the points ``X`` (B, ndim): device tensor ``J`` (B, ndim, M),
         ``J[b, i, c] = d predict(X)[b, c] / d X[b, i]``, computed analytically by forward mode through the network (``cp_mlp_jacobian``: the x operations
         contribute 1 / xscale[i], the inverse y operations yscale[c] f'(v) with f' the derivative of 10^v or sinh v).  ``columns = (start, stop)``: those
         output columns only, (B, ndim, stop - start), bit for bit the same numbers.  ``return_value=True``: ``(value, J)`` with ``value`` what
-        ``predict(X, columns=columns)`` returns, bit for bit.  Nothing is read back and the call does not wait for the device."""
+        ``predict(X, columns=columns)`` returns, bit for bit.  Nothing is read back and the call does not wait for the device.
+        ``out = (value or None, J)``: device tensors to write instead of new ones, views into wider buffers with rows of any stride
+        (:func:`base._jacobian_out`)."""
         d, X, B, head, where = self._enter(X)
         start, ncols = _columns(columns, d['net']['M'])
         width = max(ncols, 0)
-        value, jac = _empty(d, B, width), _empty(d, B, d['net']['ndim'], width)
-        _lib.check(_lib.load().cp_mlp_jacobian(*head, start, ncols, value.data_ptr(), width, jac.data_ptr(), width, *where))
+        value, ldv, jac, ldj = _jacobian_out(d, out, B, d['net']['ndim'], width, return_value or out is None)
+        if value is None:      # the kernel writes the value in any case
+            value, ldv = _empty(d, B, width), width
+        _lib.check(_lib.load().cp_mlp_jacobian(*head, start, ncols, value.data_ptr(), ldv, jac.data_ptr(), ldj, *where))
         return (value, jac) if return_value else jac
 
     def vjp(self, X, cotangent, columns=None, return_value=False):

@@ -18,7 +18,7 @@ import math
 import numpy as np
 
 from ... import _device as dv, _lib
-from .base import _columns, _cotangent, _empty, _gauss_newton, _tangent
+from .base import _columns, _cotangent, _empty, _gauss_newton, _jacobian_out, _tangent
 from .samples import DiffSampler, deriv_ncoeffs
 
 
@@ -178,17 +178,22 @@ class TaylorEmulatorEngine(object):
         _lib.check(_lib.load().cp_taylor_predict_columns(*head, start, ncols, out.data_ptr(), ncols, *where))
         return out
 
-    def jacobian(self, X, columns=None, return_value=False):
+    def jacobian(self, X, columns=None, return_value=False, out=None):
         """Derivative of :meth:`predict` with respect to the parameters at the points ``X`` (B, ndim): device tensor ``J`` (B, ndim, M),
         ``J[b, i, :] = sum_t derivatives[t, :] p_ti (x_i - c_i)^(p_ti - 1) prod_{j != i} (x_j - c_j)^p_tj``, one launch (``cp_taylor_jacobian``: the
         derivatives of the monomials are formed inside the kernel).  ``columns = (start, stop)``: those output columns only, (B, ndim, stop - start), bit
         for bit the same numbers.  ``return_value=True``: ``(predict(X, columns=columns), J)``, one more launch.  Nothing is read back and the call does
-        not wait for the device."""
+        not wait for the device.  ``out = (value or None, J)``: device tensors to write instead of new ones, views into wider buffers with rows of any
+        stride (:func:`base._jacobian_out`); the value is written where ``return_value`` asks for it."""
         d, X, (B, ndim, T, M), head, where = self._enter(X)
         start, ncols = _columns(columns, M)
-        jac = _empty(d, B, ndim, max(ncols, 0))
-        _lib.check(_lib.load().cp_taylor_jacobian(*head, start, ncols, jac.data_ptr(), max(ncols, 0), *where))
-        return (self.predict(X, columns=columns), jac) if return_value else jac
+        value, ldv, jac, ldj = _jacobian_out(d, out, B, ndim, max(ncols, 0), return_value and out is not None)
+        _lib.check(_lib.load().cp_taylor_jacobian(*head, start, ncols, jac.data_ptr(), ldj, *where))
+        if out is None:
+            return (self.predict(X, columns=columns), jac) if return_value else jac
+        if return_value:
+            _lib.check(_lib.load().cp_taylor_predict_columns(*head, start, ncols, value.data_ptr(), ldv, *where))
+        return (value, jac) if return_value else jac
 
     def vjp(self, X, cotangent, columns=None, return_value=False):
         """Vector-Jacobian product of :meth:`predict` at the points ``X`` (B, ndim): device tensor ``G`` (B, ndim),

@@ -817,6 +817,26 @@ int cp_lm_step(long long B, int ndim, double* d_x, double* d_fisher, double* d_g
                double down, double lmin, double lmax, double ftol, double* d_next, int device, void* stream);
 int cp_spd_inverse(long long B, int ndim, const double* d_a, double* d_inv, int* d_info, int device, void* stream);
 
+/* ---- Fisher matrices and normal equations under a dense precision matrix, on an explicit Jacobian (csrc/cp_gauss_newton_dense.hip) ----
+ * Per point b: J_b (ndim, ncols) the Jacobian, r_b = data_b - value_b, A_b = [J_b ; r_b] (ndim + 1, ncols), P (ncols, ncols) symmetric, shared by all
+ * points, G_b = A_b P A_b^T:  d_fisher[b] (ndim, ndim) = G_b[:ndim, :ndim],  d_grad[b] (ndim) = G_b[:ndim, ndim],  d_chi2[b] = G_b[ndim, ndim].
+ * d_jac : row b ndim + i at stride ldj >= ncols (what cp_mlp_jacobian / cp_taylor_jacobian write, or a caller's own).  d_value : (B, ncols) with row stride
+ *   ldv (read where d_data is given).  d_data : (B, ncols) with row stride ldd, one shared row (ldd = 0), or NULL: Fisher matrix only, d_grad and d_chi2 NULL
+ *   too.  d_precision : (ncols, ncols) with row stride ldp >= ncols, taken as finite and symmetric: read in full, not checked.
+ * A column c with d_precision[c][c] == 0 is dropped: its column of A is selected to exactly 0 (not multiplied), so a NaN or Inf in the Jacobian, the value
+ *   or the data at c reaches none of the three sums.
+ * One GEMM A P on the matrix cores (a row tile holds floor(64 / (ndim + 1)) whole points) whose epilogue contracts it with A over the tile's columns; the
+ *   column tiles' partial sums are added in tile order.  No atomics: two calls give the same bits; d_fisher[b] is symmetric bit for bit, and its bits
+ *   without data are those with data.  Nothing is read back and the call does not wait for the device.
+ * d_work : work_doubles >= cp_gauss_newton_dense_workspace_doubles(B, ndim, ncols) (a negated status on an error) doubles of device workspace.
+ * Checks, in this order, before any device call: B < 0, ndim < 1, ncols < 0 or a stride below ncols (ldd: neither 0 nor >= ncols): CP_EINVAL;
+ *   ndim > 32: CP_EUNSUPPORTED; more than 2^31 - 1 row tiles, 2^39 sums B (ndim^2 + ndim + 1) or 2^24 - 256 columns: CP_EUNSUPPORTED; B = 0: CP_OK; a null
+ *   pointer (d_grad or d_chi2 without d_data, or d_data without both, included) or a short workspace: CP_EINVAL.  ncols = 0 with B > 0 writes zeros. */
+long long cp_gauss_newton_dense_workspace_doubles(long long B, int ndim, long long ncols);
+int cp_gauss_newton_dense(const double* d_jac, long long ldj, long long B, int ndim, long long ncols, const double* d_value, long long ldv,
+                          const double* d_data, long long ldd, const double* d_precision, long long ldp, double* d_fisher, double* d_grad, double* d_chi2,
+                          double* d_work, long long work_doubles, int device, void* stream);
+
 /* ---- row screening utility (cp_fftlog_execute and cp_dst_execute screen their rows themselves; this pass is for callers that want
  *      the flags, e.g. to count or report the rows a batch loses) ----
  * d_x : (nrows, n) device.  d_ok[row] = 1 if every entry of the row is finite (and > 0 if require_positive: the fused log map of
