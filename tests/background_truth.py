@@ -608,13 +608,14 @@ def _report(what, fraction, level):
     return worst
 
 
-def assert_pointwise(dev, truth, f64, what='', extra=0., measure_only=False):
+def assert_pointwise(dev, truth, f64, what='', extra=0., measure_only=False, cap=CAP):
     """Every entry of the device's rows within (ALLOW x the row's level + extra) of the truth, relative to the entry; NaN exactly where the truth has it and
-    zero where it is zero.  Prints and returns the largest fraction of the allowance used (``measure_only``: without holding it to 1)."""
+    zero where it is zero.  Prints and returns the largest fraction of the allowance used (``measure_only``: without holding it to 1).  ``cap``: the
+    cap of the case's levels in FLOORs (tests/power_truth.py: 64 for spectra, P ~ T^2)."""
     dev, truth = np.asarray(dev), np.asarray(truth)
     assert dev.shape == truth.shape, (what, dev.shape, truth.shape)
     level = pointwise_level(truth, f64)
-    assert level.max() < CAP * FLOOR, '{}: the case is over the cap ({:.3g} FLOOR)'.format(what, level.max() / FLOOR)
+    assert level.max() < cap * FLOOR, '{}: the case is over the cap ({:.3g} FLOOR)'.format(what, level.max() / FLOOR)
     assert np.array_equal(np.isnan(dev), np.isnan(truth)), '{}: NaN in other places than the truth has them'.format(what)
     nan = np.isnan(truth)
     assert np.isfinite(dev[~nan]).all(), what
