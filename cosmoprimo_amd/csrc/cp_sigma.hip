@@ -105,7 +105,11 @@ __device__ __forceinline__ void front_phases(int t, const FftlogArgs& A, bool ha
 // The thread's samples are j = t0 + T r of a geometric grid: k_j and log k_j follow from the thread's first sample by one multiplication /
 // addition per step (kh0, ln0 in registers; ratio = k[T] / k[0] and its logarithm are uniform).  No memory is read inside the loop: a vector
 // load here would make the wave wait for the 256 stores of the previous pair (the vector-memory counter retires in order), which are meant
-// to drain under this arithmetic.  (k_j differs from the tabulated one by a few ulp: 1e-15 on P.)
+// to drain under this arithmetic.  What the stepping costs (restated in float64 and measured by tests/test_sigma_truth_host.py; an earlier version of this
+// comment said "a few ulp: 1e-15 on P"): k_j ends up to 7e-15 (32 ulp) from the tabulated wavenumber, growing with the number of steps, and P up to
+// 2e-14 from the spectrum at the tabulated one in the last eighth of the grid (k > 7.6 h/Mpc, where |dlnP / dlnk| = 3); log k, k^1.08 and k^1.4 are
+// stepped on their own.  On the device pk_out and sigma(r, z) stay within two such distances of the truth (tests/test_sigma_rz_edges_gpu.py holds
+// them to sixteen).  cp_sigma_rz_functional and cp_sigma8_normalise read the tabulated wavenumbers and do not pay this.
 template <int ENGINE, int T, int H>
 __device__ __forceinline__ void evaluate_spectrum(const SigmaArgs& S, long long ic, int t0, double kh0, double ln0, double ratio, double ln_ratio, double2 pw0,
                                                   double2 pw_ratio, double* slots, const MathTables* mt) {
