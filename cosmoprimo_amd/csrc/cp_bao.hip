@@ -20,6 +20,8 @@
 #include "cp_internal.h"
 #include "cp_math.h"
 #include "cp_splice_uniform.h"
+#include "cp_spline_sweeps.h"
+#include "cp_spline_system.h"
 #include "cp_wallish_dd.h"
 
 namespace {
@@ -726,11 +728,9 @@ extern "C" int cp_wallish_dd_box(const double* d_y, long long nrows, int n, int 
 // bao_filter.py:415-431: knots = [k < 5e-4 | the linear grid inside (1e-2, 1.5) | k > 2], values = [P | smoothed P on the linear grid | P],
 // CubicSpline(bc_type='clamped') evaluated at the filter's k, then pk / ((pk / pknow - 1) tophat + 1).  As spline operators on the two arrays
 // (two block-banded GEMMs of 64-wide bands, then an elementwise pass) this was 1.04 ms per 16 384 vectors.  The spline is a tridiagonal system
-// for the second derivatives M:  h_{i-1} M_{i-1} + 2 (h_{i-1} + h_i) M_i + h_i M_{i+1} = 6 (s_i - s_{i-1}),  s_i = (y_{i+1} - y_i) / h_i, with
-// s_{-1} = s_{n-1} = 0 for the clamped ends.  Its elimination factors 1 / (2 (h_{i-1} + h_i) - h_{i-1} c_{i-1}) depend on the knots only (host,
-// plan creation); a wave takes a vector's knot values into LDS and runs both sweeps as in cp_wallish_dd_box -- a lane per segment of S =
-// ceil(n / 64) knots, started `halo` knots outside its segment with d = 0 (M = 0), the halo chosen at plan creation so that what is left of the
-// start is below 1e-18 -- then evaluates  A y_j + B y_{j+1} + ((A^3 - A) M_j + (B^3 - B) M_{j+1}) h_j^2 / 6  at the queries (weights from the
+// for the second derivatives M; the system (clamped ends), its elimination factors, the halo and the queries' weights are those of
+// cp_spline_system.h (host, plan creation).  A wave takes a vector's knot values into LDS and runs the two sweeps of cp_spline_sweeps.h -- a lane
+// per segment of S = ceil(n / 64) knots -- then evaluates  A y_j + B y_{j+1} + w_2 M_j + w_3 M_{j+1}  at the queries (weights from the
 // plan).  Most knots lie on the uniform grid, where h and the factor are constants once the elimination has forgotten the junction (the
 // spacings of a linspace differ by the rounding of its knots, 1e-12 of h: the constants stand for all of them, 1e-13 on the second derivatives):
 // only the knots outside that stretch have table entries (LDS).
@@ -761,10 +761,9 @@ struct SpliceArgs {
 };
 
 // S (odd: 64 lanes x S doubles apart fall on 32 different bank pairs) knots per lane.  LDS per wave: halo + 1 | 64 S | halo + 1 doubles -- the knot
-// values with the end values repeated on either side (slopes beyond the ends vanish: the clamped boundary condition, and no index is ever
-// clamped), then d, then M in the same places, as in wallish_dd_box_kernel -- and, per workgroup, the coefficient table: slot -> (6 / h, factor,
-// h_{i-1} x factor, h_i x factor), the knots left of the uniform stretch, ONE slot for the stretch, the knots right of it.  The dependent
-// chain of the forward sweep is one FMA per knot: d_i = P_i - Q_i d_{i-1}, P_i = factor_i (sigma_i - sigma_{i-1}), sigma_i = (y_{i+1} - y_i) 6 / h_i.
+// values with the end values repeated on either side (slopes beyond the ends vanish: the clamped boundary condition), then d, then M in the same
+// places (cp_spline_sweeps.h) -- and, per workgroup, the coefficient table: slot -> (6 / h, factor, h_{i-1} x factor, h_i x factor), the knots left
+// of the uniform stretch, ONE slot for the stretch, the knots right of it.
 #ifndef CP_SPLICE_ABLATE      // diagnostic builds (tools/splice_microbench.hip): 1 no sweeps, 2 no evaluation, 4 no knot loads
 #define CP_SPLICE_ABLATE 0
 #endif
@@ -822,58 +821,9 @@ __global__ __launch_bounds__(256) void splice_kernel(const SpliceArgs A) {
     }
     wave_lds_phase();      // knot values staged, ends repeated
     if (row + (long long)gridDim.x * 4 < A.nrows) fetch(row + (long long)gridDim.x * 4, knots);
-    if (!(CP_SPLICE_ABLATE & 1)) {
-        const double beyond = buf[own + S];      // the next segment's first knot, before its owner writes there
-        const int start = own - halo;
-        double y0 = buf[start], d = 0.;
-        double sigma_m = (y0 - buf[start - 1]) * coef[slot_of(start - 1)].x;
-#pragma unroll 4
-        for (int t = 0; t < halo; ++t) {             // towards the segment: nothing stored
-            const int i = start + t;
-            const double4 c = coef[slot_of(i)];
-            const double yp = buf[i + 1];
-            const double sigma = (yp - y0) * c.x;
-            d = fma(-c.z, d, c.y * (sigma - sigma_m));
-            sigma_m = sigma;
-            y0 = yp;
-        }
-        wave_lds_phase();      // run-ins done before the neighbours' knot values become d
-#pragma unroll 4
-        for (int t = 0; t < S - 1; ++t) {
-            const int i = own + t;
-            const double4 c = coef[slot_of(i)];
-            const double yp = buf[i + 1];
-            const double sigma = (yp - y0) * c.x;
-            d = fma(-c.z, d, c.y * (sigma - sigma_m));
-            buf[i] = d;                              // (segments past the last knot: slots nobody uses)
-            sigma_m = sigma;
-            y0 = yp;
-        }
-        {
-            const int i = own + S - 1;
-            const double4 c = coef[slot_of(i)];
-            const double sigma = (beyond - y0) * c.x;
-            buf[i] = fma(-c.z, d, c.y * (sigma - sigma_m));
-        }
-    }
+    if (!(CP_SPLICE_ABLATE & 1)) cpsweep::forward<4>(slot_of, buf, coef, own, S, halo);
     wave_lds_phase();      // d complete
-    if (!(CP_SPLICE_ABLATE & 1)) {
-        double m = 0.;
-#pragma unroll 4
-        for (int t = 0; t < halo; ++t) {
-            const int i = own + S + halo - 1 - t;
-            const double d = buf[i];
-            m = i >= n - 1 ? d : fma(-coef[slot_of(i)].w, m, d);      // (beyond the last knot: M_{n-1} = d_{n-1} when the sweep gets there)
-        }
-        wave_lds_phase();
-#pragma unroll 4
-        for (int t = 0; t < S; ++t) {
-            const int i = own + S - 1 - t;
-            const double d = buf[i];
-            m = i >= n - 1 ? d : fma(-coef[slot_of(i)].w, m, d);
-            buf[i] = m;
-        }
-    }
+    if (!(CP_SPLICE_ABLATE & 1)) cpsweep::backward<4>(slot_of, buf, coef, own, S, halo, n - 1);
     wave_lds_phase();      // M complete: the evaluation gathers across segments
     // Queries that fall on a knot taken from their own column of array 0 (wallish2018: every k below and above the linear grid) return that
     // value: whole blocks of 64 such queries skip the tables.  For the others the table entries and the gathered knot values of four blocks are
@@ -938,36 +888,14 @@ extern "C" int cp_splice_plan_create(cp_splice_plan** out, int nknots, const dou
         total += piece_count[p];
     }
     if (total != n) return cp::fail(CP_EINVAL, "cp_splice_plan_create: the pieces hold %d knots, not %d", total, n);
-    for (int i = 0; i + 1 < n; ++i)
-        if (!(x[i + 1] > x[i])) return cp::fail(CP_EINVAL, "cp_splice_plan_create: knots must increase");
-    // elimination factors of the system for the second derivatives (clamped ends)
-    std::vector<double> h(n), rh(n), inv(n), c(n);
-    for (int i = 0; i + 1 < n; ++i) h[i] = x[i + 1] - x[i];
-    h[n - 1] = h[n - 2];      // (never multiplies anything that is used: s_{n-1} = 0, and M_{n-1} has no successor)
-    for (int i = 0; i < n; ++i) rh[i] = 1. / h[i];
-    inv[0] = 1. / (2. * h[0]);
-    c[0] = h[0] * inv[0];
-    for (int i = 1; i < n; ++i) {
-        const double diag = i < n - 1 ? 2. * (h[i - 1] + h[i]) : 2. * h[n - 2];
-        inv[i] = 1. / (diag - h[i - 1] * c[i - 1]);
-        c[i] = h[i] * inv[i];
-    }
-    // how far a sweep remembers its start: the forward one by h_{i-1} inv_i per knot, the backward one by c_i
-    int halo = 8;
-    for (;; halo += 8) {
-        if (halo > 128) return cp::fail(CP_EUNSUPPORTED, "cp_splice_plan_create: the elimination does not forget its start within 128 knots");
-        double worst = 0.;
-        for (int i = halo; i < n; ++i) {
-            double f = 1., b = 1.;
-            for (int t = 0; t < halo; ++t) {
-                f *= std::fabs(h[i - t - 1] * inv[i - t]);
-                b *= std::fabs(c[i - t - 1]);
-            }
-            worst = f > worst ? f : worst;
-            worst = b > worst ? b : worst;
-        }
-        if (worst < 1e-18) break;
-    }
+    if (!cpss::increasing(n, x)) return cp::fail(CP_EINVAL, "cp_splice_plan_create: knots must increase");
+    // elimination factors of the system for the second derivatives, clamped ends (cp_spline_system.h; c of the last knot, which has no successor and
+    // which no sweep reads, is 0)
+    const cpss::System sys = cpss::factors(n, x, cpss::CLAMPED);
+    const std::vector<double>& h = sys.h;
+    const std::vector<double>& inv = sys.inv;
+    const int halo = cpss::halo_of(sys);
+    if (halo > 128) return cp::fail(CP_EUNSUPPORTED, "cp_splice_plan_create: the elimination does not forget its start within 128 knots");
     // the uniform stretch: the longest run of equal spacings, shortened on the left until the factor has converged
     int best_lo = 0, best_hi = 0;
     for (int lo = 0; lo < n - 1;) {
@@ -997,10 +925,10 @@ extern "C" int cp_splice_plan_create(cp_splice_plan** out, int nknots, const dou
     if (lds > 160 * 1024) return cp::fail(CP_EUNSUPPORTED, "cp_splice_plan_create: %d knots (%d outside a uniform stretch) exceed the LDS of a CU", n, nslots);
     std::vector<double> tab((size_t)4 * nslots);
     auto fill = [&](int slot, int i) {      // 6 / h_i, factor_i, h_{i-1} factor_i, h_i factor_i
-        tab[4 * slot] = 6. * rh[i];
+        tab[4 * slot] = 6. * (1. / h[i]);      // (the rows plan divides: 6. / h[i]; either keeps its rounding)
         tab[4 * slot + 1] = inv[i];
-        tab[4 * slot + 2] = i > 0 ? h[i - 1] * inv[i] : 0.;
-        tab[4 * slot + 3] = c[i];
+        tab[4 * slot + 2] = sys.q[i];
+        tab[4 * slot + 3] = sys.c[i];
     };
     for (int i = 0; i < ntab_left; ++i) fill(i, i);
     tab[4 * ntab_left] = 6. / h0;
@@ -1030,22 +958,14 @@ extern "C" int cp_splice_plan_create(cp_splice_plan** out, int nknots, const dou
         return (p->T.piece_start[k] + i - p->T.piece_first[k]) | (p->T.piece_src[k] << 30);
     };
     for (int q = 0; q < nq; ++q) {
-        const double v = xq[q];
-        if (!(v >= x[0] && v <= x[n - 1])) {
-            qj[q] = -1;
+        const int j = qj[q] = cpss::interval_of(n, x, xq[q], false);
+        if (j < 0) {
             qcol[2 * q] = qcol[2 * q + 1] = 0;
             continue;
         }
-        int j = (int)(std::upper_bound(x, x + n, v) - x) - 1;
-        j = j > n - 2 ? n - 2 : j;
-        const double a = (x[j + 1] - v) / h[j], b = (v - x[j]) / h[j];
-        qj[q] = j;
         qcol[2 * q] = column_of(j);
         qcol[2 * q + 1] = column_of(j + 1);
-        qw[4 * q] = a;
-        qw[4 * q + 1] = b;
-        qw[4 * q + 2] = (a * a * a - a) * (h[j] * h[j]) / 6.;
-        qw[4 * q + 3] = (b * b * b - b) * (h[j] * h[j]) / 6.;
+        cpss::weights_of(x, h.data(), j, xq[q], &qw[4 * (size_t)q]);
     }
     int generic_first = nq, generic_end = 0;
     for (int q = 0; q < nq; ++q) {

@@ -233,4 +233,13 @@ __device__ __forceinline__ void wave_lds_phase() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+
+// where the spline kernels (cp_spline.hip, cp_spline_rows.hip) store the value of (row, query): (nrows, nq) row-major, or -- group > 0 --
+// (nrows / group, nq, group): the rows of a group (the redshifts of one table) become the fastest axis, i.e. the (nz, nr) -> (nr, nz) transposition
+// of sigma_rz is part of the store
+__device__ __forceinline__ long long out_index(long long row, int q, int nq, int group) {
+    if (group <= 0) return row * nq + q;
+    const long long b = row / group;
+    return (b * nq + q) * group + (row - b * group);
+}
 }  // namespace cp

@@ -8,6 +8,8 @@
 #include <cstddef>
 #include <vector>
 
+#include "cp_spline_system.h"
+
 namespace cpsu {
 
 constexpr int WIN_G = 44;      // knots outside the stretch that A, B and the outer second derivatives see on either side (all of them if fewer)
@@ -90,9 +92,7 @@ inline Built build(int n, const double* x, const int* piece_first, const int* pi
         const int j = qj[q];
         if (j < 0 || j < u0 - 1 || j > u1 || (j == u0 - 1 && wl < 1) || (j == u1 && wr < 1)) return B;
     }
-    std::vector<double> h(n);
-    for (int i = 0; i + 1 < n; ++i) h[i] = x[i + 1] - x[i];
-    h[n - 1] = h[n - 2];
+    const std::vector<double> h = cpss::spacings(n, x);
     const double h0 = (x[u1] - x[u0]) / (nm - 1);
     const double kappa = 1. / (2. * std::sqrt(3.)), kscale = 6. * kappa / (h0 * h0);
     // rows of the exact inverse: M = T^-1 R y, T symmetric tridiagonal (diagonal 2 (h_{i-1} + h_i), clamped ends 2 h_0 and 2 h_{n-2}; off-diagonal
@@ -184,12 +184,10 @@ inline Built build(int n, const double* x, const int* piece_first, const int* pi
         const int q = 64 * gb0 + e;
         if (q < generic_first || q >= generic_end) continue;      // (weights zero, interval 0: evaluated and not stored)
         const int j = qj[q];
-        const double a = (x[j + 1] - xq[q]) / h[j], b = (xq[q] - x[j]) / h[j];
         B.qe[e] = j - u0;
-        B.qw[4 * e] = a;
-        B.qw[4 * e + 1] = b;
-        B.qw[4 * e + 2] = (a * a * a - a) * (h[j] * h[j]) / 6. * kscale;
-        B.qw[4 * e + 3] = (b * b * b - b) * (h[j] * h[j]) / 6. * kscale;
+        cpss::weights_of(x, h.data(), j, xq[q], &B.qw[4 * e]);
+        B.qw[4 * e + 2] *= kscale;      // the second derivatives in units of the unscaled recursion
+        B.qw[4 * e + 3] *= kscale;
     }
     Tables& T = B.T;
     T.S = S; T.nm = nm; T.wl = wl; T.wr = wr;

@@ -31,13 +31,7 @@ using cpmath::exp10_mid;
 constexpr int TILE_Q = 256;      // at most one query per lane
 constexpr int SPAN_CAP = 480;    // knots a tile may cover when it holds more than one query: 16 rows x 480 knots = 60 KB of LDS
 
-// where the value of (row, query) is stored: (nrows, nq) row-major, or -- group > 0 -- (nrows / group, nq, group): the rows of a group (the
-// redshifts of one table) become the fastest axis, i.e. the (nz, nr) -> (nr, nz) transposition of sigma_rz is part of the store
-__device__ __forceinline__ long long out_index(long long row, int q, int nq, int group) {
-    if (group <= 0) return row * nq + q;
-    const long long b = row / group;
-    return (b * nq + q) * group + (row - b * group);
-}
+using cp::out_index;      // where the value of (row, query) is stored (cp_internal.h)
 
 struct Args {
     const double* y;    // (nrows, n)

@@ -5,12 +5,10 @@
 // As an operator (cp_spline_apply) the spline costs bandwidth x queries multiply-adds per row -- 64 per query, because the inverse of its
 // tridiagonal matrix decays by 0.27 per knot and has to be kept to 1e-17 -- and the matrix-core route multiplies whole windows of knots on top
 // (33 000 multiply-adds per row for 1024 knots -> 256 radii).  The elimination itself is ~10 operations per knot and 8 per query:
-//   * only the knots the queries touch, plus `halo` knots on either side, are read and solved (a sweep forgets where it started at the rate
-//     its factors decay; the halo is chosen at plan creation so that 1e-18 of the start is left);
+//   * only the knots the queries touch, plus `halo` knots on either side, are read and solved (the halo: cp_spline_system.h);
 //   * R = 1, 2 or 4 rows per wave: 64 / R lanes per row, a lane owns S knots (S odd: its neighbours' segments start on other banks) and runs
-//     both sweeps over halo + S knots -- values, eliminated right-hand sides and second derivatives share one LDS buffer with the end values
-//     repeated beyond either end, exactly as in splice_kernel (cp_bao.hip), whose elimination this is;
-//   * the factors (6 / h_i, 1 / pivot_i, h_{i-1} / pivot_i, h_i / pivot_i) depend on the knots only: a table in LDS, built on the host;
+//     the two sweeps of cp_spline_sweeps.h, which splice_kernel (cp_bao.hip) runs too, on its row's LDS buffer;
+//   * the factors depend on the knots only (cp_spline_system.h: all three end conditions): a table in LDS, one slot per knot of the window;
 //   * queries: A y_j + B y_{j+1} + ((A^3 - A) M_j + (B^3 - B) M_{j+1}) h_j^2 / 6, weights from the plan; scale, root, and the store with the
 //     rows of a group as the fastest axis (cp_spline_apply_grouped's layout) in the same pass.
 #include <hip/hip_runtime.h>
@@ -23,6 +21,8 @@
 #include "../../include/cosmoprimo_amd.h"
 #include "cp_error.h"
 #include "cp_internal.h"
+#include "cp_spline_sweeps.h"
+#include "cp_spline_system.h"
 
 namespace {
 
@@ -50,12 +50,6 @@ struct RowsArgs {
     double* out_m;            // (nrows, n_src) or null: the second derivatives at the knots of the window instead of the queries
     int pairs;                // out_m is (nrows, n_src, 2): the knot values with their second derivatives, (y_j, M_j)
 };
-
-__device__ __forceinline__ long long rows_out_index(long long row, int q, int nq, int group) {      // cp_spline.hip: out_index
-    if (group <= 0) return row * nq + q;
-    const long long b = row / group;
-    return (b * nq + q) * group + (row - b * group);
-}
 
 template <int R>
 __global__ __launch_bounds__(256) void spline_rows_kernel(const RowsArgs A) {
@@ -92,58 +86,9 @@ __global__ __launch_bounds__(256) void spline_rows_kernel(const RowsArgs A) {
 #ifndef CP_ROWS_ABLATE
 #define CP_ROWS_ABLATE 0      // tools/spline_rows_variants.sh, what the parts cost: 1 no forward sweep, 2 no back substitution, 4 one query per lane,
 #endif                        // 8 no values gathered from memory, 16 no root, 32 no stores
-        if (!(CP_ROWS_ABLATE & 1)) {
-            const double beyond = buf[own + S];
-            const int start = own - halo;
-            double y0 = buf[start], d = 0.;
-            double sigma_m = (y0 - buf[start - 1]) * coef[slot_of(start - 1)].x;
-#pragma unroll 8
-            for (int t = 0; t < halo; ++t) {
-                const int i = start + t;
-                const double4 c = coef[slot_of(i)];
-                const double yp = buf[i + 1];
-                const double sigma = (yp - y0) * c.x;
-                d = fma(-c.z, d, c.y * (sigma - sigma_m));
-                sigma_m = sigma;
-                y0 = yp;
-            }
-            cp::wave_lds_phase();      // run-ins done before the neighbours' knot values become d
-#pragma unroll 8
-            for (int t = 0; t < S - 1; ++t) {
-                const int i = own + t;
-                const double4 c = coef[slot_of(i)];
-                const double yp = buf[i + 1];
-                const double sigma = (yp - y0) * c.x;
-                d = fma(-c.z, d, c.y * (sigma - sigma_m));
-                buf[i] = d;
-                sigma_m = sigma;
-                y0 = yp;
-            }
-            {
-                const int i = own + S - 1;
-                const double4 c = coef[slot_of(i)];
-                const double sigma = (beyond - y0) * c.x;
-                buf[i] = fma(-c.z, d, c.y * (sigma - sigma_m));
-            }
-        }
+        if (!(CP_ROWS_ABLATE & 1)) cpsweep::forward<8>(slot_of, buf, coef, own, S, halo);
         cp::wave_lds_phase();      // d complete
-        if (!(CP_ROWS_ABLATE & 2)) {
-            double m = 0.;
-#pragma unroll 8
-            for (int t = 0; t < halo; ++t) {
-                const int i = own + S + halo - 1 - t;
-                const double d = buf[i];
-                m = i >= nw - 1 ? d : fma(-coef[slot_of(i)].w, m, d);
-            }
-            cp::wave_lds_phase();
-#pragma unroll 8
-            for (int t = 0; t < S; ++t) {
-                const int i = own + S - 1 - t;
-                const double d = buf[i];
-                m = i >= nw - 1 ? d : fma(-coef[slot_of(i)].w, m, d);
-                buf[i] = m;
-            }
-        }
+        if (!(CP_ROWS_ABLATE & 2)) cpsweep::backward<8>(slot_of, buf, coef, own, S, halo, nw - 1);
         cp::wave_lds_phase();      // M complete
         if (T.fix_first && l == 0) buf[0] = T.fix[0] * buf[1] + T.fix[1] * buf[2];
         if (T.fix_last && l == 0) buf[nw - 1] = T.fix[2] * buf[nw - 2] + T.fix[3] * buf[nw - 3];
@@ -181,7 +126,7 @@ __global__ __launch_bounds__(256) void spline_rows_kernel(const RowsArgs A) {
             double v = ((CP_ROWS_ABLATE & 8) ? w.x + w.y : w.x * src[jj] + w.y * src[jj + 1]) + (w.z * buf[jj] + w.w * buf[jj + 1]);
             v = j < 0 ? __builtin_nan("") : v * A.scale;
             if (A.post_op == CP_SPLINE_POST_SQRT && !(CP_ROWS_ABLATE & 16)) v = sqrt(v);
-            if (live && (!(CP_ROWS_ABLATE & 32) || v == 12345.678)) A.out[rows_out_index(row, q, T.nq, A.group)] = v;
+            if (live && (!(CP_ROWS_ABLATE & 32) || v == 12345.678)) A.out[cp::out_index(row, q, T.nq, A.group)] = v;
         }
     }
 }
@@ -206,69 +151,22 @@ extern "C" int cp_spline_rows_plan_create(cp_spline_rows_plan** out, int n, cons
     if (nq > (1 << 26) || n > (1 << 26))      // (a query is staged as an interval and four weights on the host: 2^26 queries are 2.4 GB; a catalogue comes in pieces)
         return cp::fail(CP_EUNSUPPORTED, "cp_spline_rows_plan_create: %d knots, %d queries (at most 2^26 each): evaluate in pieces", n, nq);
     if (bc != CP_SPLINE_NATURAL && bc != CP_SPLINE_CLAMPED && bc != CP_SPLINE_NOT_A_KNOT) return cp::fail(CP_EINVAL, "cp_spline_rows_plan_create: unknown boundary condition %d", bc);
-    for (int i = 0; i + 1 < n; ++i)
-        if (!(x[i + 1] > x[i])) return cp::fail(CP_EINVAL, "cp_spline_rows_plan_create: knots must increase");
-    // the system for the second derivatives, sub_i M_{i-1} + diag_i M_i + sup_i M_{i+1} = 6 (s_i - s_{i-1}), and its elimination factors.
-    // clamped: 2 h_0 M_0 + h_0 M_1 = 6 s_0 and its mirror image; natural: M_0 = M_{n-1} = 0 (factor 0 in the outermost rows); not-a-knot: the
-    // outermost unknowns eliminated through M_0 = (1 + h_0 / h_1) M_1 - (h_0 / h_1) M_2 and its mirror image (factor 0 again, filled in afterwards)
-    std::vector<double> h(n), inv(n), c(n), q(n), sub(n), diag(n), sup(n);
-    for (int i = 0; i + 1 < n; ++i) h[i] = x[i + 1] - x[i];
-    h[n - 1] = h[n - 2];
-    for (int i = 1; i < n - 1; ++i) {
-        sub[i] = h[i - 1];
-        diag[i] = 2. * (h[i - 1] + h[i]);
-        sup[i] = h[i];
-    }
-    sub[0] = 0.; diag[0] = 2. * h[0]; sup[0] = h[0];
-    sub[n - 1] = h[n - 2]; diag[n - 1] = 2. * h[n - 2]; sup[n - 1] = 0.;
-    const bool open_ends = bc != CP_SPLINE_CLAMPED;      // rows 0 and n - 1 are not equations of the system
-    double fix[4] = {0., 0., 0., 0.};
-    if (bc == CP_SPLINE_NOT_A_KNOT) {
-        if (n < 5) return cp::fail(CP_EUNSUPPORTED, "cp_spline_rows_plan_create: a not-a-knot spline through %d knots", n);
-        fix[0] = 1. + h[0] / h[1]; fix[1] = -h[0] / h[1];
-        fix[2] = 1. + h[n - 2] / h[n - 3]; fix[3] = -h[n - 2] / h[n - 3];
-        diag[1] += h[0] * fix[0]; sup[1] += h[0] * fix[1]; sub[1] = 0.;
-        diag[n - 2] += h[n - 2] * fix[2]; sub[n - 2] += h[n - 2] * fix[3]; sup[n - 2] = 0.;
-    }
-    inv[0] = open_ends ? 0. : 1. / diag[0];
-    c[0] = sup[0] * inv[0];
-    q[0] = 0.;
-    for (int i = 1; i < n; ++i) {
-        inv[i] = (open_ends && i == n - 1) ? 0. : 1. / (diag[i] - sub[i] * c[i - 1]);
-        c[i] = sup[i] * inv[i];
-        q[i] = sub[i] * inv[i];
-    }
+    if (!cpss::increasing(n, x)) return cp::fail(CP_EINVAL, "cp_spline_rows_plan_create: knots must increase");
+    if (bc == CP_SPLINE_NOT_A_KNOT && n < 5) return cp::fail(CP_EUNSUPPORTED, "cp_spline_rows_plan_create: a not-a-knot spline through %d knots", n);
+    // the system for the second derivatives and its elimination factors (cp_spline_system.h)
+    const cpss::System sys = cpss::factors(n, x, bc == CP_SPLINE_CLAMPED ? cpss::CLAMPED : (bc == CP_SPLINE_NATURAL ? cpss::NATURAL : cpss::NOT_A_KNOT));
     // the queries' intervals
     std::vector<int> qj(nq);
     int jmin = n, jmax = -1;
     for (int k = 0; k < nq; ++k) {
-        const double v = xq[k];
-        if (!(v >= x[0] && v <= x[n - 1]) && !(extrapolate && v == v)) {      // outside the knots: NaN, or the cubic of the end interval continued
-            qj[k] = -1;
-            continue;
-        }
-        int j = (int)(std::upper_bound(x, x + n, v) - x) - 1;
-        j = j > n - 2 ? n - 2 : (j < 0 ? 0 : j);
-        qj[k] = j;
+        const int j = qj[k] = cpss::interval_of(n, x, xq[k], extrapolate != 0);      // -1: outside the knots and not continued
+        if (j < 0) continue;
         jmin = j < jmin ? j : jmin;
         jmax = j > jmax ? j : jmax;
     }
     if (jmax < 0) jmin = jmax = 0;      // every query outside the knots: NaN everywhere, any window
-    // how far a sweep remembers its start
-    int halo = 8;
-    for (;; halo += 8) {
-        if (halo > 128) return cp::fail(CP_EUNSUPPORTED, "cp_spline_rows_plan_create: the elimination does not forget its start within 128 knots");
-        double worst = 0.;
-        for (int i = halo; i < n; ++i) {
-            double f = 1., b = 1.;
-            for (int t = 0; t < halo; ++t) {
-                f *= std::fabs(q[i - t]);
-                b *= std::fabs(c[i - t - 1]);
-            }
-            worst = std::max(worst, std::max(f, b));
-        }
-        if (worst < 1e-18 || halo >= n) break;
-    }
+    const int halo = cpss::halo_of(sys);
+    if (halo > 128) return cp::fail(CP_EUNSUPPORTED, "cp_spline_rows_plan_create: the elimination does not forget its start within 128 knots");
     const int w0 = std::max(0, jmin - halo), w1 = std::min(n, jmax + 2 + halo), nw = w1 - w0;
     // rows per wave: as many as the window's length suggests, fewer where their buffers do not fit (4 R row buffers per workgroup: with a halo of 32
     // two rows per wave end at 1632 knots, not at the 32 x 59 of their lanes)
@@ -287,20 +185,15 @@ extern "C" int cp_spline_rows_plan_create(cp_spline_rows_plan** out, int n, cons
     std::vector<double> tab((size_t)4 * nslots), qw((size_t)4 * nq, 0.);
     for (int s = 0; s < nslots; ++s) {
         const int i = std::min(w0 + s, n - 1);
-        tab[4 * s] = 6. / h[i];
-        tab[4 * s + 1] = inv[i];
-        tab[4 * s + 2] = q[i];
-        tab[4 * s + 3] = c[i];
+        tab[4 * s] = 6. / sys.h[i];
+        tab[4 * s + 1] = sys.inv[i];
+        tab[4 * s + 2] = sys.q[i];
+        tab[4 * s + 3] = sys.c[i];
     }
     for (int k = 0; k < nq; ++k) {
         if (qj[k] < 0) continue;
-        const int j = qj[k];
-        const double a = (x[j + 1] - xq[k]) / h[j], b = (xq[k] - x[j]) / h[j];
-        qw[4 * k] = a;
-        qw[4 * k + 1] = b;
-        qw[4 * k + 2] = (a * a * a - a) * (h[j] * h[j]) / 6.;
-        qw[4 * k + 3] = (b * b * b - b) * (h[j] * h[j]) / 6.;
-        qj[k] = j - w0;
+        cpss::weights_of(x, sys.h.data(), qj[k], xq[k], &qw[4 * (size_t)k]);
+        qj[k] -= w0;
     }
     cp::PlanPtr<cp_spline_rows_plan> p(new (std::nothrow) cp_spline_rows_plan());
     if (!p) return cp::fail(CP_ENOMEM, "cp_spline_rows_plan_create: host allocation failed");
@@ -308,7 +201,7 @@ extern "C" int cp_spline_rows_plan_create(cp_spline_rows_plan** out, int n, cons
     p->lds_bytes = lds;
     p->T.fix_first = bc == CP_SPLINE_NOT_A_KNOT && w0 == 0;
     p->T.fix_last = bc == CP_SPLINE_NOT_A_KNOT && w1 == n;
-    for (int i = 0; i < 4; ++i) p->T.fix[i] = fix[i];
+    for (int i = 0; i < 4; ++i) p->T.fix[i] = sys.fix[i];
     p->T.n_src = n; p->T.w0 = w0; p->T.nw = nw; p->T.nq = nq; p->T.S = S; p->T.halo = halo; p->T.R = R; p->T.nslots = nslots;
     cp::DeviceScope scope(device);
     if (!scope.ok()) return cp::fail(CP_EDEVICE, "cp_spline_rows_plan_create: cannot select device %d", device);
