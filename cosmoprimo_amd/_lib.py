@@ -10,7 +10,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libcosmoprimo_amd.so')
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 CP_OK, CP_EINVAL, CP_EUNSUPPORTED, CP_EDEVICE, CP_ENOMEM = range(5)
 EXTRAP_CONSTANT, EXTRAP_EDGE, EXTRAP_LOGLOG = range(3)
@@ -202,6 +202,7 @@ SIGNATURES['cp_taylor_predict_columns'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE +
 SIGNATURES['cp_taylor_jacobian'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + _WHERE)
 SIGNATURES['cp_taylor_vjp'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong] + _WHERE)      # d_cot, ldc; d_grad, d_work, work_doubles
 SIGNATURES['cp_taylor_jvp'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + _ARRAY + _WHERE)      # d_tan, K; d_out, ldo
+SIGNATURES['cp_taylor_jvp2'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + [ctypes.c_void_p] + _ARRAY + _ARRAY + _WHERE)      # d_tan_u; d_tan_v, K; d_out, ldo
 _GN_TAIL = _ARRAY + _ARRAY + _ARRAY + [ctypes.c_void_p] * 4 + [ctypes.c_longlong]      # d_weights, ldw; d_data, ldd; d_value, ldv; d_fisher, d_grad, d_chi2, d_work, work_doubles
 SIGNATURES['cp_taylor_gauss_newton'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _GN_TAIL + _WHERE)
 SIGNATURES['cp_taylor_gauss_newton_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong])
@@ -220,6 +221,8 @@ SIGNATURES['cp_mlp_predict_columns'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRA
 SIGNATURES['cp_mlp_jacobian'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _ARRAY + _WHERE)      # d_value, ldv; d_jac, ldj
 SIGNATURES['cp_mlp_vjp'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _ARRAY + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong] + _WHERE)      # d_cot, ldc; d_value, ldv; d_grad, d_work, work_doubles
 SIGNATURES['cp_mlp_jvp'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _ARRAY + _ARRAY + _WHERE)      # d_tan, K; d_value, ldv; d_out, ldo
+# d_tan_u; d_tan_v, K; d_value, ldv; d_first_u; d_first_v, ldf; d_out, ldo
+SIGNATURES['cp_mlp_jvp2'] = (ctypes.c_int, _MLP_HEAD + _RANGE + [ctypes.c_void_p] + _ARRAY + _ARRAY + [ctypes.c_void_p] + _ARRAY + _ARRAY + _WHERE)
 SIGNATURES['cp_taylor_fit'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])
 SIGNATURES['cp_mlp_param_count'] = (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int])
 SIGNATURES['cp_mlp_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int])

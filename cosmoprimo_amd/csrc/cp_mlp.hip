@@ -35,13 +35,17 @@
 // Jacobian-vector product (cp_mlp_jvp: out (B K, .) = tan . d predict / d x along K directions per point; mlp_forward_kernel, then mlp_tangent_kernel in its
 // jvp variant).  The tangent kernel with a row per (point, direction) pair and the input tangent tan[b][k][i] / xscale[i]: the same LDS, registers and
 // occupancy, and with K = ndim identity tangents the same bits.  No (B, ndim, .) array exists anywhere.
-// Host side.  cp_mlp_predict(_columns), cp_mlp_jacobian, cp_mlp_vjp and cp_mlp_jvp are back ends of one front: mlp_front holds their common checks and fills the
+// Second directional derivative (cp_mlp_jvp2: out (B K, .) = u . d^2 predict / d x d x . v along K pairs of directions per point; mlp_forward_kernel, for a
+// y function mlp_tangent_kernel's jvp variant once per tangent set, then mlp_tangent2_kernel of cp_mlp_tangent2.h, which carries h, du, dv and the
+// second-order term through the hidden layers and reads the value and the first-order products in its epilogue).
+// Host side.  cp_mlp_predict(_columns), cp_mlp_jacobian, cp_mlp_vjp, cp_mlp_jvp and cp_mlp_jvp2 are back ends of one front: mlp_front holds their common checks and fills the
 // forward kernel's arguments, mlp_yfunction turns the y function into a template argument, mlp_dh_launch picks mlp_dh_kernel<NJ> (vjp and training step);
 // an entry point adds its strides, grid cap, null pointers, workspace and ONE device scope, in that order.
 // Every kernel is held to its instructions (tools/compare_device_code.py).  Where kernels share source -- the jacobian, jvp and Gauss-Newton variants of
 // mlp_tangent_kernel -- they are ONE __global__ template whose variants are chosen at compile time (cp_mlp_tangent.h): a device function for the shared
 // body changed its callers' instructions, and copies of the body had to be kept equal by hand.  The small device functions named above are the only others.
 #include "cp_mlp_tangent.h"      // the tile's constants, MlpNet, mlp_load and mlp_mask, the tangent kernel and its launch
+#include "cp_mlp_tangent2.h"     // the second-order kernel of cp_mlp_jvp2 and its launch
 
 namespace {
 
@@ -785,6 +789,53 @@ extern "C" int cp_mlp_jvp(const double* d_x, long long B, int ndim, int nlayers,
     const int launched = mlp_yfunction(yfunction, [&](auto y) {
         const int forward = mlp_forward_launch<decltype(y)::value>(on, F);
         if (forward == CP_OK) mlp_tangent_launch<decltype(y)::value>(on, J, grid, 0);
+        return forward;
+    });
+    return launched != CP_OK ? launched : on.status();
+}
+
+// Up to four launches on the stream: the forward kernel writes the prediction on the range; the tangent kernel's jvp variant writes the first-order
+// products along u and along v where they are given (what cp_mlp_jvp writes; the y function's chain rule needs them); mlp_tangent2_kernel reads them
+extern "C" int cp_mlp_jvp2(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
+                           const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
+                           long long ncols, const double* d_tan_u, const double* d_tan_v, long long K, double* d_value, long long ldv, double* d_first_u,
+                           double* d_first_v, long long ldf, double* d_out, long long ldo, int device, void* stream) {
+    const char* who = "cp_mlp_jvp2";
+    MlpFwdArgs F{};
+    const int status = mlp_front(who, d_x, B, ndim, nlayers, widths, activations, M, d_params, d_xoffset, d_xscale, d_yoffset, d_yscale, yfunction, col0, ncols, &F);
+    if (status != CP_OK) return status;
+    const bool first = yfunction != CP_MLP_Y_NONE || d_first_u || d_first_v;
+    if (ldv < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the value is less than its %lld columns", who, ldv, ncols);
+    if (first && ldf < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the first-order products is less than their %lld columns", who, ldf, ncols);
+    if (ldo < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the result is less than its %lld columns", who, ldo, ncols);
+    if (K < 1) return cp::fail(CP_EINVAL, "%s: %lld directions per point (at least 1)", who, K);
+    if (K > 0x7fffffffLL || B > 0x7fffffffLL * ML_ROWS / K || (ncols + ML_COLS - 1) / ML_COLS > 65535)
+        return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %lld x %lld results (at most 2^37 rows B K, 2^31 - 1 directions, 2^24 - 256 columns)", who, B, K, ncols);
+    if (B == 0) return CP_OK;
+    if (!d_x || !d_params || !d_xoffset || !d_xscale || !d_yoffset || !d_yscale || !d_tan_u || !d_value || !d_out) return cp::fail(CP_EINVAL, "%s: null pointer", who);
+    if (d_first_v && !d_tan_v) return cp::fail(CP_EINVAL, "%s: null pointer (d_first_v without d_tan_v)", who);
+    if (yfunction != CP_MLP_Y_NONE && (!d_first_u || (d_tan_v && !d_first_v)))
+        return cp::fail(CP_EINVAL, "%s: null pointer (the y function needs the first-order products)", who);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
+    F.out = d_value, F.ldo = ldv;
+    const long long R = B * K;
+    const MlpJvp2Args S{d_x, d_params, d_xoffset, d_xscale, d_yscale, d_tan_u, d_tan_v, d_value, d_first_u, d_first_v, d_out, R, ldv, ldf, ldo, F.c0, F.cend, (int)K, F.net};
+    const dim3 grid((unsigned)((R + ML_ROWS - 1) / ML_ROWS), (unsigned)((ncols + ML_COLS - 1) / ML_COLS));      // (checked above)
+    cp::Launches on(who, stream);
+    const int launched = mlp_yfunction(yfunction, [&](auto y) {
+        constexpr int YF = decltype(y)::value;
+        const int forward = mlp_forward_launch<YF>(on, F);
+        if (forward != CP_OK) return forward;
+        const double* tans[2] = {d_tan_u, d_tan_v};
+        double* firsts[2] = {d_first_u, d_first_v};
+        for (int s = 0; s < 2; ++s) {
+            if (!firsts[s]) continue;
+            const MlpJvpArgs J{{d_x, d_params, d_xoffset, d_xscale, d_yscale, d_value, firsts[s], R, ldv, ldf, F.c0, F.cend, F.net}, tans[s], (int)K};
+            mlp_tangent_launch<YF>(on, J, grid, 0);
+        }
+        if (d_tan_v) mlp_tangent2_launch<YF, true>(on, S, grid);
+        else mlp_tangent2_launch<YF, false>(on, S, grid);
         return forward;
     });
     return launched != CP_OK ? launched : on.status();

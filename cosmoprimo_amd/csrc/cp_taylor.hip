@@ -1,6 +1,6 @@
 // cp_taylor.hip -- Taylor-expansion emulator of a calculator (reference emulators/tools/taylor.py:211-247) for batches of parameter points (gfx950)
 // + C ABI.  One GEMM kernel in float64 on the matrix cores (v_mfma_f64_16x16x4_f64), taylor_gemm_kernel of cp_taylor_gemm.h -- its tile, LDS layout and
-// monomials are described there --, with four of its front ends for the left operand launched from here:
+// monomials are described there --, with five of its front ends for the left operand launched from here:
 //   predict : out (B, M) = monomials (B, T) . derivatives (T, M); the monomials of a tile of rows are formed in LDS, chunk of terms by chunk of terms,
 //             from x - center and the integer powers -- the (B, T) matrix never exists in memory
 //   fit     : derivatives (T, M) = S (T, npoints) . Y (npoints, M); S (the finite-difference weights of every term, built on the host) is staged
@@ -9,6 +9,7 @@
 //             derivative of the monomial, p_ti (x_i - c_i)^(p_ti - 1) prod_{j != i} (x_j - c_j)^p_tj, formed in LDS chunk by chunk as the monomials are
 //   jvp     : out (B K, M) = [tan . d monomials / d x] (B K, T) . derivatives along K directions per point (cp_taylor_jvp, one launch); a row is a
 //             (point, direction) pair r = b K + k.  No (B, ndim, .) array exists anywhere
+//   jvp2    : out (B K, M) = [u . d^2 monomials / d x d x . v] (B K, T) . derivatives along K pairs of directions per point (cp_taylor_jvp2, one launch)
 // (the fifth, Gauss-Newton, from cp_taylor_gauss_newton.hip).  Every kernel is held to its instructions; the front ends share their source by being
 // variants of the one __global__ template, chosen at compile time, not by device functions for the body and not by copies.
 // Vector-Jacobian product (cp_taylor_vjp: G (B, ndim) = cot . d predict / d x).  Two launches: S (B, T) = cot (B, ncols) . D[:, columns]^T is the GEMM with
@@ -198,6 +199,27 @@ extern "C" int cp_taylor_jvp(const double* d_x, long long B, const double* d_cen
     const long long nrt = (B * K + TY_ROWS - 1) / TY_ROWS, nct = (ncols + TY_COLS - 1) / TY_COLS;
     cp::Launches on(who, stream);
     taylor_gemm_launch<TY_JVP>(on, A, dim3((unsigned)nrt, (unsigned)nct), ndim, 0);
+    return on.status();
+}
+
+// One launch: the GEMM with the jvp2 front end on the B K rows (b, k); d_tan_v NULL: the second directional derivative along d_tan_u
+extern "C" int cp_taylor_jvp2(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
+                              const double* d_derivatives, int M, long long col0, long long ncols, const double* d_tan_u, const double* d_tan_v, long long K,
+                              double* d_out, long long ldo, int device, void* stream) {
+    const char* who = "cp_taylor_jvp2";
+    const int status = taylor_front(who, B, ndim, T, max_power, M, col0, ncols, ldo, "result");
+    if (status != CP_OK) return status;
+    if (K < 1) return cp::fail(CP_EINVAL, "%s: %lld directions per point (at least 1)", who, K);
+    if (K > 0x7fffffffLL || B > 0x7fffffffLL * TY_ROWS / K || (ncols + TY_COLS - 1) / TY_COLS > 65535)
+        return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %lld x %lld results (at most 2^37 rows B K, 2^31 - 1 directions, 2^24 - 256 columns)", who, B, K, ncols);
+    if (B == 0) return CP_OK;
+    if (!d_x || !d_center || !d_powers || !d_derivatives || !d_tan_u || !d_out) return cp::fail(CP_EINVAL, "%s: null pointer", who);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
+    const TaylorJvp2Args A{{d_x, d_center, d_powers, d_derivatives, d_out, B * K, ldo, T, M, ndim, (int)col0, (int)(col0 + ncols), 0}, d_tan_u, d_tan_v ? d_tan_v : d_tan_u, (int)K};
+    const long long nrt = (B * K + TY_ROWS - 1) / TY_ROWS, nct = (ncols + TY_COLS - 1) / TY_COLS;
+    cp::Launches on(who, stream);
+    taylor_gemm_launch<TY_JVP2>(on, A, dim3((unsigned)nrt, (unsigned)nct), ndim, 0);
     return on.status();
 }
 

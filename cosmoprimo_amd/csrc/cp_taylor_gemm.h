@@ -7,6 +7,8 @@
 //   TY_JACOBIAN      TaylorArgs     a row is a (point, parameter) pair r = b ndim + i (64 is no multiple of most ndim: a point's rows may lie in two
 //                                   workgroups, every lane finds its own b and i), its entries d mono_t / d x_i = p_ti (x_i - c_i)^(p_ti - 1) prod_{j != i} ...
 //   TY_JVP           TaylorJvpArgs  a row is a (point, direction) pair r = b K + k, its entries sum_i tan[b][k][i] d mono_t / d x_i (details at the front end)
+//   TY_JVP2          TaylorJvp2Args a row is a (point, pair of directions) r = b K + k, its entries sum_ij u_i v_j d^2 mono_t / d x_i d x_j (details at the front end;
+//                                   three (ndim, 64) arrays beside the operand buffers, at most 88 KB: one workgroup per CU above ndim = 26)
 //   TY_GAUSS_NEWTON  TaylorGnArgs   the entries of the jacobian front end with the rows of cp_gauss_newton.h -- a row tile holds P = floor(64 / ndim) whole
 //                                   points, row t = p ndim + i -- and its epilogue in the place of the store: the tile of the Jacobian is never stored
 // Every kernel is held to its instructions (tools/compare_device_code.py).  Source is shared by writing one __global__ template whose variants differ under
@@ -35,7 +37,7 @@ namespace {
 typedef double ty_v4d __attribute__((ext_vector_type(4)));
 
 constexpr int TY_ROWS = 64, TY_COLS = 256, TY_KC = 32, TY_RS = 80, TY_MAX_NDIM = 32, TY_MAX_POWER = 15;
-enum { TY_FIT = 0, TY_PREDICT = 1, TY_JACOBIAN = 2, TY_JVP = 3, TY_GAUSS_NEWTON = 4 };      // the front end of the left operand
+enum { TY_FIT = 0, TY_PREDICT = 1, TY_JACOBIAN = 2, TY_JVP = 3, TY_GAUSS_NEWTON = 4, TY_JVP2 = 5 };      // the front end of the left operand
 
 struct TaylorArgs {
     const double* a;        // predict: x (R, ndim); jacobian: x (R / ndim, ndim), row r the point r / ndim and the parameter r % ndim; fit: the left operand (R, K)
@@ -53,6 +55,12 @@ struct TaylorArgs {
 struct TaylorJvpArgs : TaylorArgs {      // a: x (B, ndim); R = B K rows of the result
     const double* tan;      // (B, K, ndim)
     int Kdir;               // K directions per point
+};
+
+struct TaylorJvp2Args : TaylorArgs {     // a: x (B, ndim); R = B K rows of the result
+    const double* tan_u;    // (B, K, ndim)
+    const double* tan_v;    // (B, K, ndim); tan_u again for the second directional derivative
+    int Kdir;               // K pairs of directions per point
 };
 
 struct TaylorGnArgs {
@@ -90,9 +98,15 @@ __device__ __forceinline__ void taylor_mask(double (&b)[2][4], const bool (&keep
         for (int j = 0; j < 4; ++j) b[h][j] = keep[h] ? b[h][j] : 0.;
 }
 
+// u_i v_j + u_j v_i of the jvp2 front end, both products and the sum rounded on their own (no fused multiply-add): the same bits with u and v exchanged
+__device__ __forceinline__ double taylor_pair(double ui, double vj, double uj, double vi) {
+#pragma clang fp contract(off)
+    return ui * vj + uj * vi;
+}
+
 template <int FRONT, class Args>
 __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const Args A) {
-    constexpr bool GEN = FRONT != TY_FIT, JVP = FRONT == TY_JVP, GN = FRONT == TY_GAUSS_NEWTON, DER = FRONT == TY_JACOBIAN || GN;
+    constexpr bool GEN = FRONT != TY_FIT, JVP = FRONT == TY_JVP, JVP2 = FRONT == TY_JVP2, GN = FRONT == TY_GAUSS_NEWTON, DER = FRONT == TY_JACOBIAN || GN;
     extern __shared__ double ty_lds[];
     // ndim is read from the argument where a variant first uses it, not once up here for all: the place of that one scalar load decided the register
     // allocation of the predict, jacobian and Gauss-Newton instantiations, and every kernel is held to its instructions
@@ -101,7 +115,9 @@ __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const Args A) {
     double* const abuf = ty_lds;                       // 2 x TY_KC x TY_RS
     double* const dl = ty_lds + 2 * TY_KC * TY_RS;     // GEN: (ndim, 64) x - center of the point of each of the tile's rows
     double* tl = nullptr;                              // jvp: (ndim, 64) the tangent of each row
-    if constexpr (JVP) tl = dl + A.ndim * TY_ROWS;
+    if constexpr (JVP || JVP2) tl = dl + A.ndim * TY_ROWS;
+    [[maybe_unused]] double* tl2 = nullptr;            // jvp2: (ndim, 64) the second tangent of each row
+    if constexpr (JVP2) tl2 = tl + A.ndim * TY_ROWS;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const int l15 = lane & 15, g = lane >> 4;
     const int nchunk = (A.K + TY_KC - 1) / TY_KC;
@@ -123,7 +139,7 @@ __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const Args A) {
     [[maybe_unused]] const bool active = col0 < cend;      // (wave-uniform; an idle wave forms its share of the left operand and multiplies the last column: no branch round the MFMAs)
     if constexpr (GN) {
         mine = lane % ndim;
-    } else if constexpr (JVP) {
+    } else if constexpr (JVP || JVP2) {
         b0 = row0 / A.Kdir;
         i0 = (int)(row0 - b0 * A.Kdir);
     } else if constexpr (DER) {
@@ -139,6 +155,13 @@ __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const Args A) {
             if constexpr (GN) {
                 const int p = (e & 63) / ndim;
                 dl[e] = p < A.tail.P && b0 + p < A.tail.B ? A.x[(b0 + p) * ndim + i] - A.center[i] : 0.;      // idle rows and points past the end: finite, never stored
+            } else if constexpr (JVP2) {
+                const long long row = row0 + (e & 63);
+                const long long point = b0 + (i0 + (e & 63)) / A.Kdir;
+                const bool inside = row < A.R;      // rows past the end: finite, never stored
+                dl[e] = inside ? A.a[point * ndim + i] - A.center[i] : 0.;
+                tl[e] = inside ? A.tan_u[row * ndim + i] : 0.;
+                tl2[e] = inside ? A.tan_v[row * ndim + i] : 0.;
             } else if constexpr (JVP) {
                 const long long row = row0 + (e & 63);
                 const long long point = b0 + (i0 + (e & 63)) / A.Kdir;
@@ -168,7 +191,66 @@ __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const Args A) {
     for (int c = 0; c < nchunk; ++c) {
         double* const buf = abuf + (c & 1) * TY_KC * TY_RS;
         const int k0 = c * TY_KC;
-        if constexpr (JVP) {
+        if constexpr (JVP2) {
+            // The entry of term t is sum over the marked parameters i <= j in parameter order, i outer and j inner, of
+            //   c_ij d^2 mono_t / d x_i d x_j,   c_ii = u_i v_i,   c_ij = u_i v_j + u_j v_i  (each product and the sum rounded on its own: exchanging u and v
+            // gives the same bits) -- the full double sum over (i, j) with the two equal mixed derivatives taken together.  The derivative is the product
+            // over the marked q IN THEIR ORDER of p (p - 1) d^(p - 2) (q = i = j; the pair is skipped for p < 2), p d^(p - 1) (q = i or j) or d^p; a factor
+            // whose exponent is 0 is its coefficient alone.  Parameters of power 0 are skipped, not multiplied: neither they nor their tangent components
+            // are read.  A term of total order < 2 has no pair: exactly 0.
+            for (int tt = wave; tt < TY_KC; tt += 4) {      // a term per wave and step, a row per lane
+                const int t = k0 + tt;
+                double s = 0.;      // terms past T: zero columns of the left operand
+                if (t < A.K) {
+                    const int* pw = A.powers + (long long)t * ndim;
+                    unsigned marked = 0;
+                    unsigned long long plo = 0, phi = 0;
+                    for (int i0 = 0; i0 < ndim; i0 += 4) {
+                        int p4[4];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) p4[k] = __builtin_amdgcn_readfirstlane(pw[i0 + k < ndim ? i0 + k : ndim - 1]);
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const int i = i0 + k;
+                            int p = i < ndim ? p4[k] : 0;
+                            if (p <= 0) continue;
+                            p = p < TY_MAX_POWER ? p : TY_MAX_POWER;
+                            marked |= 1u << i;
+                            if (i < 16) plo |= (unsigned long long)p << (4 * i);
+                            else phi |= (unsigned long long)p << (4 * (i - 16));
+                        }
+                    }
+                    for (unsigned mi = marked; mi; mi &= mi - 1) {
+                        const int i = __builtin_ctz(mi);
+                        const int pi = (int)((i < 16 ? plo >> (4 * i) : phi >> (4 * (i - 16))) & 15);
+                        const double ui = tl[i * TY_ROWS + lane], vi = tl2[i * TY_ROWS + lane];
+                        for (unsigned mj = mi; mj; mj &= mj - 1) {      // j >= i
+                            const int j = __builtin_ctz(mj);
+                            if (j == i && pi < 2) continue;
+                            double m = 1.;
+                            for (unsigned mq = marked; mq; mq &= mq - 1) {
+                                const int q = __builtin_ctz(mq);
+                                const int p = (int)((q < 16 ? plo >> (4 * q) : phi >> (4 * (q - 16))) & 15);
+                                const int r = (q == i) + (q == j);      // how often this factor is differentiated
+                                const int e = p - r;
+                                const double c = (double)(r == 0 ? 1 : r == 1 ? p : p * (p - 1));
+                                if (e == 0) {
+                                    if (r) m *= c;
+                                    continue;
+                                }
+                                const double d = dl[q * TY_ROWS + lane];
+                                double v = d;      // d^e
+                                for (int x = 1; x < e; ++x) v *= d;
+                                m *= r ? c * v : v;
+                            }
+                            const double cij = j == i ? ui * vi : taylor_pair(ui, tl2[j * TY_ROWS + lane], tl[j * TY_ROWS + lane], vi);
+                            s = fma(cij, m, s);
+                        }
+                    }
+                }
+                buf[tt * TY_RS + lane] = s;
+            }
+        } else if constexpr (JVP) {
             // A wave forms whole terms, lane = row: one pass over the powers of the term (wave-uniform) marks the parameters with p_ti > 0 in a mask and packs
             // their powers into scalar registers; then, per marked i in parameter order, d mono_t / d x_i is the product over the marked j IN THEIR ORDER of
             // p d^(p - 1) (j = i) or d^p (else), each factor formed as the jacobian front end forms it, and is added as fma(tan_i, ., sum).  A parameter with
@@ -327,7 +409,7 @@ __global__ __launch_bounds__(256, 2) void taylor_gemm_kernel(const Args A) {
 // 72 KB), or the Gauss-Newton epilogue's `epilogue` doubles where those are more.
 template <int FRONT, class Args>
 void taylor_gemm_launch(cp::Launches& on, const Args& A, const dim3 grid, const int ndim, const size_t epilogue) {
-    const size_t gemm = (size_t)2 * TY_KC * TY_RS + (size_t)(FRONT == TY_FIT ? 0 : FRONT == TY_JVP ? 2 : 1) * ndim * TY_ROWS;
+    const size_t gemm = (size_t)2 * TY_KC * TY_RS + (size_t)(FRONT == TY_FIT ? 0 : FRONT == TY_JVP2 ? 3 : FRONT == TY_JVP ? 2 : 1) * ndim * TY_ROWS;
     on.run<taylor_gemm_kernel<FRONT, Args>>(grid, 256, (gemm > epilogue ? gemm : epilogue) * sizeof(double), A);
 }
 

@@ -506,6 +506,68 @@ class Emulator(object):
         values.update(fixed)
         return values, toret
 
+    def jvp2(self, params, tangents, tangents2=None, device=False, keys=None, return_value=False, return_first=False):
+        """Second directional derivatives of the varied outputs along pairs of directions in parameter space, for every point of a batch -- what
+        ``jax.jvp`` of ``jax.jvp`` of the reference's ``predict`` gives: ``sum_ij tangent_i tangent2_j d^2 output / d parameter_i d parameter_j``.
+        ``params`` and the two dictionaries of tangents as in :meth:`jvp` (scalars, ``(B,)`` or ``(B or 1, K)`` values; a missing name is a zero
+        component, a name that is no parameter raises ``KeyError``); both share one K.  ``tangents2=None``: the second directional derivative along
+        ``tangents`` (the ``r''(v, v)`` of geodesic acceleration).
+
+        Returns ``{varied key: (B,) + shape}``, or ``{varied key: (B, K) + shape}`` with K pairs, without the leading ``B`` axis if every parameter is a
+        scalar.  Fixed outputs are not returned.  Computed by second-order forward mode on the device (:meth:`MLPEmulatorEngine.jvp2`,
+        :meth:`TaylorEmulatorEngine.jvp2`), a row per (point, pair): no Hessian is formed, and exchanging the two dictionaries gives the same bits.
+        ``keys``: as in :meth:`predict` -- one call of the engine per maximal contiguous run of columns.  Host arrays by default; ``device=True``: torch
+        tensors, views into the run's buffer, and no synchronisation with the device.  ``return_value=True``: the values of
+        ``predict(params, device=device, keys=keys)`` are prepended; ``return_first=True``: what :meth:`jvp` gives along ``tangents`` (and along
+        ``tangents2``, where given) is inserted before the result."""
+        X, B, scalar = self._points(params)
+        runs, fixed = self._plan(keys)
+        T, K = self._directions(tangents, B)
+        T2 = None
+        if tangents2 is not None:
+            T2, K2 = self._directions(tangents2, B)
+            if K2 != K:
+                raise ValueError('tangents and tangents2 must share one count of directions, got {} and {}'.format(K, K2))
+        nfirst = (2 if T2 is not None else 1) if return_first else 0
+        lead = (B,) if K is None else (B, K)
+        values, firsts, toret = {}, [{} for _ in range(nfirst)], {}
+        for start, stop, entries in runs:
+            out = self.engine.jvp2(X, T, T2, columns=None if keys is None else (start, stop), return_value=return_value, return_first=return_first)
+            out = list(out) if isinstance(out, tuple) else [out]
+            host = lambda tensor: tensor if device else dv.to_host(tensor)      # noqa: E731
+            if return_value:
+                values.update(_split(host(out.pop(0)), (B,), entries, start, scalar))
+            for first in firsts:
+                first.update(_split(host(out.pop(0)), lead, entries, start, scalar))
+            toret.update(_split(host(out.pop(0)), lead, entries, start, scalar))
+        values.update(fixed)
+        result = ([values] if return_value else []) + firsts + [toret]
+        return tuple(result) if len(result) > 1 else toret
+
+    def hessian(self, params, device=False, keys=None):
+        """Second derivatives of the varied outputs with respect to the parameters at ``params`` (as in :meth:`predict`) -- what ``jax.hessian`` of the
+        reference's ``predict`` gives: ``{key: array (B, ndim, ndim) + shape}``, both ``ndim`` axes in the order of ``Emulator.params``, without the
+        leading ``B`` axis if every parameter is a scalar.  One :meth:`jvp2` call on the ``ndim (ndim + 1) / 2`` pairs of unit directions ``i <= j``,
+        mirrored: symmetric bit for bit.  Fixed outputs are not returned.  ``keys``, ``device``: as in :meth:`jvp2`."""
+        names = list(self.params)
+        ndim = len(names)
+        pairs = [(i, j) for i in range(ndim) for j in range(i, ndim)]
+        units = [{name: np.array([[float(pair[side] == n) for pair in pairs]]) for n, name in enumerate(names)} for side in range(2)]
+        X, B, scalar = self._points(params)
+        out = self.jvp2(params, units[0], units[1], device=device, keys=keys)
+        index = np.zeros((ndim, ndim), dtype='i8')
+        for p, (i, j) in enumerate(pairs):
+            index[i, j] = index[j, i] = p
+        toret = {}
+        axis = 0 if scalar else 1
+        for key, block in out.items():      # (B, npairs) + shape, or (npairs,) + shape
+            if device:      # (views stacked: no index array goes to the device)
+                full = dv.torch().stack([block.select(axis, int(p)) for p in index.ravel()], dim=axis)
+            else:
+                full = np.take(block, index.ravel(), axis=axis)
+            toret[key] = full.reshape(tuple(block.shape[:axis]) + (ndim, ndim) + tuple(block.shape[axis + 1:]))
+        return toret
+
     def _staged(self, weights, data, B, dev):
         """What :meth:`gauss_newton` and :meth:`least_squares` read of ``weights`` and ``data`` (the latter or None), checked, on the device ``dev``:
         ``([(start, stop, entries, weights block, data block or None), ...], fixed)``, a maximal contiguous run of columns of :meth:`_plan` over the keys of

@@ -14,8 +14,9 @@ mode through the network on the device (``cp_mlp_jacobian``).  ``vjp`` is its pr
 ``jax.vjp`` / ``jax.grad`` give: the gradient of a scalar function of the outputs for every point of a batch), by reverse mode (``cp_mlp_vjp``): one
 forward pass, one product with the transposed output kernel, one walk back through the hidden layers; the Jacobian is never formed.
 ``jvp`` is its product with tangents, ``sum_i tangent[b, k, i] J[b, i, c]`` (what ``jax.jvp`` / ``jax.linearize`` give), by forward mode with a row per
-(point, direction) pair (``cp_mlp_jvp``).
-``predict``, ``jacobian``, ``vjp`` and ``jvp`` open with one prologue (``_enter``: fitted?, device state, upload and check of ``X``, the leading and the
+(point, direction) pair (``cp_mlp_jvp``).  ``jvp2`` is the second directional derivative ``sum_ij u[b, k, i] v[b, k, j] d^2 predict / d x_i d x_j`` (what
+``jax.jvp`` of ``jax.jvp`` gives), by second-order forward mode with a row per (point, pair of directions) (``cp_mlp_jvp2``).
+``predict``, ``jacobian``, ``vjp``, ``jvp`` and ``jvp2`` open with one prologue (``_enter``: fitted?, device state, upload and check of ``X``, the leading and the
 last arguments of the C entry points); the full prediction is the column range (0, M) of ``cp_mlp_predict_columns``.
 
 Operations are held as numbers, not as expressions: x a chain of affine maps ('scale', 'norm') folded into one (offset, scale) per parameter, y
@@ -423,6 +424,34 @@ class MLPEmulatorEngine(object):
         _lib.check(_lib.load().cp_mlp_jvp(*head, start, ncols, tangents.data_ptr(), K, value.data_ptr(), width, out.data_ptr(), width, *where))
         out = out[:, 0] if single else out
         return (value, out) if return_value else out
+
+    def jvp2(self, X, tangents, tangents2=None, columns=None, return_value=False, return_first=False):
+        """Second directional derivatives of :meth:`predict` at the points ``X`` (B, ndim) along the pairs of directions ``tangents``, ``tangents2``, both
+        (B, ndim) -- device tensor (B, M), ``out[b, c] = sum_ij tangents[b, i] tangents2[b, j] d^2 predict(X)[b, c] / d X[b, i] d X[b, j]`` -- or
+        (B, K, ndim), K pairs per point -- (B, K, M) --, device tensors or host arrays (uploaded), in raw-parameter units; ``tangents2=None``: the
+        second directional derivative along ``tangents``.  By second-order forward mode through the network with a row per (point, pair) (``cp_mlp_jvp2``:
+        no (B, ndim, ndim, M) array anywhere; exchanging the two sets gives the same bits).  ``columns = (start, stop)``: those output columns only, bit
+        for bit the same numbers.  ``return_value=True``: ``predict(X, columns=columns)`` is prepended, bit for bit; ``return_first=True``: what
+        :meth:`jvp` gives along ``tangents`` (and along ``tangents2``, where given) is inserted before the result, bit for bit.  Nothing is read back and
+        the call does not wait for the device."""
+        d, X, B, head, where = self._enter(X)
+        start, ncols = _columns(columns, d['net']['M'])
+        width = max(ncols, 0)
+        tangents, K, single = _tangent(tangents, B, d['net']['ndim'], d['device'])
+        mixed = tangents2 is not None
+        if mixed:
+            tangents2, K2, single2 = _tangent(tangents2, B, d['net']['ndim'], d['device'])
+            if (K2, single2) != (K, single):
+                raise ValueError('tangents and tangents2 must share one shape')
+        first = return_first or d['yfunction'] != 0      # the y function's chain rule reads the first-order products
+        value, out = _empty(d, B, width), _empty(d, B, K, width)
+        firsts = [_empty(d, B, K, width) if first else None for _ in range(2 if mixed else 1)] + ([] if mixed else [None])
+        ptr = lambda tensor: tensor.data_ptr() if tensor is not None else None      # noqa: E731
+        _lib.check(_lib.load().cp_mlp_jvp2(*head, start, ncols, tangents.data_ptr(), ptr(tangents2), K, value.data_ptr(), width, ptr(firsts[0]), ptr(firsts[1]), width,
+                                           out.data_ptr(), width, *where))
+        toret = ([value] if return_value else []) + ([f[:, 0] if single else f for f in firsts if f is not None] if return_first else [])
+        toret.append(out[:, 0] if single else out)
+        return tuple(toret) if len(toret) > 1 else toret[0]
 
     def gauss_newton(self, X, weights, data=None, columns=None, return_value=False):
         """Fisher matrices and Gauss-Newton normal equations of :meth:`predict` at the points ``X`` (B, ndim), with ``J`` the Jacobian of :meth:`jacobian`:

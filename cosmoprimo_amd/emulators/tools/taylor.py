@@ -7,7 +7,8 @@ finite-difference weights, times the 1 / alpha! of the term -- is built here on 
 (``cp_taylor_fit``), and ``derivatives`` stay there.  Predict: ``out (B, M) = monomials (B, T) . derivatives`` for B parameter points at once
 (``cp_taylor_predict_columns``: the monomials are formed inside the kernel), where the reference evaluates one point per call.  Jacobian: the derivative
 of the polynomial with respect to the parameters, ``(B ndim, M) = d monomials / d x_i . derivatives`` by the same kernel (``cp_taylor_jacobian``).  Vjp: its
-product with a cotangent, without forming it (``cp_taylor_vjp``).  Jvp: its product with tangents, without forming it (``cp_taylor_jvp``).  They open
+product with a cotangent, without forming it (``cp_taylor_vjp``).  Jvp: its product with tangents, without forming it (``cp_taylor_jvp``).  Jvp2: second
+directional derivatives along pairs of tangents, the second derivatives of the monomials formed inside the kernel (``cp_taylor_jvp2``).  They open
 with one prologue (``_enter``: device state, upload and check of ``X``, the nine leading C arguments).
 
 No x / y operations (log10, PCA, ...).
@@ -228,6 +229,31 @@ class TaylorEmulatorEngine(object):
         _lib.check(_lib.load().cp_taylor_jvp(*head, start, ncols, tangents.data_ptr(), K, out.data_ptr(), width, *where))
         out = out[:, 0] if single else out
         return (self.predict(X, columns=columns), out) if return_value else out
+
+    def jvp2(self, X, tangents, tangents2=None, columns=None, return_value=False, return_first=False):
+        """Second directional derivatives of :meth:`predict` at the points ``X`` (B, ndim) along the pairs of directions ``tangents``, ``tangents2``, both
+        (B, ndim) -- device tensor (B, M), ``out[b, c] = sum_ij tangents[b, i] tangents2[b, j] d^2 predict(X)[b, c] / d X[b, i] d X[b, j]`` -- or
+        (B, K, ndim), K pairs per point -- (B, K, M) --, device tensors or host arrays (uploaded); ``tangents2=None``: the second directional derivative
+        along ``tangents``.  One launch (``cp_taylor_jvp2``: the second derivatives of the monomials contracted with the pair inside the kernel, a
+        parameter that a term does not hold skipped; no (B, ndim, ndim, M) array anywhere; exchanging the two sets gives the same bits).
+        ``columns = (start, stop)``: those output columns only, bit for bit the same numbers.  ``return_value=True``: ``predict(X, columns=columns)`` is
+        prepended, one more launch; ``return_first=True``: what :meth:`jvp` gives along ``tangents`` (and along ``tangents2``, where given) is inserted
+        before the result, a call of :meth:`jvp` each.  Nothing is read back and the call does not wait for the device."""
+        d, X, (B, ndim, T, M), head, where = self._enter(X)
+        start, ncols = _columns(columns, M)
+        width = max(ncols, 0)
+        sets = [tangents] if tangents2 is None else [tangents, tangents2]
+        tangents, K, single = _tangent(tangents, B, ndim, d['device'])
+        mixed = tangents2 is not None
+        if mixed:
+            tangents2, K2, single2 = _tangent(tangents2, B, ndim, d['device'])
+            if (K2, single2) != (K, single):
+                raise ValueError('tangents and tangents2 must share one shape')
+        out = _empty(d, B, K, width)
+        _lib.check(_lib.load().cp_taylor_jvp2(*head, start, ncols, tangents.data_ptr(), tangents2.data_ptr() if mixed else None, K, out.data_ptr(), width, *where))
+        toret = ([self.predict(X, columns=columns)] if return_value else []) + ([self.jvp(X, t, columns=columns) for t in sets] if return_first else [])
+        toret.append(out[:, 0] if single else out)
+        return tuple(toret) if len(toret) > 1 else toret[0]
 
     def gauss_newton(self, X, weights, data=None, columns=None, return_value=False):
         """Fisher matrices and Gauss-Newton normal equations of :meth:`predict` at the points ``X`` (B, ndim), with ``J`` the Jacobian of :meth:`jacobian`:

@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define CP_ABI_VERSION 4
+#define CP_ABI_VERSION 5
 
 enum cp_status {
     CP_OK = 0,
@@ -678,6 +678,13 @@ int cp_spline_tables_apply_f32(const double* d_xk, const double* d_coef, const i
  *   gives the bits of the same columns of the full call, and K = ndim identity tangents give the bits of jacobian on finite inputs.  The argument checks
  *   are those of jacobian (ldo in the place of ldj), then K < 1: CP_EINVAL, before any device call; more than 2^37 rows B K or K > 2^31 - 1:
  *   CP_EUNSUPPORTED; B = 0: CP_OK.
+ * jvp2 : second directional derivatives of predict_columns along K >= 1 pairs of directions per point, d_out (B K, ncols) with row stride ldo >= ncols,
+ *   row b K + k = sum_ij d_tan_u[b][k][i] d_tan_v[b][k][j] d^2 value[b][.] / d x[b][i] d x[b][j] (what jax.jvp of jax.jvp of the reference's predict gives);
+ *   d_tan_v NULL: d_tan_v = d_tan_u.  One launch: the entry of term t is the sum over the parameters i <= j with p_ti, p_tj > 0, in parameter order, of
+ *   c_ij d^2 mono_t / d x_i d x_j with c_ii = u_i v_i and c_ij = u_i v_j + u_j v_i, each product and the sum rounded on its own, so exchanging d_tan_u and
+ *   d_tan_v gives the same bits; the diagonal of a parameter with p_ti < 2 is skipped, a term of total order < 2 contributes exactly 0, and a parameter of
+ *   power 0 is skipped as in jvp: a NaN or Inf there, or in its tangent components, does not reach the result.  No atomics: two calls give the same bits,
+ *   a range gives the bits of the same columns of the full call.  The argument checks are those of jvp, in its order.
  * gauss_newton : Fisher matrices and Gauss-Newton normal equations of predict_columns on a range, with the arguments, the results and the contract of
  *   cp_mlp_gauss_newton below (J the Jacobian of jacobian, bit for bit; the zero-weight select; exact symmetry; no atomics; no (B, ndim, .) array), in
  *   csrc/cp_taylor_gauss_newton.hip.  d_value, where given, receives what predict_columns writes on the range.  d_work: work_doubles >=
@@ -697,6 +704,9 @@ int cp_taylor_vjp(const double* d_x, long long B, const double* d_center, const 
 int cp_taylor_jvp(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                   const double* d_derivatives, int M, long long col0, long long ncols, const double* d_tan, long long K, double* d_out, long long ldo,
                   int device, void* stream);
+int cp_taylor_jvp2(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
+                   const double* d_derivatives, int M, long long col0, long long ncols, const double* d_tan_u, const double* d_tan_v, long long K, double* d_out,
+                   long long ldo, int device, void* stream);
 long long cp_taylor_gauss_newton_workspace_doubles(long long B, int ndim, int T, int M, long long ncols);
 int cp_taylor_gauss_newton(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                            const double* d_derivatives, int M, long long col0, long long ncols, const double* d_weights, long long ldw, const double* d_data,
@@ -741,6 +751,20 @@ int cp_taylor_gauss_newton(const double* d_x, long long B, const double* d_cente
  *   inputs.  A NaN in row b of d_x makes the K rows of point b NaN, a NaN in d_tan[b][k] row b K + k, and touches no other row.  The argument checks
  *   are those of jacobian (ldo in the place of ldj), then K < 1: CP_EINVAL, before any device call; more than 2^37 rows B K or K > 2^31 - 1:
  *   CP_EUNSUPPORTED; B = 0: CP_OK.
+ * jvp2 : second directional derivatives of predict_columns along K >= 1 pairs of directions per point by second-order forward mode (what jax.jvp of
+ *   jax.jvp of the reference's predict gives; the second directional derivative with d_tan_v NULL, which means d_tan_v = d_tan_u), without any
+ *   (B, ndim, ndim, .) array.  d_tan_u, d_tan_v (B, K, ndim) contiguous, raw-parameter units; d_out (B K, ncols) with row stride ldo >= ncols, row b K + k =
+ *   sum_ij d_tan_u[b][k][i] d_tan_v[b][k][j] d^2 value[b][.] / d x[b][i] d x[b][j].  A hidden layer maps (h, du, dv, d2) to (act(z), act'(z) zu, act'(z) zv,
+ *   act''(z) (zu zv) + act'(z) z2) with zu = du @ kernel etc. from du = d_tan_u / d_xscale, dv = d_tan_v / d_xscale, d2 = 0 (relu: act'' = 0 exactly); the
+ *   output layer (no bias) multiplies d2 on the matrix cores, a = that times d_yscale[m], and the epilogue is a for no y function,
+ *   ln 10 y a + y_u y_v / y for 10^v (the quotient 0 where y = 0) and sqrt(1 + y^2) a + y (y_u y_v) / (1 + y^2) for sinh, with y the value and y_u, y_v
+ *   the first-order products.  d_value as in jvp (always written, predict_columns bit for bit).  d_first_u, d_first_v (B K, ncols) with row stride
+ *   ldf >= ncols: written where given, bit for bit what jvp writes to d_out along d_tan_u and d_tan_v; with a y function d_first_u, and with d_tan_v also
+ *   d_first_v, must be given (CP_EINVAL), without one they may be NULL; d_first_v given while d_tan_v is NULL: CP_EINVAL.  The products zu zv and y_u y_v
+ *   are rounded on their own, so exchanging d_tan_u with d_tan_v (and d_first_u with d_first_v) gives the same bits.  Up to four launches, no atomics: two
+ *   calls give the same bits, a range gives the bits of the same columns of the full call.  A NaN in row b of d_x makes the K rows of point b NaN, a NaN
+ *   in d_tan_u[b][k] or d_tan_v[b][k] row b K + k, and touches no other row.  The argument checks are those of jvp, in its order (ldf after ldv where the
+ *   first-order products are given or needed), before any device call.
  * gauss_newton : Fisher matrices and Gauss-Newton normal equations of predict_columns on a range, per point b over its columns c, J the Jacobian of
  *   jacobian: d_fisher (B, ndim, ndim) contiguous = sum_c w[b][c] J[b][i][c] J[b][j][c]; d_grad (B, ndim) = sum_c w[b][c] (data[b][c] - value[b][c]) J[b][i][c];
  *   d_chi2 (B) = sum_c w[b][c] (data[b][c] - value[b][c])^2, without any (B, ndim, .) array, workspace included (csrc/cp_mlp_gauss_newton.hip,
@@ -779,6 +803,10 @@ int cp_mlp_vjp(const double* d_x, long long B, int ndim, int nlayers, const int*
 int cp_mlp_jvp(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
                const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
                long long ncols, const double* d_tan, long long K, double* d_value, long long ldv, double* d_out, long long ldo, int device, void* stream);
+int cp_mlp_jvp2(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
+                const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
+                long long ncols, const double* d_tan_u, const double* d_tan_v, long long K, double* d_value, long long ldv, double* d_first_u,
+                double* d_first_v, long long ldf, double* d_out, long long ldo, int device, void* stream);
 long long cp_mlp_gauss_newton_workspace_doubles(long long B, int ndim, int nlayers, const int* widths, int M, long long ncols);
 int cp_mlp_gauss_newton(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
                         const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
