@@ -505,14 +505,19 @@ void launch_apply(cp::Launches& on, const Args& A, size_t lds) {
 }
 
 // scipy.interpolate.CubicSpline: tridiagonal system for the knot first derivatives s (lower, diag, upper) and the
-// right-hand side as a sparse linear map of y (entries rhs[i] = sum_k c[i][k] y[col[i][k]], at most 4 per row)
+// right-hand side as a sparse linear map of y (entries rhs[i] = sum_k c[i][k] y[col[i][k]], at most 4 per row).
+// ``xreal`` is double, or long double for knots whose neighbouring spacings differ by more than UNEVEN_KNOTS (cp_spline_operator).
+constexpr double UNEVEN_KNOTS = 4.;
+
+template <typename xreal>
 struct RhsRow {
     int col[4];
-    double c[4];
+    xreal c[4];
     int nnz;
 };
 
-void add(RhsRow& r, int col, double c) {
+template <typename xreal>
+void add(RhsRow<xreal>& r, int col, xreal c) {
     for (int k = 0; k < r.nnz; ++k)
         if (r.col[k] == col) {
             r.c[k] += c;
@@ -524,22 +529,24 @@ void add(RhsRow& r, int col, double c) {
 }
 
 // slope_i = (y[i+1] - y[i]) / dx[i] scaled by f, added to the row
-void add_slope(RhsRow& r, int i, double f, const std::vector<double>& dx) {
+template <typename xreal>
+void add_slope(RhsRow<xreal>& r, int i, xreal f, const std::vector<xreal>& dx) {
     add(r, i + 1, f / dx[i]);
     add(r, i, -f / dx[i]);
 }
 
-int build_system(int n, const double* x, int bc, std::vector<double>& lo, std::vector<double>& di, std::vector<double>& up, std::vector<RhsRow>& rhs,
-                 std::vector<double>& dx) {
+template <typename xreal>
+int build_system(int n, const double* x, int bc, std::vector<xreal>& lo, std::vector<xreal>& di, std::vector<xreal>& up, std::vector<RhsRow<xreal>>& rhs,
+                 std::vector<xreal>& dx) {
     dx.resize(n - 1);
     for (int i = 0; i < n - 1; ++i) {
-        dx[i] = x[i + 1] - x[i];
+        dx[i] = (xreal)x[i + 1] - (xreal)x[i];
         if (!(dx[i] > 0.)) return cp::fail(CP_EINVAL, "cp_spline_plan_create: knots must be strictly increasing");
     }
     lo.assign(n, 0.);
     di.assign(n, 0.);
     up.assign(n, 0.);
-    rhs.assign(n, RhsRow{{0, 0, 0, 0}, {0., 0., 0., 0.}, 0});
+    rhs.assign(n, RhsRow<xreal>{{0, 0, 0, 0}, {0., 0., 0., 0.}, 0});
     for (int i = 1; i < n - 1; ++i) {  // interior rows
         lo[i] = dx[i];
         di[i] = 2. * (dx[i - 1] + dx[i]);
@@ -549,19 +556,19 @@ int build_system(int n, const double* x, int bc, std::vector<double>& lo, std::v
     }
     if (bc == CP_SPLINE_NATURAL) {
         di[0] = 2. * dx[0]; up[0] = dx[0];
-        add(rhs[0], 1, 3.); add(rhs[0], 0, -3.);
+        add(rhs[0], 1, xreal(3.)); add(rhs[0], 0, xreal(-3.));
         di[n - 1] = 2. * dx[n - 2]; lo[n - 1] = dx[n - 2];
-        add(rhs[n - 1], n - 1, 3.); add(rhs[n - 1], n - 2, -3.);
+        add(rhs[n - 1], n - 1, xreal(3.)); add(rhs[n - 1], n - 2, xreal(-3.));
     } else if (bc == CP_SPLINE_CLAMPED) {
         di[0] = 1.; up[0] = 0.;
         di[n - 1] = 1.; lo[n - 1] = 0.;
     } else if (bc == CP_SPLINE_NOT_A_KNOT) {
         if (n < 4) return cp::fail(CP_EINVAL, "cp_spline_plan_create: not-a-knot needs at least 4 knots");
-        double d = x[2] - x[0];
+        xreal d = (xreal)x[2] - (xreal)x[0];
         di[0] = dx[1]; up[0] = d;
         add_slope(rhs[0], 0, (dx[0] + 2. * d) * dx[1] / d, dx);
         add_slope(rhs[0], 1, dx[0] * dx[0] / d, dx);
-        d = x[n - 1] - x[n - 3];
+        d = (xreal)x[n - 1] - (xreal)x[n - 3];
         di[n - 1] = dx[n - 3]; lo[n - 1] = d;
         add_slope(rhs[n - 1], n - 3, dx[n - 2] * dx[n - 2] / d, dx);
         add_slope(rhs[n - 1], n - 2, (2. * d + dx[n - 2]) * dx[n - 3] / d, dx);
@@ -594,20 +601,21 @@ bool cp_spline_plan_view(const cp_spline_plan* p, cp_spline_band_view* out) {
 
 extern "C" int cp_spline_plan_destroy(cp_spline_plan* p) { return cp::destroy_plan(p); }
 
-// Dense operator on the host (row-major nq x n); exposed so that tests can pin it against scipy without a GPU.
-extern "C" int cp_spline_operator(int n, const double* x, int nq, const double* xq, int bc, int nu, int extrapolate, double* w_out, int* inside_out) {
-    if (n < 2 || nq < 0 || !x || (nq > 0 && !xq) || !w_out) return cp::fail(CP_EINVAL, "cp_spline_operator: bad arguments");
-    if (nu < 0 || nu > 2) return cp::fail(CP_EINVAL, "cp_spline_operator: derivative order %d not in [0, 2]", nu);
-    std::vector<double> lo, di, up, dx;
-    std::vector<RhsRow> rhs;
+namespace {
+
+// The weights in the arithmetic ``xreal``, rounded to double as they are stored.
+template <typename xreal>
+int spline_operator_weights(int n, const double* x, int nq, const double* xq, int bc, int nu, int extrapolate, double* w_out, int* inside_out) {
+    std::vector<xreal> lo, di, up, dx;
+    std::vector<RhsRow<xreal>> rhs;
     int st = build_system(n, x, bc, lo, di, up, rhs, dx);
     if (st != CP_OK) return st;
     // Thomas factorisation (matrix only)
-    std::vector<double> cp(n), inv(n);
-    inv[0] = 1. / di[0];
+    std::vector<xreal> cp(n), inv(n);
+    inv[0] = xreal(1.) / di[0];
     cp[0] = up[0] * inv[0];
     for (int i = 1; i < n; ++i) {
-        inv[i] = 1. / (di[i] - lo[i] * cp[i - 1]);
+        inv[i] = xreal(1.) / (di[i] - lo[i] * cp[i - 1]);
         cp[i] = up[i] * inv[i];
     }
     // interval of each query
@@ -629,10 +637,10 @@ extern "C" int cp_spline_operator(int n, const double* x, int nq, const double* 
         kq[q] = a;
     }
     std::memset(w_out, 0, sizeof(double) * (size_t)nq * n);
-    std::vector<double> s(n), d(n);
+    std::vector<xreal> s(n), d(n);
     for (int j = 0; j < n; ++j) {  // column j: data = e_j
         for (int i = 0; i < n; ++i) {
-            double v = 0.;
+            xreal v = 0.;
             for (int k = 0; k < rhs[i].nnz; ++k)
                 if (rhs[i].col[k] == j) v += rhs[i].c[k];
             d[i] = v;
@@ -645,23 +653,44 @@ extern "C" int cp_spline_operator(int n, const double* x, int nq, const double* 
             const int k = kq[q];
             if (k < 0) continue;
             // PPoly coefficients of interval k (scipy CubicSpline): t = (s_k + s_{k+1} - 2 slope) / dx
-            const double h = dx[k];
-            const double yk = (j == k) ? 1. : 0., yk1 = (j == k + 1) ? 1. : 0.;
-            const double slope = (yk1 - yk) / h;
-            const double t = (s[k] + s[k + 1] - 2. * slope) / h;
-            const double c3 = t / h, c2 = (slope - s[k]) / h - t, c1 = s[k], c0 = yk;
-            const double u = xq[q] - x[k];
-            double v;
+            const xreal h = dx[k];
+            const xreal yk = (j == k) ? 1. : 0., yk1 = (j == k + 1) ? 1. : 0.;
+            const xreal slope = (yk1 - yk) / h;
+            const xreal t = (s[k] + s[k + 1] - 2. * slope) / h;
+            const xreal c3 = t / h, c2 = (slope - s[k]) / h - t, c1 = s[k], c0 = yk;
+            const xreal u = (xreal)xq[q] - (xreal)x[k];
+            xreal v;
             if (nu == 0) v = c0 + u * (c1 + u * (c2 + u * c3));
             else if (nu == 1) v = c1 + u * (2. * c2 + u * 3. * c3);
             else v = 2. * c2 + 6. * c3 * u;
-            w_out[(size_t)q * n + j] = v;
+            w_out[(size_t)q * n + j] = (double)v;
         }
     }
     for (int q = 0; q < nq; ++q)
         if (kq[q] < 0)
             for (int j = 0; j < n; ++j) w_out[(size_t)q * n + j] = std::numeric_limits<double>::quiet_NaN();
     return CP_OK;
+}
+
+}  // namespace
+
+// Dense operator on the host (row-major nq x n); exposed so that tests can pin it against scipy without a GPU.
+// The weights are differences of terms of size 1 / h and 1 / h^2.  For the values between knots of even spacing float64 keeps them to a few ulps of their
+// row's sum.  It does not where neighbouring spacings differ by decades (log k knots padded at both ends, a saw of spacings: derivative weights hundreds
+// of ulps from the truth, as in any float64 solve), nor for derivatives and continued end cubics on even knots (the first derivative one interval below
+// 100 uniform knots: 4e-15 of a row's largest value, 25 times what a float64 spline of the row itself loses) -- tests/test_linop_truth_host.py,
+// tests/test_linop_truth_gpu.py.  Those operators -- a ratio of neighbouring spacings above UNEVEN_KNOTS, nu > 0, or extrapolate -- get their weights in
+// extended precision (host only, once per plan); the others keep the float64 arithmetic and every bit of their weights.
+extern "C" int cp_spline_operator(int n, const double* x, int nq, const double* xq, int bc, int nu, int extrapolate, double* w_out, int* inside_out) {
+    if (n < 2 || nq < 0 || !x || (nq > 0 && !xq) || !w_out) return cp::fail(CP_EINVAL, "cp_spline_operator: bad arguments");
+    if (nu < 0 || nu > 2) return cp::fail(CP_EINVAL, "cp_spline_operator: derivative order %d not in [0, 2]", nu);
+    bool uneven = nu > 0 || extrapolate != 0;
+    for (int i = 1; i + 1 < n; ++i) {
+        const double a = x[i] - x[i - 1], b = x[i + 1] - x[i];
+        if (a > 0. && b > 0. && (a > UNEVEN_KNOTS * b || b > UNEVEN_KNOTS * a)) uneven = true;
+    }
+    if (uneven) return spline_operator_weights<long double>(n, x, nq, xq, bc, nu, extrapolate, w_out, inside_out);
+    return spline_operator_weights<double>(n, x, nq, xq, bc, nu, extrapolate, w_out, inside_out);
 }
 
 // plan from a dense (nq x n) operator; rows whose first entry is NaN mark queries that evaluate to NaN

@@ -155,13 +155,14 @@ def third_derivatives(x, y, s):
     return 6 * (s[..., :-1] + s[..., 1:] - 2 * delta) / h**2
 
 
-def evaluate(x, y, s, xq, extrapolate=False):
-    """The piecewise cubic at the shared queries xq (nq,): (rows, nq).  x (n,) or (rows, n).  Outside the knots NaN, or the end cubics continued."""
+def evaluate(x, y, s, xq, extrapolate=False, nu=0):
+    """The piecewise cubic (nu = 1, 2: its first, second derivative) at the shared queries xq (nq,): (rows, nq).  x (n,) or (rows, n).  Outside the
+    knots NaN, or the end cubics continued.  A query on an interior knot belongs to the interval that begins there, the last knot to the last interval."""
     dtype = s.dtype
     x, y = np.asarray(x).astype(dtype), np.asarray(y).astype(dtype)
     xq64 = np.asarray(xq, dtype='f8')
     if x.ndim == 2:
-        return np.stack([evaluate(x[r], y[r:r + 1], s[r:r + 1], xq64, extrapolate)[0] for r in range(len(x))])
+        return np.stack([evaluate(x[r], y[r:r + 1], s[r:r + 1], xq64, extrapolate, nu)[0] for r in range(len(x))])
     n = x.size
     q = xq64.astype(dtype)
     j = np.clip(np.searchsorted(x, q, side='right') - 1, 0, n - 2)
@@ -172,14 +173,21 @@ def evaluate(x, y, s, xq, extrapolate=False):
     c2 = (3 * delta - 2 * s0 - s1) / h
     c3 = (s0 + s1 - 2 * delta) / h**2
     t = q - x[j]
-    v = y[..., j] + t * (s0 + t * (c2 + t * c3))
+    if nu == 0:
+        v = y[..., j] + t * (s0 + t * (c2 + t * c3))
+    elif nu == 1:
+        v = s0 + t * (2 * c2 + 3 * t * c3)
+    elif nu == 2:
+        v = 2 * c2 + 6 * t * c3
+    else:
+        raise ValueError('derivative order {}'.format(nu))
     outside = (xq64 != xq64) if extrapolate else ~((xq64 >= float(x[0])) & (xq64 <= float(x[-1])))
     v[..., outside] = np.nan
     return v
 
 
-def spline(x, y, xq, bc='natural', extrapolate=False, dtype=LD):
-    return evaluate(x, y, slopes(x, y, bc, dtype), xq, extrapolate)
+def spline(x, y, xq, bc='natural', extrapolate=False, dtype=LD, nu=0):
+    return evaluate(x, y, slopes(x, y, bc, dtype), xq, extrapolate, nu)
 
 
 def knot_second_derivatives(x, y, bc='natural', dtype=LD):

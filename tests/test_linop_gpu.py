@@ -1,6 +1,7 @@
 """Dense linear operators (``cp_linop_plan_create`` + ``cp_spline_apply``): the float64 matrix-core kernel (v_mfma_f64_16x16x4_f64) against the
 vector-ALU kernel and against numpy, for shapes that exercise every edge of the 32 x 256 tiling; the fused outer-product epilogue of the spline
-operator (``cp_spline_apply_outer``) against its two-step form."""
+operator (``cp_spline_apply_outer``) against its two-step form.
+Accuracy is held by tests/test_linop_truth_gpu.py (longdouble truth, per-block allowances); the tolerances here are global scales that guard the routes only."""
 import numpy as np
 import pytest
 
