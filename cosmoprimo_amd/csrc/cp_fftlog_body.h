@@ -246,23 +246,35 @@ struct Fftlog {
     }
 
     // ---- row screening (see CP_ROW_SCREEN above) -------------------------------------------------------------------------
-    // info = exponent field of row a | exponent field of row b << 16
+    // info = magnitude field of row a | magnitude field of row b << 16.  The field is the exponent field of the row's largest |tilted sample|, with two
+    // amendments: 0 is kept for a row that IS zero, and a row whose largest sample is subnormal counts as exponent field 1 (tiny_to_one, make_info).
     struct RowFix {
         int any, nan_a, nan_b, sh_a, sh_b;  // sh: power of two applied to the row on the way in (0: none), undone on the way out
     };
+    // A row of zeros beside a live partner: its half of the packed transform holds the rounding of the partner's, where numpy's row-by-row
+    // transform gives exactly 0.  It takes the "shift" CP_ZERO_ROW_SHIFT, beyond the whole range of the format: ldexp leaves its zeros as
+    // they are on the way in and takes whatever finite values came out to (signed) zero on the way out -- no further case in the fix-ups.
+    static constexpr int CP_ZERO_ROW_SHIFT = 4096;
     static CP_HD RowFix decode_info(unsigned info) {
         const int ea = (int)(info & 0xffffu), eb = (int)(info >> 16);
         RowFix f;
         f.nan_a = ea == 2047;
         f.nan_b = eb == 2047;
         const int d = ea - eb;
+        // (a subnormal row has field 1: beside a distant partner it comes up by 2^1022, exactly, and goes back down with one rounding)
         const int scale = !f.nan_a && !f.nan_b && ea != 0 && eb != 0 && (d > CP_ROW_SCALE_SPREAD || d < -CP_ROW_SCALE_SPREAD);
         f.sh_a = scale ? 1023 - ea : 0;
         f.sh_b = scale ? 1023 - eb : 0;
-        f.any = f.nan_a | f.nan_b | scale;
+        const int zero_a = ea == 0 && eb != 0, zero_b = eb == 0 && ea != 0;
+        if (zero_a) f.sh_a = CP_ZERO_ROW_SHIFT;
+        if (zero_b) f.sh_b = CP_ZERO_ROW_SHIFT;
+        f.any = f.nan_a | f.nan_b | scale | zero_a | zero_b;
         return f;
     }
-    static CP_HD unsigned make_info(unsigned ma, unsigned mb) { return (ma >> 20) | ((mb >> 20) << 16); }
+    // hi_abs of a sample (or of a sum of |samples|) that is not zero but has an empty high dword (below 2^-1042) counts as 1
+    static CP_HD unsigned tiny_to_one(unsigned h, double v) { return (h == 0u && v != 0.) ? 1u : h; }
+    static CP_HD unsigned field(unsigned m) { return (m >> 20) | (unsigned)(m != 0u && m < (1u << 20)); }
+    static CP_HD unsigned make_info(unsigned ma, unsigned mb) { return field(ma) | (field(mb) << 16); }
     // The verdict is decoded once per pair: `gate` maps every info word that asks for nothing to 0, and the fix-ups test that word only.
     static CP_HD unsigned gate(unsigned info) { return decode_info(info).any ? info : 0u; }
     template <int N>
@@ -300,7 +312,7 @@ struct Fftlog {
             sa += __builtin_fabs(a[r]);
             sb += __builtin_fabs(b[r]);
         }
-        const unsigned ha = hi_abs(sa), hb = hi_abs(sb);
+        const unsigned ha = tiny_to_one(hi_abs(sa), sa), hb = tiny_to_one(hi_abs(sb), sb);
         ma = ma > ha ? ma : ha;
         mb = mb > hb ? mb : hb;
         return;
@@ -311,6 +323,13 @@ struct Fftlog {
             ma = ma > ha ? ma : ha;
             mb = mb > hb ? mb : hb;
         }
+        if (ma == 0u || mb == 0u) {  // rare: every high dword of a row empty -- zero throughout, or samples below 2^-1042?
+#pragma unroll
+            for (int r = 0; r < N; ++r) {
+                ma = tiny_to_one(ma, a[r]);
+                mb = tiny_to_one(mb, b[r]);
+            }
+        }
     }
     template <int N>
     static CP_HD void thread_max(const cplx* x, unsigned& ma, unsigned& mb) {
@@ -319,6 +338,13 @@ struct Fftlog {
             const unsigned ha = hi_abs(x[r].re), hb = hi_abs(x[r].im);
             ma = ma > ha ? ma : ha;
             mb = mb > hb ? mb : hb;
+        }
+        if (ma == 0u || mb == 0u) {  // rare, as above
+#pragma unroll
+            for (int r = 0; r < N; ++r) {
+                ma = tiny_to_one(ma, x[r].re);
+                mb = tiny_to_one(mb, x[r].im);
+            }
         }
     }
     // phase 0 of the variants that do not screen ahead: the thread's tilted points x[0..N) -> reduction over the workgroup (one
@@ -379,7 +405,8 @@ struct Fftlog {
                                         const FftlogArgs& A) {
         unsigned ma = 0, mb = 0;
         for (int j = 0; j < NP; ++j) {
-            const unsigned ha = hi_abs(fetch(ra, j, A) * pre[j]), hb = hi_abs(fetch(rb, j, A) * pre[j]);
+            const double va = fetch(ra, j, A) * pre[j], vb = fetch(rb, j, A) * pre[j];
+            const unsigned ha = tiny_to_one(hi_abs(va), va), hb = tiny_to_one(hi_abs(vb), vb);
             ma = ma > ha ? ma : ha;
             mb = mb > hb ? mb : hb;
         }

@@ -25,6 +25,11 @@ is base row i % 2 times an exact 2**e, |e| <= 300, another e for every (item, ke
 2j + 1 of one kernel index) therefore always differ in content and in scale.  The transform is linear and zero / 'edge' padding scale with the
 row, so the truth of a row is the truth of its base row times 2**e: longdouble work and restatement once per (base row, kernel index).  'log'
 padding is left out: over paddings this long the geometric continuation overflows, in the reference as well (test_large_sizes covers it at 2^14).
+
+The fused sizes Np = 4 ... 8192 (tests/test_fftlog_fused_truth_gpu.py): the identity holds at every size; up to Np = 32 the taps follow
+:func:`small_taps`; :func:`fused_cases` names the cases of a size; 'log' padding takes rows whose end ratios are exact (:func:`log_rows`: it is
+homogeneous in the row, so the 2**e batches serve it as well); ``batch`` / ``unscale`` / ``exponents`` take the exponent table as an argument
+(:func:`pair_table`: pairs a chosen number of binades apart, or all equal in scale).
 """
 import numpy as np
 
@@ -40,8 +45,28 @@ EXPONENT_RANGE = 300
 EXPONENTS = np.random.default_rng(20241019).integers(-EXPONENT_RANGE, EXPONENT_RANGE + 1, 4096)
 
 
+SMALL = 32      # up to here the five shifts of the large sizes collide modulo Np: the small-size rule of small_taps
+
+
+def small_taps(npad, ker=0):
+    """Taps of Np = 4 ... SMALL: min(5, Np - 1) of them, shifts distinct modulo Np, 0 and 1 among them and the third one above Np/2 (Np - 1 - ker where that
+    is, Np - 1 otherwise), the rest moved with the kernel index; the weights of :func:`taps`, cut to that number, of both signs."""
+    count = min(5, npad - 1)
+    high = npad - 1 - ker if npad - 1 - ker > npad // 2 else npad - 1
+    shifts = [0, 1]
+    for cand in [high, npad // 2 + 1 + ker, npad // 3 + 2 + 2 * ker] + list(range(2, npad)):
+        if len(shifts) < count and cand % npad not in shifts:
+            shifts.append(cand % npad)
+    shifts = np.array(shifts, dtype='i8')
+    weights = (np.roll(np.array([0.9, -0.7, 1.3, -1.1, 0.6]), ker) * (1. + 0.125 * ker))[:count]
+    assert shifts.size == count and np.unique(shifts).size == count and (shifts > npad // 2).any() and weights.min() < 0. < weights.max()
+    return shifts, weights
+
+
 def taps(npad, ker=0):
     """(shifts, weights) of kernel index ``ker``: int64 shifts in [0, npad), float64 weights."""
+    if npad <= SMALL:
+        return small_taps(npad, ker)
     shifts = np.array([3 * ker, 1, npad // 3 + 7 + 11 * ker, npad - 5 - ker, npad // 2 + 1 + 2 * ker], dtype='i8') % npad
     weights = np.roll(np.array([0.9, -0.7, 1.3, -1.1, 0.6]), ker) * (1. + 0.125 * ker)
     assert np.unique(shifts).size == shifts.size
@@ -152,28 +177,75 @@ def base_rows(n, seed=0):
     return rng.uniform(0.5, 1.5, (NBASE, n)) * rng.choice([-1., 1.], (NBASE, n))
 
 
-def exponents(nbatch, nker):
-    if nbatch * nker > EXPONENTS.size:
-        raise ValueError('at most {:d} rows'.format(EXPONENTS.size))
-    return EXPONENTS[:nbatch * nker].reshape(nbatch, nker)
+def exponents(nbatch, nker, table=None):
+    """(nbatch, nker) exponents, row-major from ``table`` (default: the module's EXPONENTS), repeated cyclically where the batch has more rows."""
+    table = EXPONENTS if table is None else np.asarray(table, dtype='i8').ravel()
+    return table[np.arange(nbatch * nker) % table.size].reshape(nbatch, nker)
 
 
-def batch(base, nbatch, nker):
+def paired_exponents(difference):
+    """A table for :func:`exponents` that gives the two members of every pair (items 2j, 2j + 1 of one kernel index, nker = 1 or 3) exponents
+    ``difference`` apart, the larger one now in the first and now in the second member, around a base that moves with the pair.
+    difference = 0: all exponents 0 -- every pair equal in scale, different in content, no fix-up taken."""
+    if difference == 0:
+        return np.zeros(1, dtype='i8')
+    pairs = np.arange(64)
+    base = (7 * pairs) % 23 - 11
+    first = np.where(pairs % 2 == 0, difference, 0)
+    return np.stack([base + first, base + difference - first], axis=1)      # (pair, member); laid out per nker by pair_table
+
+
+def pair_table(nbatch, nker, difference):
+    """(nbatch, nker) exponents whose pairs are ``difference`` apart (:func:`paired_exponents`), for ``exponents(..., table=...)``."""
+    pe = paired_exponents(difference)
+    if difference == 0:
+        return np.zeros((nbatch, nker), dtype='i8')
+    item, ker = np.meshgrid(np.arange(nbatch), np.arange(nker), indexing='ij')
+    pair = ((item // 2) * nker + ker) % pe.shape[0]
+    return pe[pair, item % 2]
+
+
+def batch(base, nbatch, nker, table=None):
     """(nbatch, nker, n): item i of kernel index ker is base row i % 2 times 2**exponents[i, ker]."""
-    scale = np.ldexp(1., exponents(nbatch, nker))
+    scale = np.ldexp(1., exponents(nbatch, nker, table))
     return base[np.arange(nbatch) % NBASE][:, None, :] * scale[:, :, None]
 
 
-def unscale(got, nbatch, nker):
+def unscale(got, nbatch, nker, table=None):
     """The device's (nbatch, nker, m) rows divided by their 2**e, exactly, in longdouble."""
     got = np.asarray(got)
     assert got.shape[:2] == (nbatch, nker)
-    return got.astype(LD) * np.ldexp(LD(1), -exponents(nbatch, nker))[:, :, None]
+    return got.astype(LD) * np.ldexp(LD(1), -exponents(nbatch, nker, table))[:, :, None]
 
 
-def base_case(n, npad, syn, extrap, keep_padding, seed=0):
-    """Truth and level of the two base rows under every kernel index of ``syn``: (base (2, n), truth (2, nker, m) longdouble, level (2, nker))."""
-    base = base_rows(n, seed)
+def log_rows(n, npad, seed=0, negative=False):
+    """(2, n) base rows for 'log' padding: :func:`base_rows` with end ratios that are exact in float64.  The end samples are rounded to 12 mantissa
+    bits and their neighbours set to a_0 (1 + 2^-k) and a_{n-1} (1 + 2^-k), k = max(6, log2 Np - 1): both ratios of the continuation (a_1 / a_0 and
+    a_{n-2} / a_{n-1}) are 1 + 2^-k exactly, it decays outwards, by at most e^2 over Np/2 steps.  (A random ratio is rounded, and the rounding is
+    raised to a power of up to Np/2 in the restatement: levels of 30 ... 1270 FLOOR.)  negative: a_1 = -a_0 (1 + 2^-k) in row 1, a left end ratio
+    the kernel hands to the library's pow."""
+    assert n >= 3
+    k = max(6, npad.bit_length() - 2)
+    a = base_rows(n, seed).copy()
+    step = 1. + 2.**-k
+    for end in (0, n - 1):
+        mant, expo = np.frexp(a[:, end])
+        a[:, end] = np.ldexp(np.round(mant * 4096.) / 4096., expo)
+    if n == 3:
+        a[:, 2] = a[:, 0]
+    a[:, 1] = a[:, 0] * step
+    a[:, n - 2] = a[:, n - 1] * step
+    if negative:
+        a[1, 1] = -a[1, 1]
+        assert n >= 4
+    assert (np.abs(a[:, 1] / a[:, 0]) == step).all() and (a[:, n - 2] / a[:, n - 1] == step).all() and (a[0, 1] / a[0, 0] == step)
+    return a
+
+
+def base_case(n, npad, syn, extrap, keep_padding, seed=0, kind='dense'):
+    """Truth and level of the two base rows under every kernel index of ``syn``: (base (2, n), truth (2, nker, m) longdouble, level (2, nker)).
+    kind: 'dense' (:func:`base_rows`), 'log' or 'logneg' (:func:`log_rows`)."""
+    base = base_rows(n, seed) if kind == 'dense' else log_rows(n, npad, seed, negative=kind == 'logneg')
     true, level = [], []
     for ker in range(syn.nker):
         t = truth(base, n, npad, syn.pre[ker], syn.post[ker], syn.taps[ker], extrap, keep_padding)
@@ -234,7 +306,135 @@ def ladder_case(npad):
 
 
 def extrap_codes(extrap):
-    """(code, value, code, value) of cp_fftlog_execute for 0 / 'edge' per side."""
+    """(code, value, code, value) of cp_fftlog_execute for a number / 'edge' / 'log' per side."""
     left, right = extrap if isinstance(extrap, tuple) else (extrap, extrap)
-    code = lambda e: (1, 0.) if e == 'edge' else (0, float(e))      # noqa: E731
+    code = lambda e: (1, 0.) if e == 'edge' else (2, 0.) if e == 'log' else (0, float(e))      # noqa: E731
     return code(left) + code(right)
+
+
+# ---- the sizes of the fused kernel (csrc/cp_fftlog_body.h), tests/test_fftlog_fused_truth_gpu.py ---------------------------------------------------
+FUSED_LADDER = [1 << e for e in range(2, 14)]
+HALF_MIN = 512      # CP_FFTLOG_HALF_MIN_NP: from here on 2 n = Np without keep_padding takes a HALF variant
+LOG_MAX_N = 2048    # the facade offers 'log' padding up to this row length
+VARIANTS = ('generic', 'log', 'half', 'half_zero')
+
+
+def variant_of(n, npad, extrap, keep_padding):
+    """The rule of select_variant (csrc/cp_fftlog_dispatch.h), restated: which kernel variant a case runs."""
+    left, right = extrap if isinstance(extrap, tuple) else (extrap, extrap)
+    if 'log' in (left, right):
+        return 'log'
+    if npad >= HALF_MIN and 2 * n == npad and not keep_padding:
+        return 'half_zero' if (left, right) == (0, 0) else 'half'
+    return 'generic'
+
+
+def fused_cases(npad, variants=VARIANTS):
+    """The cases of one fused size, [(n, extrap, keep_padding, kind)] (each is run with nker = 1 and 3; kind: the rows of :func:`base_case`):
+    generic    n = (Np/3)|1 (n and Np - n odd: in_left != out_left; 2 at Np = 4) and n = Np - 1, padding 0, 'edge', (1.5, 'edge'), cropped and with keep_padding;
+               from Np = 512 on also 2 n = Np with keep_padding (the rule of select_variant that refuses HALF), 0 and 'edge'
+    half       n = Np/2, 'edge' and (0.7, 0.), Np >= 512
+    half_zero  n = Np/2, zero padding, Np >= 512
+    log        the exact-ratio rows: 'log', ('log', 0.3), (0.2, 'log') at n = Np/2 and (Np/3)|1 (3 <= n <= 2048: Np = 4 takes n = 3, Np = 8192
+               n = 2047), and one case whose row 1 has a negative left end ratio."""
+    cases = []
+    third, half = max((npad // 3) | 1, 2), npad // 2      # (a plan needs n >= 2: Np = 4 takes n = 2 and 3)
+    if 'generic' in variants:
+        for n in (third, npad - 1):
+            for extrap in (0, 'edge', (1.5, 'edge')):
+                cases += [(n, extrap, False, 'dense'), (n, extrap, True, 'dense')]
+        if npad >= HALF_MIN:
+            cases += [(half, 0, True, 'dense'), (half, 'edge', True, 'dense')]
+    if npad >= HALF_MIN:
+        if 'half' in variants:
+            cases += [(half, 'edge', False, 'dense'), (half, (0.7, 0.), False, 'dense')]
+        if 'half_zero' in variants:
+            cases += [(half, 0, False, 'dense')]
+    if 'log' in variants:
+        sizes = sorted(set(LOG_MAX_N - 1 if n > LOG_MAX_N else max(n, 3) for n in (half, third)))
+        for n in sizes:
+            cases += [(n, 'log', n == sizes[0], 'log'), (n, ('log', 0.3), False, 'log'), (n, (0.2, 'log'), True, 'log')]
+        if sizes[-1] >= 4:
+            cases += [(sizes[-1], 'log', False, 'logneg')]
+    for n, extrap, keep, kind in cases:
+        assert 1 <= n <= npad and variant_of(n, npad, extrap, keep) in variants
+    return cases
+
+
+SPREAD = 4      # CP_ROW_SCALE_SPREAD: pairs whose magnitude fields differ by more are rescaled row by row
+
+
+def homogeneous(extrap):
+    """Whether the padding scales with the row (0, 'edge', 'log' on both sides): then the 2**e batches share the truth of their base rows."""
+    left, right = extrap if isinstance(extrap, tuple) else (extrap, extrap)
+    return all(isinstance(e, str) or e == 0 for e in (left, right))
+
+
+def tilted_top(rows, n, npad, pre, extrap):
+    """Largest |padded sample x prefactor| per row (..., n) -> (...): the magnitude the kernel's row screening measures."""
+    in_left, in_right, _ = widths(n, npad)
+    with np.errstate(all='ignore'):
+        return np.abs(ofl.pad(np.asarray(rows, dtype='f8'), (in_left, in_right), extrap) * pre).max(axis=-1)
+
+
+def pair_factor(top):
+    """The kernel's documented contract (csrc/cp_fftlog_body.h, "Row independence"): batch items 2j and 2j + 1 of a kernel index share one complex
+    transform; when the exponent fields of their tilted magnitudes ``top`` (nbatch, nker) differ by more than SPREAD each row is rescaled and
+    rounding is relative to the row itself (factor 1), within the spread nothing is done and rounding is relative to the larger row of the pair:
+    factor = that magnitude over the row's own, at most 2^(SPREAD + 1).  Rows that are zero, not finite, or without a partner: 1."""
+    top = np.asarray(top, dtype='f8')
+    nbatch = top.shape[0]
+    partner = np.arange(nbatch) ^ 1
+    partner[partner >= nbatch] = nbatch - 1
+    other = top[partner]
+    ok = np.isfinite(top) & np.isfinite(other) & (top > 0) & (other > 0)
+    field = lambda v: np.frexp(np.where(ok, v, 1.))[1]      # noqa: E731
+    near = ok & (np.abs(field(top) - field(other)) <= SPREAD)
+    with np.errstate(all='ignore'):
+        return np.where(near, np.maximum(1., other / np.where(ok, top, 1.)), 1.)
+
+
+class FusedBatch(object):
+    """One batch of a fused case: rows (nbatch, nker, n) for the device, and for its answer ``got`` the pair (comparable(got, items), true[items])
+    with the levels ``level`` of the float64 restatement and the factors ``factor`` of :func:`pair_factor`, each (nbatch, nker)."""
+
+
+def fused_batch(n, npad, syn, extrap, keep_padding, kind, nbatch, table=None, seed=0):
+    """Batch item i of kernel index ker is base row i % 2 times 2**exponents(nbatch, nker, table)[i, ker].  Padding that scales with the row
+    (:func:`homogeneous`): truth and level once per (base row, kernel index), the device's rows are unscaled exactly before they are compared.
+    A constant other than 0 does not scale: truth and level of every row as it is (such batches are kept small)."""
+    b = FusedBatch()
+    nker = syn.nker
+    b.table = table
+    b.rows = batch(base_rows(n, seed) if kind == 'dense' else log_rows(n, npad, seed, negative=kind == 'logneg'), nbatch, nker, table)
+    b.top = np.stack([tilted_top(b.rows[:, ker], n, npad, syn.pre[ker], extrap) for ker in range(nker)], axis=1)
+    b.factor = pair_factor(b.top)
+    b.homogeneous = homogeneous(extrap)
+    if b.homogeneous:
+        base, true, level = base_case(n, npad, syn, extrap, keep_padding, seed, kind)
+        b.true, b.level = expected(true, level, nbatch)
+        scale = np.ldexp(LD(1), -exponents(nbatch, nker, table))[:, :, None]
+        b.comparable = lambda got, items=slice(None): np.asarray(got)[items].astype(LD) * scale[items]      # noqa: E731  (unscaled exactly)
+    else:
+        true, level = [], []
+        for ker in range(nker):
+            t = truth(b.rows[:, ker], n, npad, syn.pre[ker], syn.post[ker], syn.taps[ker], extrap, keep_padding)
+            true.append(t)
+            level.append(levels(t, restated(b.rows[:, ker], n, npad, syn.pre[ker], syn.post[ker], syn.u[ker], extrap, keep_padding))[1])
+        b.true, b.level = np.stack(true, axis=1), np.stack(level, axis=1)
+        b.comparable = lambda got, items=slice(None): np.asarray(got)[items].astype(LD)      # noqa: E731
+    return b
+
+
+FUSED_NBATCH = 5      # two full pairs and one row without a partner, per kernel index
+
+
+def fused_table(extrap, nbatch, nker):
+    """The exponents of a case of the ladder: the module's EXPONENTS (pairs up to 2^600 apart) where the padding scales with the row, pairs 2^12
+    apart (:func:`pair_table`) beside a padding constant of order one."""
+    return None if homogeneous(extrap) else pair_table(nbatch, nker, 12)
+
+
+def grid_bound(npad, compute_units):
+    """An upper bound of any variant's grid: the device's CU count times min(32, floor(160 KiB / (16 Np)))."""
+    return compute_units * max(1, min(32, (160 * 1024) // (16 * npad)))

@@ -134,7 +134,9 @@ def test_multipoles_there_and_back(cp, golden):
 
 @pytest.mark.parametrize('n', [2, 3, 5, 8, 13, 30, 60, 100, 250, 256, 500, 512, 1000, 1024, 2048, 3000, 4096])
 def test_sizes_and_modes_vs_oracle(cp, n):
-    """Every kernel size / variant, odd batches (incomplete pair), multi-kernel, keep_padding, all extrap modes."""
+    """Every kernel size / variant, odd batches (incomplete pair), multi-kernel, keep_padding, all extrap modes: physical tables against the float64
+    oracle.  (The same sizes and variants against exact longdouble truth, with synthetic tables, pairs of every scale and more pairs than the grid:
+    tests/test_fftlog_fused_truth_gpu.py.)"""
     rng = np.random.default_rng(n)
     k = np.logspace(-3, 2, n)
     t = ofl.power_to_correlation(k, ell=[0, 2])

@@ -20,7 +20,6 @@ element); row_scale now stores such a row as zeros.  Mutations of a scratch copy
 inside the chunk fails test_second_chunk alone; mask_b one bit short fails every size, the chunk and the screening test; freq_of_pos with the radices in
 reverse order fails N1 = 32 ... 128 and 512 ... 2048 on the canary.  Two entries of rd.r swapped at N1 = 512 change nothing: every order is a valid plan.
 """
-import ctypes
 import threading
 import time
 
@@ -28,64 +27,9 @@ import numpy as np
 import pytest
 
 import fftlog_taps_truth as tt
+from fftlog_device import CANARY, Plan, lib      # noqa: F401  (lib: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-CANARY = -1.2345678912345e+77      # no transform of these rows gives this number
-
-
-@pytest.fixture(scope='module')
-def lib():
-    import torch
-    assert torch.cuda.is_available(), 'GPU tests need a ROCm device'
-    from cosmoprimo_amd import _lib
-    return _lib.load()
-
-
-class Plan(object):
-    """A cp_fftlog_plan of the synthetic tables, destroyed on the way out."""
-
-    def __init__(self, lib, n, syn):
-        import torch
-        self.lib, self.n, self.syn = lib, n, syn
-        self.dev = torch.device('cuda', torch.cuda.current_device())
-        self.handle = ctypes.c_void_p()
-
-    def __enter__(self):
-        from cosmoprimo_amd import _lib
-        syn = self.syn
-        pre, post, u = np.ascontiguousarray(syn.pre), np.ascontiguousarray(syn.post), np.ascontiguousarray(syn.u)
-        assert pre.shape == post.shape == (syn.nker, syn.npad) and u.shape == (syn.nker, syn.npad // 2 + 1) and u.dtype == np.complex128
-        _lib.check(self.lib.cp_fftlog_plan_create(ctypes.byref(self.handle), self.n, syn.npad, syn.nker, _lib.as_double_p(pre), _lib.as_double_p(post),
-                                                  _lib.as_double_p(u.view('f8')), self.dev.index))
-        return self
-
-    def __exit__(self, *exc):
-        handle, self.handle = self.handle, ctypes.c_void_p()
-        self.lib.cp_fftlog_plan_destroy(handle)
-        return False
-
-    def enqueue(self, tin, tout, extrap, keep, stream):
-        from cosmoprimo_amd import _lib
-        codes = tt.extrap_codes(extrap)
-        _lib.check(self.lib.cp_fftlog_execute(self.handle, tin.data_ptr(), tout.data_ptr(), tin.shape[0], codes[0], codes[1], codes[2], codes[3], int(keep), stream))
-
-    def __call__(self, rows, extrap, keep):
-        """rows (nbatch, nker, n) -> (nbatch, nker, m): into a buffer full of canaries with one more behind it."""
-        import torch
-        nbatch, nker, n = rows.shape
-        assert (nker, n) == (self.syn.nker, self.n)
-        m = self.syn.npad if keep else n
-        tin = torch.as_tensor(np.ascontiguousarray(rows, dtype='f8'), device=self.dev)
-        tout = torch.full((nbatch * nker * m + 1,), CANARY, dtype=torch.float64, device=self.dev)
-        self.enqueue(tin, tout, extrap, keep, torch.cuda.current_stream(self.dev).cuda_stream)
-        torch.cuda.synchronize()
-        out = tout.cpu().numpy()
-        assert out[-1] == CANARY, 'the element behind the output was written'
-        got = out[:-1].reshape(nbatch, nker, m)
-        assert not (got == CANARY).any(), '{:d} output elements were not written'.format(int((got == CANARY).sum()))
-        return got
-
 
 @pytest.mark.parametrize('npad', tt.LADDER)
 def test_every_column_plan(lib, npad):
