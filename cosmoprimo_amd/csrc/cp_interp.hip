@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256) void spline_points_kernel(const double* __rest
             const double t = (sc[lo] + sc[lo + 1] - 2. * slope) / h;
             const double c3 = t / h, c2 = (slope - sc[lo]) / h - t, c1 = sc[lo], c0 = yc[lo];
             double r;
-            if (nu == 0) r = c0 + u * (c1 + u * (c2 + u * c3));
+            if (nu == 0) r = v == xn ? yc[n - 1] : c0 + u * (c1 + u * (c2 + u * c3));   // the last knot from its far end: the sample itself, as on every other knot (u = 0)
             else if (nu == 1) r = c1 + u * (2. * c2 + u * 3. * c3);
             else r = 2. * c2 + 6. * c3 * u;
             out[(long long)c * nq + i] = r;
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(256) void spline_points_lds_kernel(const double* __
         c0s[i] = y[i]; c1s[i] = s[i]; c2s[i] = (slope - s[i]) / h - t; c3s[i] = t / h;
     }
     __syncthreads();
-    const double x0 = xs[0], xn = xs[n - 1];
+    const double x0 = xs[0], xn = xs[n - 1], yn = y[n - 1];
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += (long long)gridDim.x * blockDim.x) {
         const double v = xq[i];
         const bool inside = v >= x0 && v <= xn;
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(256) void spline_points_lds_kernel(const double* __
             }
             const double u = v - xs[lo];
             const double c0 = c0s[lo], c1 = c1s[lo], c2 = c2s[lo], c3 = c3s[lo];
-            if (nu == 0) r = c0 + u * (c1 + u * (c2 + u * c3));
+            if (nu == 0) r = v == xn ? yn : c0 + u * (c1 + u * (c2 + u * c3));   // (the last knot: the sample itself, as the general kernel)
             else if (nu == 1) r = c1 + u * (2. * c2 + u * 3. * c3);
             else r = 2. * c2 + 6. * c3 * u;
         }
