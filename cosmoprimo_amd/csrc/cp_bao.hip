@@ -303,7 +303,7 @@ extern "C" int cp_brieden_knots(const double* d_envelope, const double* d_pknow,
 // column through its own knots log10(k_fid / rescale), elimination factors through a global scratch) and cp_brieden_finish (10^x, knot-major ->
 // cosmology-major into the k_fid range of P) move every value through memory three times and turn the layout twice: 0.52 ms per 32 768 cosmologies.
 // The knots of a cosmology are a GEOMETRIC grid (k_fid is a range of the filter's geomspace) shifted by log10(rescale): uniform in log10 k, so the
-// system for the second derivatives has constant coefficients and is solved by the two first-order recursions of cp_splice_uniform.h (p = sqrt 3 - 2),
+// system for the second derivatives has constant coefficients and is solved by the two first-order recursions of cp_uniform_recursions.h (p = sqrt 3 - 2),
 // a lane per S knots in registers, the neighbours' totals by DPP shifts.  What the two extrapolated knots on either side change is A p^i + B p^(n-1-i);
 // they lie ON the lines through the first / last two samples, so the right-hand sides of the two rows at each junction vanish and A (B) follows in
 // closed form from the first (last) two second derivatives of the recursion and the three spacings there; the queries log10(k_fid) all sit at the same
@@ -315,7 +315,7 @@ namespace {
 #define CP_RS_WAVES 3      // waves per SIMD the kernel is compiled for
 #endif
 constexpr int RS_SMIN = 3, RS_SMAX = 8;      // knots per lane: 129 <= n <= 512
-constexpr double RS_P = -0.26794919243112270647, RS_KAPPA = 0.28867513459481288225;      // sqrt 3 - 2, 1 / (2 sqrt 3)
+constexpr double RS_P = cpur::P, RS_KAPPA = cpur::KAPPA;      // sqrt 3 - 2, 1 / (2 sqrt 3)
 
 struct ResampleArgs {
     const double* envelope;       // (nb, n)
@@ -337,12 +337,6 @@ struct ResampleArgs {
     const double* op;             // (np, n) the columns of the envelope operator that are not zero
     int np;
 };
-
-constexpr double rs_ipow(double x, int k) {
-    double v = 1.;
-    for (int i = 0; i < k; ++i) v *= x;
-    return v;
-}
 
 // LDS per wave: Y[n + 4] (log10 of the samples, the extrapolated values at 0, 1, n + 2, n + 3), M[n + 4] (second derivatives in units of 6 kappa / h^2).
 // S = knots (= samples = queries) per lane.  What does not depend on the cosmology is set up once: the queries and ratio_now_fid (in LDS, shared by
@@ -385,7 +379,7 @@ __global__ __launch_bounds__(OPLDS ? 768 : 256, OPLDS ? 1 : CP_RS_WAVES) void br
     crooked = __syncthreads_or(crooked);
     constexpr double LOG10E = 0.43429448190325182765;
     constexpr int REACH = (32 + S) / S;      // REACH x S >= 33 knots: p^33 = 1e-19
-    constexpr double PS = rs_ipow(RS_P, S);
+    constexpr double PS = cpur::ipow(RS_P, S);
     auto lg10 = [&](double x) { return cpmath::log_tab_any(x, &mt) * LOG10E; };
     const int own = S * lane;
     // p^i for the lane's first knot, p^(n-1-i) for its last one: beyond 40 knots from an end nothing is left (and the powers would underflow);
@@ -505,38 +499,17 @@ __global__ __launch_bounds__(OPLDS ? 768 : 256, OPLDS ? 1 : CP_RS_WAVES) void br
                 yc = yp;
             }
         }
+        const cpur::Totals own_totals = cpur::recursions<S>(g);
+        double gr = own_totals.g_first, fl = own_totals.f_last, fin = 0., gin = 0., wgt = 1.;
 #pragma unroll
-        for (int t = S - 2; t >= 0; --t) g[t] = fma(RS_P, g[t + 1], g[t]);
-        double gr = g[0];
-        double f = 0.;
-#pragma unroll
-        for (int t = 0; t < S; ++t) {
-            const double ee = fma(RS_P, f, g[t]);
-            f = t + 1 < S ? fma(-RS_P, g[t + 1], ee) : ee;
-            g[t] = ee;
-        }
-        double fl = f, fin = 0., gin = 0., wgt = 1.;
-#pragma unroll
-        for (int m = 0; m < REACH; ++m) {
-            fl = cpsu::from_left(fl);
-            gr = cpsu::from_right(gr);
+        for (int m = 0; m < REACH; ++m) {      // (a segment is short: the totals of REACH lanes on either side, p^S apart)
+            fl = cpur::wave_from_left(fl);
+            gr = cpur::wave_from_right(gr);
             fin = fma(wgt, fl, fin);
             gin = fma(wgt, gr, gin);
             wgt *= PS;
         }
-        {
-            double cg = gin, cf = fin;
-#pragma unroll
-            for (int t = S - 1; t >= 0; --t) {
-                cg *= RS_P;
-                g[t] += cg;
-            }
-#pragma unroll
-            for (int t = 0; t < S; ++t) {
-                cf *= RS_P;
-                g[t] += cf;
-            }
-        }
+        cpur::add_carries<S>(g, gin, fin);
         // ---- what the extrapolated knots change: A p^i + B p^(n-1-i), from the rows of the junctions (right-hand sides zero): the first and last two
         // second derivatives of the recursion, by shuffles from the lanes that hold them ----
         const int l_last = (n - 1) / S, t_last = (n - 1) - l_last * S, l_prev = (n - 2) / S, t_prev = (n - 2) - l_prev * S;
@@ -1044,6 +1017,25 @@ extern "C" int cp_splice_plan_info(const cp_splice_plan* p, int* elimination, in
     }
     return CP_OK;
 }
+
+namespace cpsu {
+
+// false: no instantiation for the plan's samples per segment.  (Here, with its only caller, and not in cp_splice_uniform.h: cp_dst.hip takes the row
+// functions from that header, and a launcher there would instantiate the seven kernels in that file as well.)
+inline bool launch(cp::Launches& on, const Args& A, unsigned grid, size_t lds) {
+    switch (A.T.S) {
+        case 33: on.run<splice_uniform_kernel<33>>(grid, 256, lds, A); return true;
+        case 37: on.run<splice_uniform_kernel<37>>(grid, 256, lds, A); return true;
+        case 41: on.run<splice_uniform_kernel<41>>(grid, 256, lds, A); return true;
+        case 45: on.run<splice_uniform_kernel<45>>(grid, 256, lds, A); return true;
+        case 49: on.run<splice_uniform_kernel<49>>(grid, 256, lds, A); return true;
+        case 53: on.run<splice_uniform_kernel<53>>(grid, 256, lds, A); return true;
+        case 57: on.run<splice_uniform_kernel<57>>(grid, 256, lds, A); return true;
+        default: return false;
+    }
+}
+
+}  // namespace cpsu
 
 extern "C" int cp_splice_apply(const cp_splice_plan* p, const double* d_src0, int n0, const double* d_src1, int n1, long long nrows, const double* d_tophat,
                                double* d_out, void* stream) {

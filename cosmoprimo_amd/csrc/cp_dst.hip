@@ -26,7 +26,7 @@
 #include "cp_math.h"
 #include "cp_power_eval.h"
 #include "cp_wallish_dd.h"
-#include "cp_splice_uniform_plan.h"
+#include "cp_splice_uniform.h"
 
 namespace {
 

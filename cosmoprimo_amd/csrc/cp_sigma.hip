@@ -32,6 +32,7 @@
 #include "cp_fftlog_body.h"
 #include "cp_internal.h"
 #include "cp_power_eval.h"
+#include "cp_uniform_recursions.h"
 
 namespace {
 
@@ -542,28 +543,8 @@ struct GeoArgs {
     double* out;
 };
 
-// lane l receives the value of lane l - 1 (lane 0: zero) / of lane l + 1 (lane 63: zero): DPP shifts of the whole wave, no LDS
-typedef int geo_v2i __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double wave_from_left(double v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    geo_v2i w = __builtin_bit_cast(geo_v2i, v);
-    w.x = __builtin_amdgcn_update_dpp(0, w.x, 0x138, 0xf, 0xf, true);      // wave_shr:1
-    w.y = __builtin_amdgcn_update_dpp(0, w.y, 0x138, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, w);
-#else
-    return v;
-#endif
-}
-__device__ __forceinline__ double wave_from_right(double v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    geo_v2i w = __builtin_bit_cast(geo_v2i, v);
-    w.x = __builtin_amdgcn_update_dpp(0, w.x, 0x130, 0xf, 0xf, true);      // wave_shl:1
-    w.y = __builtin_amdgcn_update_dpp(0, w.y, 0x130, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, w);
-#else
-    return v;
-#endif
-}
+using cpur::wave_from_left;      // lane l receives the value of lane l - 1 (lane 0: zero): DPP shifts of the whole wave, no LDS
+using cpur::wave_from_right;     // ... of lane l + 1 (lane 63: zero)
 
 // sqrt for the epilogue: positive normal arguments (every variance) take the hardware reciprocal-root estimate with its third-order correction
 // (cp_math.h: rsqrt_pos, relative error 1e-16) and one multiplication; zero, subnormal, negative, Inf and NaN take the library's

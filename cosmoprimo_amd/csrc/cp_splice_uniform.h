@@ -28,33 +28,8 @@
 
 namespace cpsu {
 
-constexpr double ipow(double x, int k) {
-    double v = 1.;
-    for (int i = 0; i < k; ++i) v *= x;
-    return v;
-}
-
-typedef int v2i __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double from_left(double v) {      // lane l receives lane l - 1's value, lane 0 zero (wave_shr:1)
-#if defined(__HIP_DEVICE_COMPILE__)
-    v2i w = __builtin_bit_cast(v2i, v);
-    w.x = __builtin_amdgcn_update_dpp(0, w.x, 0x138, 0xf, 0xf, true);
-    w.y = __builtin_amdgcn_update_dpp(0, w.y, 0x138, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, w);
-#else
-    return v;
-#endif
-}
-__device__ __forceinline__ double from_right(double v) {     // lane l receives lane l + 1's value, lane 63 zero (wave_shl:1)
-#if defined(__HIP_DEVICE_COMPILE__)
-    v2i w = __builtin_bit_cast(v2i, v);
-    w.x = __builtin_amdgcn_update_dpp(0, w.x, 0x130, 0xf, 0xf, true);
-    w.y = __builtin_amdgcn_update_dpp(0, w.y, 0x130, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, w);
-#else
-    return v;
-#endif
-}
+using cpur::wave_from_left;
+using cpur::wave_from_right;
 
 template <int S>
 constexpr int lds_doubles_per_wave() { return 64 * S + 2 + 128; }
@@ -62,6 +37,59 @@ constexpr int lds_doubles_per_wave() { return 64 * S + 2 + 128; }
 #ifndef CP_SPLICE_UNIFORM_ABLATE      // diagnostic builds (wrong results): 1 no recursions, 2 no evaluation, 4 no window sums
 #define CP_SPLICE_UNIFORM_ABLATE 0
 #endif
+
+// ---- a row of the uniform-stretch spliced spline, piece by piece.  Two callers: splice_uniform_kernel below (a wave per row of a batch: the knot values
+// staged into padded slots of LDS, the plan's entries staged beside them, the next row fetched ahead) and tail_splice_row (cp_wallish_tail.h: the row left in
+// LDS by the inverse transform of the fused filter, the plan's entries by batched loads from memory, reads beyond the stretch clamped).  How a caller gets
+// the knot values and the plan's entries, how it forms the second differences of a lane's knots (padded slots there, clamped reads here), every
+// wave_lds_phase and every measurement switch stay with the caller; the rest of the arithmetic is here, once.
+
+// A / p, M_left, B, M_right (sums[0 .. 3], in every lane): weighted sums over the knots next to the two junctions -- vl, vr: the lane's knot in front of /
+// behind the stretch; ww: the lane's eight weights.  Each set of weights sums to zero (a constant has no second derivative): the sums run over the
+// DIFFERENCES to the knot they belong to -- exact, and as small as the second differences the recursions work on, where the values themselves would leave
+// 1e-16 of y in sums that are 1e-3 ... 1e-7 of it (and the long interval behind the stretch multiplies its second derivatives by (its length / h)^2 ~ 1e6)
+__device__ __forceinline__ void junction_sums(const double* yu, int nm, int lane, const double* ww, double vl, double vr, double gl_last, double gr_first,
+                                              double* sums) {
+    const double ul = yu[lane < WIN_U ? lane : 0], ur = yu[lane < WIN_U ? nm - 1 - lane : 0];
+    const double yfirst = yu[0], ylast = yu[nm - 1];
+    sums[0] = fma(ww[0], vl - yfirst, ww[1] * (ul - yfirst));
+    sums[1] = fma(ww[2], vl - gl_last, ww[3] * (ul - gl_last));
+    sums[2] = fma(ww[4], ur - ylast, ww[5] * (vr - ylast));
+    sums[3] = fma(ww[6], ur - gr_first, ww[7] * (vr - gr_first));
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+        for (int o = 0; o < 4; ++o) sums[o] += __shfl_xor(sums[o], off);
+}
+
+// what the knot values add to a query of interval e, before the second derivatives take their place (e = -1 and e + 1 = nm read slots that hold no knot
+// of the stretch: replaced by the knots outside it)
+__device__ __forceinline__ double query_part(const double* yu, int nm, int e, double wx, double wy, double gl_last, double gr_first) {
+    const double ya = yu[e], yb = yu[e + 1];
+    return fma(wx, e < 0 ? gl_last : ya, wy * (e + 1 >= nm ? gr_first : yb));
+}
+
+// the two recursions over the lane's knots, from zero; the neighbours' totals with what A and B add; the second derivatives (unscaled) into `mine`
+template <int S>
+__device__ __forceinline__ void solve_segment(double* g, double m_a, double m_b, const double* sums, double* mine) {
+    const cpur::Totals totals = cpur::recursions<S>(g);
+    const double gin = fma(m_b, sums[2], wave_from_right(totals.g_first));      // G at the first knot of the next segment (+ what B adds there)
+    const double fin = fma(m_a, sums[0], wave_from_left(totals.f_last));        // F at the last knot of the previous segment (+ A / p in lane 0)
+    // (gin over all of the segment: in the lane of the stretch's last knot the carry stands for B p^(distance to that knot))
+    cpur::add_carries<S, (S < 36 ? S : 36)>(g, gin, fin);
+#pragma unroll
+    for (int t = 0; t < S; ++t) mine[t] = g[t];
+}
+
+// the second derivatives at the one knot outside either end of the stretch, into the slots next to it (behind a wave_lds_phase of the caller's)
+__device__ __forceinline__ void store_outer(double* yu, int nm, int lane, const double* sums) {
+    if (lane == 0) yu[-1] = sums[1];
+    if (lane == 1) yu[nm] = sums[3];
+}
+
+// pk / ((pk / pknow - 1) tophat + 1), bao_filter.py:421-431, as pk pknow / ((pk - pknow) tophat + pknow) with one reciprocal: the two IEEE divisions per
+// output were four fifths of the vector instructions of splice_uniform_kernel (pknow / denominator is O(1): no product of two spectra)
+__device__ __forceinline__ double damped(double p, double v, double t) { return p * (v * cpmath::recip(fma(p - v, t, v))); }
 
 // LDS: per wave yu[-1 .. 64 S] (the stretch; its first value repeated in front, its last value behind: the second differences vanish beyond the
 // stretch, and the one-sided differences at its two end knots are part of what the host's weights account for), gl[64], gr[64] (the knots
@@ -147,24 +175,10 @@ __global__ __launch_bounds__(256) void splice_uniform_kernel(const Args A) {
                 y1 = y2;
             }
         }
-        // ---- A / p, M_left, B, M_right: weighted sums over the knots next to the two junctions.  Each set of weights sums to zero (a constant has
-        // no second derivative): the sums run over the DIFFERENCES to the knot they belong to -- exact, and as small as the second differences the
-        // recursions work on, where the values themselves would leave 1e-16 of y in sums that are 1e-3 ... 1e-7 of it (and the long interval
-        // behind the stretch multiplies its second derivatives by (its length / h)^2 ~ 1e6) ----
+        // ---- A / p, M_left, B, M_right ----
         const double gl_last = gl[T.wl > 0 ? T.wl - 1 : 0], gr_first = gr[0];
         double sums[4] = {0., 0., 0., 0.};
-        if (!(CP_SPLICE_UNIFORM_ABLATE & 4)) {
-            const double vl = gl[lane], ul = yu[lane < WIN_U ? lane : 0], ur = yu[lane < WIN_U ? nm - 1 - lane : 0], vr = gr[lane];
-            const double yfirst = yu[0], ylast = yu[nm - 1];
-            sums[0] = fma(ww[0], vl - yfirst, ww[1] * (ul - yfirst));
-            sums[1] = fma(ww[2], vl - gl_last, ww[3] * (ul - gl_last));
-            sums[2] = fma(ww[4], ur - ylast, ww[5] * (vr - ylast));
-            sums[3] = fma(ww[6], ur - gr_first, ww[7] * (vr - gr_first));
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-                for (int o = 0; o < 4; ++o) sums[o] += __shfl_xor(sums[o], off);
-        }
+        if (!(CP_SPLICE_UNIFORM_ABLATE & 4)) junction_sums(yu, nm, lane, ww, gl[lane], gr[lane], gl_last, gr_first, sums);
         // ---- the queries' knot values, before the second derivatives take their place ----
         double part[NPB];
         {
@@ -173,44 +187,15 @@ __global__ __launch_bounds__(256) void splice_uniform_kernel(const Args A) {
                 part[blk] = 0.;
                 if (blk >= gb0 && blk < gb1) {
                     const int slot = 64 * (blk - gb0) + lane;
-                    const int e = qe[slot];
                     const double4 w = qw[slot];
-                    const double ya = yu[e], yb = yu[e + 1];      // (e = -1 and e + 1 = nm read the repeated end values: replaced)
-                    part[blk] = fma(w.x, e < 0 ? gl_last : ya, w.y * (e + 1 >= nm ? gr_first : yb));
+                    part[blk] = query_part(yu, nm, qe[slot], w.x, w.y, gl_last, gr_first);
                 }
             }
         }
         cp::wave_lds_phase();      // every read of the knot values is done
-        // ---- the two recursions over the lane's knots, from zero; the neighbours' totals; the second derivatives (unscaled) into LDS ----
-        if (!(CP_SPLICE_UNIFORM_ABLATE & 1)) {
-#pragma unroll
-            for (int t = S - 2; t >= 0; --t) g[t] = fma(P, g[t + 1], g[t]);
-            double c = fma(m_b, sums[2], from_right(g[0]));      // G at the first knot of the next segment (+ what B adds there)
-            double f = 0.;
-#pragma unroll
-            for (int t = 0; t < S; ++t) {
-                const double e = fma(P, f, g[t]);
-                f = t + 1 < S ? fma(-P, g[t + 1], e) : e;
-                g[t] = e;
-            }
-#pragma unroll
-            for (int t = S - 1; t >= 0; --t) {      // (all of the segment: in the lane of the stretch's last knot the carry stands for B p^(distance to that knot))
-                c *= P;
-                g[t] += c;
-            }
-            c = fma(m_a, sums[0], from_left(f));                 // F at the last knot of the previous segment (+ A / p in lane 0)
-#pragma unroll
-            for (int t = 0; t < (S < 36 ? S : 36); ++t) {
-                c *= P;
-                g[t] += c;
-            }
-            double* mine = yu + S * lane;
-#pragma unroll
-            for (int t = 0; t < S; ++t) mine[t] = g[t];
-        }
+        if (!(CP_SPLICE_UNIFORM_ABLATE & 1)) solve_segment<S>(g, m_a, m_b, sums, yu + S * lane);
         cp::wave_lds_phase();      // (the slots beyond the stretch hold no second derivative anyone reads)
-        if (lane == 0) yu[-1] = sums[1];
-        if (lane == 1) yu[nm] = sums[3];
+        store_outer(yu, nm, lane, sums);
         cp::wave_lds_phase();
         // ---- evaluation; the other queries return their own column ----
 #pragma unroll
@@ -222,9 +207,7 @@ __global__ __launch_bounds__(256) void splice_uniform_kernel(const Args A) {
                 const double4 w = qw[slot];
                 double v = part[blk] + fma(w.z, yu[e], w.w * yu[e + 1]);
                 const double p = own[blk];
-                // pk / ((pk / pknow - 1) tophat + 1), bao_filter.py:421-431, as pk pknow / ((pk - pknow) tophat + pknow) with one reciprocal: the two IEEE
-                // divisions per output were four fifths of the vector instructions of this kernel
-                if (A.tophat) v = p * (v * cpmath::recip(fma(p - v, qt[slot], v)));      // (pknow / denominator is O(1): no product of two spectra)
+                if (A.tophat) v = damped(p, v, qt[slot]);
                 if (q < T.nq) out[q] = (q >= T.gfirst && q < T.gend) ? v : p;
             } else if (blk < nblocks && q < T.nq) {
                 out[q] = own[blk];
@@ -232,20 +215,6 @@ __global__ __launch_bounds__(256) void splice_uniform_kernel(const Args A) {
         }
         if (row + step < A.nrows) fetch_own(row + step);
         cp::wave_lds_phase();      // last reads of the second derivatives before the next row is staged
-    }
-}
-
-// false: no instantiation for the plan's samples per segment
-inline bool launch(cp::Launches& on, const Args& A, unsigned grid, size_t lds) {
-    switch (A.T.S) {
-        case 33: on.run<splice_uniform_kernel<33>>(grid, 256, lds, A); return true;
-        case 37: on.run<splice_uniform_kernel<37>>(grid, 256, lds, A); return true;
-        case 41: on.run<splice_uniform_kernel<41>>(grid, 256, lds, A); return true;
-        case 45: on.run<splice_uniform_kernel<45>>(grid, 256, lds, A); return true;
-        case 49: on.run<splice_uniform_kernel<49>>(grid, 256, lds, A); return true;
-        case 53: on.run<splice_uniform_kernel<53>>(grid, 256, lds, A); return true;
-        case 57: on.run<splice_uniform_kernel<57>>(grid, 256, lds, A); return true;
-        default: return false;
     }
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "cp_spline_system.h"
+#include "cp_uniform_recursions.h"
 
 namespace cpsu {
 
@@ -16,7 +17,7 @@ constexpr int WIN_G = 44;      // knots outside the stretch that A, B and the ou
 constexpr int WIN_U = 40;      // knots of the stretch they see
 constexpr int NGB = 8;         // blocks of 64 queries evaluated through the spline
 constexpr int NPB = 16;        // blocks of 64 queries in all (the others return their own column of the first array)
-constexpr double P = -0.26794919243112270647;      // sqrt 3 - 2
+using cpur::P;                 // sqrt 3 - 2
 
 struct Tables {
     int S, nm;                   // knots per lane; knots of the uniform stretch

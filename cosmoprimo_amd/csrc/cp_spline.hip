@@ -23,6 +23,7 @@
 #include "cp_error.h"
 #include "cp_internal.h"
 #include "cp_math.h"
+#include "cp_wallish_dd.h"
 
 namespace {
 
@@ -1431,7 +1432,7 @@ extern "C" int cp_tables_rows_direct(const cp_spline_rows_plan* kplan, const cp_
 // difference otherwise; the error of that start value is damped by 0.268^64 ~ 1e-37).
 namespace {
 
-constexpr int GAP_WINDOW = 64;
+using cpdd::GAP_WINDOW;
 
 __global__ __launch_bounds__(64) void gap_spline_kernel(const double* y, const int* __restrict__ box, double* out, long long ncol, int n) {
     const long long col = blockIdx.x;
@@ -1526,22 +1527,14 @@ extern "C" int cp_gap_spline(const double* d_y, const int* d_box, double* d_out,
 // One wave per column, one pass over its second derivatives (the torch version filled and masked a copy of the whole array).
 namespace {
 
-__device__ __forceinline__ void argmax_merge(double& v, int& i, double ov, int oi) {
-    const bool take = (ov > v && !(v != v)) || (ov != ov && !(v != v)) || (((ov == v) || (ov != ov && v != v)) && oi < i);
-    if (take) {
-        v = ov;
-        i = oi;
-    }
-}
-
 __device__ __forceinline__ int wave_argmax(const double* __restrict__ row, int lo, int hi, int lane) {
     double v = -__builtin_inf();
     int idx = 0x7fffffff;
-    for (int j = lo + lane; j < hi; j += 64) argmax_merge(v, idx, row[j], j);   // ascending j: ties keep the first
-    for (int off = 32; off > 0; off >>= 1) {
+    for (int j = lo + lane; j < hi; j += 64) cpdd::argmax_merge(v, idx, row[j], j);   // ascending j: ties keep the first
+    for (int off = 32; off > 0; off >>= 1) {      // (cpdd::wave_merge, written out: behind the call the kernel takes a vector register and six scalars more)
         const double ov = __shfl_xor(v, off);
         const int oi = __shfl_xor(idx, off);
-        argmax_merge(v, idx, ov, oi);
+        cpdd::argmax_merge(v, idx, ov, oi);
     }
     return idx == 0x7fffffff ? 0 : idx;
 }

@@ -15,14 +15,15 @@
 
 #include "cp_internal.h"
 #include "cp_math.h"
+#include "cp_uniform_recursions.h"
 
 namespace cpdd {
 
 using cp::wave_lds_phase;
 
 constexpr int DD_HALO = 32;
-constexpr int DD_GAP_WINDOW = 64;      // knots on either side of the box from which its end slopes are eliminated (gap_spline_kernel: GAP_WINDOW)
-constexpr double DD_CINF = 0.26794919243112270647;      // 2 - sqrt(3)
+constexpr int GAP_WINDOW = 64;      // knots on either side of the box from which its end slopes are eliminated (remove_box*; gap_spline_kernel, cp_spline.hip)
+constexpr double DD_CINF = -cpur::P;                     // 2 - sqrt(3)
 constexpr double DD_CLAST = 1. / (2. - DD_CINF);         // the last row has diagonal 2
 constexpr int DD_NTAB = 40;                              // c_i equals its limit to the last bit from knot 30 on
 struct DdTable {
@@ -175,39 +176,13 @@ __device__ __forceinline__ void second_derivatives_and_box(double* buf, const do
 // p f_{t-1} is M_t / sqrt 3, f_t = e_t - p g_{t+1}), both from zero; what the knots outside its segment add comes from the neighbours' segment
 // totals by one DPP shift each way (a segment away the weight is p^32 = 5e-19), and at the two ends from the lane's own sums (the mirror image of
 // the causal sum in front of knot 0 is the anti-causal sum at knot 1).  64 register steps and 66 LDS accesses per lane where the elimination walks
-// 128 knots through LDS with three accesses each (cp_splice_uniform.h: the same recursions on the uniform stretch of the spliced spline).
-typedef int dd_v2i __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double dd_from_left(double v) {      // lane l receives lane l - 1's value, lane 0 zero (wave_shr:1)
-#if defined(__HIP_DEVICE_COMPILE__)
-    dd_v2i w = __builtin_bit_cast(dd_v2i, v);
-    w.x = __builtin_amdgcn_update_dpp(0, w.x, 0x138, 0xf, 0xf, true);
-    w.y = __builtin_amdgcn_update_dpp(0, w.y, 0x138, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, w);
-#else
-    return v;
-#endif
-}
-__device__ __forceinline__ double dd_from_right(double v) {     // lane l receives lane l + 1's value, lane 63 zero (wave_shl:1)
-#if defined(__HIP_DEVICE_COMPILE__)
-    dd_v2i w = __builtin_bit_cast(dd_v2i, v);
-    w.x = __builtin_amdgcn_update_dpp(0, w.x, 0x130, 0xf, 0xf, true);
-    w.y = __builtin_amdgcn_update_dpp(0, w.y, 0x130, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, w);
-#else
-    return v;
-#endif
-}
-constexpr double dd_ipow(double x, int k) {
-    double v = 1.;
-    for (int i = 0; i < k; ++i) v *= x;
-    return v;
-}
-
+// 128 knots through LDS with three accesses each.  The recursions and the carries are cpur::recursions / cpur::add_carries (cp_uniform_recursions.h, which
+// names the other users); the mirror terms of the two ends stand between the two calls.
 // ---- wave reductions by DPP (row operations within 16 lanes, then row_bcast15 / row_bcast31 across the rows: the total arrives in lane 63) ----
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double dd_dpp(double v) {      // lanes the row mask leaves out keep their own value
 #if defined(__HIP_DEVICE_COMPILE__)
-    dd_v2i w = __builtin_bit_cast(dd_v2i, v);
+    cpur::v2i w = __builtin_bit_cast(cpur::v2i, v);
     w.x = __builtin_amdgcn_update_dpp(w.x, w.x, CTRL, ROW_MASK, 0xf, false);
     w.y = __builtin_amdgcn_update_dpp(w.y, w.y, CTRL, ROW_MASK, 0xf, false);
     return __builtin_bit_cast(double, w);
@@ -265,7 +240,7 @@ template <class LAY = PaddedLayout<32>, bool SCALED = true>
 __device__ __forceinline__ void second_derivatives_and_box_recursive(const double* buf, int lane, int margin_first, int margin_second, double* m, int& first,
                                                                      int& second) {
     constexpr int S = 32, N = 64 * S;
-    constexpr double P = -DD_CINF, SCALE = 1.7320508075688772935;      // 6 kappa = 6 / (2 sqrt 3)
+    constexpr double P = cpur::P, SCALE = 6. * cpur::KAPPA;      // sqrt 3
     auto at = [&](int i) { return buf[LAY::at(i)]; };
     const int own = S * lane;
     {
@@ -278,35 +253,11 @@ __device__ __forceinline__ void second_derivatives_and_box_recursive(const doubl
             y0 = yp;
         }
     }
-#pragma unroll
-    for (int t = S - 2; t >= 0; --t) m[t] = fma(P, m[t + 1], m[t]);
-    const double g1 = m[1];
-    double gin = dd_from_right(m[0]);
-    double f = 0., fs2 = 0.;
-#pragma unroll
-    for (int t = 0; t < S; ++t) {
-        const double e = fma(P, f, m[t]);
-        f = t + 1 < S ? fma(-P, m[t + 1], e) : e;
-        if (t == S - 2) fs2 = f;
-        m[t] = e;
-    }
-    double fin = dd_from_left(f);
-    gin = lane == 63 ? fma(dd_ipow(P, S - 1), fin, fs2) : gin;      // the anti-causal sum at the mirror image of knot n - 2
-    fin = lane == 0 ? fma(dd_ipow(P, S - 1), gin, g1) : fin;        // the causal sum at the mirror image of knot 1
-    {
-        double c = gin;
-#pragma unroll
-        for (int t = S - 1; t >= 0; --t) {
-            c *= P;
-            m[t] += c;
-        }
-        c = fin;
-#pragma unroll
-        for (int t = 0; t < S; ++t) {
-            c *= P;
-            m[t] += c;
-        }
-    }
+    const cpur::Totals own_totals = cpur::recursions<S>(m);
+    double gin = cpur::wave_from_right(own_totals.g_first), fin = cpur::wave_from_left(own_totals.f_last);
+    gin = lane == 63 ? fma(cpur::ipow(P, S - 1), fin, own_totals.f_before_last) : gin;      // the anti-causal sum at the mirror image of knot n - 2
+    fin = lane == 0 ? fma(cpur::ipow(P, S - 1), gin, own_totals.g_second) : fin;           // the causal sum at the mirror image of knot 1
+    cpur::add_carries<S>(m, gin, fin);
     // arg-max over [margin_first, n - margin_first) and over [first + margin_second, n - margin_first): first index on ties, NaN as the largest value
     // (numpy's argmax).  Sequences without a NaN -- a wave-uniform test on a sum that any NaN (or infinity) poisons -- take masked_argmax: the lane's
     // maximum as a chain of v_max, the wave's by DPP, the index from one pass of equality tests: a third of the instructions of the general walk,
@@ -360,7 +311,7 @@ __device__ __forceinline__ void second_derivatives_and_box_recursive(const doubl
 
 // The removal of the box [a, b] (cp_gap_spline, bao_filter.py:395-405): the clamped spline through the x^2-weighted coefficients with the knots
 // [a, b] left out returns the datum at every kept knot, so only the box is rewritten; its two end slopes come from eliminations started
-// DD_GAP_WINDOW knots to either side (the arithmetic of gap_spline_kernel, cp_spline.hip), run by two lanes side by side on values the wave has
+// GAP_WINDOW knots to either side (the arithmetic of gap_spline_kernel, cp_spline.hip), run by two lanes side by side on values the wave has
 // brought into LDS.  `stage(lo, L, R, hi, zl, zr)` fills zl[i - lo] = y_i (i + 1)^2 for lo <= i <= L and zr[i - R] likewise for R <= i <= hi
 // (all lanes take part); `seq` is where the rewritten knots go.  Returns false when nothing is removed (an invalid box: the sequence stays).
 template <int S, class Stage>
@@ -369,10 +320,10 @@ __device__ __forceinline__ bool remove_box(double* buf, const double* gtab, int 
     if (a < 1 || b > N - 2 || b < a) return false;
     const int L = a - 1, R = b + 1;
     const double g = (double)(R - L);
-    const int i0 = L - DD_GAP_WINDOW > 0 ? L - DD_GAP_WINDOW : 0, i1 = R + DD_GAP_WINDOW < N - 1 ? R + DD_GAP_WINDOW : N - 1;
+    const int i0 = L - GAP_WINDOW > 0 ? L - GAP_WINDOW : 0, i1 = R + GAP_WINDOW < N - 1 ? R + GAP_WINDOW : N - 1;
     const int lo = i0 > 0 ? i0 - 1 : 0, hi = i1 < N - 1 ? i1 + 1 : N - 1;
     double* zl = buf;                              // z(lo .. L)
-    double* zr = buf + DD_GAP_WINDOW + 8;          // z(R .. hi)
+    double* zr = buf + GAP_WINDOW + 8;          // z(R .. hi)
     stage(lo, L, R, hi, zl, zr);
     wave_lds_phase();      // zl / zr written by all lanes, read by lanes 0 and 1
     auto z = [&](int i) { return i <= L ? zl[i - lo] : zr[i - R]; };
@@ -441,12 +392,12 @@ __device__ __forceinline__ bool remove_box(double* buf, const double* gtab, int 
 template <int S, class LAY, bool INPLACE = false>
 __device__ __forceinline__ bool remove_box_parallel(const double* ybuf, const double* gtab, int lane, int a, int b, double* seq, bool* all_finite = nullptr) {
     constexpr int N = 64 * S;
-    static_assert(DD_GAP_WINDOW == 64, "a knot of either window per lane");
+    static_assert(GAP_WINDOW == 64, "a knot of either window per lane");
     if (all_finite) *all_finite = true;
     if (a < 1 || b > N - 2 || b < a) return false;
     const int L = a - 1, R = b + 1;
     const double g = (double)(R - L), inv_g = cpmath::recip(g);      // (the quotients below as reciprocals: thirteen IEEE divisions in a row per sequence were a quarter of the kernel's vector instructions, all of them in one dependent chain)
-    const int i0 = L - DD_GAP_WINDOW > 0 ? L - DD_GAP_WINDOW : 0, i1 = R + DD_GAP_WINDOW < N - 1 ? R + DD_GAP_WINDOW : N - 1;
+    const int i0 = L - GAP_WINDOW > 0 ? L - GAP_WINDOW : 0, i1 = R + GAP_WINDOW < N - 1 ? R + GAP_WINDOW : N - 1;
     auto z = [&](int i) {
         const double x = (double)(i + 1);
         return ybuf[LAY::at(i)] * (x * x);

@@ -46,7 +46,7 @@ __device__ __forceinline__ TailArgsK tail_args() {
     return p;
 }
 
-// the queries that go through the spline: v = part + w.z M_j + w.w M_{j+1}, then pk / ((pk / pknow - 1) tophat + 1) as splice_uniform_kernel forms it
+// the queries that go through the spline: v = part + w.z M_j + w.w M_{j+1}, then the damping (cpsu::damped)
 __device__ __forceinline__ void tail_evaluate(const double* yu, double* outrow, int lane, const double* part, const double* pkrow) {
     TailArgsK g = tail_args();
     const int ngb = g->U.ngb, gb0 = g->U.gb0, nq = g->U.nq, gfirst = g->U.gfirst, gend = g->U.gend;
@@ -76,18 +76,17 @@ __device__ __forceinline__ void tail_evaluate(const double* yu, double* outrow, 
             const int j = jv[e];
             double v = part[e] + fma(wz[e], yu[j], ww[e] * yu[j + 1]);
             const double p = q < nq ? pv[e] : 0.;
-            if (tophat) v = p * (v * cpmath::recip(fma(p - v, (q < nq ? tv[e] : 0.), v)));
+            if (tophat) v = cpsu::damped(p, v, q < nq ? tv[e] : 0.);
             if (q >= gfirst && q < gend && !(CP_TAIL_ABLATE & 16)) outrow[q] = v;
         }
     }
 }
 
 // the spliced spline of ONE row by one wave: `row` = the transformed row in LDS, natural order (its stretch starts at column col_u; the slot in front of
-// the stretch and the slots behind it up to 64 SU belong to the row and are free).  The arithmetic of cpsu::splice_uniform_kernel, statement for statement.
+// the stretch and the slots behind it up to 64 SU belong to the row and are free).  The arithmetic is that of cpsu::splice_uniform_kernel: the row functions of
+// cp_splice_uniform.h; here the plan's entries come by batched loads through tail_args() and reads beyond the stretch are clamped.
 template <int SU>
 __device__ __forceinline__ void tail_splice_row(double* row, double* outrow, int lane, const double* pkrow) {
-    using cpsu::P;
-    using cpsu::WIN_U;
     using cpsu::NGB;
     TailArgsK g0 = tail_args();
     const int nm = g0->U.nm, wl = g0->U.wl;
@@ -108,16 +107,7 @@ __device__ __forceinline__ void tail_splice_row(double* row, double* outrow, int
         for (int o = 0; o < 8; ++o) ww[o] = win[64 * o + lane];
         gl_last = __shfl(gvl, wl > 0 ? wl - 1 : 0);
         gr_first = __shfl(gvr, 0);
-        const double ul = yu[lane < WIN_U ? lane : 0], ur = yu[lane < WIN_U ? nm - 1 - lane : 0];
-        const double yfirst = yu[0], ylast = yu[nm - 1];
-        sums[0] = fma(ww[0], gvl - yfirst, ww[1] * (ul - yfirst));
-        sums[1] = fma(ww[2], gvl - gl_last, ww[3] * (ul - gl_last));
-        sums[2] = fma(ww[4], ur - ylast, ww[5] * (gvr - ylast));
-        sums[3] = fma(ww[6], ur - gr_first, ww[7] * (gvr - gr_first));
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-            for (int o = 0; o < 4; ++o) sums[o] += __shfl_xor(sums[o], off);
+        cpsu::junction_sums(yu, nm, lane, ww, gvl, gvr, gl_last, gr_first, sums);
     }
     // ---- the queries' knot values, before the second derivatives take their place ----
     double part[NGB];
@@ -140,9 +130,7 @@ __device__ __forceinline__ void tail_splice_row(double* row, double* outrow, int
         for (int e = 0; e < NGB; ++e) {
             part[e] = 0.;
             if (e < ngb) {
-                const int j = jv[e];
-                const double ya = yu[j], yb = yu[j + 1];      // (j = -1 and j + 1 = nm read slots of the row that hold no knot: replaced)
-                part[e] = fma(wx[e], j < 0 ? gl_last : ya, wy[e] * (j + 1 >= nm ? gr_first : yb));
+                part[e] = cpsu::query_part(yu, nm, jv[e], wx[e], wy[e], gl_last, gr_first);
             }
         }
     }
@@ -166,35 +154,9 @@ __device__ __forceinline__ void tail_splice_row(double* row, double* outrow, int
         }
     }
     cp::wave_lds_phase();      // every read of the knot values is done
-    {
-#pragma unroll
-        for (int t = SU - 2; t >= 0; --t) g[t] = fma(P, g[t + 1], g[t]);
-        double c = fma(m_b, sums[2], cpdd::dd_from_right(g[0]));      // G at the first knot of the next segment (+ what B adds there)
-        double f = 0.;
-#pragma unroll
-        for (int t = 0; t < SU; ++t) {
-            const double e = fma(P, f, g[t]);
-            f = t + 1 < SU ? fma(-P, g[t + 1], e) : e;
-            g[t] = e;
-        }
-#pragma unroll
-        for (int t = SU - 1; t >= 0; --t) {
-            c *= P;
-            g[t] += c;
-        }
-        c = fma(m_a, sums[0], cpdd::dd_from_left(f));                 // F at the last knot of the previous segment (+ A / p in lane 0)
-#pragma unroll
-        for (int t = 0; t < (SU < 36 ? SU : 36); ++t) {
-            c *= P;
-            g[t] += c;
-        }
-        double* mine = yu + SU * lane;
-#pragma unroll
-        for (int t = 0; t < SU; ++t) mine[t] = g[t];
-    }
+    cpsu::solve_segment<SU>(g, m_a, m_b, sums, yu + SU * lane);
     cp::wave_lds_phase();
-    if (lane == 0) yu[-1] = sums[1];
-    if (lane == 1) yu[nm] = sums[3];
+    cpsu::store_outer(yu, nm, lane, sums);
     cp::wave_lds_phase();
     tail_evaluate(yu, outrow, lane, part, pkrow);
 }

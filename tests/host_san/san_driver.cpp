@@ -4,7 +4,8 @@
 //   * the special functions and the FFTLog table setup behind the C ABI (cp_special.cpp, cp_fftlog_setup.cpp),
 //   * the per-thread phases of the fused FFTLog kernel through the emulator (tests/host_emu/emu_fftlog.cpp): the kernel's LDS is a heap
 //     array of exactly the size the launch requests, its rows are heap arrays of exactly n samples, so an index of the kernel that leaves
-//     its LDS allocation or its rows is an AddressSanitizer report here (GPU sanitizers are not available on the pool).
+//     its LDS allocation or its rows is an AddressSanitizer report here (GPU sanitizers are not available on the pool),
+//   * the per-lane recursions of the uniform-grid spline solves through their emulator (tests/host_emu/emu_uniform_recursions.cpp).
 // Exit status 0 and a last line "ok" mean no report; numerical checks are the business of tests/test_fftlog_host.py.
 #include <algorithm>
 #include <cmath>
@@ -190,7 +191,25 @@ static void interp_tables() {
     }
 }
 
+// the per-lane recursions of the uniform-grid spline solves (csrc/cp_uniform_recursions.h) through their emulator, compiled into this program: every
+// instance on exact-size rows, among them the causal carry cut at 36 of 57 knots
+#include "../host_emu/emu_uniform_recursions.cpp"
+
+static void uniform_recursions() {
+    const int cases[][2] = {{32, 32}, {33, 33}, {57, 57}, {57, 36}};
+    for (const auto& c : cases) {
+        std::vector<double> r((size_t)64 * c[0]), out(r.size(), -7.);
+        for (size_t i = 0; i < r.size(); ++i) r[i] = std::sin(0.01 * i) + 1e-3 * std::cos(1.7 * i);
+        for (int swapped : {0, 1}) EXPECT(emu_uniform_recursions(c[0], c[1], r.data(), out.data(), swapped) == 0);
+        bool finite = true;
+        for (double v : out) finite = finite && std::isfinite(v) && v != -7.;
+        EXPECT(finite);
+    }
+    EXPECT(emu_uniform_recursions(33, 36, nullptr, nullptr, 0) == 1);
+}
+
 int main() {
+    uniform_recursions();
     interp_tables();
     special_functions();
     table_setup_errors();

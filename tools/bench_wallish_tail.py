@@ -18,9 +18,14 @@ fid = cp.Cosmology(engine='eisenstein_hu')
 interp = cosmo.get_fourier().pk_interpolator(z=np.array([0.]))
 f = PowerSpectrumBAOFilter(interp, engine='wallish2018', cosmo=cosmo, cosmo_fid=fid)
 ops = f._operators()
-coef = f._even_now.new_empty((n, 4096))      # the rewritten coefficients as the filter left them: any smooth sequences serve the timing
-coef.view(2 * n, 2048)[0::2] = f._even_now
-coef.view(2 * n, 2048)[1::2] = f._odd_now
+if f._even_now is not None:
+    coef = f._even_now.new_empty((n, 4096))      # the rewritten coefficients as the filter left them: any smooth sequences serve the timing
+    coef.view(2 * n, 2048)[0::2] = f._even_now
+    coef.view(2 * n, 2048)[1::2] = f._odd_now
+else:      # (an analytic batch goes through cp_wallish_full, which keeps no sequences: the decaying rows with a bump of tools/bench_dd_box.py, seeded)
+    x = 1. + torch.arange(2048, device=dev, dtype=torch.float64)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    coef = (torch.randn((2 * n, 2048), generator=gen, device=dev, dtype=torch.float64) / x**1.5 + 3e-3 * torch.exp(-0.5 * ((x - 0.35 * 2048) / 12.)**2)).view(n, 4096)
 pk = f._pk_rows.contiguous()
 box = torch.empty((2 * n, 2), dtype=torch.int32, device=dev)
 out = torch.empty_like(pk)
