@@ -211,6 +211,9 @@ SIGNATURES['cp_mlp_gauss_newton_workspace_doubles'] = (ctypes.c_longlong, [ctype
 SIGNATURES['cp_lm_layout'] = (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)])
 # B, ndim; the state x, fisher, grad, chi2, lambda, status, naccepted; the trial xt, fisher_t, grad_t, chi2_t; lo, hi; up, down, lmin, lmax, ftol; next
 SIGNATURES['cp_lm_step'] = (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int] + [ctypes.c_void_p] * 13 + [ctypes.c_double] * 5 + [ctypes.c_void_p] + _WHERE)
+SIGNATURES['cp_lm_step_velocity'] = (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int] + [ctypes.c_void_p] * 13 + [ctypes.c_double] * 5 + [ctypes.c_void_p] * 2 + _WHERE)
+# B, ndim; the state x, fisher, grad, lambda, status; lo, hi; velocity, h; alpha; next, naccelerated
+SIGNATURES['cp_lm_accelerate'] = (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int] + [ctypes.c_void_p] * 9 + [ctypes.c_double] + [ctypes.c_void_p] * 2 + _WHERE)
 SIGNATURES['cp_spd_inverse'] = (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int] + [ctypes.c_void_p] * 3 + _WHERE)
 SIGNATURES['cp_gauss_newton_dense_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_longlong])
 # d_jac, ldj; B, ndim, ncols; d_value, ldv; d_data, ldd; d_precision, ldp; d_fisher, d_grad, d_chi2, d_work, work_doubles

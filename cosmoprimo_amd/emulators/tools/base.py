@@ -12,7 +12,8 @@ The helpers that both engines' ``predict`` / ``jacobian`` / ``vjp`` open with (`
 import this module, which imports them only where it builds one.  Nothing on the path of a call imports anything: at B = 1 a call is its Python.
 
 ``Emulator.least_squares`` runs batched Levenberg-Marquardt fits on ``gauss_newton``; what stands between two of its calls is one launch, :func:`lm_step` (with
-:func:`lm_state` and :func:`spd_inverse`: module-level, over device tensors, for normal equations of any origin).  Under a dense precision matrix
+:func:`lm_state` and :func:`spd_inverse`: module-level, over device tensors, for normal equations of any origin; with ``geodesic=True`` also the engines' ``jvp2``
+and ``vjp`` and one more launch, :func:`lm_accelerate`).  Under a dense precision matrix
 (``precision=``) the normal equations come from :func:`gauss_newton_dense`, module-level as well: one GEMM on a Jacobian of any origin, which the engines'
 ``jacobian`` write run by run into one buffer (``out=``).
 """
@@ -115,19 +116,8 @@ def lm_state(x, lambda0=1e-3):
             'lambda': torch.full((B,), float(lambda0), dtype=torch.float64, device=x.device), 'status': new(B, dtype=torch.int32), 'naccepted': new(B, dtype=torch.int32)}
 
 
-def lm_step(state, trial, lo, hi, lambda_up=10., lambda_down=0.1, lambda_min=1e-12, lambda_max=1e12, ftol=1e-8):
-    """Everything between two ``gauss_newton`` calls of B Levenberg-Marquardt fits at once, in one launch (``cp_lm_step``, csrc/cp_lm.hip), whatever
-    produced the normal equations.  ``state``: contiguous device tensors ``x`` (B, ndim), ``fisher`` (B, ndim, ndim), ``gradient`` (B, ndim), ``chi2``,
-    ``lambda`` (B,) float64, ``status``, ``naccepted`` (B,) int32 (:func:`lm_state`), updated in place.  ``trial``: ``x``, ``fisher``, ``gradient``,
-    ``chi2``, what ``gauss_newton`` returned at ``trial['x']``.  ``lo``, ``hi``: (ndim,) device tensors, the box (infinite where open).
-
-    Per fit: a fit whose ``status`` is not 0 is left alone.  The trial is accepted if its ``chi2`` is finite and not above the state's; it is then copied
-    into the state, ``lambda`` is multiplied by ``lambda_down`` (not below ``lambda_min``; not on the first acceptance), and the fit has converged
-    (``status = 1``) if ``chi2`` went down by no more than ``ftol`` times itself.  A rejected trial multiplies ``lambda`` by ``lambda_up``; beyond
-    ``lambda_max`` the fit has stalled (``status = 2``); a start that is not finite fails (``status = 3``).  A running fit then holds the parameters that
-    sit on a bound with the gradient pointing out of the box, solves ``(F + lambda diag F) delta = g`` on the others by Cholesky (a pivot that is not
-    positive: ``status = 3``) and moves them by ``delta``, clipped to the box.  Returns ``next`` (B, ndim), the next trial point: ``x`` for a fit that is
-    not running.  Nothing is read back and the call does not wait for the device."""
+def _lm_checked(state, lo, hi):
+    """What :func:`lm_step` and :func:`lm_accelerate` check of the state and the box: ``(B, ndim, shapes, lo, hi)``."""
     torch = dv.torch()
     x = state['x']
     if x.ndim != 2:
@@ -139,19 +129,77 @@ def lm_step(state, trial, lo, hi, lambda_up=10., lambda_down=0.1, lambda_min=1e-
         if tuple(tensor.shape) != shapes[name] or tensor.dtype != (torch.int32 if name in ('status', 'naccepted') else torch.float64) or not tensor.is_contiguous() \
                 or tensor.device != x.device:
             raise ValueError('state[{!r}] must be a contiguous {} tensor of shape {} on {}'.format(name, 'int32' if name in ('status', 'naccepted') else 'float64', shapes[name], x.device))
+    lo, hi = (dv.to_device(bound, x.device).reshape(-1) for bound in (lo, hi))
+    if int(lo.shape[0]) != ndim or int(hi.shape[0]) != ndim:
+        raise ValueError('lo and hi must be of shape ({:d},)'.format(ndim))
+    return B, ndim, shapes, lo, hi
+
+
+def lm_step(state, trial, lo, hi, lambda_up=10., lambda_down=0.1, lambda_min=1e-12, lambda_max=1e12, ftol=1e-8, return_velocity=False):
+    """Everything between two ``gauss_newton`` calls of B Levenberg-Marquardt fits at once, in one launch (``cp_lm_step``, csrc/cp_lm.hip), whatever
+    produced the normal equations.  ``state``: contiguous device tensors ``x`` (B, ndim), ``fisher`` (B, ndim, ndim), ``gradient`` (B, ndim), ``chi2``,
+    ``lambda`` (B,) float64, ``status``, ``naccepted`` (B,) int32 (:func:`lm_state`), updated in place.  ``trial``: ``x``, ``fisher``, ``gradient``,
+    ``chi2``, what ``gauss_newton`` returned at ``trial['x']``.  ``lo``, ``hi``: (ndim,) device tensors, the box (infinite where open).
+
+    Per fit: a fit whose ``status`` is not 0 is left alone.  The trial is accepted if its ``chi2`` is finite and not above the state's; it is then copied
+    into the state, ``lambda`` is multiplied by ``lambda_down`` (not below ``lambda_min``; not on the first acceptance), and the fit has converged
+    (``status = 1``) if ``chi2`` went down by no more than ``ftol`` times itself.  A rejected trial multiplies ``lambda`` by ``lambda_up``; beyond
+    ``lambda_max`` the fit has stalled (``status = 2``); a start that is not finite fails (``status = 3``).  A running fit then holds the parameters that
+    sit on a bound with the gradient pointing out of the box, solves ``(F + lambda diag F) delta = g`` on the others by Cholesky (a pivot that is not
+    positive: ``status = 3``) and moves them by ``delta``, clipped to the box.  Returns ``next`` (B, ndim), the next trial point: ``x`` for a fit that is
+    not running.  Nothing is read back and the call does not wait for the device.
+
+    ``return_velocity=True``: ``(next, velocity)``, the same launch (``cp_lm_step_velocity``) and the same bits; ``velocity`` (B, ndim) is ``delta`` on the
+    free parameters of a running fit and exactly 0 elsewhere: what :func:`lm_accelerate` takes."""
+    torch = dv.torch()
+    x = state['x']
+    B, ndim, shapes, lo, hi = _lm_checked(state, lo, hi)
     read = []
     for name in LM_TRIAL:
         tensor = dv.to_device(trial[name], x.device, cache=False)
         if tuple(tensor.shape) != shapes[name]:
             raise ValueError('trial[{!r}] must be of shape {}, got {}'.format(name, shapes[name], tuple(tensor.shape)))
         read.append(tensor)
-    lo, hi = (dv.to_device(bound, x.device).reshape(-1) for bound in (lo, hi))
-    if int(lo.shape[0]) != ndim or int(hi.shape[0]) != ndim:
-        raise ValueError('lo and hi must be of shape ({:d},)'.format(ndim))
     out = torch.empty_like(x)
-    _lib.check(_lib.load().cp_lm_step(B, ndim, *[state[name].data_ptr() for name in LM_STATE], *[tensor.data_ptr() for tensor in read], lo.data_ptr(), hi.data_ptr(),
-                                      float(lambda_up), float(lambda_down), float(lambda_min), float(lambda_max), float(ftol), out.data_ptr(), x.device.index,
-                                      dv.stream_of(x.device)))
+    head = [B, ndim] + [state[name].data_ptr() for name in LM_STATE] + [tensor.data_ptr() for tensor in read] + [lo.data_ptr(), hi.data_ptr()] \
+        + [float(lambda_up), float(lambda_down), float(lambda_min), float(lambda_max), float(ftol), out.data_ptr()]
+    if not return_velocity:
+        _lib.check(_lib.load().cp_lm_step(*head, x.device.index, dv.stream_of(x.device)))
+        return out
+    velocity = torch.empty_like(x)
+    _lib.check(_lib.load().cp_lm_step_velocity(*head, velocity.data_ptr(), x.device.index, dv.stream_of(x.device)))
+    return out, velocity
+
+
+def lm_accelerate(state, velocity, curvature, lo, hi, alpha=0.75, naccelerated=None):
+    """Geodesic acceleration (Transtrum & Sethna 2012) of the step :func:`lm_step` just solved, in one launch (``cp_lm_accelerate``, csrc/cp_lm.hip).
+    ``state``: as :func:`lm_step` left it (read only); ``velocity`` (B, ndim): what ``lm_step(..., return_velocity=True)`` returned beside ``next``;
+    ``curvature`` (B, ndim): ``h = J W y''(v, v)``, the vector-Jacobian product of the weighted second directional derivative of the prediction along the
+    velocity, whatever produced it; ``lo``, ``hi``: the box.
+
+    Per running fit: ``a = -(F + lambda diag F)^-1 h`` on the free parameters (the held set of :func:`lm_step`); the correction is taken where
+    ``sv > 0``, ``sa`` is finite and ``4 sa <= alpha^2 sv``, with ``sa = sum F_ii a_i^2`` and ``sv = sum F_ii v_i^2`` over the free parameters
+    (``2 |a| / |v| <= alpha`` in the Marquardt-scaled norm of the solve): ``next = clip(x + (v + a / 2))``.  Elsewhere ``next`` is the plain step
+    ``clip(x + v)``, the bits of :func:`lm_step`'s ``next``; a fit that is over, or whose pivot fails, gets ``x``.  Returns ``next`` (B, ndim).
+    ``naccelerated``: (B,) contiguous int32 device tensor, incremented in place where the correction is taken.  Nothing is read back and the call does not
+    wait for the device."""
+    torch = dv.torch()
+    x = state['x']
+    B, ndim, shapes, lo, hi = _lm_checked(state, lo, hi)
+    read = []
+    for name, tensor in (('velocity', velocity), ('curvature', curvature)):
+        tensor = dv.to_device(tensor, x.device, cache=False)
+        if tuple(tensor.shape) != (B, ndim):
+            raise ValueError('{} must be of shape {}, got {}'.format(name, (B, ndim), tuple(tensor.shape)))
+        read.append(tensor.to(torch.float64).contiguous())
+    if naccelerated is None:
+        naccelerated = torch.zeros((B,), dtype=torch.int32, device=x.device)
+    elif not dv.is_torch(naccelerated) or tuple(naccelerated.shape) != (B,) or naccelerated.dtype != torch.int32 or not naccelerated.is_contiguous() or naccelerated.device != x.device:
+        raise ValueError('naccelerated must be a contiguous int32 tensor of shape {} on {}'.format((B,), x.device))
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().cp_lm_accelerate(B, ndim, *[state[name].data_ptr() for name in ('x', 'fisher', 'gradient', 'lambda', 'status')], lo.data_ptr(), hi.data_ptr(),
+                                            read[0].data_ptr(), read[1].data_ptr(), float(alpha), out.data_ptr(), naccelerated.data_ptr(), x.device.index,
+                                            dv.stream_of(x.device)))
     return out
 
 
@@ -726,7 +774,7 @@ class Emulator(object):
         return (values,) + (toret if isinstance(toret, tuple) else (toret,))
 
     def least_squares(self, params, weights, data, bounds=None, niterations=20, lambda0=1e-3, lambda_up=10., lambda_down=0.1, lambda_min=1e-12, lambda_max=1e12,
-                      ftol=1e-8, device=False, precision=None):
+                      ftol=1e-8, device=False, precision=None, geodesic=False, alpha=0.75):
         """B weighted least-squares fits of ``data`` to the emulated outputs at once, by Levenberg-Marquardt on the device: ``niterations`` times
         :meth:`gauss_newton` at the trial points, then :func:`lm_step` (one launch: acceptance, the damping of each fit, the active set of the box, the
         damped Cholesky solve, the stopping rule).  ``params``: the start, as :meth:`predict` takes it (scalars or arrays of B values); ``weights``,
@@ -743,7 +791,14 @@ class Emulator(object):
 
         ``precision``: a dense precision matrix (N, N), ``weights`` then the sequence of the keys its rows and columns follow, as :meth:`gauss_newton` takes
         them.  It is permuted and staged once; an iteration is the engine's ``jacobian`` calls, :func:`gauss_newton_dense` and :func:`lm_step`, and
-        ``info['covariance']`` the inverse of the dense-precision Fisher matrix."""
+        ``info['covariance']`` the inverse of the dense-precision Fisher matrix.
+
+        ``geodesic=True``: geodesic acceleration (Transtrum & Sethna 2012) of every step.  After :func:`lm_step` (which then also returns the velocity
+        ``v`` it solved) an iteration takes, per run of columns, the second directional derivative ``q = y''(v, v)`` at the accepted point (the engine's
+        ``jvp2``, a row per fit), its cotangent ``where(w == 0, 0, w q)`` -- under a dense precision ``P`` the masked ``q`` of all runs times ``P``, masked
+        again -- and the engine's ``vjp`` of it, the runs' results added in run order: ``h = J W q``; then :func:`lm_accelerate` takes
+        ``x + v + a / 2`` with ``a = -(F + lambda diag F)^-1 h`` where ``2 |a| / |v| <= alpha`` and the plain step elsewhere.  ``info`` then also holds
+        ``naccelerated`` (B,), the count of corrections each fit took.  ``alpha`` must be finite and positive (``ValueError``)."""
         X, B, scalar = self._points(params)
         torch = dv.torch()
         if data is None:
@@ -766,6 +821,16 @@ class Emulator(object):
         lo, hi = (dv.to_device(np.array([limits[name][side] for name in names], dtype='f8'), dev) for side in (0, 1))
         x = torch.clamp(dv.to_device(X, dev, cache=False), min=lo, max=hi)
         state = lm_state(x, lambda0=lambda0)
+        controls = dict(lambda_up=lambda_up, lambda_down=lambda_down, lambda_min=lambda_min, lambda_max=lambda_max, ftol=ftol)
+        if geodesic:
+            alpha = float(alpha)
+            if not (0. < alpha < float('inf')):
+                raise ValueError('alpha must be finite and positive, got {}'.format(alpha))
+            naccelerated = torch.zeros((B,), dtype=torch.int32, device=dev)
+            zero = torch.zeros((), dtype=torch.float64, device=dev)
+            if precision is not None:
+                dropped = precision.diagonal() == 0
+                second = torch.empty((B, N), dtype=torch.float64, device=dev)
         for iteration in range(int(niterations)):
             totals = None
             if precision is not None:
@@ -777,16 +842,36 @@ class Emulator(object):
             if totals is None:
                 totals = (torch.zeros((B, ndim, ndim), dtype=torch.float64, device=dev), torch.zeros((B, ndim), dtype=torch.float64, device=dev),
                           torch.zeros((B,), dtype=torch.float64, device=dev))
-            x = lm_step(state, dict(zip(LM_TRIAL, (x,) + tuple(totals))), lo, hi, lambda_up=lambda_up, lambda_down=lambda_down, lambda_min=lambda_min,
-                        lambda_max=lambda_max, ftol=ftol)
+            trial = dict(zip(LM_TRIAL, (x,) + tuple(totals)))
+            if not geodesic:
+                x = lm_step(state, trial, lo, hi, **controls)
+                continue
+            x, velocity = lm_step(state, trial, lo, hi, return_velocity=True, **controls)
+            at, curvature = state['x'], None
+            if precision is not None:
+                for start, stop, entries, q0 in runs:
+                    second[:, q0:q0 + stop - start] = self.engine.jvp2(at, velocity, columns=(start, stop))
+                cotangent = torch.where(dropped, zero, torch.matmul(torch.where(dropped, zero, second), precision))
+                for start, stop, entries, q0 in runs:
+                    grad = self.engine.vjp(at, cotangent[:, q0:q0 + stop - start], columns=(start, stop))
+                    curvature = grad if curvature is None else curvature + grad
+            else:
+                for start, stop, entries, wblock, dblock in staged:
+                    grad = self.engine.vjp(at, torch.where(wblock == 0, zero, wblock * self.engine.jvp2(at, velocity, columns=(start, stop))), columns=(start, stop))
+                    curvature = grad if curvature is None else curvature + grad
+            if curvature is None:
+                curvature = torch.zeros((B, ndim), dtype=torch.float64, device=dev)
+            x = lm_accelerate(state, velocity, curvature, lo, hi, alpha=alpha, naccelerated=naccelerated)
         covariance = spd_inverse(state['fisher'])[0]
         out = dict(state, covariance=covariance)
+        if geodesic:
+            out['naccelerated'] = naccelerated
         if not device:
             out = {name: dv.to_host(value) for name, value in out.items()}
         if scalar:
             out = {name: value[0] for name, value in out.items()}
         best = {name: out['x'][..., i] for i, name in enumerate(names)}
-        info = {name: out[name] for name in ('fisher', 'covariance', 'status', 'naccepted', 'lambda')}
+        info = {name: out[name] for name in ('fisher', 'covariance', 'status', 'naccepted', 'lambda') + (('naccelerated',) if geodesic else ())}
         info['gradient'] = {name: out['gradient'][..., i] for i, name in enumerate(names)}
         return best, out['chi2'], info
 

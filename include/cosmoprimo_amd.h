@@ -835,14 +835,36 @@ int cp_mlp_adam(double* d_params, double* d_m, double* d_v, const double* d_grad
  *   Every operation is a float64 operation rounded once (no FMA contraction), divisions and square roots correctly rounded.
  * cp_spd_inverse : d_inv[b] (ndim, ndim) = d_a[b]^-1 by the same Cholesky, the triangle computed once and mirrored (symmetric bit for bit); d_info[b]
  *   (int32) = 0, or the 1-based index of the first failing pivot: d_inv[b] is then NaN throughout.
- * cp_lm_layout : what the two launches use -- lanes per fit (the smallest power of two >= ndim: 64 / lanes fits per wave) and fits per workgroup.
+ * cp_lm_step_velocity : cp_lm_step (the same kernel; the state and d_next come out bit for bit), which also writes d_velocity (B, ndim): the delta of
+ *   rule 5 on the free parameters of a fit whose status is still 0 after the factorisation, exact 0 elsewhere (held parameters, fits that are over).
+ * cp_lm_accelerate : geodesic acceleration (Transtrum & Sethna 2012) of the step cp_lm_step_velocity left behind.  Read only: the state d_x, d_fisher,
+ *   d_grad, d_lambda, d_status as that call left it, the box, d_velocity (v) and d_h (B, ndim), h = J W y''(v, v): the vector-Jacobian product of the
+ *   weighted second directional derivative of the prediction along v.  Written: d_next (B, ndim) for every fit; d_naccelerated (B) int32, incremented
+ *   where the correction is taken.  Per fit, in this order:
+ *   1. status != 0: next = x, the counter untouched.
+ *   2. the held set of rule 5 again, from x, grad, status; the factor of F + lambda diag F with it taken out; a pivot that is not > 0 or not finite:
+ *      next = x, the counter untouched.
+ *   3. a = the solution of that system with the right-hand side -h_i on the free parameters, 0 on the held.
+ *   4. sa = sum_i (F_ii a_i) a_i, sv = sum_i (F_ii v_i) v_i over the free parameters, i ascending, each from 0.
+ *   5. the correction is taken if and only if sv > 0, sa is finite and 4 sa <= (alpha alpha) sv (2 |a| / |v| <= alpha in the Marquardt-scaled norm):
+ *      next_i = min(max(x_i + (v_i + 0.5 a_i), lo_i), hi_i) on the free parameters, the counter + 1.
+ *   6. else the plain step, next_i = min(max(x_i + v_i, lo_i), hi_i): the bits of cp_lm_step's d_next.  A held parameter stays at x_i exactly.
+ * cp_lm_layout : what these launches use -- lanes per fit (the smallest power of two >= ndim: 64 / lanes fits per wave) and fits per workgroup.
  * Checks, in this order, before any device call: B < 0 or ndim < 1: CP_EINVAL; ndim > 32: CP_EUNSUPPORTED; more than 2^31 - 1 workgroups of fits:
- *   CP_EUNSUPPORTED; B = 0: CP_OK; a null pointer: CP_EINVAL; up > 1, 0 < down <= 1, 0 < lmin <= lmax, ftol >= 0, none a NaN: else CP_EINVAL. */
+ *   CP_EUNSUPPORTED; B = 0: CP_OK; a null pointer: CP_EINVAL; up > 1, 0 < down <= 1, 0 < lmin <= lmax, ftol >= 0, none a NaN: else CP_EINVAL; alpha
+ *   finite and > 0: else CP_EINVAL. */
 enum cp_lm_status { CP_LM_RUNNING = 0, CP_LM_CONVERGED = 1, CP_LM_STALLED = 2, CP_LM_FAILED = 3 };
 int cp_lm_layout(int ndim, int* lanes_per_fit, int* fits_per_workgroup);
 int cp_lm_step(long long B, int ndim, double* d_x, double* d_fisher, double* d_grad, double* d_chi2, double* d_lambda, int* d_status, int* d_naccepted,
                const double* d_xt, const double* d_fisher_t, const double* d_grad_t, const double* d_chi2_t, const double* d_lo, const double* d_hi, double up,
                double down, double lmin, double lmax, double ftol, double* d_next, int device, void* stream);
+int cp_lm_step_velocity(long long B, int ndim, double* d_x, double* d_fisher, double* d_grad, double* d_chi2, double* d_lambda, int* d_status,
+                        int* d_naccepted, const double* d_xt, const double* d_fisher_t, const double* d_grad_t, const double* d_chi2_t, const double* d_lo,
+                        const double* d_hi, double up, double down, double lmin, double lmax, double ftol, double* d_next, double* d_velocity, int device,
+                        void* stream);
+int cp_lm_accelerate(long long B, int ndim, const double* d_x, const double* d_fisher, const double* d_grad, const double* d_lambda, const int* d_status,
+                     const double* d_lo, const double* d_hi, const double* d_velocity, const double* d_h, double alpha, double* d_next, int* d_naccelerated,
+                     int device, void* stream);
 int cp_spd_inverse(long long B, int ndim, const double* d_a, double* d_inv, int* d_info, int device, void* stream);
 
 /* ---- Fisher matrices and normal equations under a dense precision matrix, on an explicit Jacobian (csrc/cp_gauss_newton_dense.hip) ----

@@ -3,7 +3,7 @@ same rules written with what there was before them: ``Emulator.gauss_newton(devi
 ``torch.cholesky_solve``: the forms that do not wait for the device), a dozen library launches per iteration.
 
     python tools/bench_least_squares.py [--batch 10000 64 1] [--ndim 8] [--nhidden 64 64 64] [--outputs 1024] [--order 3] [--iterations 20] [--repeats 20]
-                                        [--warmup 3] [--processes 5] [--only mlp|taylor] [--once] [--out FILE]
+                                        [--warmup 3] [--processes 5] [--only mlp|taylor] [--once] [--geodesic] [--out FILE]
 
 The two configurations of tools/bench_gauss_newton.py (MLP: ndim = 8, hidden (64, 64, 64), M = 1024, y operation log10; Taylor: 8 parameters at order 3,
 M = 1024).  Per batch size B fits at once: the data is the prediction at B points with 1 % of noise, the weights are per point, the starts lie up to 2 % of
@@ -11,7 +11,13 @@ the ranges away, 20 iterations.  Timed with HIP events on the current stream, th
 ``--processes`` fresh processes one after the other.  Before timing, one step of each route from the same state is held to the longdouble truth of
 tests/lm_reference.py by its level rule, and the routes' final chi2 are compared.  Condition (exit status 1 if missed): at the first batch size the median of
 ``least_squares`` is below the median of the torch route in every process.  ``--once`` runs each route once after the warm-up and times nothing: the run to
-put under ``rocprofv3 --kernel-trace --stats``.  Needs neither the reference nor the oracle."""
+put under ``rocprofv3 --kernel-trace --stats``.  Needs neither the reference nor the oracle.
+
+``--geodesic``: after the two routes (timed exactly as without the option), ``least_squares(geodesic=True)`` and ``least_squares`` are timed alternating in a
+loop of their own; one ``lm_accelerate`` from a recorded state is held to the longdouble truth of tests/lm_accel_reference.py (the fits whose gate lies
+within a factor 1.25 of equality are left out: there the decision may fall either way); and for the noisy data and for noise-free data the count of
+``gauss_newton`` evaluations (iterations) each route needs until every fit has ``status == 1`` is found by bisection (at most ``--most``) and reported,
+with the count of corrections taken.  Nothing of this enters the exit status."""
 import argparse
 import itertools
 import os
@@ -87,6 +93,87 @@ def check_one_step(torch, lines, recorded, lo, hi):
                  % (ours.tobytes() == next64.tobytes()))
 
 
+def check_one_acceleration(torch, lines, emulator, recorded, weights, lo, hi):
+    """One lm_accelerate from the state and the trial ``recorded`` against the longdouble truth, a block a fit, 16 levels (tests/lm_accel_reference.py)."""
+    import lm_accel_reference as la
+    import lm_reference as lr
+    from cosmoprimo_amd.emulators.tools import lm_accelerate, lm_step
+    names = list(emulator.params)
+    state = {name: value.clone() for name, value in recorded['state'].items()}
+    nxt, v = lm_step(state, recorded['trial'], lo, hi, return_velocity=True, **CONTROLS)
+    at = {name: state['x'][:, i] for i, name in enumerate(names)}
+    q = emulator.jvp2(at, {name: v[:, i] for i, name in enumerate(names)}, device=True)
+    h = emulator.vjp(at, {key: weights[key] * q[key] for key in weights}, device=True)
+    h = torch.stack([h[name] for name in names], dim=1)
+    count = torch.zeros(len(v), dtype=torch.int32, device=v.device)
+    ours = lm_accelerate(state, v, h, lo, hi, naccelerated=count).cpu().numpy()
+    host = lambda d: {name: value.cpu().numpy() for name, value in d.items()}      # noqa: E731
+    args = (host(state), v.cpu().numpy(), h.cpu().numpy(), lo.cpu().numpy(), hi.cpu().numpy())
+    (next64, taken64), (nextld, takenld) = la.accelerate(*args, dtype='f8'), la.accelerate(*args, dtype=np.longdouble)
+    ratio = la.gate_ratio(*args, dtype='f8')
+    clear = ~((ratio > 0.8) & (ratio < 1.25))
+    taken = count.cpu().numpy() == 1
+    assert np.array_equal(taken[clear], taken64[clear]) and np.array_equal(taken64[clear], takenld[clear])
+    same = clear | ((taken == taken64) & (taken64 == takenld))
+    lr.assert_within(ours[same], nextld[same], next64[same], 'lm_accelerate')
+    lines.append('  one lm_accelerate from a recorded state: within 16 levels of the longdouble truth; %d of %d fits take the correction (%d within 1.25 of the gate); the bits '
+                 'of the float64 restatement: %s' % (taken.sum(), len(taken), (~clear).sum(), ours.tobytes() == next64.tobytes()))
+
+
+def evaluations(emulator, start, weights, data, geodesic, most):
+    """(the least count of iterations after which every fit has status 1, or None if ``most`` do not suffice; status counts and corrections there)"""
+    def run(n):
+        info = emulator.least_squares(start, weights, data, niterations=n, device=True, geodesic=geodesic, **CONTROLS)[2]
+        status = info['status'].cpu().numpy()
+        return bool((status == 1).all()), np.bincount(status, minlength=4).tolist(), (info['naccelerated'].cpu().numpy() if geodesic else None)
+
+    last = run(most)
+    if not last[0]:
+        return None, last[1], last[2]
+    below, above = 0, most
+    while above - below > 1:
+        middle = (below + above) // 2
+        now = run(middle)
+        if now[0]:
+            above, last = middle, now
+        else:
+            below = middle
+    return above, last[1], last[2]
+
+
+def compare_geodesic(torch, lines, emulator, start, weights, data, clean, recorded, lo, hi, args):
+    check_one_acceleration(torch, lines, emulator, recorded, weights, lo, hi)
+    if args.once:
+        emulator.least_squares(start, weights, data, niterations=args.iterations, device=True, geodesic=True, **CONTROLS)
+        torch.cuda.synchronize()
+        return
+    for what, d in (('noisy', data), ('noise-free', clean)):
+        for geodesic in (False, True):
+            count, status, taken = evaluations(emulator, start, weights, d, geodesic, args.most)
+            lines.append('  %-10s data, %-8s: every fit has status 1 after %s evaluations (status counts there %s%s)' % (
+                what, 'geodesic' if geodesic else 'plain', count if count is not None else 'more than %d' % args.most, status,
+                '; corrections taken per fit %d .. %d, mean %.2f' % (taken.min(), taken.max(), taken.mean()) if taken is not None else ''))
+    routes = [('least_squares', lambda: emulator.least_squares(start, weights, data, niterations=args.iterations, device=True, **CONTROLS)),
+              ('least_squares, geodesic', lambda: emulator.least_squares(start, weights, data, niterations=args.iterations, device=True, geodesic=True, **CONTROLS))]
+    for _ in range(args.warmup):
+        for name, fn in routes:
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name, fn in routes}
+    for _ in range(args.repeats):
+        for name, fn in routes:      # alternating
+            begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            begin.record()
+            fn()
+            end.record()
+            end.synchronize()
+            times[name].append(begin.elapsed_time(end))
+    for name, t in times.items():
+        t = np.array(t)
+        lines.append('  %-24s median %8.3f ms  (min %8.3f, max %8.3f over %d), %.3f ms an iteration' % (name, np.median(t), t.min(), t.max(), len(t), np.median(t) / args.iterations))
+    lines.append('  the correction costs %.3f ms an iteration' % ((np.median(times['least_squares, geodesic']) - np.median(times['least_squares'])) / args.iterations))
+
+
 def compare(torch, lines, emulator, truth, M, args, rng):
     B, ndim = (int(n) for n in truth.shape)
     names = list(emulator.params)
@@ -115,6 +202,8 @@ def compare(torch, lines, emulator, truth, M, args, rng):
         for name, fn in routes:
             fn()
         torch.cuda.synchronize()
+        if args.geodesic:
+            compare_geodesic(torch, lines, emulator, start, weights, data, {'y': value}, recorded, lo, hi, args)
         return None
     times = {name: [] for name, fn in routes}
     for _ in range(args.repeats):
@@ -130,6 +219,8 @@ def compare(torch, lines, emulator, truth, M, args, rng):
         lines.append('  %-22s median %8.3f ms  (min %8.3f, max %8.3f over %d)' % (name, np.median(t), t.min(), t.max(), len(t)))
     ratio = np.median(times['gauss_newton + torch']) / np.median(times['least_squares'])
     lines.append('  gauss_newton + torch / least_squares = %.2f' % ratio)
+    if args.geodesic:
+        compare_geodesic(torch, lines, emulator, start, weights, data, {'y': value}, recorded, lo, hi, args)
     return ratio
 
 
@@ -183,6 +274,8 @@ def main():
     parser.add_argument('--processes', type=int, default=5)
     parser.add_argument('--only', choices=['mlp', 'taylor'], default=None)
     parser.add_argument('--once', action='store_true')
+    parser.add_argument('--geodesic', action='store_true')
+    parser.add_argument('--most', type=int, default=200, help='the iterations at which --geodesic gives up counting evaluations')
     parser.add_argument('--out', default=None)
     parser.add_argument('--child', action='store_true', help=argparse.SUPPRESS)
     args = parser.parse_args()
