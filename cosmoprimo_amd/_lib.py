@@ -201,6 +201,7 @@ SIGNATURES['cp_taylor_predict'] = (ctypes.c_int, _TAYLOR_HEAD + [ctypes.c_void_p
 SIGNATURES['cp_taylor_predict_columns'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + _WHERE)
 SIGNATURES['cp_taylor_jacobian'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + _WHERE)
 SIGNATURES['cp_taylor_vjp'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong] + _WHERE)      # d_cot, ldc; d_grad, d_work, work_doubles
+SIGNATURES['cp_taylor_vjp2'] = SIGNATURES['cp_taylor_vjp']      # d_hess in the place of d_grad
 SIGNATURES['cp_taylor_jvp'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + _ARRAY + _ARRAY + _WHERE)      # d_tan, K; d_out, ldo
 SIGNATURES['cp_taylor_jvp2'] = (ctypes.c_int, _TAYLOR_HEAD + _RANGE + [ctypes.c_void_p] + _ARRAY + _ARRAY + _WHERE)      # d_tan_u; d_tan_v, K; d_out, ldo
 _GN_TAIL = _ARRAY + _ARRAY + _ARRAY + [ctypes.c_void_p] * 4 + [ctypes.c_longlong]      # d_weights, ldw; d_data, ldd; d_value, ldv; d_fisher, d_grad, d_chi2, d_work, work_doubles
@@ -223,6 +224,7 @@ SIGNATURES['cp_mlp_predict'] =(ctypes.c_int, _MLP_HEAD + [ctypes.c_void_p] + _WH
 SIGNATURES['cp_mlp_predict_columns'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _WHERE)
 SIGNATURES['cp_mlp_jacobian'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _ARRAY + _WHERE)      # d_value, ldv; d_jac, ldj
 SIGNATURES['cp_mlp_vjp'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _ARRAY + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong] + _WHERE)      # d_cot, ldc; d_value, ldv; d_grad, d_work, work_doubles
+SIGNATURES['cp_mlp_vjp2'] = SIGNATURES['cp_mlp_vjp']      # d_hess in the place of d_grad
 SIGNATURES['cp_mlp_jvp'] = (ctypes.c_int, _MLP_HEAD + _RANGE + _ARRAY + _ARRAY + _ARRAY + _WHERE)      # d_tan, K; d_value, ldv; d_out, ldo
 # d_tan_u; d_tan_v, K; d_value, ldv; d_first_u; d_first_v, ldf; d_out, ldo
 SIGNATURES['cp_mlp_jvp2'] = (ctypes.c_int, _MLP_HEAD + _RANGE + [ctypes.c_void_p] + _ARRAY + _ARRAY + [ctypes.c_void_p] + _ARRAY + _ARRAY + _WHERE)
@@ -230,6 +232,8 @@ SIGNATURES['cp_taylor_fit'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, cty
 SIGNATURES['cp_mlp_param_count'] = (ctypes.c_longlong, [ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int])
 SIGNATURES['cp_mlp_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int])
 SIGNATURES['cp_taylor_vjp_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int])
+SIGNATURES['cp_taylor_vjp2_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int])
+SIGNATURES['cp_mlp_vjp2_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int])
 SIGNATURES['cp_mlp_vjp_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, ctypes.c_int, ctypes.c_longlong])
 SIGNATURES['cp_mlp_loss_grad'] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p])

@@ -56,6 +56,10 @@ int check_operands(const char* who, long long ncols, long long ldw, const double
 int check_pointers(const char* who, const double* d_weights, const double* d_data, const double* d_fisher, const double* d_grad, const double* d_chi2,
                    const double* d_work, long long work_doubles, const Plan& plan, const char* sizer);
 void sum_launch(cp::Launches& on, const Plan& plan, const Tail& tail, double* d_fisher, double* d_grad, double* d_chi2);
+// cp_mlp_gauss_newton.hip: mlp_tangent_kernel in its Gauss-Newton variant for the y function, then the summing kernel -- the last two launches of
+// cp_mlp_gauss_newton, for the entry points that contract a Jacobian with weights of their own (cp_mlp_vjp2); the value on the range is tail.value
+void mlp_launch(cp::Launches& on, const double* d_x, const double* d_params, const double* d_xoffset, const double* d_xscale, const double* d_yscale,
+                const cp::MlpLayout& net, int yfunction, const Plan& plan, const Tail& tail, double* d_fisher, double* d_grad, double* d_chi2);
 
 #ifdef __HIPCC__
 // the epilogue of one wave on its 64 x 64 accumulators: this lane's row of sums over the wave's columns colw .. colw + 63 into the wave's F[k][lane]

@@ -38,6 +38,9 @@
 // Second directional derivative (cp_mlp_jvp2: out (B K, .) = u . d^2 predict / d x d x . v along K pairs of directions per point; mlp_forward_kernel, for a
 // y function mlp_tangent_kernel's jvp variant once per tangent set, then mlp_tangent2_kernel of cp_mlp_tangent2.h, which carries h, du, dv and the
 // second-order term through the hidden layers and reads the value and the first-order products in its epilogue).
+// Contracted second derivative (cp_mlp_vjp2: hess (B, ndim, ndim) = sum_c cot d^2 predict / d x d x; the first two launches of cp_mlp_vjp, with a
+// y function mlp_omega_kernel and the Gauss-Newton launches on its signed weights, then mlp_curvature_kernel of cp_mlp_curvature.h, a row per (point,
+// pair i <= j): the output layer is contracted with the cotangent once per point, before the second-order pass).  No (B, ., ncols) array beyond vjp's.
 // Host side.  cp_mlp_predict(_columns), cp_mlp_jacobian, cp_mlp_vjp, cp_mlp_jvp and cp_mlp_jvp2 are back ends of one front: mlp_front holds their common checks and fills the
 // forward kernel's arguments, mlp_yfunction turns the y function into a template argument, mlp_dh_launch picks mlp_dh_kernel<NJ> (vjp and training step);
 // an entry point adds its strides, grid cap, null pointers, workspace and ONE device scope, in that order.
@@ -46,6 +49,7 @@
 // body changed its callers' instructions, and copies of the body had to be kept equal by hand.  The small device functions named above are the only others.
 #include "cp_mlp_tangent.h"      // the tile's constants, MlpNet, mlp_load and mlp_mask, the tangent kernel and its launch
 #include "cp_mlp_tangent2.h"     // the second-order kernel of cp_mlp_jvp2 and its launch
+#include "cp_mlp_curvature.h"    // the contracted second-order kernel of cp_mlp_vjp2
 
 namespace {
 
@@ -665,7 +669,97 @@ void mlp_dh_launch(cp::Launches& on, const double* r, long long ldr, const doubl
     }
 }
 
+// workspace of cp_mlp_vjp2: that of cp_mlp_vjp, then with a y function the Gauss-Newton workspace (its slot for the value first), its result and omega
+struct MlpVjp2Work {
+    cpgn::Plan plan;
+    long long gn, fisher, omega, total;
+};
+
+int mlp_vjp2_work(const char* who, const MlpNet& net, long long B, long long ncols, int yfunction, MlpWork* ws, MlpVjp2Work* w2) {
+    mlp_vjp_work(net, B, ncols, ws);
+    w2->gn = w2->fisher = w2->omega = 0, w2->total = ws->total;
+    if (yfunction == CP_MLP_Y_NONE) return CP_OK;
+    const int status = cpgn::plan(who, B, net.ndim, ncols, &w2->plan);
+    if (status != CP_OK) return status;
+    if ((B * ncols + 255) / 256 > 0x7fffffffLL)      // the grid of mlp_omega_kernel (the plan has capped B and ncols: no overflow)
+        return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %lld cotangents under a y function (at most 2^39)", who, B, ncols);
+    w2->gn = w2->total, w2->total += w2->plan.total;
+    w2->fisher = w2->total, w2->total += B * net.ndim * net.ndim;
+    w2->omega = w2->total, w2->total += B * ncols;
+    return CP_OK;
+}
+
+// rows B npairs of mlp_curvature_kernel against its grid, the column tiles of the forward kernel
+bool mlp_vjp2_fits(long long B, int ndim, long long ncols) {
+    const long long npairs = (long long)ndim * (ndim + 1) / 2;
+    return B <= 0x7fffffffLL * ML_ROWS / npairs && (ncols + ML_COLS - 1) / ML_COLS <= 65535;
+}
+
 }  // namespace
+
+extern "C" long long cp_mlp_vjp2_workspace_doubles(long long B, int ndim, int nlayers, const int* widths, int M, long long ncols, int yfunction) {
+    const char* who = "cp_mlp_vjp2_workspace_doubles";
+    MlpNet net;
+    if (B < 0) return -(long long)cp::fail(CP_EINVAL, "%s: negative count of points", who);
+    const int status = mlp_net(who, ndim, nlayers, widths, nullptr, M, &net);
+    if (status != CP_OK) return -(long long)status;
+    if (yfunction < CP_MLP_Y_NONE || yfunction > CP_MLP_Y_SINH) return -(long long)cp::fail(CP_EINVAL, "%s: y function %d (0 none, 1 10^v, 2 sinh)", who, yfunction);
+    if (ncols < 1 || ncols > M) return -(long long)cp::fail(CP_EINVAL, "%s: %lld columns of %d", who, ncols, M);
+    if (!mlp_vjp2_fits(B, ndim, ncols)) return -(long long)cp::fail(CP_EUNSUPPORTED, "%s: %lld points of %d parameters (at most 2^37 rows B ndim (ndim + 1) / 2)", who, B, ndim);
+    MlpWork ws;
+    MlpVjp2Work w2;
+    const int planned = mlp_vjp2_work(who, net, B, ncols, yfunction, &ws, &w2);
+    return planned == CP_OK ? w2.total : -(long long)planned;
+}
+
+// The launches on the stream: the forward kernel in its vjp mode and mlp_dh_kernel as in cp_mlp_vjp (the value goes to d_value, or with a y function
+// to the workspace if there is none); with a y function mlp_omega_kernel, the tangent kernel's Gauss-Newton variant and gn_sum_kernel on omega; then
+// mlp_curvature_kernel, which adds that sum and is the one writer of d_hess
+extern "C" int cp_mlp_vjp2(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
+                           const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
+                           long long ncols, const double* d_cot, long long ldc, double* d_value, long long ldv, double* d_hess, double* d_work,
+                           long long work_doubles, int device, void* stream) {
+    const char* who = "cp_mlp_vjp2";
+    MlpFwdArgs F{};
+    int status = mlp_front(who, d_x, B, ndim, nlayers, widths, activations, M, d_params, d_xoffset, d_xscale, d_yoffset, d_yscale, yfunction, col0, ncols, &F);
+    if (status != CP_OK) return status;
+    if (ldc < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the cotangent is less than its %lld columns", who, ldc, ncols);
+    if (d_value && ldv < ncols) return cp::fail(CP_EINVAL, "%s: row stride %lld of the value is less than its %lld columns", who, ldv, ncols);
+    if (!mlp_vjp2_fits(B, ndim, ncols))
+        return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d x %d second derivatives of %lld columns (at most 2^37 rows B ndim (ndim + 1) / 2, 2^24 - 256 columns)", who, B, ndim,
+                        ndim, ncols);
+    const MlpNet& N = F.net;
+    MlpVjp2Work w2;
+    status = mlp_vjp2_work(who, N, B, ncols, yfunction, &F.ws, &w2);
+    if (status != CP_OK) return status;
+    if (B == 0) return CP_OK;
+    if (!d_x || !d_params || !d_xoffset || !d_xscale || !d_yoffset || !d_yscale || !d_cot || !d_hess || !d_work) return cp::fail(CP_EINVAL, "%s: null pointer", who);
+    const MlpWork& ws = F.ws;
+    if (work_doubles < w2.total) return cp::fail(CP_EINVAL, "%s: workspace of %lld doubles, %lld needed (cp_mlp_vjp2_workspace_doubles)", who, work_doubles, w2.total);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
+    cp::Launches on(who, stream);
+    const bool curved = yfunction != CP_MLP_Y_NONE;      // the y function's own curvature: omega J J
+    double* const value = d_value || !curved ? d_value : d_work + w2.gn + w2.plan.value;
+    const long long ldvalue = d_value ? ldv : ncols;
+    F.cot = d_cot, F.out = value, F.work = d_work, F.ldo = ldvalue, F.ldc = ldc;
+    const int launched = mlp_yfunction(yfunction, [&](auto y) { return mlp_forward_launch<ML_VJP + decltype(y)::value>(on, F); });
+    if (launched != CP_OK) return launched;
+    mlp_dh_launch(on, d_work + ws.resid, ncols, d_params + N.off[N.L] + col0, M, B, N.d[N.L], (int)ncols, ws, d_work + ws.part);
+    if (curved) {
+        double* const omega = d_work + w2.omega;
+        const unsigned nblocks = (unsigned)((B * ncols + 255) / 256);      // (checked by mlp_vjp2_work)
+        if (yfunction == CP_MLP_Y_EXP10) on.run<mlp_omega_kernel<CP_MLP_Y_EXP10>>(nblocks, 256, 0, d_cot, ldc, value, ldvalue, B, ncols, omega);
+        else on.run<mlp_omega_kernel<CP_MLP_Y_SINH>>(nblocks, 256, 0, d_cot, ldc, value, ldvalue, B, ncols, omega);
+        const cpgn::Tail tail{omega, nullptr, value, d_work + w2.gn + w2.plan.part, ncols, 0, ldvalue, B, ndim, w2.plan.P, (int)col0, (int)(col0 + ncols)};
+        cpgn::mlp_launch(on, d_x, d_params, d_xoffset, d_xscale, d_yscale, N, yfunction, w2.plan, tail, d_work + w2.fisher, nullptr, nullptr);
+    }
+    const int npairs = ndim * (ndim + 1) / 2;
+    const long long R = B * npairs;
+    const MlpCurvArgs C{d_x, d_params, d_xoffset, d_xscale, d_work + ws.part, curved ? d_work + w2.fisher : nullptr, d_hess, B, R, npairs, ws.nsl, N};
+    on.run<mlp_curvature_kernel>((unsigned)((R + ML_ROWS - 1) / ML_ROWS), 64 * ML_CW, (size_t)4 * N.nr * ML_PS * sizeof(double), C);
+    return on.status();
+}
 
 // For cp_mlp_gauss_newton (cp_mlp_gauss_newton.hip; declared in cp_internal.h): the checks of mlp_front under its name with the network's layout, and the
 // forward kernel on a range of columns among its launches -- what cp_mlp_predict_columns launches, so the value it writes has those bits.

@@ -16,6 +16,8 @@
 // the front end of the fit -- both operands are then contiguous as that front end wants them, the left one (cot, row stride lda) along the contraction
 // and the right one, rows [col0, col0 + ncols) of a TRANSPOSED copy (M, T) of the derivatives that the caller keeps, along the terms -- and
 // taylor_input_grad_kernel contracts S with the derivatives of the monomials, which it forms as the jacobian front end does.  No (B, ndim, .) array exists.
+// Contracted second derivative (cp_taylor_vjp2: hess (B, ndim, ndim) = sum_c cot d^2 predict / d x d x).  The S GEMM of cp_taylor_vjp, then
+// taylor_curvature_kernel contracts S with the second derivatives of the monomials, a row per (point, pair i <= j), and writes both mirror entries.
 #include "cp_taylor_gemm.h"
 
 namespace {
@@ -99,6 +101,92 @@ __global__ __launch_bounds__(256) void taylor_input_grad_kernel(const double* x,
         __syncthreads();
     }
     if (wave == 0 && r < R) grad[r] = g;
+}
+
+// hess[b][i][j] = hess[b][j][i] = sum_t S[b][t] d^2 mono_t / d x_i d x_j for cp_taylor_vjp2: a row per (point, pair i <= j), r = b npairs + p over the pairs in
+// the order (0, 0), (0, 1), ..., (1, 1), ...; 64 rows per workgroup, a row per lane of each of its four waves, the chunks, the two buffers, the flags and
+// the summing wave of taylor_input_grad_kernel.  The second derivative of a monomial as the jvp2 front end of the GEMM forms its pair terms: the product
+// over the parameters of power p > 0 IN THEIR ORDER of p (p - 1) d^(p - 2) (the parameter is i = j), p d^(p - 1) (it is i or j) or d^p, a power formed by
+// repeated multiplication and a factor whose exponent is 0 its coefficient alone (the powers wave-uniform, the lane's pair a select; factors of power 0
+// skipped).  A term without a factor of x_i or of x_j, or with p < 2 on the diagonal, is flagged and SKIPPED, not added as 0 x S: neither a NaN under
+// power 0 nor a NaN of S in such a term reaches the result; an expansion of order 1 gives exactly 0.
+// LDS: 2 x 32 x 64 x 8 + ndim x 64 x 8 + 2 x 4 x 64 x 4 bytes, at most 50 KB.
+__global__ __launch_bounds__(256) void taylor_curvature_kernel(const double* x, const double* center, const int* powers, const double* S, const long long R,
+                                                               const int ndim, const int npairs, const int T, double* hess) {
+    extern __shared__ double ty_lds[];
+    double* const mbuf = ty_lds;                                                   // 2 x TY_KC x 64
+    double* const dl = ty_lds + 2 * TY_KC * TY_ROWS;                               // (ndim, 64) x - center of the point of each row
+    unsigned* const skip = reinterpret_cast<unsigned*>(dl + ndim * TY_ROWS);       // 2 x 4 x 64: bit q of [wave][row] for the term tt = wave + 4 q
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * TY_ROWS + lane;
+    const long long point = (r < R ? r : R - 1) / npairs;      // rows past the end repeat the last one (never stored)
+    int pi = 0, pj = (int)((r < R ? r : R - 1) - point * npairs);
+    for (int n = ndim; pj >= n; --n) pj -= n, ++pi;      // parameter i holds the n = ndim - i pairs (i, i) .. (i, ndim - 1)
+    pj += pi;
+    for (int i = wave; i < ndim; i += 4) dl[i * TY_ROWS + lane] = x[point * ndim + i] - center[i];
+    __syncthreads();
+    const double* Sr = S + point * T;
+    const int nchunk = (T + TY_KC - 1) / TY_KC;
+    double g = 0.;
+#pragma unroll 1
+    for (int c = -1; c < nchunk; ++c) {
+        if (c + 1 < nchunk) {      // this wave's terms of chunk c + 1
+            double* const buf = mbuf + ((c + 1) & 1) * TY_KC * TY_ROWS;
+            unsigned flags = 0;
+#pragma unroll 1
+            for (int q = 0; q < TY_KC / 4; ++q) {
+                const int tt = wave + 4 * q, t = (c + 1) * TY_KC + tt;
+                double m = 0.;
+                bool zero = true;      // terms past T
+                if (t < T) {
+                    m = 1., zero = false;
+                    const int* pw = powers + (long long)t * ndim;
+                    for (int i0 = 0; i0 < ndim; i0 += 4) {      // four powers requested at a time (scalar loads: one wait for the four, not one each)
+                        int p4[4];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) p4[k] = __builtin_amdgcn_readfirstlane(pw[i0 + k < ndim ? i0 + k : ndim - 1]);
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const int i = i0 + k;
+                            int p = i < ndim ? p4[k] : 0;      // (past the last parameter: a factor of power 0 of nobody's parameter)
+                            const int times = (pi == i) + (pj == i);      // how often this lane differentiates the factor
+                            if (p <= 0) {
+                                zero = zero || times > 0;
+                                continue;
+                            }
+                            p = p < TY_MAX_POWER ? p : TY_MAX_POWER;
+                            zero = zero || times > p;
+                            const double d = dl[i * TY_ROWS + lane];
+                            double v2 = 1., v1 = 1., v0 = d;      // d^(p - 2), d^(p - 1), d^p; an exponent of 0 (or less) is 1: the coefficient alone
+                            for (int e = 2; e <= p; ++e) v2 = v1, v1 = v0, v0 *= d;
+                            m *= times == 0 ? v0 : times == 1 ? (double)p * v1 : (double)(p * (p - 1)) * v2;
+                        }
+                    }
+                }
+                buf[tt * TY_ROWS + lane] = m;
+                flags |= zero ? 1u << q : 0u;
+            }
+            skip[(((c + 1) & 1) * 4 + wave) * TY_ROWS + lane] = flags;
+        }
+        if (c >= 0 && wave == 0) {      // chunk c, formed before the last barrier, in term order
+            const double* const buf = mbuf + (c & 1) * TY_KC * TY_ROWS;
+            unsigned flags[4];
+#pragma unroll
+            for (int w = 0; w < 4; ++w) flags[w] = skip[((c & 1) * 4 + w) * TY_ROWS + lane];
+            const int t0 = c * TY_KC, n = T - t0 < TY_KC ? T - t0 : TY_KC;
+            for (int tt = 0; tt < n; ++tt) {
+                const double m = buf[tt * TY_ROWS + lane], s = Sr[t0 + tt];
+                const bool zero = (flags[tt & 3] >> (tt >> 2)) & 1u;
+                g = zero ? g : fma(s, m, g);
+            }
+        }
+        __syncthreads();
+    }
+    if (wave == 0 && r < R) {
+        double* const hb = hess + point * ndim * ndim;
+        hb[pi * ndim + pj] = g;
+        hb[pj * ndim + pi] = g;
+    }
 }
 
 // The GEMM among the launches of the entry point that calls it: its grid's check; the launch status is the entry point's to read
@@ -250,6 +338,39 @@ extern "C" int cp_taylor_vjp(const double* d_x, long long B, const double* d_cen
     const long long R = B * ndim;
     on.run<taylor_input_grad_kernel>((unsigned)((R + TY_ROWS - 1) / TY_ROWS), 256, (size_t)(2 * TY_KC + ndim) * TY_ROWS * sizeof(double) + 2 * 4 * TY_ROWS * sizeof(unsigned),
                                      d_x, d_center, d_powers, d_work, R, ndim, T, d_grad);
+    return on.status();
+}
+
+extern "C" long long cp_taylor_vjp2_workspace_doubles(long long B, int T) {
+    if (B < 0 || T < 1) return -(long long)cp::fail(CP_EINVAL, "cp_taylor_vjp2_workspace_doubles: need T >= 1 and a non-negative count of points");
+    if (B > 0x7fffffffLL * TY_ROWS / (TY_MAX_NDIM * (TY_MAX_NDIM + 1) / 2))
+        return -(long long)cp::fail(CP_EUNSUPPORTED, "cp_taylor_vjp2_workspace_doubles: %lld points (at most 2^28)", B);
+    return B * T;
+}
+
+// Two launches: the S GEMM of cp_taylor_vjp, then taylor_curvature_kernel on the B ndim (ndim + 1) / 2 rows (b, i <= j)
+extern "C" int cp_taylor_vjp2(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
+                              const double* d_derivatives_t, int M, long long col0, long long ncols, const double* d_cot, long long ldc, double* d_hess,
+                              double* d_work, long long work_doubles, int device, void* stream) {
+    const char* who = "cp_taylor_vjp2";
+    const int status = taylor_front(who, B, ndim, T, max_power, M, col0, ncols, ldc, "cotangent");
+    if (status != CP_OK) return status;
+    const int npairs = ndim * (ndim + 1) / 2;
+    if (B > 0x7fffffffLL * TY_ROWS / npairs || (T + TY_COLS - 1) / TY_COLS > 65535)
+        return cp::fail(CP_EUNSUPPORTED, "%s: %lld x %d x %d second derivatives of %d terms (at most 2^37 rows B ndim (ndim + 1) / 2, 2^24 - 256 terms)", who, B, ndim, ndim, T);
+    if (B == 0) return CP_OK;
+    if (!d_x || !d_center || !d_powers || !d_derivatives_t || !d_cot || !d_hess || !d_work) return cp::fail(CP_EINVAL, "%s: null pointer", who);
+    if (work_doubles < B * T) return cp::fail(CP_EINVAL, "%s: workspace of %lld doubles, %lld needed (cp_taylor_vjp2_workspace_doubles)", who, work_doubles, B * T);
+    cp::DeviceScope scope(device);
+    if (!scope.ok()) return cp::fail(CP_EDEVICE, "%s: cannot select device %d", who, device);
+    // S (B, T) = cot (B, ncols) . Dt[col0 : col0 + ncols] (ncols, T)
+    const TaylorArgs A{d_cot, nullptr, nullptr, d_derivatives_t + col0 * T, d_work, B, T, (int)ncols, T, 0, 0, T, ldc};
+    cp::Launches on(who, stream);
+    const int launched = taylor_launch<TY_FIT>(on, A);
+    if (launched != CP_OK) return launched;
+    const long long R = B * npairs;
+    on.run<taylor_curvature_kernel>((unsigned)((R + TY_ROWS - 1) / TY_ROWS), 256, (size_t)(2 * TY_KC + ndim) * TY_ROWS * sizeof(double) + 2 * 4 * TY_ROWS * sizeof(unsigned),
+                                    d_x, d_center, d_powers, d_work, R, ndim, npairs, T, d_hess);
     return on.status();
 }
 

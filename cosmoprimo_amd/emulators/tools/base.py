@@ -6,7 +6,7 @@ by output key for B parameter points at once.
 One front, four back ends.  The four methods share one plan (``Emulator._plan``: the keys asked for -> the maximal contiguous runs of columns of
 :func:`column_runs`, the ``(key, shape, lo, hi)`` entries each run holds, the fixed outputs to return) and one split (``_split``: a run's buffer ->
 ``{key: view}``); each is then one call of the engine per run and nothing else.  What ``Emulator`` uses of an engine: ``name``, ``device``, ``_dev``
-(for its device), and ``predict`` / ``jacobian`` / ``vjp`` / ``jvp`` with ``columns=`` / ``return_value=``.
+(for its device), and ``predict`` / ``jacobian`` / ``vjp`` / ``vjp2`` / ``jvp`` with ``columns=`` / ``return_value=``.
 
 The helpers that both engines' ``predict`` / ``jacobian`` / ``vjp`` open with (``_columns``, ``_cotangent``, ``_tangent``, ``_operand``, ``_gauss_newton``, ``_empty``) live here as well; the engines
 import this module, which imports them only where it builds one.  Nothing on the path of a call imports anything: at B = 1 a call is its Python.
@@ -500,6 +500,46 @@ class Emulator(object):
         values.update(fixed)
         return values, grads
 
+    def vjp2(self, params, cotangents, device=False, return_value=False):
+        """Second derivatives of the varied outputs contracted with cotangents: the Hessian with respect to the parameters of ``sum cotangent * output`` at
+        fixed cotangents, for every point of a batch -- the second-order part of what ``jax.hessian`` of a scalar function of the reference's ``predict``
+        gives (with ``cotangents = w (data - y)`` the residual-curvature term of the Hessian of chi2, :meth:`chi2_hessian`).  ``params`` and ``cotangents``
+        as in :meth:`vjp`: ``{varied key: array or tensor}``, each broadcastable to ``(B,) + shape`` of that output; a fixed key contributes nothing, an
+        unknown key raises ``KeyError``, an empty dictionary gives zeros.
+
+        Returns ``(B, ndim, ndim)`` in the order of ``Emulator.params`` (no leading axis if every parameter is a scalar),
+        ``sum over keys and entries of cotangent * d^2 output / d parameter_i d parameter_j``, symmetric bit for bit.  Computed on the device
+        (:meth:`MLPEmulatorEngine.vjp2`, :meth:`TaylorEmulatorEngine.vjp2`) without forming any second derivative of an output: the columns are planned by
+        :func:`column_runs` over the cotangents' varied keys, one call of the engine per maximal contiguous run on that range only, the runs' matrices
+        added in run order.  Host array by default; ``device=True``: a torch tensor, and no synchronisation with the device.  ``return_value=True``:
+        ``(values, matrices)``, ``values`` what ``predict(params, device=device, keys=list(cotangents))`` returns."""
+        X, B, scalar = self._points(params)
+        torch = dv.torch()
+        runs, fixed = self._plan(list(cotangents), exact=True)
+        dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, *cotangents.values())
+        total, values = None, {}
+        for start, stop, entries in runs:
+            blocks = [torch.broadcast_to(dv.to_device(cotangents[key], dev, cache=False).to(torch.float64), (B,) + shape).reshape(B, hi - lo)
+                      for key, shape, lo, hi in entries if hi > lo]
+            out = self.engine.vjp2(X, blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1), columns=(start, stop), return_value=return_value)
+            value, hess = out if return_value else (None, out)
+            total = hess if total is None else total + hess
+            if return_value:
+                values.update(_split(value if device else dv.to_host(value), (B,), entries, start, scalar))
+        if total is None:
+            total = torch.zeros((B, len(self.params), len(self.params)), dtype=torch.float64, device=dev)
+        if not device:
+            total = dv.to_host(total)
+        total = total[0] if scalar else total
+        if not return_value:
+            return total
+        for key in self.varied_keys:      # empty outputs hold no column and join no run
+            if key in cotangents and key not in values:
+                values[key] = self.predict(params, device=device, keys=[key])[key]
+        values = {key: values[key] for key in self.varied_keys if key in values}      # predict's order: the calculator's, then the fixed outputs
+        values.update(fixed)
+        return values, total
+
     def _directions(self, tangents, B):
         """(T (B, ndim) or (B, K, ndim) float64, K or None) of ``tangents = {parameter name: value}``, a host array unless a tangent is a device tensor: a
         value of dimension <= 1 broadcasts against (B,) and is one direction, one of dimension 2 is (B or 1, K); a missing name is a zero component."""
@@ -772,6 +812,50 @@ class Emulator(object):
         values = {key: values[key] for key in self.varied_keys if key in values}      # predict's order: the calculator's, then the fixed outputs
         values.update(fixed)
         return (values,) + (toret if isinstance(toret, tuple) else (toret,))
+
+    def chi2_hessian(self, params, weights, data, device=False, precision=None, return_value=False):
+        """The full half Hessian of chi2 of a weighted least-squares fit of ``data`` to the emulated outputs, for every point of a batch:
+        ``(hessian, gradient, chi2)`` with ``gradient`` and ``chi2`` those of ``gauss_newton(params, weights, data=data, precision=precision)``, bit for
+        bit, and ``hessian = fisher - vjp2(q)`` (B, ndim, ndim) ``= 1/2 d^2 chi2 / d theta d theta``: the Gauss-Newton half Hessian minus the
+        residual-curvature term ``sum_c q_c d^2 y_c``, so that ``d gradient_i / d theta_j = -hessian_ij`` -- what ``jax.hessian`` of the reference's
+        ``1/2 chi2(predict(theta))`` gives, for Newton steps, Laplace approximations and Riemannian samplers where the residuals are not small.
+        ``params``, ``weights``, ``data``, ``precision`` and their argument rules as in :meth:`gauss_newton`.  One :meth:`gauss_newton` call gives the value,
+        the Fisher matrix, the gradient and chi2; the cotangent is formed on the device: with diagonal weights ``q = w (data - y)``, exactly 0 where
+        ``w == 0`` (a select: NaN data under a zero weight stay masked); with ``precision`` ``q = (data - y) P``, the columns with ``P[c, c] == 0``
+        dropped as :func:`gauss_newton_dense` drops them; then one :meth:`vjp2` call.  Host arrays by default (no leading axis if every parameter is a
+        scalar); ``device=True``: torch tensors, and no synchronisation with the device.  ``return_value=True``: the values are prepended."""
+        torch = dv.torch()
+        values, fisher, gradient, chi2 = self.gauss_newton(params, weights, data=data, device=True, return_value=True, precision=precision)
+        X, B, scalar = self._points(params)
+        dev = fisher.device
+        sizes = dict(zip(self.varied_keys, self.varied_shapes))
+        block = lambda operand, key: torch.broadcast_to(dv.to_device(operand, dev, cache=False).to(torch.float64), (B,) + sizes[key])      # noqa: E731
+        if precision is None:
+            cotangents = {}
+            for key in weights:
+                if key not in sizes:      # a fixed output: its derivatives are zero
+                    continue
+                w = block(weights[key], key)
+                cotangents[key] = torch.where(w == 0., torch.zeros_like(w), w * (block(data[key], key) - values[key].reshape((B,) + sizes[key])))
+        else:
+            runs, N, precision, dblock = self._staged_dense(weights, precision, data, B, dev)
+            cotangents = {}
+            if N:
+                vblock = torch.cat([values[key].reshape(B, hi - lo) for start, stop, entries, q0 in runs for key, shape, lo, hi in entries], dim=1)
+                dropped = torch.diagonal(precision) == 0.
+                r = dblock - vblock
+                r = torch.where(dropped, torch.zeros_like(r), r)
+                q = r @ precision
+                q = torch.where(dropped, torch.zeros_like(q), q)
+                for start, stop, entries, q0 in runs:
+                    for key, shape, lo, hi in entries:
+                        cotangents[key] = q[:, q0 + lo - start:q0 + hi - start].reshape((B,) + shape)
+        hessian = fisher - self.vjp2(params, cotangents, device=True)
+        host = (lambda tensor: tensor) if device else (lambda tensor: dv.to_host(tensor) if dv.is_torch(tensor) else tensor)      # noqa: E731
+        toret = (host(hessian), {name: host(g) for name, g in gradient.items()}, host(chi2))
+        if return_value:
+            toret = ({key: host(value) for key, value in values.items()},) + toret
+        return toret
 
     def least_squares(self, params, weights, data, bounds=None, niterations=20, lambda0=1e-3, lambda_up=10., lambda_down=0.1, lambda_min=1e-12, lambda_max=1e12,
                       ftol=1e-8, device=False, precision=None, geodesic=False, alpha=0.75):

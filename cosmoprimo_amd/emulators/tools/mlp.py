@@ -409,6 +409,28 @@ class MLPEmulatorEngine(object):
                                   *where))
         return (value, grad) if return_value else grad
 
+    def vjp2(self, X, cotangent, columns=None, return_value=False):
+        """Second derivatives of :meth:`predict` contracted with a cotangent at the points ``X`` (B, ndim): device tensor ``C`` (B, ndim, ndim),
+        ``C[b, i, j] = sum_c cotangent[b, c] d^2 predict(X)[b, c] / d X[b, i] d X[b, j]``, symmetric bit for bit -- with ``cotangent = w (data - predict)``
+        the residual-curvature term of the Hessian of chi2 (``cp_mlp_vjp2``: the output layer is contracted with the cotangent once per point as in
+        :meth:`vjp`, then second-order forward mode with a row per (point, pair i <= j) ends in a dot product over the last hidden layer; with a
+        y function its own curvature is a Gauss-Newton contraction with signed weights; no (B, ndim (ndim + 1) / 2, M) array anywhere).  ``cotangent``,
+        ``columns`` and ``return_value`` as in :meth:`vjp`.  Nothing is read back and the call does not wait for the device."""
+        d, X, B, head, where = self._enter(X)
+        net = d['net']
+        start, ncols = _columns(columns, net['M'])
+        width = max(ncols, 0)
+        cotangent, ldc = _cotangent(cotangent, B, width, d['device'])
+        lib = _lib.load()
+        need = int(lib.cp_mlp_vjp2_workspace_doubles(B, net['ndim'], net['L'], net['widths'], net['M'], width, d['yfunction']))
+        if need < 0:
+            _lib.check(-need)
+        work, hess = _empty(d, need), _empty(d, B, net['ndim'], net['ndim'])
+        value = _empty(d, B, width) if return_value else None
+        _lib.check(lib.cp_mlp_vjp2(*head, start, ncols, cotangent.data_ptr(), ldc, value.data_ptr() if return_value else None, width, hess.data_ptr(), work.data_ptr(), need,
+                                   *where))
+        return (value, hess) if return_value else hess
+
     def jvp(self, X, tangents, columns=None, return_value=False):
         """Jacobian-vector product of :meth:`predict` at the points ``X`` (B, ndim) along ``tangents`` (B, ndim) -- device tensor (B, M),
         ``out[b, c] = sum_i tangents[b, i] d predict(X)[b, c] / d X[b, i]`` -- or (B, K, ndim), K directions per point -- (B, K, M) --, a device tensor or

@@ -214,6 +214,23 @@ class TaylorEmulatorEngine(object):
         _lib.check(lib.cp_taylor_vjp(*head, start, ncols, cotangent.data_ptr(), ldc, grad.data_ptr(), work.data_ptr(), need, *where))
         return (self.predict(X, columns=columns), grad) if return_value else grad
 
+    def vjp2(self, X, cotangent, columns=None, return_value=False):
+        """Second derivatives of :meth:`predict` contracted with a cotangent at the points ``X`` (B, ndim): device tensor ``C`` (B, ndim, ndim),
+        ``C[b, i, j] = sum_c cotangent[b, c] d^2 predict(X)[b, c] / d X[b, i] d X[b, j]``, symmetric bit for bit (``cp_taylor_vjp2``: the first GEMM of
+        :meth:`vjp`, (B, T), then its contraction with the second derivatives of the monomials, a row per (point, pair i <= j); no
+        (B, ndim (ndim + 1) / 2, M) array anywhere).  ``cotangent``, ``columns`` and ``return_value`` as in :meth:`vjp`.  Nothing is read back and the
+        call does not wait for the device."""
+        d, X, (B, ndim, T, M), head, where = self._enter(X, derivatives='derivatives_t')
+        start, ncols = _columns(columns, M)
+        cotangent, ldc = _cotangent(cotangent, B, max(ncols, 0), d['device'])
+        lib = _lib.load()
+        need = int(lib.cp_taylor_vjp2_workspace_doubles(B, T))
+        if need < 0:
+            _lib.check(-need)
+        work, hess = _empty(d, need), _empty(d, B, ndim, ndim)
+        _lib.check(lib.cp_taylor_vjp2(*head, start, ncols, cotangent.data_ptr(), ldc, hess.data_ptr(), work.data_ptr(), need, *where))
+        return (self.predict(X, columns=columns), hess) if return_value else hess
+
     def jvp(self, X, tangents, columns=None, return_value=False):
         """Jacobian-vector product of :meth:`predict` at the points ``X`` (B, ndim) along ``tangents`` (B, ndim) -- device tensor (B, M),
         ``out[b, c] = sum_i tangents[b, i] d predict(X)[b, c] / d X[b, i]`` -- or (B, K, ndim), K directions per point -- (B, K, M) --, a device tensor or

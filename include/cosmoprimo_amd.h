@@ -670,6 +670,15 @@ int cp_spline_tables_apply_f32(const double* d_xk, const double* d_coef, const i
  *   in their order, the derivatives of the monomials formed as in jacobian.  A term with p_ti = 0 is skipped (not added as 0): a NaN or Inf in a
  *   parameter that only ever has power 0 leaves G finite.  No atomics: two calls give the same bits.  The argument checks are those of jacobian, plus
  *   ldc and the workspace, before any device call; B = 0: CP_OK.
+ * vjp2 : the second derivatives of predict_columns contracted with a cotangent, d_hess (B, ndim, ndim) contiguous, d_hess[b][i][j] = sum_c d_cot[b][c]
+ *   d^2 out[b][col0 + c] / d x[b][i] d x[b][j] (what jax.hessian of a scalar of the reference's predict needs: the residual-curvature term of the Hessian
+ *   of chi2), without any (B, ., ncols) array.  The arguments of vjp with d_hess in the place of d_grad; d_work: work_doubles >=
+ *   cp_taylor_vjp2_workspace_doubles(B, T) = B T.  Two launches: the S GEMM of vjp, then d_hess[b][i][j] = sum_t S[b][t] d^2 mono_t / d x_i d x_j over the
+ *   terms in their order, a row per (point, pair i <= j), the second derivatives of the monomials formed as the pair terms of jvp2.  One triangle is
+ *   computed and mirrored: symmetric bit for bit.  A term with p_ti = 0 or p_tj = 0, or with p_ti < 2 on the diagonal, is skipped (not added as 0): an
+ *   expansion of order 1 gives exactly 0, and a NaN or Inf in a parameter that only ever has power 0 leaves the result finite.  No atomics: two calls
+ *   give the same bits.  A NaN in row b of d_cot makes point b's matrix NaN and touches no other point.  The argument checks are those of vjp, in its
+ *   order, before any device call; more than 2^37 rows B ndim (ndim + 1) / 2: CP_EUNSUPPORTED; B = 0: CP_OK.
  * jvp : the Jacobian-vector product of predict_columns along K >= 1 directions per point (what jax.jvp / jax.linearize of the reference's predict give),
  *   without any (B, ndim, .) array.  d_tan (B, K, ndim) contiguous, raw-parameter units; d_out (B K, ncols) with row stride ldo >= ncols, row b K + k =
  *   sum_i d_tan[b][k][i] d out[b][col0 ..] / d x[b][i].  One launch: the GEMM with the left-operand entry sum_i tan_i p_ti (x_i - c_i)^(p_ti - 1)
@@ -707,6 +716,10 @@ int cp_taylor_jvp(const double* d_x, long long B, const double* d_center, const 
 int cp_taylor_jvp2(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                    const double* d_derivatives, int M, long long col0, long long ncols, const double* d_tan_u, const double* d_tan_v, long long K, double* d_out,
                    long long ldo, int device, void* stream);
+long long cp_taylor_vjp2_workspace_doubles(long long B, int T);
+int cp_taylor_vjp2(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
+                   const double* d_derivatives_t, int M, long long col0, long long ncols, const double* d_cot, long long ldc, double* d_hess, double* d_work,
+                   long long work_doubles, int device, void* stream);
 long long cp_taylor_gauss_newton_workspace_doubles(long long B, int ndim, int T, int M, long long ncols);
 int cp_taylor_gauss_newton(const double* d_x, long long B, const double* d_center, const int* d_powers, int ndim, int T, int max_power,
                            const double* d_derivatives, int M, long long col0, long long ncols, const double* d_weights, long long ldw, const double* d_data,
@@ -743,6 +756,19 @@ int cp_taylor_gauss_newton(const double* d_x, long long B, const double* d_cente
  *   in slices of the columns; one kernel sums the slices in their order and walks the hidden layers back in LDS (dz = dh act'(z), dh = dz . kernel^T;
  *   relu: act' = 0 at z <= 0), ending with / d_xscale[i].  No atomics: two calls give the same bits.  A NaN in row b of d_x or of d_cot makes row b of
  *   d_grad NaN and touches no other row.  The argument checks are those of jacobian, plus ldc and the workspace, before any device call; B = 0: CP_OK.
+ * vjp2 : the second derivatives of predict_columns contracted with a cotangent, d_hess (B, ndim, ndim) contiguous, d_hess[b][i][j] = sum_c d_cot[b][c]
+ *   d^2 value[b][c] / d x[b][i] d x[b][j] in raw-parameter units (what jax.hessian of a scalar of the reference's predict needs: with d_cot = w (data - value)
+ *   the residual-curvature term of the Hessian of chi2), without any (B, ., ncols) array beyond the weighted cotangent of vjp.  The arguments of vjp with
+ *   d_hess in the place of d_grad; d_work: work_doubles >= cp_mlp_vjp2_workspace_doubles(B, ..., ncols, yfunction) (minus the status on an error).  The
+ *   output layer is linear without bias, so it is contracted with the cotangent once per point, before the second-order pass: the forward kernel and
+ *   dh = w . kernel_out[:, col0 ..]^T of vjp; then a row per (point, pair i <= j) carries (h, du, dv, d2) through the hidden layers as jvp2 does, from the unit
+ *   tangents e_i / d_xscale[i], e_j / d_xscale[j], and ends with sum_k d2[k] dh[k] in ascending k.  With a y function the term sum_c omega J_i J_j is added,
+ *   omega = d_cot / value for 10^v (0 where value = 0) and d_cot value / (1 + value^2) for sinh: the Gauss-Newton contraction of gauss_newton with these
+ *   signed weights (an omega of exactly 0 drops its column).  One triangle is computed and mirrored, one writer per entry: symmetric bit for bit; no
+ *   atomics: two calls give the same bits; relu without a y function gives exactly 0.  A NaN in row b of d_x or of d_cot makes point b's matrix NaN and
+ *   touches no other point.  d_value as in vjp.  Columns outside the range are never read.  The argument checks are those of vjp, in its order, before any
+ *   device call; more than 2^37 rows B ndim (ndim + 1) / 2, or with a y function the caps of gauss_newton or more than 2^39 cotangents: CP_EUNSUPPORTED;
+ *   B = 0: CP_OK.
  * jvp : the Jacobian-vector product of predict_columns along K >= 1 directions per point by forward mode (what jax.jvp / jax.linearize of the reference's
  *   predict give), without any (B, ndim, .) array.  d_tan (B, K, ndim) contiguous, raw-parameter units; d_value as in jacobian (always written,
  *   predict_columns bit for bit); d_out (B K, ncols) with row stride ldo >= ncols, row b K + k = sum_i d_tan[b][k][i] d value[b][.] / d x[b][i]: the
@@ -800,6 +826,11 @@ int cp_mlp_vjp(const double* d_x, long long B, int ndim, int nlayers, const int*
                const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
                long long ncols, const double* d_cot, long long ldc, double* d_value, long long ldv, double* d_grad, double* d_work, long long work_doubles,
                int device, void* stream);
+long long cp_mlp_vjp2_workspace_doubles(long long B, int ndim, int nlayers, const int* widths, int M, long long ncols, int yfunction);
+int cp_mlp_vjp2(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
+                const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
+                long long ncols, const double* d_cot, long long ldc, double* d_value, long long ldv, double* d_hess, double* d_work, long long work_doubles,
+                int device, void* stream);
 int cp_mlp_jvp(const double* d_x, long long B, int ndim, int nlayers, const int* widths, const int* activations, int M, const double* d_params,
                const double* d_xoffset, const double* d_xscale, const double* d_yoffset, const double* d_yscale, int yfunction, long long col0,
                long long ncols, const double* d_tan, long long K, double* d_value, long long ldv, double* d_out, long long ldo, int device, void* stream);
