@@ -216,6 +216,11 @@ SIGNATURES['cp_lm_step_velocity'] = (ctypes.c_int, [ctypes.c_longlong, ctypes.c_
 # B, ndim; the state x, fisher, grad, lambda, status; lo, hi; velocity, h; alpha; next, naccelerated
 SIGNATURES['cp_lm_accelerate'] = (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int] + [ctypes.c_void_p] * 9 + [ctypes.c_double] + [ctypes.c_void_p] * 2 + _WHERE)
 SIGNATURES['cp_spd_inverse'] = (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int] + [ctypes.c_void_p] * 3 + _WHERE)
+SIGNATURES['cp_hmc_factor'] = (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int] + [ctypes.c_void_p] * 3 + _WHERE)      # B, ndim; metric, factor, status
+# B, ndim, t_close, t_open; the state x, grad, chi2, status, naccepted, nout; the trajectory z, h0, eps, out; the trial xt, grad_t, chi2_t; factor, lo, hi, step;
+# jitter, seed; next, sample, sample_chi2
+SIGNATURES['cp_hmc_step'] = (ctypes.c_int, [ctypes.c_longlong, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong] + [ctypes.c_void_p] * 17 +
+                             [ctypes.c_double, ctypes.c_ulonglong] + [ctypes.c_void_p] * 3 + _WHERE)
 SIGNATURES['cp_gauss_newton_dense_workspace_doubles'] = (ctypes.c_longlong, [ctypes.c_longlong, ctypes.c_int, ctypes.c_longlong])
 # d_jac, ldj; B, ndim, ncols; d_value, ldv; d_data, ldd; d_precision, ldp; d_fisher, d_grad, d_chi2, d_work, work_doubles
 SIGNATURES['cp_gauss_newton_dense'] = (ctypes.c_int, _ARRAY + [ctypes.c_longlong, ctypes.c_int, ctypes.c_longlong] + _ARRAY + _ARRAY + _ARRAY + [ctypes.c_void_p] * 4 +

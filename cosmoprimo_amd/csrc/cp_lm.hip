@@ -21,9 +21,15 @@
 
 #pragma clang fp contract(off)
 
+#include "cp_group_cholesky.h"      // group_value, lm_factor, lm_solve (lm_forward, then lm_backward): shared with cp_hmc.hip
+
 namespace {
 
-constexpr int lm_threads(int G) { return G == 32 ? 128 : 256; }
+using cp::group_value;
+using cp::lm_factor;
+using cp::lm_finite;
+using cp::lm_solve;
+using cp::lm_threads;
 
 struct LmArgs {
     long long B;
@@ -47,8 +53,6 @@ struct LmAccelArgs {
     int* naccelerated;
 };
 
-__device__ __forceinline__ bool lm_finite(double v) { return fabs(v) <= DBL_MAX; }
-
 // a parameter on a bound with the gradient pointing out of the box: held, by cp_lm_step and by cp_lm_accelerate alike
 __device__ __forceinline__ bool lm_on_bound(double x, double g, double lo, double hi) { return (x >= hi && g > 0.) || (x <= lo && g < 0.); }
 
@@ -57,56 +61,6 @@ template <int G>
 __device__ __forceinline__ unsigned lm_held(bool hold, int lane, int i) {
     const unsigned long long all = __ballot(hold);
     return (unsigned)((all >> (lane - i)) & (G == 32 ? 0xffffffffull : (1ull << G) - 1ull));
-}
-
-// the value lane j of this lane's group holds
-template <int G>
-__device__ __forceinline__ double group_value(double v, int j) {
-    return G == 1 ? v : __shfl(v, j, G);
-}
-
-// In place: the group's raw matrix in L (row i, column j at L[i (G + 1) + j]; the triangle j <= i is read) becomes its Cholesky factor.  diag: this
-// lane's diagonal entry as the system takes it; held: the group's held parameters, a bit each.  lii: L[i][i].  Returns 0, or the 1-based column of the
-// first pivot that is not > 0 or not finite (what follows it is then meaningless, and harmless).
-template <int G>
-__device__ __forceinline__ int lm_factor(double* L, const int i, const int n, const unsigned held, const double diag, double& lii) {
-    constexpr int S = G + 1;
-    const bool hi = (held >> i) & 1u;
-    int bad = 0;
-    lii = 1.;
-    for (int j = 0; j < n; ++j) {
-        double t = i == j ? diag : L[i * S + j];
-        if (hi || ((held >> j) & 1u)) t = i == j ? 1. : 0.;
-        for (int k = 0; k < j; ++k) t -= L[i * S + k] * L[j * S + k];
-        const double d = group_value<G>(t, j);
-        if (!bad && !(d > 0. && lm_finite(d))) bad = j + 1;
-        const double r = sqrt(d);
-        if (i == j) lii = r;
-        if (i >= j) L[i * S + j] = i == j ? r : t / r;
-        cp::wave_lds_phase();
-    }
-    return bad;
-}
-
-// z_i of L L^T z = r, r_i this lane's right-hand side with r_k = 0 for k < first; z is valid for i >= first (all of it with first = 0)
-template <int G>
-__device__ __forceinline__ double lm_solve(const double* L, const int i, const int n, const double lii, double r, const int first) {
-    constexpr int S = G + 1;
-    for (int j = first; j < n; ++j) {
-        double q = 0.;
-        if (i == j) q = r / lii;
-        const double y = group_value<G>(q, j);
-        if (i > j) r -= L[i * S + j] * y;
-        else if (i == j) r = y;
-    }
-    for (int j = n - 1; j >= first; --j) {
-        double q = 0.;
-        if (i == j) q = r / lii;
-        const double z = group_value<G>(q, j);
-        if (i < j) r -= L[j * S + i] * z;
-        else if (i == j) r = z;
-    }
-    return r;
 }
 
 template <int G>
@@ -260,17 +214,11 @@ __global__ __launch_bounds__(lm_threads(G)) void spd_inverse_kernel(const long l
     if (fit && i == 0) info[b] = bad;
 }
 
-int lanes_of(int ndim) {
-    int G = 1;
-    while (G < ndim) G *= 2;
-    return G;
-}
-
 // what the entry points check first, in this order; *per_workgroup: fits of a workgroup
 int lm_front(const char* who, long long B, int ndim, int* G, int* per_workgroup) {
     if (B < 0 || ndim < 1) return cp::fail(CP_EINVAL, "%s: %lld fits of %d parameters", who, B, ndim);
     if (ndim > 32) return cp::fail(CP_EUNSUPPORTED, "%s: %d parameters (at most 32)", who, ndim);
-    *G = lanes_of(ndim);
+    *G = cp::lm_lanes_of(ndim);
     *per_workgroup = lm_threads(*G) / *G;
     if (B > 0x7fffffffLL * *per_workgroup)
         return cp::fail(CP_EUNSUPPORTED, "%s: %lld fits of %d parameters (at most 2^31 - 1 workgroups of %d fits)", who, B, ndim, *per_workgroup);

@@ -16,6 +16,9 @@ import this module, which imports them only where it builds one.  Nothing on the
 and ``vjp`` and one more launch, :func:`lm_accelerate`).  Under a dense precision matrix
 (``precision=``) the normal equations come from :func:`gauss_newton_dense`, module-level as well: one GEMM on a Jacobian of any origin, which the engines'
 ``jacobian`` write run by run into one buffer (``out=``).
+
+``Emulator.hmc`` runs batched Hamiltonian Monte Carlo chains on the same evaluations; what stands between two of them is again one launch, :func:`hmc_step`
+(with :func:`hmc_state` and :func:`hmc_factor`: module-level, over device tensors, for gradients of any origin).
 """
 import numpy as np
 
@@ -213,6 +216,106 @@ def spd_inverse(a):
     inv, info = torch.empty_like(a), torch.empty((int(a.shape[0]),), dtype=torch.int32, device=a.device)
     _lib.check(_lib.load().cp_spd_inverse(int(a.shape[0]), int(a.shape[1]), a.data_ptr(), inv.data_ptr(), info.data_ptr(), a.device.index, dv.stream_of(a.device)))
     return inv, info
+
+
+HMC_STATE = ('x', 'gradient', 'chi2', 'status', 'naccepted', 'nout')
+HMC_TRAJECTORY = ('z', 'h0', 'eps', 'out')
+HMC_TRIAL = ('x', 'gradient', 'chi2')
+
+
+def hmc_state(x, gradient, chi2):
+    """The state of B Hamiltonian Monte Carlo chains that start at ``x`` (B, ndim), with ``gradient`` (B, ndim) and ``chi2`` (B,) what ``gauss_newton``
+    returned there (float64 device tensors, copied), as :func:`hmc_step` takes it: nothing accepted yet, no trajectory open (``z``, ``h0``, ``eps``,
+    ``out`` zero), ``status = 0``, and 3 -- by a ``torch.where``, nothing is read back -- where ``chi2`` is not finite: such a chain never moves."""
+    torch = dv.torch()
+    if x.ndim != 2 or tuple(gradient.shape) != tuple(x.shape) or tuple(chi2.shape) != (int(x.shape[0]),):
+        raise ValueError('x and gradient of shape (B, ndim) and chi2 of shape (B,), got {}, {} and {}'.format(tuple(x.shape), tuple(gradient.shape), tuple(chi2.shape)))
+    B, ndim = (int(s) for s in x.shape)
+    new = lambda *shape, **kwargs: torch.zeros(shape, dtype=kwargs.get('dtype', torch.float64), device=x.device)      # noqa: E731
+    chi2 = chi2.to(torch.float64).clone()
+    status = torch.where(torch.isfinite(chi2), new(B, dtype=torch.int32), torch.full((B,), 3, dtype=torch.int32, device=x.device))
+    return {'x': x.to(torch.float64).clone(), 'gradient': gradient.to(torch.float64).clone(), 'chi2': chi2, 'status': status, 'naccepted': new(B, dtype=torch.int32),
+            'nout': new(B, dtype=torch.int32), 'z': new(B, ndim), 'h0': new(B), 'eps': new(B), 'out': new(B, dtype=torch.int32)}
+
+
+def _hmc_step_size(step_size, B, device):
+    """The step sizes of B chains as ``cp_hmc_step`` reads them: a contiguous float64 tensor (B,) on ``device``, from a scalar (a fill on the device) or (B,)."""
+    torch = dv.torch()
+    if not dv.is_torch(step_size) and np.ndim(step_size) == 0:
+        return torch.full((B,), float(step_size), dtype=torch.float64, device=device)
+    step_size = dv.to_device(step_size, device)
+    if step_size.ndim == 0:
+        return step_size.expand(B).contiguous()
+    if tuple(step_size.shape) != (B,):
+        raise ValueError('step_size must be a scalar or of shape ({:d},), got {}'.format(B, tuple(step_size.shape)))
+    return step_size
+
+
+def hmc_factor(metric, status):
+    """The Cholesky factors ``L`` (B, ndim, ndim) of the mass matrices ``metric`` (B, ndim, ndim), a device tensor (its lower triangle is read), in one launch
+    (``cp_hmc_factor``, csrc/cp_hmc.hip): lower triangular, the strict upper triangle zero.  ``status``: (B,) contiguous int32 device tensor (that of
+    :func:`hmc_state`), set in place to 3 where a pivot is not positive and finite -- the chain then never moves -- and left as it is elsewhere."""
+    torch = dv.torch()
+    metric = metric.to(torch.float64).contiguous()
+    if metric.ndim != 3 or metric.shape[1] != metric.shape[2]:
+        raise ValueError('matrices of shape (B, ndim, ndim), got {}'.format(tuple(metric.shape)))
+    B, ndim = int(metric.shape[0]), int(metric.shape[1])
+    if not dv.is_torch(status) or tuple(status.shape) != (B,) or status.dtype != torch.int32 or not status.is_contiguous() or status.device != metric.device:
+        raise ValueError('status must be a contiguous int32 tensor of shape {} on {}'.format((B,), metric.device))
+    factor = torch.empty_like(metric)
+    _lib.check(_lib.load().cp_hmc_factor(B, ndim, metric.data_ptr(), factor.data_ptr(), status.data_ptr(), metric.device.index, dv.stream_of(metric.device)))
+    return factor
+
+
+def hmc_step(state, trial, factor, lo, hi, step_size, t_close=None, t_open=None, jitter=0.1, seed=0, sample=None, sample_chi2=None):
+    """Everything between two ``gauss_newton`` calls of B Hamiltonian Monte Carlo chains of ``exp(-chi2 / 2)`` at once, in one launch (``cp_hmc_step``,
+    csrc/cp_hmc.hip), whatever produced the gradients.  ``state``: contiguous device tensors ``x`` (B, ndim), ``gradient`` (B, ndim), ``chi2`` (B,) float64,
+    ``status``, ``naccepted``, ``nout`` (B,) int32, and the open trajectory: the whitened momentum ``z`` (B, ndim), ``h0``, ``eps`` (B,), ``out`` (B,) int32
+    (:func:`hmc_state`), updated in place.  ``trial``: ``x``, ``gradient``, ``chi2``, what ``gauss_newton`` returned at ``trial['x']``.  ``factor``: what
+    :func:`hmc_factor` returned.  ``lo``, ``hi``: (ndim,), the box.  ``step_size``: a scalar or (B,), in units of the whitened coordinates.
+
+    With neither ``t_close`` nor ``t_open`` the call is a leapfrog step inside a trajectory: a kick by the trial's gradient and a drift.  ``t_close``: the
+    number of the trajectory the call closes (half a kick, then accept or reject against ``-log u`` of that trajectory's stream; ``naccepted`` counts);
+    ``sample`` (B, ndim) and ``sample_chi2`` (B,), contiguous float64 device tensors given together, then take the state.  ``t_open``: the number of the
+    trajectory it opens, after the close where both are given: fresh momenta, ``eps = step_size (1 + jitter (2 u - 1))``, half a kick and a drift.  A drift
+    that leaves the box marks the chain ``out``: it stays where it is until its trajectory closes, which then rejects it (``nout`` counts), so nothing is
+    ever evaluated outside the box.  The random numbers are Philox4x32-10 of ``(seed, chain, trajectory)`` in the kernel: they do not depend on B.
+    A chain with ``status != 0`` is left alone.  Returns ``next`` (B, ndim), the next trial point.  Nothing is read back and the call does not wait for the
+    device."""
+    torch = dv.torch()
+    x = state['x']
+    if x.ndim != 2:
+        raise ValueError('the state holds x of shape (B, ndim), got {}'.format(tuple(x.shape)))
+    B, ndim = (int(s) for s in x.shape)
+    shapes = {'x': (B, ndim), 'gradient': (B, ndim), 'z': (B, ndim)}
+    for name in HMC_STATE + HMC_TRAJECTORY:      # written in place: taken as they are or not at all
+        tensor, integer = state[name], name in ('status', 'naccepted', 'nout', 'out')
+        if tuple(tensor.shape) != shapes.get(name, (B,)) or tensor.dtype != (torch.int32 if integer else torch.float64) or not tensor.is_contiguous() or tensor.device != x.device:
+            raise ValueError('state[{!r}] must be a contiguous {} tensor of shape {} on {}'.format(name, 'int32' if integer else 'float64', shapes.get(name, (B,)), x.device))
+    lo, hi = (dv.to_device(bound, x.device).reshape(-1) for bound in (lo, hi))
+    if int(lo.shape[0]) != ndim or int(hi.shape[0]) != ndim:
+        raise ValueError('lo and hi must be of shape ({:d},)'.format(ndim))
+    read = []
+    for name in HMC_TRIAL:
+        tensor = dv.to_device(trial[name], x.device, cache=False)
+        if tuple(tensor.shape) != shapes.get(name, (B,)):
+            raise ValueError('trial[{!r}] must be of shape {}, got {}'.format(name, shapes.get(name, (B,)), tuple(tensor.shape)))
+        read.append(tensor.to(torch.float64).contiguous())
+    if not dv.is_torch(factor) or tuple(factor.shape) != (B, ndim, ndim) or factor.dtype != torch.float64 or not factor.is_contiguous() or factor.device != x.device:
+        raise ValueError('factor must be a contiguous float64 tensor of shape {} on {}'.format((B, ndim, ndim), x.device))
+    step_size = _hmc_step_size(step_size, B, x.device)
+    if (sample is None) != (sample_chi2 is None):
+        raise ValueError('sample and sample_chi2 are given together')
+    for name, tensor, shape in (('sample', sample, (B, ndim)), ('sample_chi2', sample_chi2, (B,))):
+        if tensor is not None and (not dv.is_torch(tensor) or tuple(tensor.shape) != shape or tensor.dtype != torch.float64 or not tensor.is_contiguous() or tensor.device != x.device):
+            raise ValueError('{} must be a contiguous float64 tensor of shape {} on {}'.format(name, shape, x.device))
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().cp_hmc_step(B, ndim, -1 if t_close is None else int(t_close), -1 if t_open is None else int(t_open),
+                                       *[state[name].data_ptr() for name in HMC_STATE + HMC_TRAJECTORY], *[tensor.data_ptr() for tensor in read], factor.data_ptr(),
+                                       lo.data_ptr(), hi.data_ptr(), step_size.data_ptr(), float(jitter), int(seed) & 0xffffffffffffffff, out.data_ptr(),
+                                       sample.data_ptr() if sample is not None else None, sample_chi2.data_ptr() if sample_chi2 is not None else None,
+                                       x.device.index, dv.stream_of(x.device)))
+    return out
 
 
 def _rows(x, shape, device, what):
@@ -958,6 +1061,102 @@ class Emulator(object):
         info = {name: out[name] for name in ('fisher', 'covariance', 'status', 'naccepted', 'lambda') + (('naccelerated',) if geodesic else ())}
         info['gradient'] = {name: out['gradient'][..., i] for i, name in enumerate(names)}
         return best, out['chi2'], info
+
+    def hmc(self, params, weights, data, nsamples=100, nwarmup=20, thin=1, nleapfrog=6, step_size=0.25, jitter=0.1, metric=None, bounds=None, seed=42, device=False,
+            precision=None):
+        """B independent Hamiltonian Monte Carlo chains of ``exp(-chi2 / 2)`` inside the box, on the device: one :meth:`gauss_newton` evaluation and one
+        launch of :func:`hmc_step` per leapfrog step (kick, drift and box test; at the end of a trajectory also the accept / reject, the sample and the
+        momenta of the next one, drawn by a counter-based generator in the kernel).  Nothing is tested on the host.  ``params``: the start, as
+        :meth:`predict` takes it (scalars or arrays of B values); ``weights``, ``data``, ``precision``, ``bounds``: as :meth:`least_squares` takes them, with
+        the same errors; they are staged once, and the start is clipped to the box.  ``metric``: the mass matrix, (ndim, ndim) or (B, ndim, ndim) in the
+        order of ``Emulator.params`` (e.g. ``least_squares(...)[2]['fisher']``; another shape: ``ValueError``); by default the Fisher matrix
+        :meth:`gauss_newton` returns at the start, per chain.  ``step_size``: a scalar or (B,), in units of the coordinates the metric whitens: 0.25 x 6
+        steps, about pi / 2, is a quarter period of a Gaussian target under its own Fisher metric; every trajectory multiplies it by
+        ``1 + jitter (2 u - 1)``, ``0 <= jitter < 1``.  The run is ``nwarmup + nsamples thin`` trajectories of ``nleapfrog`` steps; the state after every
+        ``thin``-th trajectory past the warm-up is a sample.  A trajectory that leaves the box is rejected (exact for a target that is zero outside it):
+        the chain waits at its last point inside, and the emulator is never evaluated outside the box.  A chain whose start has no finite ``chi2``, whose
+        metric is not positive definite or whose step size is not finite and positive has ``status = 3`` and stays at its start.  The same ``seed`` gives
+        the same bits, whatever B.
+
+        Returns ``(samples, chi2, info)``: ``samples`` ``{parameter name: (nsamples, B)}``, ``chi2`` (nsamples, B) there, ``info`` a dictionary of
+        ``naccepted``, ``nout`` (the trajectories that left the box), ``status`` (B,), ``acceptance`` (``naccepted`` over the number of trajectories),
+        ``metric`` (B, ndim, ndim) and ``step_size`` (B,); no batch axis if every parameter is a scalar.  Host arrays by default; ``device=True``: torch
+        tensors, and no synchronisation with the device anywhere."""
+        X, B, scalar = self._points(params)
+        torch = dv.torch()
+        if data is None:
+            raise ValueError('hmc needs data')
+        nsamples, nwarmup, thin, nleapfrog = int(nsamples), int(nwarmup), int(thin), int(nleapfrog)
+        if nsamples < 1 or nwarmup < 0 or thin < 1 or nleapfrog < 1:
+            raise ValueError('nsamples, thin and nleapfrog must be at least 1 and nwarmup at least 0, got {:d}, {:d}, {:d} and {:d}'.format(nsamples, thin, nleapfrog, nwarmup))
+        jitter = float(jitter)
+        if not (0. <= jitter < 1.):
+            raise ValueError('jitter must be in [0, 1), got {}'.format(jitter))
+        names = list(self.params)
+        ndim = len(names)
+        if metric is not None and tuple(np.shape(metric)) not in ((ndim, ndim), (B, ndim, ndim)):
+            raise ValueError('metric must be of shape {} or {}, got {}'.format((ndim, ndim), (B, ndim, ndim), tuple(np.shape(metric))))
+        if precision is not None:
+            dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, precision)
+            runs, N, precision, dblock = self._staged_dense(weights, precision, data, B, dev)
+            jac, value = (torch.empty(shape, dtype=torch.float64, device=dev) for shape in ((B, ndim, N), (B, N)))
+        else:
+            dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, *weights.values())
+            staged, fixed = self._staged(weights, data, B, dev)
+        limits = dict(self.params)
+        if bounds is not None:
+            unknown = [name for name in bounds if name not in limits]
+            if unknown:
+                raise KeyError('no parameter {}'.format(unknown))
+            limits.update({name: tuple(limit) for name, limit in bounds.items()})
+        lo, hi = (dv.to_device(np.array([limits[name][side] for name in names], dtype='f8'), dev) for side in (0, 1))
+
+        def evaluate(x):
+            """``(fisher, gradient, chi2)`` at ``x`` (B, ndim), as :meth:`least_squares` forms them."""
+            totals = None
+            if precision is not None:
+                totals = self._dense_normal_equations(x, runs, precision, dblock, jac, value)
+            else:
+                for start, stop, entries, wblock, dblock_ in staged:
+                    out = self.engine.gauss_newton(x, wblock, data=dblock_, columns=(start, stop))
+                    totals = out if totals is None else tuple(a + b for a, b in zip(totals, out))
+            if totals is None:
+                totals = (torch.zeros((B, ndim, ndim), dtype=torch.float64, device=dev), torch.zeros((B, ndim), dtype=torch.float64, device=dev),
+                          torch.zeros((B,), dtype=torch.float64, device=dev))
+            return totals
+
+        x = torch.clamp(dv.to_device(X, dev, cache=False), min=lo, max=hi)
+        fisher, gradient, chi2 = evaluate(x)
+        state = hmc_state(x, gradient, chi2)
+        if metric is None:
+            metric = fisher
+        else:
+            metric = dv.to_device(metric, dev)
+            metric = (metric.expand(B, ndim, ndim) if metric.ndim == 2 else metric).contiguous()
+        factor = hmc_factor(metric, state['status'])
+        step = _hmc_step_size(step_size, B, dev)
+        ntrajectories = nwarmup + nsamples * thin
+        samples, samples_chi2 = torch.empty((nsamples, B, ndim), dtype=torch.float64, device=dev), torch.empty((nsamples, B), dtype=torch.float64, device=dev)
+        controls = dict(jitter=jitter, seed=seed)
+        x = hmc_step(state, {name: state[name] for name in HMC_TRIAL}, factor, lo, hi, step, t_open=0, **controls)
+        for t in range(ntrajectories):
+            for leap in range(nleapfrog):
+                trial = dict(zip(HMC_TRIAL, (x,) + tuple(evaluate(x)[1:])))
+                if leap < nleapfrog - 1:
+                    x = hmc_step(state, trial, factor, lo, hi, step, **controls)
+                    continue
+                s, rest = divmod(t - nwarmup + 1, thin)
+                record = t >= nwarmup and rest == 0
+                x = hmc_step(state, trial, factor, lo, hi, step, t_close=t, t_open=t + 1 if t + 1 < ntrajectories else None,
+                             sample=samples[s - 1] if record else None, sample_chi2=samples_chi2[s - 1] if record else None, **controls)
+        out = {'samples': samples, 'chi2': samples_chi2, 'naccepted': state['naccepted'], 'nout': state['nout'], 'status': state['status'],
+               'acceptance': state['naccepted'].to(torch.float64) / ntrajectories, 'metric': metric, 'step_size': step}
+        if not device:
+            out = {name: dv.to_host(value) for name, value in out.items()}
+        if scalar:
+            out = {name: (value[:, 0] if name in ('samples', 'chi2') else value[0]) for name, value in out.items()}
+        samples = {name: out['samples'][..., i] for i, name in enumerate(names)}
+        return samples, out['chi2'], {name: out[name] for name in ('naccepted', 'nout', 'status', 'acceptance', 'metric', 'step_size')}
 
     def to_calculator(self, device=False):
         """Callable ``**params -> dict`` with the contract of ``get_calculator``'s."""

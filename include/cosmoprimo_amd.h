@@ -898,6 +898,46 @@ int cp_lm_accelerate(long long B, int ndim, const double* d_x, const double* d_f
                      int device, void* stream);
 int cp_spd_inverse(long long B, int ndim, const double* d_a, double* d_inv, int* d_info, int device, void* stream);
 
+/* ---- batched Hamiltonian Monte Carlo chains on the gradients of cp_*_gauss_newton (csrc/cp_hmc.hip) ----
+ * B independent chains of exp(-chi2 / 2) inside a box, 1 <= ndim <= 32 parameters; everything on the device, one launch per call, nothing read back, no
+ * atomics (two calls give the same bits; a chain reads and writes nothing of another).  The layout is cp_lm_layout's, a chain for a fit.  The mass
+ * matrix of chain b is metric[b] = L L^T; the momentum is kept whitened (p = L z, kinetic energy z.z / 2), g = -1/2 d chi2 / d theta is gauss_newton's
+ * gradient: a kick is z += e L^-1 g, a drift x += e L^-T z.
+ * cp_hmc_factor : d_factor[b] (ndim, ndim) = the Cholesky factor L of d_metric[b] (the triangle j <= i is read), by the factorisation of cp_lm_step
+ *   (columns in order); the strict upper triangle is written as 0.  d_status[b] (int32) = 3 where a pivot is not > 0 or not finite (d_factor[b] is then
+ *   meaningless), left as it is elsewhere.
+ * cp_hmc_step : everything between two calls of gauss_newton.  State per chain, read and written: d_x (B, ndim), d_grad (B, ndim), d_chi2 (B), d_status,
+ *   d_naccepted, d_nout (B) int32.  Trajectory, read and written: the whitened momentum d_z (B, ndim), d_h0 (B), d_eps (B), d_out (B) int32.  Read only: the
+ *   trial d_xt, d_grad_t, d_chi2_t (what gauss_newton returned at d_xt), d_factor, the box d_lo, d_hi (ndim; +-inf allowed), d_step (B).  Written: d_next
+ *   (B, ndim), the next trial point; d_sample (B, ndim) and d_sample_chi2 (B), null together, where the call closes.  t_close, t_open: the trajectory the
+ *   call closes and the one it opens, < 0 for none.  Per chain, in this order:
+ *   1. status != 0: nothing of the state or the trajectory changes, next = x; if t_close >= 0 and d_sample is given, sample = x, sample_chi2 = chi2.
+ *   2. inner step (t_close < 0 and t_open < 0): out: next = xt.  Else the kick z_i += eps (L^-1 g_t)_i, by forward substitution, then the drift of rule 5
+ *      from xt.
+ *   3. close (t_close >= 0): out: nout += 1, the trial is rejected.  Else z_i += (0.5 eps) (L^-1 g_t)_i; K1 = 0.5 sum_i z_i z_i, i ascending, from 0.;
+ *      H1 = 0.5 chi2_t + K1; e from slot 16 of trajectory t_close; the trial is accepted if and only if chi2_t and H1 are finite and H1 - h0 < e.
+ *      Accepted: x, grad, chi2 take the trial's, naccepted += 1.  Then, if d_sample is given, sample = x, sample_chi2 = chi2.
+ *   4. open (t_open >= 0, after rule 3 where both apply): a step_b that is not finite and > 0: status = 3, next = x.  Else z is drawn from trajectory
+ *      t_open; eps = step_b (1 + jitter (2 u_j - 1)); h0 = 0.5 chi2 + 0.5 sum_i z_i z_i; out = 0; z_i += (0.5 eps) (L^-1 g)_i with the state's gradient;
+ *      the drift of rule 5 from x.  A close without an open: next = x.
+ *   5. drift: v = L^-T z by back substitution, descending; cand_i = base_i + eps v_i; if any cand_i is not finite, < lo_i or > hi_i: out = 1 and
+ *      next = base -- the chain stays where it is until its trajectory closes, so the emulator is never evaluated outside its box --; else next = cand.
+ *   Rejecting a trajectory that leaves the box is exact for a target that is zero outside it.
+ *   Every operation but log, sin, cos and sqrt is a float64 operation rounded once (no FMA contraction).
+ * Random numbers: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85, round r with key + r increment),
+ *   key = (seed low, seed high 32 bits), counter = (b low, b high, t, slot), 0 <= t < 2^32: a chain's stream depends on (seed, b, t) only.  The words
+ *   w0..w3 give u_a = min(((w0 >> 5) 2^26 + (w1 >> 6) + 0.5) 2^-53, 1 - 2^-53) and u_b likewise from w2, w3, strictly inside (0, 1) (the minimum binds
+ *   for the largest 53-bit integer alone, which the rounded sum takes to 2^53).  Slots 0..15: the normals of parameters 2 s and 2 s + 1,
+ *   r = sqrt(-2 log u_a), angle = 6.283185307179586 u_b, r cos(angle) and r sin(angle).  Slot 16: u_j = u_a, e = -log(u_b).
+ * Checks, in this order, before any device call: B < 0 or ndim < 1: CP_EINVAL; ndim > 32: CP_EUNSUPPORTED; more than 2^31 - 1 workgroups of chains:
+ *   CP_EUNSUPPORTED; t_close or t_open >= 2^32: CP_EUNSUPPORTED; B = 0: CP_OK; a null pointer (the two sample pointers may be null together): CP_EINVAL;
+ *   0 <= jitter < 1 and not a NaN: else CP_EINVAL. */
+int cp_hmc_factor(long long B, int ndim, const double* d_metric, double* d_factor, int* d_status, int device, void* stream);
+int cp_hmc_step(long long B, int ndim, long long t_close, long long t_open, double* d_x, double* d_grad, double* d_chi2, int* d_status, int* d_naccepted,
+                int* d_nout, double* d_z, double* d_h0, double* d_eps, int* d_out, const double* d_xt, const double* d_grad_t, const double* d_chi2_t,
+                const double* d_factor, const double* d_lo, const double* d_hi, const double* d_step, double jitter, unsigned long long seed, double* d_next,
+                double* d_sample, double* d_sample_chi2, int device, void* stream);
+
 /* ---- Fisher matrices and normal equations under a dense precision matrix, on an explicit Jacobian (csrc/cp_gauss_newton_dense.hip) ----
  * Per point b: J_b (ndim, ncols) the Jacobian, r_b = data_b - value_b, A_b = [J_b ; r_b] (ndim + 1, ncols), P (ncols, ncols) symmetric, shared by all
  * points, G_b = A_b P A_b^T:  d_fisher[b] (ndim, ndim) = G_b[:ndim, :ndim],  d_grad[b] (ndim) = G_b[:ndim, ndim],  d_chi2[b] = G_b[ndim, ndim].
