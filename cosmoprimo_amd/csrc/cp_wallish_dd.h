@@ -6,10 +6,11 @@
 // The clamped cubic spline through (x = 1 .. n, y) has second derivatives M with  2 M_0 + M_1 = 6 (y_1 - y_0),  M_{i-1} + 4 M_i + M_{i+1} =
 // 6 (y_{i+1} - 2 y_i + y_{i-1}),  M_{n-2} + 2 M_{n-1} = -6 (y_{n-1} - y_{n-2}):  what scipy's CubicSpline(bc_type='clamped')(x, nu=2) returns
 // (bao_filter.py:377-382).  A wave holds a sequence in LDS and runs the elimination itself: lane l owns the knots [S l, S l + S), S = n / 64.
-// The modified diagonal c_i = 1 / (4 - c_{i-1}) does not depend on the data and converges to 2 - sqrt(3) within 40 knots; the forward recurrence
-// d_i = (rhs_i - d_{i-1}) c_i forgets its start at that rate (0.268 per knot), so a lane starts DD_HALO = 32 knots to the left of its own with
-// d = 0 (5e-19 of the starting error is left when it reaches them; the first two lanes start at knot 0 and are exact), and the back
-// substitution M_i = d_i - c_i M_{i+1} the same from the right.  64 + 64 dependent steps per sequence instead of 4096.
+// The modified diagonal c_i = 1 / (4 - c_{i-1}) does not depend on the data and converges to 2 - sqrt(3) by a factor 0.072 per knot: in float64 it is
+// constant from knot 15 on (tests/test_wallish_truth_host.py).  The forward recurrence d_i = (rhs_i - d_{i-1}) c_i forgets its start at 0.268 per knot,
+// so a lane starts DD_HALO = 32 knots to the left of its own with d = 0 (0.268^32 = 5e-19 of the starting error is left when it reaches them; the
+// lanes whose run-in reaches knot 0 are exact), and the back substitution M_i = d_i - c_i M_{i+1} the same from the right:
+// in extended precision the scheme lies 8e-20 of the largest |M| from the solve over all knots.  64 + 64 dependent steps per sequence instead of 4096.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,7 +26,7 @@ constexpr int DD_HALO = 32;
 constexpr int GAP_WINDOW = 64;      // knots on either side of the box from which its end slopes are eliminated (remove_box*; gap_spline_kernel, cp_spline.hip)
 constexpr double DD_CINF = -cpur::P;                     // 2 - sqrt(3)
 constexpr double DD_CLAST = 1. / (2. - DD_CINF);         // the last row has diagonal 2
-constexpr int DD_NTAB = 40;                              // c_i equals its limit to the last bit from knot 30 on
+constexpr int DD_NTAB = 40;                              // c_i equals its last entry to the last bit from knot 15 on (from 1/2; from knot 14 on from 0)
 struct DdTable {
     double c[DD_NTAB];
     constexpr DdTable() : c() {
@@ -198,7 +199,7 @@ __device__ __forceinline__ int dd_dpp(int v) {
     return v;
 #endif
 }
-__device__ __forceinline__ double wave_max(double v) {      // the maximum over the wave, in every lane (no NaN among the values)
+__device__ __forceinline__ double wave_max(double v) {      // the maximum over the wave, in every lane (finite values: masked_argmax)
     v = fmax(v, dd_dpp<0xB1, 0xf>(v));      // quad_perm [1, 0, 3, 2]
     v = fmax(v, dd_dpp<0x4E, 0xf>(v));      // quad_perm [2, 3, 0, 1]
     v = fmax(v, dd_dpp<0x141, 0xf>(v));     // row_half_mirror
@@ -218,8 +219,9 @@ __device__ __forceinline__ int wave_min(int v) {
     return __builtin_amdgcn_readlane(v, 63);
 }
 
-// first index of the maximum of the wave's knots i = own + t with lo <= t < hi (own, lo, hi per lane; the range may be empty in a lane); no NaN among
-// the values.  0 when the range is empty in every lane (as wave_merge returns for it).
+// first index of the maximum of the wave's knots i = own + t with lo <= t < hi (own, lo, hi per lane; the range may be empty in a lane).  The caller
+// sends only sequences whose every value is finite: with a NaN among them fmax would drop it and no equality test would find the maximum; with an
+// infinity the recursion has made a NaN beside it.  0 when the range is empty in every lane (as wave_merge returns for it).
 template <int S>
 __device__ __forceinline__ int masked_argmax(const double* m, int own, int lo, int hi) {
     const double ninf = -__builtin_inf();
@@ -331,7 +333,7 @@ __device__ __forceinline__ bool remove_box(double* buf, const double* gtab, int 
     if (lane == 0) {            // forward sweep up to L: s_L + cpL s_R = dpL
         double cp = 0., dp = i0 == 0 ? 0. : 0.5 * (z(i0 + 1) - z(i0 - 1));      // clamped: s_0 = 0
         if (L != i0) {
-            // (1 / (4 - cp) does not depend on the data: 0, 1/4, 4/15, ... from a table, its limit after 40 knots -- no division in the chain)
+            // (1 / (4 - cp) does not depend on the data: 0, 1/4, 4/15, ... from a table whose last entry stands for every knot beyond it -- no division in the chain)
             double zm = z(i0), z0 = z(i0 + 1);
 #pragma unroll 4
             for (int i = i0 + 1; i < L; ++i) {

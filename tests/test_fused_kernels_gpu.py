@@ -386,7 +386,14 @@ def test_wallish_dd_box(n):
     separately = torch.empty_like(ty)
     _lib.check(lib.cp_gap_spline(ty.data_ptr(), box.data_ptr(), separately.data_ptr(), nseq, n, 0, dv.stream_of(dev)))
     keep = [i for i in range(nseq) if i != 5]
-    np.testing.assert_allclose(filled.cpu().numpy()[keep], separately.cpu().numpy()[keep], rtol=1e-9, atol=1e-13 * np.abs(y[keep]).max())
+    # (tolerances: tests/wallish_truth.py holds both kernels to 16 levels of at most 32 x 1.1e-16 of a block's largest value against the truth -- 6e-14 each)
+    got_filled, got_separately, gbox = filled.cpu().numpy(), separately.cpu().numpy(), box.cpu().numpy()
+    for i in keep:
+        a, b = gbox[i]
+        inside = np.zeros(n, dtype=bool)
+        inside[a:b + 1] = True
+        assert np.array_equal(got_filled[i, ~inside], y[i, ~inside]) and np.array_equal(got_separately[i, ~inside], y[i, ~inside])
+        np.testing.assert_allclose(got_filled[i, inside], got_separately[i, inside], rtol=0., atol=1.2e-13 * np.abs(got_separately[i, inside]).max())
     assert not torch.equal(filled, ty)
     got, gbox = dd.cpu().numpy(), box.cpu().numpy()
     assert np.array_equal(gbox, box2.cpu().numpy())
@@ -394,7 +401,7 @@ def test_wallish_dd_box(n):
         if i == 5:
             continue
         ref = interpolate.CubicSpline(x, y[i], bc_type='clamped')(x, nu=2)
-        np.testing.assert_allclose(got[i], ref, rtol=1e-9, atol=1e-13 * np.abs(ref).max() + 1e-300)
+        np.testing.assert_allclose(got[i], ref, rtol=0., atol=1e-13 * np.abs(ref).max() + 1e-300)
         first = got[i][mf:-mf].argmax() + mf
         second = first + ms + got[i][first + ms:-mf].argmax()
         assert tuple(gbox[i]) == (first + off[0], second + off[1]), i

@@ -11,6 +11,7 @@ NF = 36 against NF = S moves a result by p^37 = 7e-22 of a neighbour's total, be
 instance is run here for its bounds and pinned bit for bit by tests/test_uniform_recursion_bits_gpu.py.)"""
 import ctypes
 import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -25,7 +26,12 @@ CASES = [(32, 32), (33, 33), (57, 57), (57, 36)]
 
 @pytest.fixture(scope='module')
 def emu():
-    lib = ctypes.CDLL(os.path.join(HERE, 'host_emu', 'libemu_uniform_recursions.so'))
+    src = os.path.join(HERE, 'host_emu', 'emu_uniform_recursions.cpp')
+    out = os.path.join(HERE, 'host_emu', 'libemu_uniform_recursions.so')
+    dep = os.path.join(os.path.dirname(HERE), 'cosmoprimo_amd', 'csrc', 'cp_uniform_recursions.h')
+    if not os.path.isfile(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(dep)):      # (as the other harnesses of tests/host_emu: built where build() has not left it)
+        subprocess.check_call(['g++', '-O1', '-std=c++17', '-shared', '-fPIC', '-o', out, src])
+    lib = ctypes.CDLL(out)
     lib.emu_uniform_recursions.restype = ctypes.c_int
     lib.emu_uniform_recursions.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
     lib.emu_uniform_recursions_p.restype = ctypes.c_double
