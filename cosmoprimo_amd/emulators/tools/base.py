@@ -3,10 +3,15 @@ The ``Emulator`` front end under the reference's name (cosmoprimo/emulators/tool
 sample a calculator, fit an engine on the concatenation (npoints, M) of its flattened varied outputs, and give ``predict``, ``jacobian``, ``vjp`` and ``jvp`` back
 by output key for B parameter points at once.
 
-One front, four back ends.  The four methods share one plan (``Emulator._plan``: the keys asked for -> the maximal contiguous runs of columns of
+One front, four back ends.  Every method shares one plan (``Emulator._plan``: the keys asked for -> the maximal contiguous runs of columns of
 :func:`column_runs`, the ``(key, shape, lo, hi)`` entries each run holds, the fixed outputs to return) and one split (``_split``: a run's buffer ->
-``{key: view}``); each is then one call of the engine per run and nothing else.  What ``Emulator`` uses of an engine: ``name``, ``device``, ``_dev``
-(for its device), and ``predict`` / ``jacobian`` / ``vjp`` / ``vjp2`` / ``jvp`` with ``columns=`` / ``return_value=``.
+``{key: view}``), and reads top to bottom as points, plan or objective, loop, format.  The loops are three: ``Emulator._forward`` behind ``jacobian``,
+``jvp`` and ``jvp2`` (the engine once per run, every tensor it returns split by key), ``Emulator._reverse`` behind ``vjp`` and ``vjp2`` (a run's operands
+as one block, :func:`_block`; the runs' results added in run order), and the objective ``_Chi2`` behind ``gauss_newton``, ``chi2_hessian``,
+``least_squares`` and ``hmc``: weights or a dense precision, and data, checked and staged once, then ``evaluate`` (Fisher matrix, gradient, chi2 at any
+points), ``cotangent`` (of residuals or second derivatives, under either kind of weights), ``pull`` and ``curvature``.  What ``Emulator`` uses of an
+engine: ``name``, ``device``, ``_dev`` (for its device: ``Emulator._device_of``), and ``predict`` / ``jacobian`` / ``jvp`` / ``jvp2`` / ``vjp`` / ``vjp2`` /
+``gauss_newton`` with ``columns=`` / ``return_value=``.
 
 The helpers that both engines' ``predict`` / ``jacobian`` / ``vjp`` open with (``_columns``, ``_cotangent``, ``_tangent``, ``_operand``, ``_gauss_newton``, ``_empty``) live here as well; the engines
 import this module, which imports them only where it builds one.  Nothing on the path of a call imports anything: at B = 1 a call is its Python.
@@ -105,7 +110,34 @@ def _gauss_newton(d, check, entry, need, head, where, B, ndim, start, ncols, wei
     return toret[0] if len(toret) == 1 else toret
 
 
-LM_STATE = ('x', 'fisher', 'gradient', 'chi2', 'lambda', 'status', 'naccepted')
+def _in_place(tensor, shape, dtype, device):
+    """Is ``tensor`` what a launch writes in place: a contiguous torch tensor of that shape and dtype on ``device``, taken as it is or not at all?"""
+    return dv.is_torch(tensor) and tuple(tensor.shape) == shape and tensor.dtype == dtype and tensor.is_contiguous() and tensor.device == device
+
+
+def _checked_state(state, spec, lo, hi):
+    """What :func:`lm_step`, :func:`lm_accelerate` and :func:`hmc_step` check of the state they write in place and of the box: ``(B, ndim, shapes, lo, hi)``.
+    ``spec``: ``{name: (rank, dtype name)}`` of the state's tensors, one of rank r of shape ``(B,) + (ndim,) * (r - 1)``."""
+    torch = dv.torch()
+    x = state['x']
+    if x.ndim != 2:
+        raise ValueError('the state holds x of shape (B, ndim), got {}'.format(tuple(x.shape)))
+    B, ndim = (int(s) for s in x.shape)
+    by_rank, shapes = (None, (B,), (B, ndim), (B, ndim, ndim)), {}
+    for name, (rank, dtype) in spec.items():      # the predicate of _in_place, in line: this runs per tensor between any two evaluations of a fit or a chain
+        tensor, shape = state[name], by_rank[rank]
+        if tuple(tensor.shape) != shape or tensor.dtype != getattr(torch, dtype) or not tensor.is_contiguous() or tensor.device != x.device:
+            raise ValueError('state[{!r}] must be a contiguous {} tensor of shape {} on {}'.format(name, dtype, shape, x.device))
+        shapes[name] = shape
+    lo, hi = (dv.to_device(bound, x.device).reshape(-1) for bound in (lo, hi))
+    if int(lo.shape[0]) != ndim or int(hi.shape[0]) != ndim:
+        raise ValueError('lo and hi must be of shape ({:d},)'.format(ndim))
+    return B, ndim, shapes, lo, hi
+
+
+LM_SPEC = {'x': (2, 'float64'), 'fisher': (3, 'float64'), 'gradient': (2, 'float64'), 'chi2': (1, 'float64'), 'lambda': (1, 'float64'), 'status': (1, 'int32'),
+           'naccepted': (1, 'int32')}
+LM_STATE = tuple(LM_SPEC)
 LM_TRIAL = ('x', 'fisher', 'gradient', 'chi2')
 
 
@@ -117,25 +149,6 @@ def lm_state(x, lambda0=1e-3):
     new = lambda *shape, **kwargs: torch.zeros(shape, dtype=kwargs.get('dtype', torch.float64), device=x.device)      # noqa: E731
     return {'x': x.clone(), 'fisher': new(B, ndim, ndim), 'gradient': new(B, ndim), 'chi2': torch.full((B,), float('inf'), dtype=torch.float64, device=x.device),
             'lambda': torch.full((B,), float(lambda0), dtype=torch.float64, device=x.device), 'status': new(B, dtype=torch.int32), 'naccepted': new(B, dtype=torch.int32)}
-
-
-def _lm_checked(state, lo, hi):
-    """What :func:`lm_step` and :func:`lm_accelerate` check of the state and the box: ``(B, ndim, shapes, lo, hi)``."""
-    torch = dv.torch()
-    x = state['x']
-    if x.ndim != 2:
-        raise ValueError('the state holds x of shape (B, ndim), got {}'.format(tuple(x.shape)))
-    B, ndim = (int(s) for s in x.shape)
-    shapes = {'x': (B, ndim), 'fisher': (B, ndim, ndim), 'gradient': (B, ndim), 'chi2': (B,), 'lambda': (B,), 'status': (B,), 'naccepted': (B,)}
-    for name in LM_STATE:      # written in place: taken as they are or not at all
-        tensor = state[name]
-        if tuple(tensor.shape) != shapes[name] or tensor.dtype != (torch.int32 if name in ('status', 'naccepted') else torch.float64) or not tensor.is_contiguous() \
-                or tensor.device != x.device:
-            raise ValueError('state[{!r}] must be a contiguous {} tensor of shape {} on {}'.format(name, 'int32' if name in ('status', 'naccepted') else 'float64', shapes[name], x.device))
-    lo, hi = (dv.to_device(bound, x.device).reshape(-1) for bound in (lo, hi))
-    if int(lo.shape[0]) != ndim or int(hi.shape[0]) != ndim:
-        raise ValueError('lo and hi must be of shape ({:d},)'.format(ndim))
-    return B, ndim, shapes, lo, hi
 
 
 def lm_step(state, trial, lo, hi, lambda_up=10., lambda_down=0.1, lambda_min=1e-12, lambda_max=1e12, ftol=1e-8, return_velocity=False):
@@ -156,7 +169,7 @@ def lm_step(state, trial, lo, hi, lambda_up=10., lambda_down=0.1, lambda_min=1e-
     free parameters of a running fit and exactly 0 elsewhere: what :func:`lm_accelerate` takes."""
     torch = dv.torch()
     x = state['x']
-    B, ndim, shapes, lo, hi = _lm_checked(state, lo, hi)
+    B, ndim, shapes, lo, hi = _checked_state(state, LM_SPEC, lo, hi)
     read = []
     for name in LM_TRIAL:
         tensor = dv.to_device(trial[name], x.device, cache=False)
@@ -188,7 +201,7 @@ def lm_accelerate(state, velocity, curvature, lo, hi, alpha=0.75, naccelerated=N
     wait for the device."""
     torch = dv.torch()
     x = state['x']
-    B, ndim, shapes, lo, hi = _lm_checked(state, lo, hi)
+    B, ndim, shapes, lo, hi = _checked_state(state, LM_SPEC, lo, hi)
     read = []
     for name, tensor in (('velocity', velocity), ('curvature', curvature)):
         tensor = dv.to_device(tensor, x.device, cache=False)
@@ -197,7 +210,7 @@ def lm_accelerate(state, velocity, curvature, lo, hi, alpha=0.75, naccelerated=N
         read.append(tensor.to(torch.float64).contiguous())
     if naccelerated is None:
         naccelerated = torch.zeros((B,), dtype=torch.int32, device=x.device)
-    elif not dv.is_torch(naccelerated) or tuple(naccelerated.shape) != (B,) or naccelerated.dtype != torch.int32 or not naccelerated.is_contiguous() or naccelerated.device != x.device:
+    elif not _in_place(naccelerated, (B,), torch.int32, x.device):
         raise ValueError('naccelerated must be a contiguous int32 tensor of shape {} on {}'.format((B,), x.device))
     out = torch.empty_like(x)
     _lib.check(_lib.load().cp_lm_accelerate(B, ndim, *[state[name].data_ptr() for name in ('x', 'fisher', 'gradient', 'lambda', 'status')], lo.data_ptr(), hi.data_ptr(),
@@ -220,6 +233,8 @@ def spd_inverse(a):
 
 HMC_STATE = ('x', 'gradient', 'chi2', 'status', 'naccepted', 'nout')
 HMC_TRAJECTORY = ('z', 'h0', 'eps', 'out')
+HMC_SPEC = {'x': (2, 'float64'), 'gradient': (2, 'float64'), 'chi2': (1, 'float64'), 'status': (1, 'int32'), 'naccepted': (1, 'int32'), 'nout': (1, 'int32'),
+            'z': (2, 'float64'), 'h0': (1, 'float64'), 'eps': (1, 'float64'), 'out': (1, 'int32')}      # HMC_STATE, then HMC_TRAJECTORY
 HMC_TRIAL = ('x', 'gradient', 'chi2')
 
 
@@ -260,7 +275,7 @@ def hmc_factor(metric, status):
     if metric.ndim != 3 or metric.shape[1] != metric.shape[2]:
         raise ValueError('matrices of shape (B, ndim, ndim), got {}'.format(tuple(metric.shape)))
     B, ndim = int(metric.shape[0]), int(metric.shape[1])
-    if not dv.is_torch(status) or tuple(status.shape) != (B,) or status.dtype != torch.int32 or not status.is_contiguous() or status.device != metric.device:
+    if not _in_place(status, (B,), torch.int32, metric.device):
         raise ValueError('status must be a contiguous int32 tensor of shape {} on {}'.format((B,), metric.device))
     factor = torch.empty_like(metric)
     _lib.check(_lib.load().cp_hmc_factor(B, ndim, metric.data_ptr(), factor.data_ptr(), status.data_ptr(), metric.device.index, dv.stream_of(metric.device)))
@@ -284,30 +299,20 @@ def hmc_step(state, trial, factor, lo, hi, step_size, t_close=None, t_open=None,
     device."""
     torch = dv.torch()
     x = state['x']
-    if x.ndim != 2:
-        raise ValueError('the state holds x of shape (B, ndim), got {}'.format(tuple(x.shape)))
-    B, ndim = (int(s) for s in x.shape)
-    shapes = {'x': (B, ndim), 'gradient': (B, ndim), 'z': (B, ndim)}
-    for name in HMC_STATE + HMC_TRAJECTORY:      # written in place: taken as they are or not at all
-        tensor, integer = state[name], name in ('status', 'naccepted', 'nout', 'out')
-        if tuple(tensor.shape) != shapes.get(name, (B,)) or tensor.dtype != (torch.int32 if integer else torch.float64) or not tensor.is_contiguous() or tensor.device != x.device:
-            raise ValueError('state[{!r}] must be a contiguous {} tensor of shape {} on {}'.format(name, 'int32' if integer else 'float64', shapes.get(name, (B,)), x.device))
-    lo, hi = (dv.to_device(bound, x.device).reshape(-1) for bound in (lo, hi))
-    if int(lo.shape[0]) != ndim or int(hi.shape[0]) != ndim:
-        raise ValueError('lo and hi must be of shape ({:d},)'.format(ndim))
+    B, ndim, shapes, lo, hi = _checked_state(state, HMC_SPEC, lo, hi)
     read = []
     for name in HMC_TRIAL:
         tensor = dv.to_device(trial[name], x.device, cache=False)
-        if tuple(tensor.shape) != shapes.get(name, (B,)):
-            raise ValueError('trial[{!r}] must be of shape {}, got {}'.format(name, shapes.get(name, (B,)), tuple(tensor.shape)))
+        if tuple(tensor.shape) != shapes[name]:
+            raise ValueError('trial[{!r}] must be of shape {}, got {}'.format(name, shapes[name], tuple(tensor.shape)))
         read.append(tensor.to(torch.float64).contiguous())
-    if not dv.is_torch(factor) or tuple(factor.shape) != (B, ndim, ndim) or factor.dtype != torch.float64 or not factor.is_contiguous() or factor.device != x.device:
+    if not _in_place(factor, (B, ndim, ndim), torch.float64, x.device):
         raise ValueError('factor must be a contiguous float64 tensor of shape {} on {}'.format((B, ndim, ndim), x.device))
     step_size = _hmc_step_size(step_size, B, x.device)
     if (sample is None) != (sample_chi2 is None):
         raise ValueError('sample and sample_chi2 are given together')
     for name, tensor, shape in (('sample', sample, (B, ndim)), ('sample_chi2', sample_chi2, (B,))):
-        if tensor is not None and (not dv.is_torch(tensor) or tuple(tensor.shape) != shape or tensor.dtype != torch.float64 or not tensor.is_contiguous() or tensor.device != x.device):
+        if tensor is not None and not _in_place(tensor, shape, torch.float64, x.device):
             raise ValueError('{} must be a contiguous float64 tensor of shape {} on {}'.format(name, shape, x.device))
     out = torch.empty_like(x)
     _lib.check(_lib.load().cp_hmc_step(B, ndim, -1 if t_close is None else int(t_close), -1 if t_open is None else int(t_open),
@@ -433,6 +438,147 @@ def _split(out, lead, entries, start, scalar):
     return toret
 
 
+def _block(operands, entries, B, dev):
+    """The operands ``{key: array or tensor}`` of the ``entries`` of a run as one float64 tensor (B, ncols) on ``dev``, in the order of the columns: each is
+    broadcast to ``(B,) + shape`` of its output; an output without columns holds none."""
+    torch = dv.torch()
+    blocks = [torch.broadcast_to(dv.to_device(operands[key], dev, cache=False).to(torch.float64), (B,) + shape).reshape(B, hi - lo)
+              for key, shape, lo, hi in entries if hi > lo]
+    return blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1)
+
+
+class _Chi2(object):
+
+    """The chi2 of a fit of ``data`` to the emulated outputs, as :meth:`Emulator.gauss_newton`, :meth:`Emulator.chi2_hessian`, :meth:`Emulator.least_squares` and
+    :meth:`Emulator.hmc` share it: ``weights``, ``data`` (or None) and ``precision`` (or None) as :meth:`Emulator.gauss_newton` takes them, checked -- its
+    ``KeyError`` / ``ValueError`` / ``TypeError`` are raised here -- and staged once on the device ``dev`` for B points, ``X`` (B, ndim) among what the device is
+    resolved from.  ``runs``: the maximal contiguous runs ``[(start, stop, entries), ...]`` of :meth:`Emulator._plan` over the varied keys asked for (``keys``);
+    ``weights`` and ``data``: per run, the operands as (B, stop - start) blocks (``data``: None each without data); ``fixed``: the fixed outputs asked for.
+
+    Under a dense ``precision`` over the outputs ``weights`` lists (a sequence of distinct varied keys: those outputs flattened in C order and concatenated
+    as listed, N entries), run r fills the columns ``columns[r]`` (a slice) of the N columns of the data vector in the order of the column plan; ``precision``
+    (N, N), given in the listed order, is permuted here, once and on the device, to that order; ``jac`` (B, ndim, N) and ``value`` (B, N) are the buffers the
+    engine's ``jacobian`` writes into, ``data`` views of one (B, N) block and ``weights`` None."""
+
+    def __init__(self, emulator, weights, data, precision, X, B):
+        torch = dv.torch()
+        self.engine, self.B, self.ndim, self.has_data, self._masks = emulator.engine, B, len(emulator.params), data is not None, None
+        if precision is None:
+            self.dev = dev = emulator._device_of(X, *weights.values())
+            self.keys, self.precision = weights, None
+            self.runs, self.fixed = emulator._plan(list(weights), exact=True)
+            if data is not None:
+                unknown = [key for key in data if key not in weights]
+                if unknown:
+                    raise KeyError('data for {}, which hold no weights'.format(unknown))
+                missing = [key for key in weights if key in emulator.varied_keys and key not in data]
+                if missing:
+                    raise ValueError('no data for {}'.format(missing))
+            self.weights = [_block(weights, entries, B, dev) for start, stop, entries in self.runs]
+            self.data = [_block(data, entries, B, dev) if data is not None else None for start, stop, entries in self.runs]
+            return
+        self.dev = dev = emulator._device_of(X, precision)
+        if isinstance(weights, dict):
+            raise TypeError('with a precision matrix, weights is the sequence of the output keys its rows and columns follow, not a dictionary')
+        self.keys = keys = [weights] if isinstance(weights, str) else list(weights)
+        if len(set(keys)) != len(keys):
+            raise ValueError('keys listed twice in {}'.format(keys))
+        unknown = [key for key in keys if key not in emulator.varied_keys]
+        if unknown:
+            raise KeyError('no varied output {}'.format(unknown))
+        if data is not None:
+            unknown = [key for key in data if key not in keys]
+            if unknown:
+                raise KeyError('data for {}, which the precision matrix does not cover'.format(unknown))
+            missing = [key for key in keys if key not in data]
+            if missing:
+                raise ValueError('no data for {}'.format(missing))
+        sizes = {key: int(np.prod(shape, dtype='i8')) for key, shape in zip(emulator.varied_keys, emulator.varied_shapes)}
+        listed, N = {}, 0      # where a key starts in the listed order
+        for key in keys:
+            listed[key] = N
+            N += sizes[key]
+        if tuple(np.shape(precision)) != (N, N):
+            raise ValueError('precision must be of shape ({0:d}, {0:d}) for {1}, got {2}'.format(N, keys, tuple(np.shape(precision))))
+        self.runs, self.fixed = (emulator._plan(keys, exact=True)[0] if keys else []), {}
+        self.columns, order, q = [], [], 0
+        for start, stop, entries in self.runs:
+            self.columns.append(slice(q, q + stop - start))
+            order += [np.arange(listed[key], listed[key] + hi - lo) for key, shape, lo, hi in entries]
+            q += stop - start
+        order = np.concatenate(order) if order else np.zeros(0, dtype='i8')
+        precision = precision.to(device=dev, dtype=torch.float64) if dv.is_torch(precision) else dv.upload(np.asarray(precision, dtype='f8'), dev)
+        if not np.array_equal(order, np.arange(N)):
+            index = dv.upload(order.astype('i8'), dev)
+            precision = precision.index_select(0, index).index_select(1, index)
+        self.precision, self.weights, self._data = precision.contiguous(), None, None
+        if data is not None:
+            self._data = _block(data, [entry for start, stop, entries in self.runs for entry in entries], B, dev) if N else torch.zeros((B, 0), dtype=torch.float64, device=dev)
+        self.data = [self._data[:, cols] if data is not None else None for cols in self.columns]
+        self.jac, self.value = (torch.empty(shape, dtype=torch.float64, device=dev) for shape in ((B, self.ndim, N), (B, N)))
+
+    def _zeros(self, *shape):
+        return dv.torch().zeros(shape, dtype=dv.torch().float64, device=self.dev)
+
+    def evaluate(self, x, return_value=False):
+        """One evaluation at the points ``x`` (B, ndim): ``(fisher,)``, with data ``(fisher, gradient, chi2)``, device tensors (B, ndim, ndim), (B, ndim) and
+        (B,); ``return_value=True``: ``(values, totals)``, ``values`` the prediction per run, (B, stop - start).  Diagonal weights: the engine's
+        ``gauss_newton`` once per run, the runs' results added in run order (no run: zeros).  Dense precision: the engine's ``jacobian`` once per run, written
+        straight into its column slice of ``jac`` and -- with data, or where the value is asked for -- of ``value``, then :func:`gauss_newton_dense`."""
+        if self.precision is not None:
+            value = self.value if self.has_data or return_value else None
+            for (start, stop, entries), cols in zip(self.runs, self.columns):
+                self.engine.jacobian(x, columns=(start, stop), return_value=value is not None, out=(value[:, cols] if value is not None else None, self.jac[:, :, cols]))
+            totals = gauss_newton_dense(self.jac, value, self.precision, data=self._data)
+            totals = totals if isinstance(totals, tuple) else (totals,)
+            return ([self.value[:, cols] for cols in self.columns], totals) if return_value else totals
+        totals, values = None, []
+        for (start, stop, entries), wblock, dblock in zip(self.runs, self.weights, self.data):
+            out = self.engine.gauss_newton(x, wblock, data=dblock, columns=(start, stop), return_value=return_value)
+            out = out if isinstance(out, tuple) else (out,)
+            if return_value:
+                values.append(out[0])
+                out = out[1:]
+            totals = out if totals is None else tuple(a + b for a, b in zip(totals, out))
+        if totals is None:
+            totals = (self._zeros(self.B, self.ndim, self.ndim),) + ((self._zeros(self.B, self.ndim), self._zeros(self.B)) if self.has_data else ())
+        return (values, totals) if return_value else totals
+
+    def cotangent(self, blocks):
+        """Yield, per run, the cotangent (B, stop - start) of the ``blocks`` ``q`` -- per run a residual ``data - y`` or a second derivative of ``y`` -- under the
+        weights: ``where(w == 0, 0, w q)`` (a select: NaN under a zero weight stay masked); under a dense precision ``P`` the ``q`` of all runs, the columns
+        with ``P[c, c] == 0`` dropped as :func:`gauss_newton_dense` drops them, times ``P``, masked again.  ``blocks`` may be a generator: diagonal weights
+        take a run's block when its cotangent is asked for, a precision, which couples the runs, takes them all first."""
+        torch = dv.torch()
+        if self._masks is None:
+            self._masks = (self._zeros(), self.precision.diagonal() == 0 if self.precision is not None else None)
+        zero, dropped = self._masks
+        if self.precision is None:
+            for w, q in zip(self.weights, blocks):
+                yield torch.where(w == 0, zero, w * q)
+            return
+        blocks = list(blocks)
+        if blocks:
+            q = torch.where(dropped, zero, blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1))
+            q = torch.where(dropped, zero, torch.matmul(q, self.precision))
+            for cols in self.columns:
+                yield q[:, cols]
+
+    def pull(self, method, x, blocks, rank):
+        """The engine's ``method`` ('vjp', 'vjp2') at ``x`` on the cotangent ``blocks`` of :meth:`cotangent`, once per run, the runs' results
+        (B,) + (ndim,) * rank added in run order (no run: zeros)."""
+        total = None
+        for (start, stop, entries), block in zip(self.runs, blocks):
+            out = getattr(self.engine, method)(x, block, columns=(start, stop))
+            total = out if total is None else total + out
+        return total if total is not None else self._zeros(self.B, *((self.ndim,) * rank))
+
+    def curvature(self, at, velocity):
+        """``h = J W y''(v, v)`` (B, ndim) for :func:`lm_accelerate`: per run the second directional derivative of the prediction along ``velocity`` at the
+        points ``at`` (the engine's ``jvp2``, a row per fit), its :meth:`cotangent`, and the engine's ``vjp`` of that."""
+        return self.pull('vjp', at, self.cotangent(self.engine.jvp2(at, velocity, columns=(start, stop)) for start, stop, entries in self.runs), 1)
+
+
 class Emulator(object):
 
     """Emulate a calculator ``**params -> dict of arrays``: sample it (:meth:`set_samples`), :meth:`fit`, then :meth:`predict` at B parameter points at once.
@@ -483,13 +629,17 @@ class Emulator(object):
         self.engine.fit(samples.matrix(), Y, samples.attrs, params=list(self.params), **kwargs)
         return self
 
+    def _device_of(self, *operands):
+        """The device of a call: the fitted engine's, else what :func:`_device.resolve_device` makes of the engine's ``device`` and the ``operands``."""
+        return self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, *operands)
+
     def _points(self, params):
         """(X (B, ndim) in the order of ``self.params``, a host array unless a parameter is a device tensor; B; whether every parameter is a scalar)."""
         missing = [name for name in self.params if name not in params]
         if missing:
             raise ValueError('missing parameters {}'.format(missing))
         values = [params[name] for name in self.params]
-        dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, *values)
+        dev = self._device_of(*values)
         torch = dv.torch()
         sizes = {int(np.prod(np.shape(v))) for v in values if np.ndim(v) > 0}
         if len(sizes) > 1:
@@ -550,18 +700,50 @@ class Emulator(object):
         ``keys``: as in :meth:`predict` -- the columns are planned by :func:`column_runs`, one call of the engine per maximal contiguous run, and no other
         column is computed.  ``return_value=True``: ``(values, jacobian)``, ``values`` what ``predict(params, device=device, keys=keys)`` returns."""
         X, B, scalar = self._points(params)
-        runs, fixed = self._plan(keys)
-        values, toret = {}, {}
+        return self._forward('jacobian', X, scalar, self._plan(keys), keys, device, [(B,)] * bool(return_value) + [(B, len(self.params))], return_value=return_value)
+
+    def _forward(self, method, X, scalar, plan, keys, device, leads, *operands, **flags):
+        """The run loop of :meth:`jacobian`, :meth:`jvp` and :meth:`jvp2`: the engine's ``method`` on ``X`` and ``operands`` once per run of
+        ``plan = self._plan(keys)`` (``columns=None`` for every output), each tensor it returns split by key with its lead shape of ``leads`` (host arrays
+        unless ``device``), the values -- the first, under ``return_value=True`` among the ``flags`` -- completed by the fixed outputs.  Returns the
+        dictionaries as a tuple, a single one as it is."""
+        runs, fixed = plan
+        toret = [{} for lead in leads]
         for start, stop, entries in runs:
-            out = self.engine.jacobian(X, columns=None if keys is None else (start, stop), return_value=return_value)
-            value, jac = out if return_value else (None, out)
-            toret.update(_split(jac if device else dv.to_host(jac), (B, len(self.params)), entries, start, scalar))
+            out = getattr(self.engine, method)(X, *operands, columns=None if keys is None else (start, stop), **flags)
+            for result, lead, tensor in zip(toret, leads, out if isinstance(out, tuple) else (out,)):
+                result.update(_split(tensor if device else dv.to_host(tensor), lead, entries, start, scalar))
+        if flags.get('return_value'):
+            toret[0].update(fixed)
+        return tuple(toret) if len(toret) > 1 else toret[0]
+
+    def _values(self, params, values, asked, fixed, device):
+        """``values`` -- the varied outputs the runs of a plan over the keys ``asked`` gave -- as ``predict(params, device=device, keys=list(asked))``
+        returns them: with the outputs that hold no column, in the calculator's order, then the ``fixed`` outputs."""
+        for key in self.varied_keys:      # empty outputs hold no column and join no run
+            if key in asked and key not in values:
+                values[key] = self.predict(params, device=device, keys=[key])[key]
+        values = {key: values[key] for key in self.varied_keys if key in values}
+        values.update(fixed)
+        return values
+
+    def _reverse(self, method, rank, params, cotangents, device, return_value):
+        """The run loop of :meth:`vjp` (``rank`` 1) and :meth:`vjp2` (2): the engine's ``method`` once per run of the plan over the cotangents' varied keys,
+        on that run's block of cotangents, the runs' results (B,) + (ndim,) * rank added in run order (no run: zeros).  Returns ``(values, total, scalar)``:
+        ``values`` what ``predict(params, device=device, keys=list(cotangents))`` returns (None unless asked for), ``total`` a host array unless ``device``."""
+        X, B, scalar = self._points(params)
+        runs, fixed = self._plan(list(cotangents), exact=True)
+        dev = self._device_of(X, *cotangents.values())
+        total, values = None, {}
+        for start, stop, entries in runs:
+            out = getattr(self.engine, method)(X, _block(cotangents, entries, B, dev), columns=(start, stop), return_value=return_value)
+            value, result = out if return_value else (None, out)
+            total = result if total is None else total + result
             if return_value:
                 values.update(_split(value if device else dv.to_host(value), (B,), entries, start, scalar))
-        if not return_value:
-            return toret
-        values.update(fixed)
-        return values, toret
+        if total is None:
+            total = dv.torch().zeros((B,) + (len(self.params),) * rank, dtype=dv.torch().float64, device=dev)
+        return self._values(params, values, cotangents, fixed, device) if return_value else None, total if device else dv.to_host(total), scalar
 
     def vjp(self, params, cotangents, device=False, return_value=False):
         """Vector-Jacobian product: the gradient with respect to the parameters of a scalar function of the outputs whose derivative with respect to
@@ -572,76 +754,27 @@ class Emulator(object):
 
         Returns ``{parameter name: (B,) array}`` in the order of ``Emulator.params``, ``sum over keys and entries of cotangent * d output / d parameter``
         (scalars if every parameter is a scalar).  Computed by reverse mode on the device (:meth:`MLPEmulatorEngine.vjp`,
-        :meth:`TaylorEmulatorEngine.vjp`) without forming the Jacobian: the columns are planned by :func:`column_runs` over the cotangents' varied keys,
-        one call of the engine per maximal contiguous run on that range only, the runs' results added in run order.  Host arrays by default;
-        ``device=True``: the views ``G[:, i]`` of one (B, ndim) tensor, and no synchronisation with the device.  ``return_value=True``:
+        :meth:`TaylorEmulatorEngine.vjp`) without forming the Jacobian, on the columns of the cotangents' varied keys only (:meth:`_reverse`).  Host arrays by
+        default; ``device=True``: the views ``G[:, i]`` of one (B, ndim) tensor, and no synchronisation with the device.  ``return_value=True``:
         ``(values, gradients)``, ``values`` what ``predict(params, device=device, keys=list(cotangents))`` returns."""
-        X, B, scalar = self._points(params)
-        torch = dv.torch()
-        runs, fixed = self._plan(list(cotangents), exact=True)
-        dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, *cotangents.values())
-        total, values = None, {}
-        for start, stop, entries in runs:
-            blocks = [torch.broadcast_to(dv.to_device(cotangents[key], dev, cache=False).to(torch.float64), (B,) + shape).reshape(B, hi - lo)
-                      for key, shape, lo, hi in entries if hi > lo]
-            out = self.engine.vjp(X, blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1), columns=(start, stop), return_value=return_value)
-            value, grad = out if return_value else (None, out)
-            total = grad if total is None else total + grad
-            if return_value:
-                values.update(_split(value if device else dv.to_host(value), (B,), entries, start, scalar))
-        if total is None:
-            total = torch.zeros((B, len(self.params)), dtype=torch.float64, device=dev)
-        if not device:
-            total = dv.to_host(total)
+        values, total, scalar = self._reverse('vjp', 1, params, cotangents, device, return_value)
         grads = {name: (total[0, i] if scalar else total[:, i]) for i, name in enumerate(self.params)}
-        if not return_value:
-            return grads
-        for key in self.varied_keys:      # empty outputs hold no column and join no run
-            if key in cotangents and key not in values:
-                values[key] = self.predict(params, device=device, keys=[key])[key]
-        values = {key: values[key] for key in self.varied_keys if key in values}      # predict's order: the calculator's, then the fixed outputs
-        values.update(fixed)
-        return values, grads
+        return (values, grads) if return_value else grads
 
     def vjp2(self, params, cotangents, device=False, return_value=False):
         """Second derivatives of the varied outputs contracted with cotangents: the Hessian with respect to the parameters of ``sum cotangent * output`` at
         fixed cotangents, for every point of a batch -- the second-order part of what ``jax.hessian`` of a scalar function of the reference's ``predict``
         gives (with ``cotangents = w (data - y)`` the residual-curvature term of the Hessian of chi2, :meth:`chi2_hessian`).  ``params`` and ``cotangents``
-        as in :meth:`vjp`: ``{varied key: array or tensor}``, each broadcastable to ``(B,) + shape`` of that output; a fixed key contributes nothing, an
-        unknown key raises ``KeyError``, an empty dictionary gives zeros.
+        as in :meth:`vjp`, with its rules for fixed, unknown and no keys.
 
         Returns ``(B, ndim, ndim)`` in the order of ``Emulator.params`` (no leading axis if every parameter is a scalar),
         ``sum over keys and entries of cotangent * d^2 output / d parameter_i d parameter_j``, symmetric bit for bit.  Computed on the device
-        (:meth:`MLPEmulatorEngine.vjp2`, :meth:`TaylorEmulatorEngine.vjp2`) without forming any second derivative of an output: the columns are planned by
-        :func:`column_runs` over the cotangents' varied keys, one call of the engine per maximal contiguous run on that range only, the runs' matrices
-        added in run order.  Host array by default; ``device=True``: a torch tensor, and no synchronisation with the device.  ``return_value=True``:
-        ``(values, matrices)``, ``values`` what ``predict(params, device=device, keys=list(cotangents))`` returns."""
-        X, B, scalar = self._points(params)
-        torch = dv.torch()
-        runs, fixed = self._plan(list(cotangents), exact=True)
-        dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, *cotangents.values())
-        total, values = None, {}
-        for start, stop, entries in runs:
-            blocks = [torch.broadcast_to(dv.to_device(cotangents[key], dev, cache=False).to(torch.float64), (B,) + shape).reshape(B, hi - lo)
-                      for key, shape, lo, hi in entries if hi > lo]
-            out = self.engine.vjp2(X, blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1), columns=(start, stop), return_value=return_value)
-            value, hess = out if return_value else (None, out)
-            total = hess if total is None else total + hess
-            if return_value:
-                values.update(_split(value if device else dv.to_host(value), (B,), entries, start, scalar))
-        if total is None:
-            total = torch.zeros((B, len(self.params), len(self.params)), dtype=torch.float64, device=dev)
-        if not device:
-            total = dv.to_host(total)
+        (:meth:`MLPEmulatorEngine.vjp2`, :meth:`TaylorEmulatorEngine.vjp2`) without forming any second derivative of an output (:meth:`_reverse`).  Host
+        array by default; ``device=True``: a torch tensor, and no synchronisation with the device.  ``return_value=True``: ``(values, matrices)``, ``values``
+        what ``predict(params, device=device, keys=list(cotangents))`` returns."""
+        values, total, scalar = self._reverse('vjp2', 2, params, cotangents, device, return_value)
         total = total[0] if scalar else total
-        if not return_value:
-            return total
-        for key in self.varied_keys:      # empty outputs hold no column and join no run
-            if key in cotangents and key not in values:
-                values[key] = self.predict(params, device=device, keys=[key])[key]
-        values = {key: values[key] for key in self.varied_keys if key in values}      # predict's order: the calculator's, then the fixed outputs
-        values.update(fixed)
-        return values, total
+        return (values, total) if return_value else total
 
     def _directions(self, tangents, B):
         """(T (B, ndim) or (B, K, ndim) float64, K or None) of ``tangents = {parameter name: value}``, a host array unless a tangent is a device tensor: a
@@ -653,7 +786,7 @@ class Emulator(object):
             xp, values = np, {name: np.asarray(value, dtype='f8') for name, value in tangents.items()}
         else:
             xp = dv.torch()
-            dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, *tangents.values())
+            dev = self._device_of(*tangents.values())
             values = {name: dv.to_device(value, dev, cache=False) for name, value in tangents.items()}
             values[None] = xp.zeros((), dtype=xp.float64, device=dev)
         if any(v.ndim > 2 for v in values.values()):
@@ -683,19 +816,9 @@ class Emulator(object):
         buffer, and no synchronisation with the device.  ``return_value=True``: ``(values, tangents_out)``, ``values`` what
         ``predict(params, device=device, keys=keys)`` returns."""
         X, B, scalar = self._points(params)
-        runs, fixed = self._plan(keys)
+        plan = self._plan(keys)
         T, K = self._directions(tangents, B)
-        values, toret = {}, {}
-        for start, stop, entries in runs:
-            out = self.engine.jvp(X, T, columns=None if keys is None else (start, stop), return_value=return_value)
-            value, tan = out if return_value else (None, out)
-            toret.update(_split(tan if device else dv.to_host(tan), (B,) if K is None else (B, K), entries, start, scalar))
-            if return_value:
-                values.update(_split(value if device else dv.to_host(value), (B,), entries, start, scalar))
-        if not return_value:
-            return toret
-        values.update(fixed)
-        return values, toret
+        return self._forward('jvp', X, scalar, plan, keys, device, [(B,)] * bool(return_value) + [(B,) if K is None else (B, K)], T, return_value=return_value)
 
     def jvp2(self, params, tangents, tangents2=None, device=False, keys=None, return_value=False, return_first=False):
         """Second directional derivatives of the varied outputs along pairs of directions in parameter space, for every point of a batch -- what
@@ -712,7 +835,7 @@ class Emulator(object):
         ``predict(params, device=device, keys=keys)`` are prepended; ``return_first=True``: what :meth:`jvp` gives along ``tangents`` (and along
         ``tangents2``, where given) is inserted before the result."""
         X, B, scalar = self._points(params)
-        runs, fixed = self._plan(keys)
+        plan = self._plan(keys)
         T, K = self._directions(tangents, B)
         T2 = None
         if tangents2 is not None:
@@ -720,20 +843,8 @@ class Emulator(object):
             if K2 != K:
                 raise ValueError('tangents and tangents2 must share one count of directions, got {} and {}'.format(K, K2))
         nfirst = (2 if T2 is not None else 1) if return_first else 0
-        lead = (B,) if K is None else (B, K)
-        values, firsts, toret = {}, [{} for _ in range(nfirst)], {}
-        for start, stop, entries in runs:
-            out = self.engine.jvp2(X, T, T2, columns=None if keys is None else (start, stop), return_value=return_value, return_first=return_first)
-            out = list(out) if isinstance(out, tuple) else [out]
-            host = lambda tensor: tensor if device else dv.to_host(tensor)      # noqa: E731
-            if return_value:
-                values.update(_split(host(out.pop(0)), (B,), entries, start, scalar))
-            for first in firsts:
-                first.update(_split(host(out.pop(0)), lead, entries, start, scalar))
-            toret.update(_split(host(out.pop(0)), lead, entries, start, scalar))
-        values.update(fixed)
-        result = ([values] if return_value else []) + firsts + [toret]
-        return tuple(result) if len(result) > 1 else toret
+        leads = [(B,)] * bool(return_value) + [(B,) if K is None else (B, K)] * (nfirst + 1)
+        return self._forward('jvp2', X, scalar, plan, keys, device, leads, T, T2, return_value=return_value, return_first=return_first)
 
     def hessian(self, params, device=False, keys=None):
         """Second derivatives of the varied outputs with respect to the parameters at ``params`` (as in :meth:`predict`) -- what ``jax.hessian`` of the
@@ -759,81 +870,6 @@ class Emulator(object):
             toret[key] = full.reshape(tuple(block.shape[:axis]) + (ndim, ndim) + tuple(block.shape[axis + 1:]))
         return toret
 
-    def _staged(self, weights, data, B, dev):
-        """What :meth:`gauss_newton` and :meth:`least_squares` read of ``weights`` and ``data`` (the latter or None), checked, on the device ``dev``:
-        ``([(start, stop, entries, weights block, data block or None), ...], fixed)``, a maximal contiguous run of columns of :meth:`_plan` over the keys of
-        ``weights`` each, its operands broadcast to (B, stop - start)."""
-        torch = dv.torch()
-        runs, fixed = self._plan(list(weights), exact=True)
-        if data is not None:
-            unknown = [key for key in data if key not in weights]
-            if unknown:
-                raise KeyError('data for {}, which hold no weights'.format(unknown))
-            missing = [key for key in weights if key in self.varied_keys and key not in data]
-            if missing:
-                raise ValueError('no data for {}'.format(missing))
-
-        def block(operands, entries):
-            blocks = [torch.broadcast_to(dv.to_device(operands[key], dev, cache=False).to(torch.float64), (B,) + shape).reshape(B, hi - lo)
-                      for key, shape, lo, hi in entries if hi > lo]
-            return blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1)
-
-        return [(start, stop, entries, block(weights, entries), block(data, entries) if data is not None else None) for start, stop, entries in runs], fixed
-
-    def _staged_dense(self, keys, precision, data, B, dev):
-        """What :meth:`gauss_newton` and :meth:`least_squares` read of a dense ``precision`` over the outputs ``keys`` (a sequence of distinct varied keys) and of
-        ``data`` (or None), checked, on the device ``dev``: ``(runs, N, precision, data block (B, N) or None)``.  ``runs``: ``[(start, stop, entries, q0), ...]``,
-        the maximal contiguous runs of :meth:`_plan` over ``keys``, run r filling the columns ``[q0, q0 + stop - start)`` of the N columns of the data
-        vector in the order of the column plan.  ``precision`` is given in the listed order (the outputs flattened in C order and concatenated as
-        listed); it is permuted here, once and on the device, to the order of the column plan."""
-        torch = dv.torch()
-        if isinstance(keys, dict):
-            raise TypeError('with a precision matrix, weights is the sequence of the output keys its rows and columns follow, not a dictionary')
-        keys = [keys] if isinstance(keys, str) else list(keys)
-        if len(set(keys)) != len(keys):
-            raise ValueError('keys listed twice in {}'.format(keys))
-        unknown = [key for key in keys if key not in self.varied_keys]
-        if unknown:
-            raise KeyError('no varied output {}'.format(unknown))
-        if data is not None:
-            unknown = [key for key in data if key not in keys]
-            if unknown:
-                raise KeyError('data for {}, which the precision matrix does not cover'.format(unknown))
-            missing = [key for key in keys if key not in data]
-            if missing:
-                raise ValueError('no data for {}'.format(missing))
-        sizes = {key: int(np.prod(shape, dtype='i8')) for key, shape in zip(self.varied_keys, self.varied_shapes)}
-        listed, N = {}, 0      # where a key starts in the listed order
-        for key in keys:
-            listed[key] = N
-            N += sizes[key]
-        if tuple(np.shape(precision)) != (N, N):
-            raise ValueError('precision must be of shape ({0:d}, {0:d}) for {1}, got {2}'.format(N, keys, tuple(np.shape(precision))))
-        runs, order, q = [], [], 0
-        for start, stop, entries in (self._plan(keys, exact=True)[0] if keys else []):
-            runs.append((start, stop, entries, q))
-            order += [np.arange(listed[key], listed[key] + hi - lo) for key, shape, lo, hi in entries]
-            q += stop - start
-        order = np.concatenate(order) if order else np.zeros(0, dtype='i8')
-        precision = precision.to(device=dev, dtype=torch.float64) if dv.is_torch(precision) else dv.upload(np.asarray(precision, dtype='f8'), dev)
-        if not np.array_equal(order, np.arange(N)):
-            index = dv.upload(order.astype('i8'), dev)
-            precision = precision.index_select(0, index).index_select(1, index)
-        dblock = None
-        if data is not None:
-            blocks = [torch.broadcast_to(dv.to_device(data[key], dev, cache=False).to(torch.float64), (B,) + shape).reshape(B, hi - lo)
-                      for start, stop, entries, q0 in runs for key, shape, lo, hi in entries]
-            dblock = blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1) if blocks else torch.zeros((B, 0), dtype=torch.float64, device=dev)
-        return runs, N, precision.contiguous(), dblock
-
-    def _dense_normal_equations(self, X, runs, precision, dblock, jac, value):
-        """One evaluation under a dense precision matrix: the engine's ``jacobian`` once per run, written straight into its column slice of ``jac``
-        (B, ndim, N) and -- where ``value`` (B, N) is given -- of ``value``, then :func:`gauss_newton_dense`."""
-        for start, stop, entries, q0 in runs:
-            q1 = q0 + stop - start
-            self.engine.jacobian(X, columns=(start, stop), return_value=value is not None, out=(value[:, q0:q1] if value is not None else None, jac[:, :, q0:q1]))
-        return gauss_newton_dense(jac, value, precision, data=dblock)
-
     def gauss_newton(self, params, weights, data=None, device=False, return_value=False, precision=None):
         """Fisher matrices and Gauss-Newton normal equations of a weighted least-squares fit of ``data`` to the emulated outputs, for every point of a batch,
         with ``J`` the Jacobian of :meth:`jacobian` and ``y`` the prediction: ``fisher[b, i, j] = sum w J_i J_j``,
@@ -848,73 +884,38 @@ class Emulator(object):
 
         Returns ``fisher`` (B, ndim, ndim) in the order of ``Emulator.params`` (no leading axis if every parameter is a scalar), or with ``data``
         ``(fisher, gradient, chi2)``, ``gradient`` ``{parameter name: (B,)}`` as :meth:`vjp` returns its gradients and ``chi2`` (B,).  Computed on the
-        device without forming the Jacobian (:meth:`MLPEmulatorEngine.gauss_newton`, :meth:`TaylorEmulatorEngine.gauss_newton`): the columns are planned
-        by :func:`column_runs` over the varied keys of ``weights``, one call of the engine per maximal contiguous run, the runs' results added in run
-        order.  Host arrays by default; ``device=True``: torch tensors, and no synchronisation with the device.  ``return_value=True``: the values are
-        prepended, what ``predict(params, device=device, keys=list(weights))`` returns.
+        device without forming the Jacobian (:meth:`MLPEmulatorEngine.gauss_newton`, :meth:`TaylorEmulatorEngine.gauss_newton`), on the columns of the
+        varied keys of ``weights`` only.  Host arrays by default; ``device=True``: torch tensors, and no synchronisation with the device.
+        ``return_value=True``: the values are prepended, what ``predict(params, device=device, keys=list(weights))`` returns.
 
         ``precision``: a dense precision matrix, ``chi2 = r^T P r`` with ``r = data - y``, ``fisher = J P J^T``, ``gradient = J P r``.  ``weights`` is then
         the sequence of the distinct varied keys the data vector is made of -- those outputs flattened in C order and concatenated in the listed order, N
         entries -- (a dictionary raises ``TypeError``, a fixed or unknown key ``KeyError``), ``precision`` (N, N), symmetric, a host array or a device tensor,
         shared by all points (another shape: ``ValueError``), ``data`` ``{key: ...}`` for exactly those keys.  A column with ``precision[c, c] == 0`` is
-        dropped whatever it holds.  The precision is permuted once, on the device, to the order of the column plan; each maximal contiguous run is one
-        ``jacobian`` call of the engine, which writes straight into its column slice of one (B, ndim, N) Jacobian; :func:`gauss_newton_dense` contracts it
-        in one GEMM on the matrix cores.  Returns, ``device=`` and ``return_value=`` as above."""
+        dropped whatever it holds.  The engine's ``jacobian`` writes the (B, ndim, N) Jacobian run by run and :func:`gauss_newton_dense` contracts it in
+        one GEMM on the matrix cores.  Returns, ``device=`` and ``return_value=`` as above.  The staging and the evaluation of both routes: ``_Chi2``."""
         X, B, scalar = self._points(params)
-        torch = dv.torch()
-        if precision is not None:
-            dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, precision)
-            runs, N, precision, dblock = self._staged_dense(weights, precision, data, B, dev)
-            ndim = len(self.params)
-            new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)      # noqa: E731
-            jac, value = new(B, ndim, N), new(B, N) if data is not None or return_value else None
-            totals = self._dense_normal_equations(X, runs, precision, dblock, jac, value)
-            totals = totals if isinstance(totals, tuple) else (totals,)
-            if not device:
-                totals = tuple(dv.to_host(total) for total in totals)
-            toret = totals[0][0] if scalar else totals[0]
-            if data is not None:
-                toret = (toret, {name: (totals[1][0, i] if scalar else totals[1][:, i]) for i, name in enumerate(self.params)}, totals[2][0] if scalar else totals[2])
-            if not return_value:
-                return toret
-            values = {}
-            for start, stop, entries, q0 in runs:
-                block = value[:, q0:q0 + stop - start]
-                values.update(_split(block if device else dv.to_host(block.contiguous()), (B,), entries, start, scalar))
-            listed = [weights] if isinstance(weights, str) else list(weights)
-            for key in self.varied_keys:      # empty outputs hold no column and join no run
-                if key in listed and key not in values:
-                    values[key] = self.predict(params, device=device, keys=[key])[key]
-            values = {key: values[key] for key in self.varied_keys if key in values}      # predict's order: the calculator's
-            return (values,) + (toret if isinstance(toret, tuple) else (toret,))
-        dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, *weights.values())
-        staged, fixed = self._staged(weights, data, B, dev)
-        ndim = len(self.params)
-        totals, values = None, {}
-        for start, stop, entries, wblock, dblock in staged:
-            out = self.engine.gauss_newton(X, wblock, data=dblock, columns=(start, stop), return_value=return_value)
-            out = out if isinstance(out, tuple) else (out,)
-            if return_value:
-                values.update(_split(out[0] if device else dv.to_host(out[0]), (B,), entries, start, scalar))
-                out = out[1:]
-            totals = out if totals is None else tuple(a + b for a, b in zip(totals, out))
-        if totals is None:
-            totals = (torch.zeros((B, ndim, ndim), dtype=torch.float64, device=dev),)
-            if data is not None:
-                totals += (torch.zeros((B, ndim), dtype=torch.float64, device=dev), torch.zeros((B,), dtype=torch.float64, device=dev))
+        objective = _Chi2(self, weights, data, precision, X, B)
+        out = objective.evaluate(X, return_value=return_value)
+        values, totals = out if return_value else (None, out)
+        return self._normal_equations(objective, params, totals, values, scalar, device)
+
+    def _normal_equations(self, objective, params, totals, values, scalar, device):
+        """What :meth:`gauss_newton` and :meth:`chi2_hessian` return of an evaluation of ``objective`` at ``params``: of the device tensors ``totals``, the
+        matrix (B, ndim, ndim), then with data the gradient by parameter name and chi2; before them, where ``values`` (per run, (B, stop - start)) is not
+        None, what ``predict(params, device=device, keys=...)`` returns for the keys of the objective.  Host arrays unless ``device``, no leading axis if
+        ``scalar``; a single result as it is."""
         if not device:
             totals = tuple(dv.to_host(total) for total in totals)
-        toret = totals[0][0] if scalar else totals[0]
-        if data is not None:
-            toret = (toret, {name: (totals[1][0, i] if scalar else totals[1][:, i]) for i, name in enumerate(self.params)}, totals[2][0] if scalar else totals[2])
-        if not return_value:
-            return toret
-        for key in self.varied_keys:      # empty outputs hold no column and join no run
-            if key in weights and key not in values:
-                values[key] = self.predict(params, device=device, keys=[key])[key]
-        values = {key: values[key] for key in self.varied_keys if key in values}      # predict's order: the calculator's, then the fixed outputs
-        values.update(fixed)
-        return (values,) + (toret if isinstance(toret, tuple) else (toret,))
+        toret = (totals[0][0] if scalar else totals[0],)
+        if len(totals) > 1:
+            toret += ({name: (totals[1][0, i] if scalar else totals[1][:, i]) for i, name in enumerate(self.params)}, totals[2][0] if scalar else totals[2])
+        if values is not None:
+            split = {}
+            for (start, stop, entries), block in zip(objective.runs, values):
+                split.update(_split(block if device else dv.to_host(block.contiguous()), (objective.B,), entries, start, scalar))
+            toret = (self._values(params, split, objective.keys, objective.fixed, device),) + toret
+        return toret[0] if len(toret) == 1 else toret
 
     def chi2_hessian(self, params, weights, data, device=False, precision=None, return_value=False):
         """The full half Hessian of chi2 of a weighted least-squares fit of ``data`` to the emulated outputs, for every point of a batch:
@@ -922,43 +923,29 @@ class Emulator(object):
         bit, and ``hessian = fisher - vjp2(q)`` (B, ndim, ndim) ``= 1/2 d^2 chi2 / d theta d theta``: the Gauss-Newton half Hessian minus the
         residual-curvature term ``sum_c q_c d^2 y_c``, so that ``d gradient_i / d theta_j = -hessian_ij`` -- what ``jax.hessian`` of the reference's
         ``1/2 chi2(predict(theta))`` gives, for Newton steps, Laplace approximations and Riemannian samplers where the residuals are not small.
-        ``params``, ``weights``, ``data``, ``precision`` and their argument rules as in :meth:`gauss_newton`.  One :meth:`gauss_newton` call gives the value,
-        the Fisher matrix, the gradient and chi2; the cotangent is formed on the device: with diagonal weights ``q = w (data - y)``, exactly 0 where
+        ``params``, ``weights``, ``data``, ``precision`` and their argument rules as in :meth:`gauss_newton`.  One evaluation gives the value, the Fisher
+        matrix, the gradient and chi2; the cotangent of the residuals is formed on the device: with diagonal weights ``q = w (data - y)``, exactly 0 where
         ``w == 0`` (a select: NaN data under a zero weight stay masked); with ``precision`` ``q = (data - y) P``, the columns with ``P[c, c] == 0``
-        dropped as :func:`gauss_newton_dense` drops them; then one :meth:`vjp2` call.  Host arrays by default (no leading axis if every parameter is a
+        dropped as :func:`gauss_newton_dense` drops them; then the engine's ``vjp2`` of it, run by run.  Host arrays by default (no leading axis if every parameter is a
         scalar); ``device=True``: torch tensors, and no synchronisation with the device.  ``return_value=True``: the values are prepended."""
-        torch = dv.torch()
-        values, fisher, gradient, chi2 = self.gauss_newton(params, weights, data=data, device=True, return_value=True, precision=precision)
         X, B, scalar = self._points(params)
-        dev = fisher.device
-        sizes = dict(zip(self.varied_keys, self.varied_shapes))
-        block = lambda operand, key: torch.broadcast_to(dv.to_device(operand, dev, cache=False).to(torch.float64), (B,) + sizes[key])      # noqa: E731
-        if precision is None:
-            cotangents = {}
-            for key in weights:
-                if key not in sizes:      # a fixed output: its derivatives are zero
-                    continue
-                w = block(weights[key], key)
-                cotangents[key] = torch.where(w == 0., torch.zeros_like(w), w * (block(data[key], key) - values[key].reshape((B,) + sizes[key])))
-        else:
-            runs, N, precision, dblock = self._staged_dense(weights, precision, data, B, dev)
-            cotangents = {}
-            if N:
-                vblock = torch.cat([values[key].reshape(B, hi - lo) for start, stop, entries, q0 in runs for key, shape, lo, hi in entries], dim=1)
-                dropped = torch.diagonal(precision) == 0.
-                r = dblock - vblock
-                r = torch.where(dropped, torch.zeros_like(r), r)
-                q = r @ precision
-                q = torch.where(dropped, torch.zeros_like(q), q)
-                for start, stop, entries, q0 in runs:
-                    for key, shape, lo, hi in entries:
-                        cotangents[key] = q[:, q0 + lo - start:q0 + hi - start].reshape((B,) + shape)
-        hessian = fisher - self.vjp2(params, cotangents, device=True)
-        host = (lambda tensor: tensor) if device else (lambda tensor: dv.to_host(tensor) if dv.is_torch(tensor) else tensor)      # noqa: E731
-        toret = (host(hessian), {name: host(g) for name, g in gradient.items()}, host(chi2))
-        if return_value:
-            toret = ({key: host(value) for key, value in values.items()},) + toret
-        return toret
+        objective = _Chi2(self, weights, data, precision, X, B)
+        values, (fisher, gradient, chi2) = objective.evaluate(X, return_value=True)
+        residuals = [block - value for block, value in zip(objective.data, values)]
+        hessian = fisher - objective.pull('vjp2', X, objective.cotangent(residuals), 2)
+        return self._normal_equations(objective, params, (hessian, gradient, chi2), values if return_value else None, scalar, device)
+
+    def _box(self, bounds, X, dev):
+        """``(lo, hi, x)``: the box ``bounds = {name: (lo, hi)}`` of :meth:`least_squares` and :meth:`hmc` -- by default, and for the names it leaves out,
+        the limits of ``Emulator.params``; a name that is no parameter raises ``KeyError`` -- as (ndim,) tensors on ``dev``, and the start ``X`` clipped to it."""
+        limits = dict(self.params)
+        if bounds is not None:
+            unknown = [name for name in bounds if name not in limits]
+            if unknown:
+                raise KeyError('no parameter {}'.format(unknown))
+            limits.update({name: tuple(limit) for name, limit in bounds.items()})
+        lo, hi = (dv.to_device(np.array([limits[name][side] for name in self.params], dtype='f8'), dev) for side in (0, 1))
+        return lo, hi, dv.torch().clamp(dv.to_device(X, dev, cache=False), min=lo, max=hi)
 
     def least_squares(self, params, weights, data, bounds=None, niterations=20, lambda0=1e-3, lambda_up=10., lambda_down=0.1, lambda_min=1e-12, lambda_max=1e12,
                       ftol=1e-8, device=False, precision=None, geodesic=False, alpha=0.75):
@@ -981,74 +968,31 @@ class Emulator(object):
         ``info['covariance']`` the inverse of the dense-precision Fisher matrix.
 
         ``geodesic=True``: geodesic acceleration (Transtrum & Sethna 2012) of every step.  After :func:`lm_step` (which then also returns the velocity
-        ``v`` it solved) an iteration takes, per run of columns, the second directional derivative ``q = y''(v, v)`` at the accepted point (the engine's
-        ``jvp2``, a row per fit), its cotangent ``where(w == 0, 0, w q)`` -- under a dense precision ``P`` the masked ``q`` of all runs times ``P``, masked
-        again -- and the engine's ``vjp`` of it, the runs' results added in run order: ``h = J W q``; then :func:`lm_accelerate` takes
+        ``v`` it solved) an iteration takes ``h = J W y''(v, v)`` at the accepted point (``_Chi2.curvature``: the engine's ``jvp2``, a row per fit, the
+        cotangent of that under the weights or the precision, and the engine's ``vjp`` of it); then :func:`lm_accelerate` takes
         ``x + v + a / 2`` with ``a = -(F + lambda diag F)^-1 h`` where ``2 |a| / |v| <= alpha`` and the plain step elsewhere.  ``info`` then also holds
         ``naccelerated`` (B,), the count of corrections each fit took.  ``alpha`` must be finite and positive (``ValueError``)."""
         X, B, scalar = self._points(params)
         torch = dv.torch()
         if data is None:
             raise ValueError('least_squares needs data')
-        if precision is not None:
-            dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, precision)
-            runs, N, precision, dblock = self._staged_dense(weights, precision, data, B, dev)
-            jac, value = (torch.empty(shape, dtype=torch.float64, device=dev) for shape in ((B, len(self.params), N), (B, N)))
-        else:
-            dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, *weights.values())
-            staged, fixed = self._staged(weights, data, B, dev)
+        objective = _Chi2(self, weights, data, precision, X, B)
         names = list(self.params)
-        ndim = len(names)
-        limits = dict(self.params)
-        if bounds is not None:
-            unknown = [name for name in bounds if name not in limits]
-            if unknown:
-                raise KeyError('no parameter {}'.format(unknown))
-            limits.update({name: tuple(limit) for name, limit in bounds.items()})
-        lo, hi = (dv.to_device(np.array([limits[name][side] for name in names], dtype='f8'), dev) for side in (0, 1))
-        x = torch.clamp(dv.to_device(X, dev, cache=False), min=lo, max=hi)
+        lo, hi, x = self._box(bounds, X, objective.dev)
         state = lm_state(x, lambda0=lambda0)
         controls = dict(lambda_up=lambda_up, lambda_down=lambda_down, lambda_min=lambda_min, lambda_max=lambda_max, ftol=ftol)
         if geodesic:
             alpha = float(alpha)
             if not (0. < alpha < float('inf')):
                 raise ValueError('alpha must be finite and positive, got {}'.format(alpha))
-            naccelerated = torch.zeros((B,), dtype=torch.int32, device=dev)
-            zero = torch.zeros((), dtype=torch.float64, device=dev)
-            if precision is not None:
-                dropped = precision.diagonal() == 0
-                second = torch.empty((B, N), dtype=torch.float64, device=dev)
+            naccelerated = torch.zeros((B,), dtype=torch.int32, device=objective.dev)
         for iteration in range(int(niterations)):
-            totals = None
-            if precision is not None:
-                totals = self._dense_normal_equations(x, runs, precision, dblock, jac, value)
-            else:
-                for start, stop, entries, wblock, dblock in staged:
-                    out = self.engine.gauss_newton(x, wblock, data=dblock, columns=(start, stop))
-                    totals = out if totals is None else tuple(a + b for a, b in zip(totals, out))
-            if totals is None:
-                totals = (torch.zeros((B, ndim, ndim), dtype=torch.float64, device=dev), torch.zeros((B, ndim), dtype=torch.float64, device=dev),
-                          torch.zeros((B,), dtype=torch.float64, device=dev))
-            trial = dict(zip(LM_TRIAL, (x,) + tuple(totals)))
+            trial = dict(zip(LM_TRIAL, (x,) + objective.evaluate(x)))
             if not geodesic:
                 x = lm_step(state, trial, lo, hi, **controls)
                 continue
             x, velocity = lm_step(state, trial, lo, hi, return_velocity=True, **controls)
-            at, curvature = state['x'], None
-            if precision is not None:
-                for start, stop, entries, q0 in runs:
-                    second[:, q0:q0 + stop - start] = self.engine.jvp2(at, velocity, columns=(start, stop))
-                cotangent = torch.where(dropped, zero, torch.matmul(torch.where(dropped, zero, second), precision))
-                for start, stop, entries, q0 in runs:
-                    grad = self.engine.vjp(at, cotangent[:, q0:q0 + stop - start], columns=(start, stop))
-                    curvature = grad if curvature is None else curvature + grad
-            else:
-                for start, stop, entries, wblock, dblock in staged:
-                    grad = self.engine.vjp(at, torch.where(wblock == 0, zero, wblock * self.engine.jvp2(at, velocity, columns=(start, stop))), columns=(start, stop))
-                    curvature = grad if curvature is None else curvature + grad
-            if curvature is None:
-                curvature = torch.zeros((B, ndim), dtype=torch.float64, device=dev)
-            x = lm_accelerate(state, velocity, curvature, lo, hi, alpha=alpha, naccelerated=naccelerated)
+            x = lm_accelerate(state, velocity, objective.curvature(state['x'], velocity), lo, hi, alpha=alpha, naccelerated=naccelerated)
         covariance = spd_inverse(state['fisher'])[0]
         out = dict(state, covariance=covariance)
         if geodesic:
@@ -1096,37 +1040,10 @@ class Emulator(object):
         ndim = len(names)
         if metric is not None and tuple(np.shape(metric)) not in ((ndim, ndim), (B, ndim, ndim)):
             raise ValueError('metric must be of shape {} or {}, got {}'.format((ndim, ndim), (B, ndim, ndim), tuple(np.shape(metric))))
-        if precision is not None:
-            dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, precision)
-            runs, N, precision, dblock = self._staged_dense(weights, precision, data, B, dev)
-            jac, value = (torch.empty(shape, dtype=torch.float64, device=dev) for shape in ((B, ndim, N), (B, N)))
-        else:
-            dev = self.engine._dev['device'] if self.engine._dev is not None else dv.resolve_device(self.engine.device, X, *weights.values())
-            staged, fixed = self._staged(weights, data, B, dev)
-        limits = dict(self.params)
-        if bounds is not None:
-            unknown = [name for name in bounds if name not in limits]
-            if unknown:
-                raise KeyError('no parameter {}'.format(unknown))
-            limits.update({name: tuple(limit) for name, limit in bounds.items()})
-        lo, hi = (dv.to_device(np.array([limits[name][side] for name in names], dtype='f8'), dev) for side in (0, 1))
-
-        def evaluate(x):
-            """``(fisher, gradient, chi2)`` at ``x`` (B, ndim), as :meth:`least_squares` forms them."""
-            totals = None
-            if precision is not None:
-                totals = self._dense_normal_equations(x, runs, precision, dblock, jac, value)
-            else:
-                for start, stop, entries, wblock, dblock_ in staged:
-                    out = self.engine.gauss_newton(x, wblock, data=dblock_, columns=(start, stop))
-                    totals = out if totals is None else tuple(a + b for a, b in zip(totals, out))
-            if totals is None:
-                totals = (torch.zeros((B, ndim, ndim), dtype=torch.float64, device=dev), torch.zeros((B, ndim), dtype=torch.float64, device=dev),
-                          torch.zeros((B,), dtype=torch.float64, device=dev))
-            return totals
-
-        x = torch.clamp(dv.to_device(X, dev, cache=False), min=lo, max=hi)
-        fisher, gradient, chi2 = evaluate(x)
+        objective = _Chi2(self, weights, data, precision, X, B)
+        dev = objective.dev
+        lo, hi, x = self._box(bounds, X, dev)
+        fisher, gradient, chi2 = objective.evaluate(x)
         state = hmc_state(x, gradient, chi2)
         if metric is None:
             metric = fisher
@@ -1141,7 +1058,7 @@ class Emulator(object):
         x = hmc_step(state, {name: state[name] for name in HMC_TRIAL}, factor, lo, hi, step, t_open=0, **controls)
         for t in range(ntrajectories):
             for leap in range(nleapfrog):
-                trial = dict(zip(HMC_TRIAL, (x,) + tuple(evaluate(x)[1:])))
+                trial = dict(zip(HMC_TRIAL, (x,) + objective.evaluate(x)[1:]))
                 if leap < nleapfrog - 1:
                     x = hmc_step(state, trial, factor, lo, hi, step, **controls)
                     continue
