@@ -62,7 +62,10 @@ __device__ __forceinline__ double log_pos(double x) {
 
 // sin(x) for |x| < 1e6 (k rs_drag reaches 1e4 at k = 100 h/Mpc): n = round(x / (pi / 2)), r = x - n pi/2 with pi/2 in two pieces (33 + 53
 // bits: n times the first is exact), then the degree-13 / degree-14 polynomials of sin and cos on [-pi/4, pi/4] picked by n mod 4; absolute
-// error below 2e-16 (checked against extended precision on 6e5 arguments up to 1e6).  Larger arguments take the library function.
+// error below 2e-16 (checked against extended precision on 6e5 arguments up to 1e6, and on the doubles next to every multiple of pi / 2 and every tie of
+// the rounding up to 1e6: 1.75e-16, tests/test_math_edges_gpu.py).  Larger arguments take the library function.  Known deviation: sin_bounded(-0.) is +0
+// (the product r z poly of the series is +0 for r = -0, and +0 + -0 = +0; fma(r, z poly, r) loses it the same way): recorded, not fixed -- a copysign
+// is one more instruction in every sine of wallish2018, and no caller reads the sign of a zero.
 __device__ __forceinline__ double sin_bounded(double x) {
     if (!(fabs(x) < 1e6)) return sin_any(x);      // (also -Inf and arguments below -1e6: the two-piece reduction is exact for |n| < 2^20 only)
     const double n = rint(x * 6.36619772367581382433e-01);
@@ -107,7 +110,9 @@ __device__ __forceinline__ double exp_mid(double x) {
     return ldexp(p, (int)n);
 }
 
-// 1 / sqrt(x) for positive, finite, normal x: the hardware estimate (2^-23) and one third-order correction y (1 + e / 2 + 3 e^2 / 8), e = 1 - x y^2
+// 1 / sqrt(x) for positive, finite, normal x: the hardware estimate (2^-23) and one third-order correction y (1 + e / 2 + 3 e^2 / 8), e = 1 - x y^2.
+// Relative error below 1.7e-16: half an ulp of the result (1.11e-16), the half ulp of the product x y carried into e and halved by the series (0.56e-16), the
+// e^3 term left out (1e-20) -- whatever the estimate, while it is good to 2^-20.  Roots of even powers of two are exact.
 __device__ __forceinline__ double rsqrt_pos(double x) {
     const double y = __builtin_amdgcn_rsq(x);
     const double e = fma(-x * y, y, 1.);
@@ -154,6 +159,11 @@ __device__ __forceinline__ double exp10_mid(double x) {
 // with r = x - n log10(2) / 64 in two pieces (|r| <= 0.00236), 2^(j / 64) from a table of 64 correctly rounded doubles in LDS and 10^r - 1 by its
 // degree-5 series (remainder 4e-17): relative error 2.4e-16 over |x| < 300 (tests/test_math_gpu.py, against 80-bit arithmetic), 10 double-precision
 // instructions where exp10_mid takes 20 and six selects.  NO range handling: the caller sends tiles that hold |x| >= 300, Inf or NaN to exp10_mid.
+// The budget: the table entry within half an ulp (at most 1.11e-16 of it), the final fma within half an ulp of the result (1.11e-16), the series
+// remainder (4e-17), the roundings inside p and r (|p| < 0.0055: 2e-18) -- 2.7e-16 if all of them met at their largest, which they do not: on the
+// doubles next to every tie of the reduction and every integer, |x| < 300 (1.2e6 arguments, tests/test_math_edges_gpu.py, against pow(10, x) in 80-bit
+// arithmetic) the largest error is 2.303e-16.  (Against e^(x ln 10) in 80-bit arithmetic the same results stand at 2.57e-16: ln 10 rounded to 64 bits
+// times |x| = 300 is 3.7e-17 of the "truth" itself.)
 // 2^(j / 64), j < 64, correctly rounded (shared by exp10_tab and exp_tab)
 __device__ const double exp2_table[64] = {
     1, 1.0108892860517005, 1.0218971486541166, 1.0330248790212284, 1.0442737824274138, 1.0556451783605572, 1.0671404006768237, 1.0787607977571199,
@@ -234,7 +244,9 @@ __device__ __forceinline__ void fill_math_tables(MathTables* t) {
 
 // e^x: n = round(64 x / ln 2), ln(2) / 64 in two pieces (|r| <= 0.0055), e^r - 1 by its degree-5 series (remainder 4e-17), 2^((n & 63) / 64)
 // from the table, ldexp -- relative error 2.3e-16 (tests/test_math_gpu.py, against 80-bit arithmetic over |x| < 700), 11 double-precision instructions where
-// exp_mid takes 20.  Arguments below -800 give 0 (as beyond -745 anyway), NaN passes.
+// exp_mid takes 20.  Arguments below -800 give 0 (as beyond -745 anyway), NaN passes; arguments above 709.78 give Inf through ldexp, but +Inf itself gives
+// NaN (its reduced argument is Inf - Inf); subnormal results within one unit of 2^-1074.  On the doubles next to every tie of the reduction (1.2e6
+// arguments, every wrap of n & 63): 2.296e-16 (tests/test_math_edges_gpu.py).
 // (exp_tab_core: without the clamp of very negative arguments -- for callers whose arguments stay within +-2e7: beyond, the conversion of n saturates,
 // the result is still 0 / Inf of the right sign through ldexp, but the clamp keeps the reduction exact down to the underflow)
 __device__ __forceinline__ double exp_tab_core(double x, const MathTables* t);
